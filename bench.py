@@ -9,6 +9,16 @@ Metric (BASELINE.json): posterior (mean + var + Jacobian) predictions/sec, N=819
 batch of M = 500 000 synthetic queries already resident in HBM (configs[2]); with N GPUs every rank
 runs the same per-GPU batch on its own query shard (configs[3]: 8 x 500k = 4M, weak scaling) after ONE
 RCCL broadcast of the model fitted on rank 0.  Prints one JSON line on rank 0.
+
+A plain run does only what the headline needs: set up (fit, resident queries), W warm-up steps, K timed steps, the
+outputs of the last step if --dump-outputs DIR is given, the JSON line.  --full adds what takes measurements of its
+own: the repeat fits behind fit_ms, the CPU baseline (--cpu-sample) and, on one GPU, the `secondary` records (mode J+Jvar,
+configs[1], configs[4]; --no-secondary drops them).
+
+--dump-outputs DIR writes, after the timed steps, the arrays the timed path returned in its last step as DIR/<name>.npy
+(exact: mean, var, J, and Jvar with --jvar, fp64; --config svgp: the same four, fp32), rank 0's queries only.  The inputs
+are seeded, so two builds run with the same arguments compare output for output; above DUMP_LIMIT_BYTES every array keeps
+the same seeded sample of query rows (see dump_outputs).
 """
 import argparse
 import json
@@ -24,6 +34,7 @@ if ROOT not in sys.path:
 
 PEAK_FP64_MFMA_TFLOPS = 78.6      # MI355X datasheet fp64 matrix peak (not in MI355X_MICROARCH.md)
 PEAK_FP32_MFMA_TFLOPS = 157.3     # MI355X_MICROARCH.md "Peak FP32 (matrix)": v_mfma_f32_16x16x4_f32, 64 FLOP/clk/SIMD
+DUMP_LIMIT_BYTES = 60_000_000     # --dump-outputs: array data written at most (under 64 MB in all with the .npy headers)
 
 
 def flops_per_query(N, D, O, jvar):
@@ -45,6 +56,22 @@ def synthetic_sources(N, D=3, seed=0):
     X = rng.uniform(0, 1, (N, D))
     Y = 0.05 * np.sin(4 * X) + 0.01 * rng.standard_normal((N, D))
     return X, Y
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the arrays a step returned to its caller (torch tensors or numpy, row i = query i), copied to the
+    host after the timed region and written as DIR/<name>.npy in their own dtype.  When they hold more than `limit` bytes
+    together, every array keeps the same fixed sample of rows (seeded, ascending).  Returns {name: shape written}."""
+    host = {k: np.ascontiguousarray(v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in arrays.items() if v is not None}
+    M = next(iter(host.values())).shape[0]
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        rows = np.sort(np.random.default_rng(seed).choice(M, M * limit // total, replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in host.items()}
 
 
 def cpu_baseline(N, D, O, sample, jvar):
@@ -192,16 +219,22 @@ def main():
     ap.add_argument("--n-source", type=int, default=8192)
     ap.add_argument("--queries", type=int, default=500_000, help="queries per GPU per step")
     ap.add_argument("--jvar", action="store_true", help="also compute the Jacobian variance (mode J+Jvar)")
-    ap.add_argument("--cpu-sample", type=int, default=2000, help="queries of the CPU baseline (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=2000, help="queries of the CPU baseline of --full (0 = skip)")
     ap.add_argument("--config", choices=["exact", "svgp"], default="exact",
                     help="exact: the headline metric (BASELINE configs[2]/[3]); svgp: configs[4], fp32 SVGP-MIMO path")
     ap.add_argument("--inducing", type=int, default=2048, help="inducing points of --config svgp")
     ap.add_argument("--dry-run", action="store_true", help="multi-rank skeleton over gloo on the CPU, no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: repeat fits (fit_ms), CPU baseline, `secondary` records")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the `secondary` records (mode J+Jvar, configs[1], configs[4]) measured after the headline on one GPU")
+                    help="with --full: skip the `secondary` records (mode J+Jvar, configs[1], configs[4]) measured after the headline on one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     # ---- launcher: before torch / the library / any HIP call
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -322,9 +355,12 @@ def pmc_traffic(key, n_source, queries):
     return None, None
 
 
+def exact_queries(M, D, seed):
+    return np.random.default_rng(seed).uniform(-0.1, 1.1, (M, D))
+
+
 def exact_buffers(torch, dev, M, D, O, jvar, seed):
-    xq_host = np.random.default_rng(seed).uniform(-0.1, 1.1, (M, D))
-    xq = torch.from_numpy(xq_host).to(dev)
+    xq = torch.from_numpy(exact_queries(M, D, seed)).to(dev)
     mean = torch.empty((M, O), dtype=torch.float64, device=dev)
     var = torch.empty((M,), dtype=torch.float64, device=dev)
     J = torch.empty((M, O, D), dtype=torch.float64, device=dev)
@@ -332,9 +368,10 @@ def exact_buffers(torch, dev, M, D, O, jvar, seed):
     return xq, mean, var, J, Jvar
 
 
-def measure_exact(ctx, args, N, M, jvar, steps, warmup, c=0.1, noise=1e-4):
+def measure_exact(ctx, args, N, M, jvar, steps, warmup, c=0.1, noise=1e-4, dump=None):
     """K timed steps of the fused predict pass of a fitted exact-GP handle over M resident queries; returns the record of
-    this mode (value over all ranks, dominant-kernel duration from the library's hipEvents, roofline fields)."""
+    this mode (value over all ranks, dominant-kernel duration from the library's hipEvents, roofline fields).  dump: the
+    --dump-outputs directory (rank 0 writes the last step's outputs there)."""
     torch, dist, h, rank, world, dev, use_dist = ctx
     D = O = 3
     xq, mean, var, J, Jvar = exact_buffers(torch, dev, M, D, O, jvar, 1 + rank)
@@ -351,10 +388,12 @@ def measure_exact(ctx, args, N, M, jvar, steps, warmup, c=0.1, noise=1e-4):
               and (Jvar is None or bool(torch.isfinite(Jvar).all())))
     if not ok and not os.environ.get("GPT_BENCH_ABLATE"):     # timing-only ablation builds compute wrong values
         raise SystemExit("bench: non-finite or out-of-range outputs")
+    dumped = dump_outputs(dump, {"mean": mean, "var": var, "J": J, "Jvar": Jvar}) if dump and rank == 0 else None
     kflops = var_kernel_flops_per_query(N, D, jvar) * M
     achieved = kflops / (kern_ms * 1e-3) / 1e12
     traffic, traffic_source = pmc_traffic("jvar" if jvar else "j", N, M)
     return {"value": world * M * steps / elapsed, "elapsed_s": elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps,
+            "dumped": dumped,
             "warmup": warmup, "flops_per_query": flops_per_query(N, D, O, jvar),
             "roofline": {"bound": "mfma", "kernel": "k_var (variance / Jacobian-variance triangular MFMA GEMM)",
                          "achieved": achieved, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -399,29 +438,30 @@ def run_exact(args):
     torch, dist, h, rank, world, dev, use_dist, ranks_seen = init_ranks(args)
     N, D, O, M = args.n_source, 3, 3, args.queries
 
-    # ---- fit on rank 0, broadcast the factor (outside the timed region; reported)
+    # ---- fit on rank 0, broadcast the factor (outside the timed region; the fit's time is reported with --full)
     fit_ms = fit_timings = fit_ms_median = fit_total_median = None
     if rank == 0:
         X, Y = synthetic_sources(N, D)
         ls = np.array([0.1] * D)
         h.fit(X, Y, ls, 0.1, 1e-4, 1e-10)                  # first call: allocations + code load
         walls, totals = [], []
-        for _ in range(3):                                 # three repeat fits: the fastest is reported as fit_ms / fit_phases_ms (the
+        for _ in range(3 if args.full else 0):             # three repeat fits: the fastest is reported as fit_ms / fit_phases_ms (the
             t0 = time.perf_counter()                       # second call is still 4 % slow: tools/fit_stream_probe.py 9.83-9.91 ms, then
             h.fit(X, Y, ls, 0.1, 1e-4, 1e-10)              # 9.45-9.55), the median beside it (rounds 1 and 2 reported the second call)
             ms = (time.perf_counter() - t0) * 1e3
             walls.append(ms); totals.append(h.fit_timings()["total"])
             if fit_ms is None or ms < fit_ms:
                 fit_ms, fit_timings = ms, h.fit_timings()
-        fit_ms_median, fit_total_median = float(np.median(walls)), float(np.median(totals))
+        if walls:
+            fit_ms_median, fit_total_median = float(np.median(walls)), float(np.median(totals))
     bcast_ms, bcast_bytes = broadcast_fitted(torch, dist, h, rank, dev, use_dist)
 
     ctx = (torch, dist, h, rank, world, dev, use_dist)
-    rec = measure_exact(ctx, args, N, M, args.jvar, args.steps, args.warmup)
+    rec = measure_exact(ctx, args, N, M, args.jvar, args.steps, args.warmup, dump=args.dump_outputs)
 
-    # ---- the other single-GPU configurations, after the headline's timed region, same process (N = 1 only)
+    # ---- --full: the other single-GPU configurations, after the headline's timed region, same process (N = 1 only)
     secondary = None
-    if world == 1 and not use_dist and args.secondary:
+    if args.full and world == 1 and not use_dist and args.secondary:
         from gaussian_process_transportation_amd import _lib
         secondary = {}
         if not args.jvar:
@@ -441,7 +481,7 @@ def run_exact(args):
             "metric": "posterior (mean+var+Jacobian) preds/sec, N=8192 source pts, 3-D fp64",
             "value": rec["value"], "unit": "predictions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": rec["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": {"workload": f"N={N} source pts, M={M} queries per GPU per step, D=O=3, "
                                    f"mean+var+Jacobian{'+Jacobian variance' if args.jvar else ''}, RBF GP, fp64"
                                    + (f"; {world}x{M} queries sharded, one RCCL broadcast of the factor" if world > 1 else ""),
@@ -466,12 +506,14 @@ def run_exact(args):
             out["value_incl_bcast"] = world * M * args.steps / (rec["elapsed_s"] + bcast_ms * 1e-3)
             out["value_note"] = ("value = queries of all ranks / time of the K timed steps (max over ranks), the model broadcast "
                                  "excluded; value_incl_bcast = the same queries / (that time + bcast_ms)")
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(N, D, O, args.cpu_sample, args.jvar)
         else:
             out["cpu_baseline"] = None
         if secondary is not None:
             out["secondary"] = secondary
+        if rec["dumped"] is not None:
+            out["dumped_outputs"] = rec["dumped"]
         print(json.dumps(out), flush=True)
     h.close()
     if use_dist:
@@ -515,10 +557,10 @@ def svgp_cpu_baseline(Z, sample):
                       f"numpy BLAS threads; conversion (3 fp32 inverses) took {t_fit:.2f} s", "fit_s": t_fit}
 
 
-def measure_svgp(ctx, args, Z, M, steps, warmup, h=None, bcast=None):
+def measure_svgp(ctx, args, Z, M, steps, warmup, h=None, bcast=None, dump=None):
     """BASELINE configs[4]: SVGP-MIMO derivative path, Z inducing points, T = D = 3, M resident queries, fp32.
     A step = mean (M,T), variance (M,T), Jacobian (M,T,D) and Jacobian variance (M,T,D) of one batch.  Fits the model
-    on a handle of its own unless one is passed in (already fitted / broadcast)."""
+    on a handle of its own unless one is passed in (already fitted / broadcast).  dump: as in measure_exact."""
     from gaussian_process_transportation_amd import _lib
     torch, dist, _, rank, world, dev, use_dist = ctx
     T, D = 3, 3
@@ -546,6 +588,7 @@ def measure_svgp(ctx, args, Z, M, steps, warmup, h=None, bcast=None):
               and float(var.min()) >= 0.0 and float(var.max()) <= 1.0 + 1e-5)
     if not ok and not os.environ.get("GPT_BENCH_ABLATE"):     # timing-only ablation builds compute wrong values
         raise SystemExit("bench (svgp): non-finite or out-of-range outputs")
+    dumped = dump_outputs(dump, {"mean": mean, "var": var, "J": J, "Jvar": Jvar}) if dump and rank == 0 else None
     if own:
         h.close()
     fq, fq_var = svgp_flops_per_query(Z, D, T)
@@ -554,6 +597,7 @@ def measure_svgp(ctx, args, Z, M, steps, warmup, h=None, bcast=None):
     return {"workload": f"BASELINE configs[4]: SVGP exact conversion, Z={Z} inducing pts, T=D=3, M={M} queries per GPU "
                         "per step, mean+std+Jacobian+Jacobian std, fp32 prediction (fp64 factorisation)",
             "value": world * M * steps / elapsed, "elapsed_s": elapsed, "ms_per_step": elapsed / steps * 1e3, "fit_ms": fit_ms,
+            "dumped": dumped,
             "flops_per_query": fq,
             "roofline": {"bound": "mfma", "kernel": "k_var<float> (stacked per-task triangular MFMA GEMM, v_mfma_f32_16x16x4_f32)",
                          "achieved": achieved, "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
@@ -571,17 +615,19 @@ def run_svgp(args):
     if rank == 0:
         Zp, Sigma, y, osc, ls = svgp_synthetic_model(Z, T, D)
         h.fit_svgp(Zp, y, Sigma, ls, osc, dtype=_lib.GPT_F32)
-        t0 = time.perf_counter()
-        h.fit_svgp(Zp, y, Sigma, ls, osc, dtype=_lib.GPT_F32)
-        fit_ms = (time.perf_counter() - t0) * 1e3
+        if args.full:                                      # fit_ms: a repeat fit
+            t0 = time.perf_counter()
+            h.fit_svgp(Zp, y, Sigma, ls, osc, dtype=_lib.GPT_F32)
+            fit_ms = (time.perf_counter() - t0) * 1e3
     bcast_ms, bcast_bytes = broadcast_fitted(torch, dist, h, rank, dev, use_dist)
-    rec = measure_svgp((torch, dist, None, rank, world, dev, use_dist), args, Z, M, args.steps, args.warmup, h=h)
+    rec = measure_svgp((torch, dist, None, rank, world, dev, use_dist), args, Z, M, args.steps, args.warmup, h=h,
+                       dump=args.dump_outputs)
     if rank == 0:
         out = {
             "metric": "SVGP-MIMO posterior (mean+std+Jacobian+Jacobian std) preds/sec, 2048 inducing pts, 3 tasks, 3-D fp32",
             "value": rec["value"], "unit": "predictions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": rec["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": rec["workload"], "inducing": Z, "tasks": T, "queries_per_gpu": M},
             "flops_per_query": rec["flops_per_query"], "achieved_tflops_whole_path": rec["value"] * rec["flops_per_query"] / 1e12 / world,
             "roofline": rec["roofline"],
@@ -589,7 +635,9 @@ def run_svgp(args):
         }
         if use_dist and bcast_ms is not None:
             out["value_incl_bcast"] = world * M * args.steps / (rec["elapsed_s"] + bcast_ms * 1e-3)
-        out["cpu_baseline"] = svgp_cpu_baseline(Z, args.cpu_sample * 5) if world == 1 and args.cpu_sample > 0 else None
+        out["cpu_baseline"] = svgp_cpu_baseline(Z, args.cpu_sample * 5) if args.full and world == 1 and args.cpu_sample > 0 else None
+        if rec["dumped"] is not None:
+            out["dumped_outputs"] = rec["dumped"]
         print(json.dumps(out), flush=True)
     h.close()
     if use_dist:

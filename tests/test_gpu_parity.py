@@ -1328,6 +1328,40 @@ def test_headline_launch_shape_against_reference_vectors():
     h.close()
 
 
+@pytest.mark.parametrize("mode", ["J", "J+Jvar"])
+def test_bench_plain_run_dumps_what_it_computed(tmp_path, mode):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (a smaller model and batch): K timed steps, no
+    --full records, and the arrays of its last step in DIR equal to the CPU oracle on the same seeded inputs."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    from oracle import gp_oracle as orc
+    N, M = 1024, 4096
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--n-source", str(N), "--queries", str(M),
+            "--dump-outputs", str(tmp_path)] + (["--jvar"] if mode == "J+Jvar" else [])
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *argv], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+    assert out["value"] == pytest.approx(M * 1e3 / out["ms_per_step"], rel=1e-9)
+    assert out["full"] is False and out["cpu_baseline"] is None and "secondary" not in out and out["fit_ms"] is None
+    names = ["mean", "var", "J"] + (["Jvar"] if mode == "J+Jvar" else [])
+    assert sorted(out["dumped_outputs"]) == sorted(names) and sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in names)
+    X, Y, Xq = orc.synthetic_problem(N, M)
+    c, ls, noise = 0.1, np.array([0.1] * 3), 1e-4
+    L, a = orc.gpr_fit(X, Y, c, ls, noise, 1e-10)
+    ref = dict(zip(("mean", "var", "J", "Jvar"), orc.posterior_all_fast(Xq, X, L, a, c, ls, noise, want_jvar=(mode == "J+Jvar"))))
+    for name in names:
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float64
+        assert_parity(got, ref[name], RTOL, f"bench --dump-outputs {name} ({mode})")
+
+
 def test_reference_grid_size_at_n8192_against_reference_vectors():
     """N = 8192 with M = 10^4 queries — the size of the reference's plotting grids (plot_utils.py:13, 287-288): 157
     column blocks on 256 workgroups, i.e. the item-list / cut-sweep path with many blocks, against the golden queries

@@ -270,6 +270,31 @@ def test_bench_launcher_does_not_touch_the_gpu_stack():
     assert "import torch" not in launcher and "_lib" not in launcher and "os.exec" not in src
 
 
+def test_bench_dump_outputs_keeps_rows_together_under_the_limit(tmp_path):
+    """bench.py --dump-outputs: arrays within the byte limit are written whole, in their own dtype; above it every array
+    keeps the same seeded rows (ascending), the same from call to call, and the data stays within the limit."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    M = 1000
+    arrays = {"mean": np.arange(3 * M, dtype=np.float64).reshape(M, 3), "var": np.arange(M, dtype=np.float32), "Jvar": None}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays) == {"mean": [M, 3], "var": [M]}
+    assert sorted(os.listdir(tmp_path / "whole")) == ["mean.npy", "var.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "mean.npy"), arrays["mean"])
+    assert np.load(tmp_path / "whole" / "var.npy").dtype == np.float32
+    limit = 10_000                                            # 28 bytes a row: 357 rows
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert shapes == {"mean": [357, 3], "var": [357]}
+    m, v = np.load(tmp_path / "a" / "mean.npy"), np.load(tmp_path / "a" / "var.npy")
+    assert m.nbytes + v.nbytes <= limit
+    rows = v.astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(m, arrays["mean"][rows])
+    for name in ("mean", "var"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))
+    assert 500_000 * (3 + 1 + 9) * 8 <= bench.DUMP_LIMIT_BYTES < 64_000_000 - 4 * 128    # the headline's outputs go out whole
+
+
 VI_GEN, VI_FIRST, VI_ZERO = 1, 2, 4
 
 

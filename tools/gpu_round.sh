@@ -20,7 +20,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
     run_step pytest_gpu 600 python -m pytest tests -m gpu -x -q
     tail -n 15 "$OUT/pytest_gpu.log"
 fi
-run_step bench 400 python bench.py "$@"
+run_step bench 400 python bench.py --full "$@"
 tail -n 3 "$OUT/bench.log"
 if [ "${SKIP_PROF:-0}" != "1" ]; then
     export TMPDIR=/tmp
