@@ -31,6 +31,7 @@ SIGNATURES = {
     "gpt_set_stream": (C.c_int, [_vp, _vp]),
     "gpt_synchronize": (C.c_int, [_vp]),
     "gpt_set_dtype": (C.c_int, [_vp, C.c_int]),
+    "gpt_set_matern_derivatives": (C.c_int, [_vp, C.c_int]),
     "gpt_fit": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double]),
     "gpt_fit_kernel": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int]),
     "gpt_fit_noise_matrix": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, _dp, C.c_int, C.c_double, _dp, C.c_double, C.c_int]),
@@ -214,6 +215,10 @@ class Handle:
     def set_dtype(self, dtype):
         """Element type of the models fitted from now on: GPT_F64 (default) or GPT_F32."""
         check(self.lib.gpt_set_dtype(self._h, int(dtype)), "gpt_set_dtype")
+
+    def set_matern_derivatives(self, enable=True):
+        """J / Jvar / dvar of Matern 3/2 and 5/2 models: the analytic derivatives of the posterior (default: refused)."""
+        check(self.lib.gpt_set_matern_derivatives(self._h, int(bool(enable))), "gpt_set_matern_derivatives")
 
     def fit(self, X, Y, length_scale, constant_value, noise_level, alpha, kernel_type=0):
         """kernel_type: 0 RBF, 1/2/3 Matern nu = 0.5 / 1.5 / 2.5 (GPT_KERNEL_* of include/gpt_hip.h)."""

@@ -149,6 +149,7 @@ hipError_t var_prepare(VarWorkspace& ws, hipStream_t s, const KernelParams& p, i
 struct gpt_handle {
     int device = 0;
     int dtype_next = DT_F64;       // element type of models fitted from now on (gpt_set_dtype)
+    bool matern_derivatives = false;   // derivatives of Matern 3/2 / 5/2 models enabled (gpt_set_matern_derivatives)
     hipStream_t own_stream = nullptr, stream = nullptr;
     // model blob
     unsigned char* blob = nullptr;
@@ -441,6 +442,12 @@ int gpt_synchronize(gpt_handle* h) {
     return GPT_OK;
 }
 
+int gpt_set_matern_derivatives(gpt_handle* h, int enable) {
+    if (!h) return fail(GPT_E_ARG, "gpt_set_matern_derivatives: NULL handle");
+    h->matern_derivatives = enable != 0;
+    return GPT_OK;
+}
+
 int gpt_set_dtype(gpt_handle* h, int dtype) {
     if (!h) return fail(GPT_E_ARG, "gpt_set_dtype: NULL handle");
     if (dtype != GPT_F64 && dtype != GPT_F32) return fail(GPT_E_ARG, "gpt_set_dtype: dtype must be GPT_F64 or GPT_F32");
@@ -694,8 +701,13 @@ int gpt_predict_all_dev(gpt_handle* h, const void* Xq, int64_t M, void* mean, vo
     if (!h->committed) return fail(GPT_E_STATE, "predict: model is not fitted");
     if (M < 0 || (M > 0 && !Xq)) return fail(GPT_E_ARG, "predict: bad query buffer");
     if (M == 0) return GPT_OK;
-    if ((J || Jvar || dvar) && h->p.ktype != GPT_KERNEL_RBF)
-        return fail(GPT_E_ARG, "derivative / Jacobian variance / d variance are defined for the RBF kernel only");
+    // derivatives: RBF, and Matern 3/2 and 5/2 once enabled (gpt_exp.h, derivative columns); Matern 1/2 is not differentiable at the sources
+    if ((J || Jvar || dvar) && h->p.ktype == GPT_KERNEL_MATERN12)
+        return fail(GPT_E_ARG, "derivative / Jacobian variance / d variance: Matern 1/2 (nu = 0.5) is not differentiable at the "
+                               "training points and its derivative has infinite prior variance; use RBF, Matern 3/2 or Matern 5/2");
+    if ((J || Jvar || dvar) && h->p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
+        return fail(GPT_E_ARG, "derivative / Jacobian variance / d variance of a Matern model: the reference applies its RBF formulas "
+                               "(refused here); gpt_set_matern_derivatives(h, 1) enables the analytic derivatives of the Matern posterior");
     if (dvar && h->p.ntask != 1) return fail(GPT_E_ARG, "d variance is not defined for the multi-task (SVGP) model");
     if (int rc = set_device(h)) return rc;
     hipStream_t s = h->stream;

@@ -132,4 +132,64 @@ __device__ __forceinline__ void kernel_tab4(const float (&h)[4], const float lnc
     for (int e = 0; e < 4; ++e) k[e] = kernel_tab<KT>(h[e], lnc, T);
 }
 
+// Derivative columns (the Jacobian sums of k_mean_jac, the dk_d columns of k_var) of the twice-differentiable kernels:
+//   d k(x, X) / d x_d = c g(r) u_d,  u_d = (X_d - x_d) / l_d^2,
+//   RBF g = exp(-r^2/2) (= k / c)    Matern 3/2 g = 3 exp(-sqrt3 r)    Matern 5/2 g = 5/3 (1 + sqrt5 r) exp(-sqrt5 r)
+// and the prior variance of a derivative, -d^2 k / d tau_d^2 at tau = 0, is c g(0) / l_d^2 (kernel_g0).  Matern 1/2 is not
+// differentiable at r = 0 and has none.  g shares the exponential of k, so the Matern forms below take both from ONE exp; for
+// RBF the callers keep kernel_tab (g = k: the same code as before).
+constexpr double kernel_g0(const int kt) { return kt == KT_MATERN32 ? 3.0 : (kt == KT_MATERN52 ? 5.0 / 3.0 : 1.0); }
+
+__device__ __forceinline__ double kexp(const double a, const double* __restrict__ T) { return exp_tab(a, T); }
+__device__ __forceinline__ float kexp(const float a, const double* __restrict__) { return __builtin_amdgcn_exp2f(a * 1.44269504088896341f); }
+__device__ __forceinline__ double ksqrt(const double x) { return sqrt(x); }
+__device__ __forceinline__ float ksqrt(const float x) { return __builtin_sqrtf(x); }
+
+// t = sqrt(nu') r  ->  prefactor of exp(-t) in k (kcol) or in g
+template <int KT, typename R>
+__device__ __forceinline__ R matern_t(const R h) {
+    static_assert(KT == KT_MATERN32 || KT == KT_MATERN52, "derivative columns: Matern 3/2 and 5/2");
+    return (KT == KT_MATERN32 ? (R)1.7320508075688772 : (R)2.23606797749979) * ksqrt(h + h);
+}
+template <int KT, typename R>
+__device__ __forceinline__ R matern_pre_k(const R t) { return KT == KT_MATERN32 ? (R)1 + t : (R)1 + t + t * t * (R)(1.0 / 3.0); }
+template <int KT, typename R>
+__device__ __forceinline__ R matern_pre_g(const R t) { return KT == KT_MATERN32 ? (R)3 : (R)(5.0 / 3.0) * ((R)1 + t); }
+
+// k_mean_jac: c k (returned) and c g (in g) of one source point, from h = r^2/2
+template <int KT, typename R>
+__device__ __forceinline__ R kernel_tab_kg(const R h, const R lnc, const double* __restrict__ T, R& g) {
+    const R t = matern_t<KT>(h);
+    const R e = kexp(lnc - t, T);
+    g = matern_pre_g<KT>(t) * e;
+    return matern_pre_k<KT>(t) * e;
+}
+
+// k_var: a lane's column is a k* column (dcol false: c k, the same value as kernel_tab) or a derivative column (c g)
+template <int KT, typename R>
+__device__ __forceinline__ R kernel_tab_col(const R h, const R lnc, const double* __restrict__ T, const bool dcol) {
+    const R t = matern_t<KT>(h);
+    return (dcol ? matern_pre_g<KT>(t) : matern_pre_k<KT>(t)) * kexp(lnc - t, T);
+}
+template <int KT>
+__device__ __forceinline__ void kernel_tab4_col(const double (&h)[4], const double lnc, const double* __restrict__ T, const bool dcol,
+                                                double (&k)[4]) {
+    double a[4], pre[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const double t = matern_t<KT>(h[e]);
+        a[e] = lnc - t;
+        pre[e] = dcol ? matern_pre_g<KT>(t) : matern_pre_k<KT>(t);
+    }
+    exp_tab4(a, T, k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) k[e] = pre[e] * k[e];
+}
+template <int KT>
+__device__ __forceinline__ void kernel_tab4_col(const float (&h)[4], const float lnc, const double* __restrict__ T, const bool dcol,
+                                                float (&k)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) k[e] = kernel_tab_col<KT>(h[e], lnc, T, dcol);
+}
+
 }  // namespace gpt

@@ -45,6 +45,10 @@ class DeviceGroup:
         for h in self.handles:
             h.close()
 
+    def set_matern_derivatives(self, enable=True):
+        for h in self.handles:
+            h.set_matern_derivatives(enable)
+
     # ---- fits: first device, then one device-to-device copy of the model per further device
     def _replicate(self):
         for h in self.handles[1:]:

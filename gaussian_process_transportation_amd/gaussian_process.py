@@ -80,12 +80,16 @@ class _FittedView:
 
 class GaussianProcess:
     def __init__(self, kernel, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=5, n_targets=None,
-                 device=0, verbose=True, dtype="float64", devices=None):
+                 device=0, verbose=True, dtype="float64", devices=None, matern_derivatives=False):
         """Arguments as the reference's (:17-23); `device`, `devices`, `verbose` and `dtype` are additions.  dtype="float32"
         keeps the fp64 factorisation and runs the prediction kernels in fp32 (outputs float32; return_cov / samples need
         float64): twice the fp64 rate, ~1e-4 of the output scale.  devices=[0, 1, ...] (default: the one `device`): the fit
         and the hyper-parameter search run on devices[0], the fitted model is copied to the others and predict / derivative
-        / derivative_of_variance shard their rows over all of them (device_group.py) — same results, same call."""
+        / derivative_of_variance shard their rows over all of them (device_group.py) — same results, same call.
+        matern_derivatives=True: derivative / derivative_of_variance / posterior / prefetch_posterior of a Matern(nu=1.5 or
+        2.5) model return the analytic derivatives of its posterior (the reference multiplies the Matern k* by the RBF
+        coefficient instead, which this path does not reproduce).  Default False: those calls raise NotImplementedError, as
+        the reference's numbers or a refusal are the drop-in's rule.  No effect on RBF models; nu=0.5 is refused either way."""
         self._kernel_in = kernel
         self.kernel = kernel
         self.alpha = alpha
@@ -97,6 +101,7 @@ class GaussianProcess:
             raise ValueError("devices must name at least one GPU")
         self.device = self.devices[0] if self.devices else device
         self.verbose = verbose
+        self.matern_derivatives = bool(matern_derivatives)
         if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.float32)):
             raise ValueError("dtype must be float64 or float32")
         self._dtype = _lib.GPT_F32 if np.dtype(dtype) == np.dtype(np.float32) else _lib.GPT_F64
@@ -131,6 +136,7 @@ class GaussianProcess:
         if self._handle is None:
             self._handle = self._new_handle()
         self._handle.set_dtype(self._dtype)
+        self._handle.set_matern_derivatives(self.matern_derivatives)
         self._handle.fit(self.X, self.Y, ls, c, noise, self.alpha, self._ktype)
         self._K_inv = None
         # fitted kernel object with the reference's attribute protocol (:38-41)
@@ -167,10 +173,18 @@ class GaussianProcess:
             self._K_inv = W.T @ W
         return self._K_inv
 
-    def _require_rbf(self, what):
-        if self._ktype != 0:
+    def _require_derivatives(self, what):
+        """RBF: the reference's formulas.  Matern 3/2 and 5/2: the analytic derivatives of the posterior, opt-in."""
+        if self._ktype == 0:
+            return
+        if self._ktype == 1:
+            raise NotImplementedError(f"{what}(): Matern(nu=0.5) is not differentiable at the training points (its derivative "
+                                      "has infinite prior variance); derivatives need RBF or Matern with nu=1.5 / 2.5")
+        if not self.matern_derivatives:
             raise NotImplementedError(f"{what}() implements the RBF formulas of the reference (gaussian_process.py:63-126); "
-                                      "the reference silently applies them to any kernel, this path refuses")
+                                      "the reference silently applies them to any kernel, this path refuses.  "
+                                      "GaussianProcess(..., matern_derivatives=True) gives the analytic derivatives of the "
+                                      "Matern posterior instead (not the reference's numbers)")
 
     def _require_fit(self):
         if self._handle is None:
@@ -213,7 +227,7 @@ class GaussianProcess:
     def derivative(self, x, return_var=False):
         """(:63-102)  J (M,O,D) = d mean_o / d x_d; with return_var also its variance, tiled over outputs."""
         self._require_fit()
-        self._require_rbf("derivative")
+        self._require_derivatives("derivative")
         out = self._memo_lookup(x) or self._handle.predict_all(x, J=True, Jvar=bool(return_var))
         if not return_var:
             return out["J"]
@@ -223,7 +237,7 @@ class GaussianProcess:
     def derivative_of_variance(self, x):
         """(:104-126)  (D, M) array of d var / d x_d."""
         self._require_fit()
-        self._require_rbf("derivative_of_variance")
+        self._require_derivatives("derivative_of_variance")
         return self._handle.predict_all(x, dvar=True)["dvar"]
 
     # ------------------------------------------------------------------ fused metric path
@@ -233,7 +247,7 @@ class GaussianProcess:
         instead of 1 + 4) and kept for the next calls with the same x.  Used by
         GaussianProcessTransportation.apply_transportation, which asks for both at the same positions."""
         self._require_fit()
-        self._require_rbf("prefetch_posterior")
+        self._require_derivatives("prefetch_posterior")
         xk = np.array(x, dtype=np.float64, order="C", copy=True)
         self._memo = (xk, self._handle.predict_all(xk, mean=True, var=True, J=True, Jvar=True))
 
@@ -250,5 +264,5 @@ class GaussianProcess:
     def posterior(self, x, jacobian_variance=False):
         """One call for mean (M,O), raw variance (M,), Jacobian (M,O,D) [and Jacobian variance (M,D)]."""
         self._require_fit()
-        self._require_rbf("posterior")
+        self._require_derivatives("posterior")
         return self._handle.predict_all(x, mean=True, var=True, J=True, Jvar=bool(jacobian_variance))

@@ -23,11 +23,14 @@ def _reference_default_kernel():
 
 
 class GaussianProcessTransportation:
-    def __init__(self, kernel_transport=None, optimizer="fmin_l_bfgs_b", device=0, verbose=True, devices=None):
+    def __init__(self, kernel_transport=None, optimizer="fmin_l_bfgs_b", device=0, verbose=True, devices=None,
+                 matern_derivatives=False):
         """`devices=[0, 1, ...]`: apply_transportation() shards the demonstration's rows over these GPUs (the fit stays on
-        devices[0]); default: the one `device`."""
+        devices[0]); default: the one `device`.  `matern_derivatives=True`: a Matern(nu=1.5 / 2.5) kernel_transport
+        transports velocities and orientations with the analytic derivatives of its posterior (GaussianProcess)."""
         kernel = _reference_default_kernel() if kernel_transport is None else kernel_transport
-        regressor = GaussianProcess(kernel=kernel, optimizer=optimizer, device=device, verbose=verbose, devices=devices)
+        regressor = GaussianProcess(kernel=kernel, optimizer=optimizer, device=device, verbose=verbose, devices=devices,
+                                    matern_derivatives=matern_derivatives)
         self.method = PolicyTransportation(regressor, verbose=verbose)
 
     def _input(self, name):

@@ -66,6 +66,11 @@ int gpt_synchronize(gpt_handle* h);
 /* Element type of the models this handle fits from now on (default GPT_F64). */
 int gpt_set_dtype(gpt_handle* h, int dtype);
 
+/* (new) Derivatives (J, Jvar, d var) of Matern 3/2 and 5/2 models on this handle: 0 (default) refuses them with GPT_E_ARG, as
+ * the reference's numbers for them are its RBF formulas applied to a Matern k*; 1 gives the analytic derivatives of the Matern
+ * posterior (gpt_fit_kernel, gpt_derivative).  Per handle, kept across fits; no effect on RBF models, Matern 1/2 stays refused. */
+int gpt_set_matern_derivatives(gpt_handle* h, int enable);
+
 /* fit — replaces GaussianProcess.fit (models/gaussian_process.py:25-43) for fixed hyper-
  * parameters: sklearn's K = c*RBF(X/l) + (noise_level + alpha)*I, L = cholesky(K), alpha_ =
  * cho_solve(L, Y) (sklearn/_gpr.py:346-364) plus the factor of K^-1 the derivative code needs
@@ -78,8 +83,11 @@ int gpt_fit(gpt_handle* h, const double* X, const double* Y, int64_t N, int D, i
 
 /* The same for `ConstantKernel * Matern(nu) + WhiteKernel` (sklearn/gaussian_process/kernels.py:1717-1778), the
  * kernel the reference's examples use for their dynamics GP (example/2D/surface_generalization.py:49,
- * example/3D/surface_generalization_3D.py:42).  gpt_fit == kernel_type GPT_KERNEL_RBF.  Derivative entry points
- * stay RBF-only (the reference's derivative formulas, gaussian_process.py:63-126, are RBF formulas). */
+ * example/3D/surface_generalization_3D.py:42).  gpt_fit == kernel_type GPT_KERNEL_RBF.  The derivative entry points
+ * (J, Jvar, d var) give the analytic derivatives of this model's posterior for Matern 3/2 and 5/2:
+ *   d k(x, X_n) / d x_d = c g(r) (X_n,d - x_d) / l_d^2,  g = 3 e^{-sqrt3 r} (3/2),  5/3 (1 + sqrt5 r) e^{-sqrt5 r} (5/2),
+ * not the RBF coefficient the reference's gaussian_process.py:63-126 applies to any kernel — once enabled by
+ * gpt_set_matern_derivatives (GPT_E_ARG before).  Matern 1/2 is not differentiable at the training points: GPT_E_ARG. */
 #define GPT_KERNEL_RBF 0
 #define GPT_KERNEL_MATERN12 1
 #define GPT_KERNEL_MATERN32 2
@@ -93,7 +101,7 @@ int gpt_fit_kernel(gpt_handle* h, const double* X, const double* Y, int64_t N, i
  * K = c*k(X,X) + Sigma + alpha_jitter*I with a full SPD matrix Sigma (N,N) (the per-task pseudo-point covariance)
  * in place of the scalar noise; alpha = K^-1 Y.  One handle per task (O = 1, c = that task's outputscale).
  * Afterwards gpt_predict_all gives mean, var = c - k*^T K^-1 k* (k** carries no noise: :120-123), the Jacobian
- * and its variance c/l_d^2 - dk_d^T K^-1 dk_d (:132-153).  Host memory. */
+ * and its variance c g(0)/l_d^2 - dk_d^T K^-1 dk_d (:132-153; g(0) as at gpt_derivative).  Host memory. */
 int gpt_fit_noise_matrix(gpt_handle* h, const double* X, const double* Y, int64_t N, int D, int O,
                          const double* length_scale, int n_ls, double constant_value, const double* Sigma,
                          double alpha_jitter, int kernel_type);
@@ -118,8 +126,10 @@ int gpt_fit_svgp(gpt_handle* h, const double* Z, const double* y, const double* 
 int gpt_predict(gpt_handle* h, const void* Xq, int64_t M, void* mean, void* var);
 
 /* derivative — replaces GaussianProcess.derivative (gaussian_process.py:63-102).
- * J (M,O,D) with J[m,o,d] = d mean_o / d x_d; Jvar (M,D) = c/l_d^2 - dk_d^T K^-1 dk_d (the
- * reference tiles it over O).  Jvar may be NULL.  Host memory. */
+ * J (M,O,D) with J[m,o,d] = d mean_o / d x_d; Jvar (M,D) = c g(0)/l_d^2 - dk_d^T K^-1 dk_d (the
+ * reference tiles it over O), g(0) = 1 (RBF), 3 (Matern 3/2), 5/3 (Matern 5/2): the prior variance of the
+ * derivative, -d^2 k / d tau_d^2 at tau = 0.  Jvar may be NULL.  Host memory.  Matern 3/2 / 5/2 models: GPT_E_ARG unless
+ * gpt_set_matern_derivatives enabled them; Matern 1/2: GPT_E_ARG. */
 int gpt_derivative(gpt_handle* h, const void* Xq, int64_t M, void* J, void* Jvar);
 
 /* derivative_of_variance — replaces GaussianProcess.derivative_of_variance

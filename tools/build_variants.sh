@@ -13,7 +13,7 @@ for spec in "$@"; do
   (
     /opt/rocm/bin/hipcc $FLAGS $defs -c $C/$file.hip -o $C/build/${file}_$name.o || exit 1
     objs=""
-    for f in gpt_api gpt_fit gpt_predict; do
+    for f in gpt_api gpt_fit gpt_predict gpt_predict_matern; do
       if [ "$f" = "$file" ]; then objs="$objs $C/build/${file}_$name.o"; else objs="$objs $C/build/$f.o"; fi
     done
     /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o $C/build/libgpt_$name.so $objs

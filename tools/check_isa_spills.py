@@ -1,4 +1,4 @@
-"""Compile csrc/gpt_predict.hip with -save-temps and report, per k_var instantiation, register use and whether any
+"""Compile csrc/gpt_predict.hip and csrc/gpt_predict_matern.hip (device code) to assembly and report, per k_var instantiation, register use and whether any
 basic block of the hot loop (>= 64 MFMAs, no exp: the reload sweeps) contains scratch (spill) instructions.  A spill
 reload there costs more than its own latency: it is a vector-memory operation, so the `s_waitcnt vmcnt` in front of its
 use also drains the A-fragment loads in flight (measured round 2: 24 such reloads appeared in the fp64 kernel when the
@@ -11,12 +11,17 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc", "gpt_predict.hip")
+CSRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
+SRCS = [os.path.join(CSRC, f) for f in ("gpt_predict.hip", "gpt_predict_matern.hip")]     # every unit that instantiates k_var
 with tempfile.TemporaryDirectory() as d:
     # device side only (-save-temps also runs the host pass over the intermediate files, which hipcc 7.2 rejects for this source)
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc",
-                    "--cuda-device-only", "-S", SRC, "-o", "dev.s"] + sys.argv[1:], cwd=d, check=True, capture_output=True)
-    s = open(os.path.join(d, "dev.s")).read()
+    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc",
+                               "--cuda-device-only", "-S", src, "-o", f"dev{i}.s"] + sys.argv[1:], cwd=d,
+                              stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) for i, src in enumerate(SRCS)]
+    for p in procs:
+        if p.wait() != 0:
+            sys.exit(f"hipcc failed ({p.args[-3 - len(sys.argv[1:])]})")
+    s = "".join(open(os.path.join(d, f"dev{i}.s")).read() for i in range(len(SRCS)))
 bad = 0
 for name in re.findall(r"^(_ZN3gpt5k_varI\w+):", s, flags=re.M):
     i = s.index("\n" + name + ":")
