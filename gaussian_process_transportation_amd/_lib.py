@@ -62,6 +62,10 @@ SIGNATURES = {
     "gpt_set_profiling": (C.c_int, [_vp, C.c_int]),
     "gpt_reserve": (C.c_int, [_vp, C.c_int64, C.c_int]),
     "gpt_predict_timings": (C.c_int, [_vp, _dp]),
+    "gpt_svgp_train": (C.c_int, [C.c_int, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                 C.POINTER(_i64), _i64, C.POINTER(_i64), _i64, C.c_double, _dp]),
+    "gpt_svgp_elbo_grad": (C.c_int, [C.c_int, _dp, _dp, _i64, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                     _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
 }
 
 _lib = None
@@ -187,6 +191,61 @@ def debug_fit_plan(n_padded, form=-1, panel=-1, streams=-1):
     check(lib.gpt_debug_fit_plan(n_padded, form, panel, streams, counts, ops.ctypes.data_as(C.POINTER(_i64))))
     return {"arena": counts[1], "form": counts[2], "n_events": counts[3], "allocated": counts[4], "side_eighths": counts[5],
             "ops": ops[:counts[0], :17]}
+
+
+SVGP_PARAMS = ("Z", "m", "C", "raw_ls", "raw_os", "raw_noise")
+
+
+def _svgp_params(params, D, T):
+    """Validated C-contiguous float64 copies of the SVGP training parameters (see gpt_svgp_train)."""
+    p = {k: np.ascontiguousarray(params[k], dtype=np.float64).copy() for k in SVGP_PARAMS}
+    Zn = p["Z"].shape[0] if p["Z"].ndim == 2 else -1
+    shapes = {"Z": (Zn, D), "m": (T, Zn), "C": (T, Zn, Zn), "raw_ls": (D,), "raw_os": (T,), "raw_noise": (T + 1,)}
+    for k, shp in shapes.items():
+        if p[k].shape != shp:
+            raise ValueError(f"SVGP parameter {k} has shape {p[k].shape}, expected {shp}")
+    return p, Zn
+
+
+def svgp_train(X, Y, params, idx, batch_begin, lr=0.01, device=0):
+    """Adam on the SVGP's negative ELBO over the schedule (gpt_svgp_train).  `params` (dict of SVGP_PARAMS) is updated in
+    place; returns the per-step loss (n_steps,)."""
+    lib = load()
+    require_gpu()
+    X = as_f64(X, 2, "X")
+    Y = as_f64(Y, 2, "y")
+    (N, D), T = X.shape, Y.shape[1]
+    if Y.shape[0] != N:
+        raise ValueError("X and Y have different numbers of rows")
+    p, Zn = _svgp_params(params, D, T)
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    bb = np.ascontiguousarray(batch_begin, dtype=np.int64)
+    n_steps = max(bb.size - 1, 0)
+    trace = np.zeros(max(n_steps, 1))
+    ip = C.POINTER(_i64)
+    check(lib.gpt_svgp_train(int(device), dptr(X), dptr(Y), N, D, T, Zn, dptr(p["Z"]), dptr(p["m"]), dptr(p["C"]), dptr(p["raw_ls"]),
+                             dptr(p["raw_os"]), dptr(p["raw_noise"]), idx.ctypes.data_as(ip), idx.size, bb.ctypes.data_as(ip),
+                             n_steps, float(lr), dptr(trace)), "gpt_svgp_train")
+    for k in SVGP_PARAMS:
+        params[k] = p[k]
+    return trace[:n_steps]
+
+
+def svgp_elbo_grad(Xb, Yb, params, num_data, device=0):
+    """(loss, {name: gradient}) of one minibatch (gpt_svgp_elbo_grad)."""
+    lib = load()
+    require_gpu()
+    Xb = as_f64(Xb, 2, "X")
+    Yb = as_f64(Yb, 2, "y")
+    (b, D), T = Xb.shape, Yb.shape[1]
+    if Yb.shape[0] != b:
+        raise ValueError("X and Y have different numbers of rows")
+    p, Zn = _svgp_params(params, D, T)
+    g = {k: np.zeros_like(p[k]) for k in SVGP_PARAMS}
+    loss = C.c_double()
+    check(lib.gpt_svgp_elbo_grad(int(device), dptr(Xb), dptr(Yb), b, int(num_data), D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
+                                 C.byref(loss), *(dptr(g[k]) for k in SVGP_PARAMS)), "gpt_svgp_elbo_grad")
+    return loss.value, g
 
 
 class Handle:

@@ -375,6 +375,8 @@ int factorise(gpt_handle* h, int64_t N, int NP, int kernel_type, double c, doubl
 
 }  // namespace
 
+void gpt::set_last_error(const char* msg) { g_err = msg; }
+
 extern "C" {
 
 int gpt_device_count(void) {

@@ -64,6 +64,9 @@ struct PerDeviceOnce {
     template <class F> void run(F&& f) { std::call_once(flags[current_device()], f); }
 };
 
+// The calling thread's gpt_last_error() text (gpt_api.hip), for the C entry points of the other units.
+void set_last_error(const char* msg);
+
 // Model parameters passed by value to the prediction kernels.
 struct KernelParams {
     double c;            // constant_value (prior variance)

@@ -1,0 +1,537 @@
+// Variational training of the SVGP transport model (include/gpt_hip.h: gpt_svgp_train, gpt_svgp_elbo_grad).
+// Replaces the reference's StocasticVariationalGaussianProcess.fit (policy_transportation/models/torch/
+// stocastic_variational_gaussian_process_derivatives.py:168-187): Adam on gpytorch's whitened variational ELBO, fp64.
+//
+// One optimiser step = two launches on one stream, no host synchronisation between steps:
+//   svgp_task_step   <<<T, 256>>>  one workgroup per task: forward, the analytic backward, the task's own raw gradients
+//                                   and their Adam update; partial gradients of the shared parameters (Z, length-scale,
+//                                   global noise) and the task's loss go to part[t]
+//   svgp_shared_step <<<1, 256>>>  sums part[0..T-1] in task order, chains the raw length-scale / global noise, Adam
+//                                   on the shared parameters, loss trace
+// Every reduction runs in a fixed order (no floating-point atomics): two runs with the same inputs are bit-identical.
+// Notation and the derivation of the backward: DESIGN.md "SVGP training".
+#include "gpt_common.h"
+#include "../../include/gpt_hip.h"
+
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace gpt;
+
+namespace {
+
+constexpr int NT = 256;                      // threads per workgroup (16 x 16 in the Cholesky's trailing update)
+constexpr int SV_MAX_Z = 1024, SV_MAX_T = 32, SV_MAX_B = 1024;
+constexpr int64_t SV_MAX_STEPS = 1 << 24;    // the failure code packs (step, task) into one int
+constexpr double JITTER = 1e-4;              // gpytorch's float32 Cholesky jitter (as read)
+constexpr double NOISE_FLOOR = 1e-4;         // GreaterThan(1e-4) on each likelihood noise
+constexpr double BETA1 = 0.9, BETA2 = 0.999, ADAM_EPS = 1e-8;
+constexpr double LOG_2PI = 1.8378770664093453;
+
+struct SvArgs {
+    const double* X;      // (N, D) training inputs
+    const double* Y;      // (N, T) training targets
+    const int* idx;       // schedule: rows of X / Y
+    double* theta;        // parameters: [raw_ls (D) | Z (Zn*D) | raw_noise_global] then per task [raw_os, raw_noise_t, m (Zn), C (Zn*Zn)]
+    double* grad;         // gradients, same layout
+    double* m1;           // Adam first moments, same layout
+    double* m2;           // Adam second moments, same layout
+    double* part;         // per task: [loss, d loss / d noise_t, d / d ls (D), d / d Z (Zn*D)]
+    double* ws;           // per task workspace
+    double* loss;         // per-step loss trace (device)
+    int* fail;            // INT_MAX, or step * 64 + task of the first non-positive pivot
+    int64_t ws_stride, part_stride, task_stride, n_shared;
+    int N, D, T, Zn, bmax;
+    double num_data;      // N of the ELBO's KL scaling
+};
+
+__device__ inline double softplus(double x) { return x > 20.0 ? x : log1p(exp(x)); }
+__device__ inline double softplus_grad(double x) { if (x > 20.0) return 1.0; double z = exp(x); return z / (z + 1.0); }
+
+// Fixed-order sum over the workgroup (every thread returns the total).
+__device__ double block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// torch.optim.Adam's update of one element (single-tensor path): bc1 = 1 - beta1^k, bc2s = sqrt(1 - beta2^k).
+__device__ inline void adam(double& p, double g, double& a, double& b, double lr, double bc1, double bc2s) {
+    a = a + (1.0 - BETA1) * (g - a);
+    b = b * BETA2 + (1.0 - BETA2) * g * g;
+    p = p + (-(lr / bc1)) * (a / (sqrt(b) / bc2s + ADAM_EPS));
+}
+
+// ---- one task's forward, backward and own-parameter update --------------------------------------------------------
+// Workspace (doubles): M0, M1, M2 (Zn x Zn each), Kx, A, U, Ab, B (Zn x bmax each, row stride b), Xb (bmax x D), yb (bmax).
+__global__ __launch_bounds__(NT) void svgp_task_step(SvArgs a, int step, int b0, int b, int apply, double lr, double bc1, double bc2s) {
+    __shared__ double s_il[MAX_D];           // 1 / length-scale
+    __shared__ double s_red[NT];
+    __shared__ double s_piv[SV_MAX_Z];       // sqrt of the Cholesky pivots
+    __shared__ double s_mu[SV_MAX_B], s_r[SV_MAX_B], s_e[SV_MAX_B];
+    if (*a.fail != INT_MAX) return;          // an earlier step stopped on a non-positive pivot
+    const int t = blockIdx.x, tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int Zn = a.Zn, D = a.D, T = a.T;
+    const double* th = a.theta;
+    const double* Zp = th + D;
+    double* tt = a.theta + a.n_shared + (int64_t)t * a.task_stride;
+    double* gt = a.grad + a.n_shared + (int64_t)t * a.task_stride;
+    const double* mv = tt + 2;
+    const double* Cm = tt + 2 + Zn;
+    const double c = softplus(tt[0]);
+    const double sig2 = (NOISE_FLOOR + softplus(tt[1])) + (NOISE_FLOOR + softplus(th[D + Zn * D]));
+    const int64_t ZZ = (int64_t)Zn * Zn, ZB = (int64_t)Zn * a.bmax;
+    double* M0 = a.ws + (int64_t)t * a.ws_stride;
+    double* M1 = M0 + ZZ;
+    double* M2 = M1 + ZZ;
+    double* Kx = M2 + ZZ;
+    double* Am = Kx + ZB;
+    double* U = Am + ZB;
+    double* Ab = U + ZB;
+    double* Bm = Ab + ZB;
+    double* Xb = Bm + ZB;
+    double* yb = Xb + (int64_t)a.bmax * D;
+
+    if (tid < D) s_il[tid] = 1.0 / softplus(th[tid]);
+    for (int k = tid; k < b; k += NT) {
+        const int row = a.idx[b0 + k];
+        for (int d = 0; d < D; ++d) Xb[k * D + d] = a.X[(int64_t)row * D + d];
+        yb[k] = a.Y[(int64_t)row * T + t];
+    }
+    __syncthreads();
+
+    // K(Z,Z) + eps I -> M0 (lower triangle), K(Z,X_b) -> Kx
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), j = (int)(e - (int64_t)i * Zn);
+        if (j > i) continue;
+        double q = 0.0;
+        for (int d = 0; d < D; ++d) { const double u = (Zp[i * D + d] - Zp[j * D + d]) * s_il[d]; q += u * u; }
+        M0[e] = c * exp(-0.5 * q) + (i == j ? JITTER : 0.0);
+    }
+    for (int e = tid; e < Zn * b; e += NT) {
+        const int i = e / b, k = e - i * b;
+        double q = 0.0;
+        for (int d = 0; d < D; ++d) { const double u = (Zp[i * D + d] - Xb[k * D + d]) * s_il[d]; q += u * u; }
+        Kx[e] = c * exp(-0.5 * q);
+    }
+    __syncthreads();
+
+    // Cholesky, right-looking on the unscaled columns (one barrier per column): K_ik -= K_ij K_kj / K_jj, i >= k > j
+    for (int j = 0; j < Zn; ++j) {
+        const double p = M0[(int64_t)j * Zn + j];
+        if (!(p > 0.0)) {                                        // the same value in every thread: a uniform exit
+            if (tid == 0) atomicMin(a.fail, step * 64 + t);
+            return;
+        }
+        const double ip = 1.0 / p;
+        for (int i = j + 1 + ty; i < Zn; i += 16) {
+            const double lij = M0[(int64_t)i * Zn + j] * ip;
+            for (int k = j + 1 + tx; k <= i; k += 16) M0[(int64_t)i * Zn + k] -= lij * M0[(int64_t)k * Zn + j];
+        }
+        __syncthreads();
+    }
+    for (int j = tid; j < Zn; j += NT) s_piv[j] = sqrt(M0[(int64_t)j * Zn + j]);
+    __syncthreads();
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), j = (int)(e - (int64_t)i * Zn);
+        M0[e] = j > i ? 0.0 : (i == j ? s_piv[i] : M0[e] / s_piv[j]);
+    }
+    __syncthreads();
+
+    // W = L^-1 -> M1, one column per thread (forward substitution against e_c)
+    for (int cc = tid; cc < Zn; cc += NT) {
+        for (int i = 0; i < cc; ++i) M1[(int64_t)i * Zn + cc] = 0.0;
+        for (int i = cc; i < Zn; ++i) {
+            double s = i == cc ? 1.0 : 0.0;
+            const double* Li = M0 + (int64_t)i * Zn;
+            for (int j = cc; j < i; ++j) s -= Li[j] * M1[(int64_t)j * Zn + cc];
+            M1[(int64_t)i * Zn + cc] = s / Li[i];
+        }
+    }
+    __syncthreads();
+
+    // A = W K(Z,X_b)
+    for (int e = tid; e < Zn * b; e += NT) {
+        const int i = e / b, k = e - i * b;
+        const double* Wi = M1 + (int64_t)i * Zn;
+        double s = 0.0;
+        for (int j = 0; j <= i; ++j) s += Wi[j] * Kx[j * b + k];
+        Am[e] = s;
+    }
+    __syncthreads();
+
+    // mu = A^T m, U = C^T A
+    for (int k = tid; k < b; k += NT) {
+        double s = 0.0;
+        for (int i = 0; i < Zn; ++i) s += Am[i * b + k] * mv[i];
+        s_mu[k] = s;
+    }
+    for (int e = tid; e < Zn * b; e += NT) {
+        const int j = e / b, k = e - j * b;
+        double s = 0.0;
+        for (int i = j; i < Zn; ++i) s += Cm[(int64_t)i * Zn + j] * Am[i * b + k];
+        U[e] = s;
+    }
+    __syncthreads();
+
+    // v_k = c + eps + |U_k|^2 - |A_k|^2; e_k = (y_k - mu_k)^2 + v_k
+    for (int k = tid; k < b; k += NT) {
+        double uu = 0.0, aa = 0.0;
+        for (int i = 0; i < Zn; ++i) { const double u = U[i * b + k], x = Am[i * b + k]; uu += u * u; aa += x * x; }
+        const double r = yb[k] - s_mu[k];
+        s_r[k] = r;
+        s_e[k] = r * r + (c + JITTER + uu - aa);
+    }
+    __syncthreads();
+    double pe = 0.0;
+    for (int k = tid; k < b; k += NT) pe += s_e[k];
+    const double sum_e = block_sum(pe, s_red);
+    double pkl = 0.0;
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), j = (int)(e - (int64_t)i * Zn);
+        if (j <= i) pkl += Cm[e] * Cm[e];
+    }
+    for (int i = tid; i < Zn; i += NT) pkl += mv[i] * mv[i] - 2.0 * log(fabs(Cm[(int64_t)i * Zn + i]));
+    const double kl = 0.5 * (block_sum(pkl, s_red) - Zn);
+    const double invN = 1.0 / a.num_data;
+    const double w = 1.0 / (b * sig2);
+    const double loss_t = 0.5 * (LOG_2PI + log(sig2)) + 0.5 * w * sum_e + kl * invN;
+    const double dsig2 = 0.5 / sig2 - 0.5 * w * sum_e / sig2;
+
+    // Abar = m gmu^T + w (C U - A), gmu_k = -w r_k; d/dm, d/dC (own gradients)
+    for (int e = tid; e < Zn * b; e += NT) {
+        const int i = e / b, k = e - i * b;
+        const double* Ci = Cm + (int64_t)i * Zn;
+        double s = 0.0;
+        for (int j = 0; j <= i; ++j) s += Ci[j] * U[j * b + k];
+        Ab[e] = mv[i] * (-w * s_r[k]) + w * (s - Am[e]);
+    }
+    for (int i = tid; i < Zn; i += NT) {
+        double s = 0.0;
+        for (int k = 0; k < b; ++k) s += Am[i * b + k] * s_r[k];
+        gt[2 + i] = -w * s + mv[i] * invN;
+    }
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), j = (int)(e - (int64_t)i * Zn);
+        double g = 0.0;
+        if (j <= i) {
+            double s = 0.0;
+            for (int k = 0; k < b; ++k) s += Am[i * b + k] * U[j * b + k];
+            g = w * s + (Cm[e] - (i == j ? 1.0 / Cm[e] : 0.0)) * invN;
+        }
+        gt[2 + Zn + e] = g;
+    }
+    __syncthreads();
+
+    // B = W^T Abar (= d loss / d K(Z,X_b)); Q = sym(Phi(-Abar A^T)) -> M0 (L is no longer needed)
+    for (int e = tid; e < Zn * b; e += NT) {
+        const int j = e / b, k = e - j * b;
+        double s = 0.0;
+        for (int i = j; i < Zn; ++i) s += M1[(int64_t)i * Zn + j] * Ab[i * b + k];
+        Bm[e] = s;
+    }
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), j = (int)(e - (int64_t)i * Zn);
+        const int p = i > j ? i : j, q = i > j ? j : i;
+        double s = 0.0;
+        for (int k = 0; k < b; ++k) s += Ab[p * b + k] * Am[q * b + k];
+        M0[e] = -0.5 * s;
+    }
+    __syncthreads();
+    // Kbar = W^T Q W (= d loss / d K(Z,Z)): M2 = Q W, then M0 = W^T M2
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int i = (int)(e / Zn), l = (int)(e - (int64_t)i * Zn);
+        const double* Qi = M0 + (int64_t)i * Zn;
+        double s = 0.0;
+        for (int j = l; j < Zn; ++j) s += Qi[j] * M1[(int64_t)j * Zn + l];
+        M2[e] = s;
+    }
+    __syncthreads();
+    for (int64_t e = tid; e < ZZ; e += NT) {
+        const int mm = (int)(e / Zn), l = (int)(e - (int64_t)mm * Zn);
+        double s = 0.0;
+        for (int i = mm; i < Zn; ++i) s += M1[(int64_t)i * Zn + mm] * M2[(int64_t)i * Zn + l];
+        M0[e] = s;
+    }
+    __syncthreads();
+
+    // shared-parameter partials, one inducing point (row i) per thread:
+    //   dK_ij/dc = K_ij / c, dK_ij/dl_d = K_ij diff_d^2 / l_d^3, dK_ij/dz_id = -K_ij diff_d / l_d^2 (both rows of Kbar)
+    double* pt = a.part + (int64_t)t * a.part_stride;
+    double pc = 0.0, pls[MAX_D];
+    for (int d = 0; d < D; ++d) pls[d] = 0.0;
+    for (int i = tid; i < Zn; i += NT) {
+        double gz[MAX_D];
+        for (int d = 0; d < D; ++d) gz[d] = 0.0;
+        for (int j = 0; j < Zn; ++j) {
+            double q = 0.0;
+            for (int d = 0; d < D; ++d) { const double u = (Zp[i * D + d] - Zp[j * D + d]) * s_il[d]; q += u * u; }
+            const double kb = M0[(int64_t)i * Zn + j], kk = c * exp(-0.5 * q);
+            const double f = kb * kk, f2 = (kb + M0[(int64_t)j * Zn + i]) * kk;
+            pc += f;
+            for (int d = 0; d < D; ++d) {
+                const double u = (Zp[i * D + d] - Zp[j * D + d]) * s_il[d];
+                pls[d] += f * u * u * s_il[d];
+                gz[d] -= f2 * u * s_il[d];
+            }
+        }
+        for (int k = 0; k < b; ++k) {
+            const double f = Bm[i * b + k] * Kx[i * b + k];
+            pc += f;
+            for (int d = 0; d < D; ++d) {
+                const double u = (Zp[i * D + d] - Xb[k * D + d]) * s_il[d];
+                pls[d] += f * u * u * s_il[d];
+                gz[d] -= f * u * s_il[d];
+            }
+        }
+        for (int d = 0; d < D; ++d) pt[2 + D + i * D + d] = gz[d];
+    }
+    const double dc = block_sum(pc, s_red) / c + 0.5 / sig2;       // + the prior variance term of v_k
+    for (int d = 0; d < D; ++d) {
+        const double s = block_sum(pls[d], s_red);
+        if (tid == 0) pt[2 + d] = s;
+    }
+    if (tid == 0) {
+        pt[0] = loss_t;
+        pt[1] = dsig2;
+        gt[0] = dc * softplus_grad(tt[0]);
+        gt[1] = dsig2 * softplus_grad(tt[1]);
+    }
+    __syncthreads();
+    if (!apply) return;
+    for (int64_t e = tid; e < a.task_stride; e += NT) {
+        const int64_t o = a.n_shared + (int64_t)t * a.task_stride + e;
+        adam(a.theta[o], a.grad[o], a.m1[o], a.m2[o], lr, bc1, bc2s);
+    }
+}
+
+// ---- shared parameters: fixed-order sum over the tasks, chain rule, Adam ---------------------------------------------
+__global__ __launch_bounds__(NT) void svgp_shared_step(SvArgs a, int step, int apply, double lr, double bc1, double bc2s) {
+    if (*a.fail != INT_MAX) return;
+    const int D = a.D, Zn = a.Zn, T = a.T;
+    for (int64_t e = threadIdx.x; e < a.n_shared; e += NT) {
+        double g = 0.0;
+        if (e < D) {
+            for (int t = 0; t < T; ++t) g += a.part[(int64_t)t * a.part_stride + 2 + e];
+            g *= softplus_grad(a.theta[e]);
+        } else if (e < D + (int64_t)Zn * D) {
+            for (int t = 0; t < T; ++t) g += a.part[(int64_t)t * a.part_stride + 2 + D + (e - D)];
+        } else {
+            for (int t = 0; t < T; ++t) g += a.part[(int64_t)t * a.part_stride + 1];
+            g *= softplus_grad(a.theta[e]);
+        }
+        a.grad[e] = g;
+        if (apply) adam(a.theta[e], g, a.m1[e], a.m2[e], lr, bc1, bc2s);
+    }
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += a.part[(int64_t)t * a.part_stride];
+        a.loss[step] = s;
+    }
+}
+
+int fail(int code, const std::string& msg) {
+    set_last_error(msg.c_str());
+    return code;
+}
+
+#define SVCHK(expr)                                                                               \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) return fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// Device buffers of one call; released on every return path.
+struct SvBuffers {
+    std::vector<void*> ptrs;
+    hipStream_t stream = nullptr;
+    ~SvBuffers() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <class T> hipError_t alloc(T** p, size_t count) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
+        if (e == hipSuccess) ptrs.push_back(q);
+        *p = static_cast<T*>(q);
+        return e;
+    }
+};
+
+bool finite(const double* p, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+// The whole schedule: shared by gpt_svgp_train (apply = 1) and gpt_svgp_elbo_grad (one step, apply = 0).
+struct SvCall {
+    const double *X, *Y;
+    int64_t N, num_data;
+    int D, T, Zn;
+    double *Z, *m, *C, *raw_ls, *raw_os, *raw_noise;       // in / out (out only when apply)
+    const int64_t *idx, *bb;
+    int64_t n_idx, n_steps;
+    double lr;
+    int apply;
+    double* loss_trace;                                     // n_steps
+    double* grads[6];                                       // gZ, gm, gC, g_raw_ls, g_raw_os, g_raw_noise (apply = 0)
+};
+
+int run(int device, const char* who, const SvCall& c) {
+    const std::string w = who;
+    if (!c.X || !c.Y || !c.Z || !c.m || !c.C || !c.raw_ls || !c.raw_os || !c.raw_noise || !c.idx || !c.bb)
+        return fail(GPT_E_ARG, w + ": NULL argument");
+    if (c.D < 1 || c.D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(c.D));
+    if (c.T < 1 || c.T > SV_MAX_T) return fail(GPT_E_ARG, w + ": T (tasks) must be 1 .. 32, got " + std::to_string(c.T));
+    if (c.Zn < 1 || c.Zn > SV_MAX_Z) return fail(GPT_E_ARG, w + ": inducing points must be 1 .. 1024, got " + std::to_string(c.Zn));
+    if (c.N < 1 || c.N > INT_MAX || c.num_data < 1) return fail(GPT_E_ARG, w + ": N must be >= 1");
+    if (c.n_steps < 1) return fail(GPT_E_ARG, w + ": empty schedule (no optimiser step)");
+    if (c.n_steps > SV_MAX_STEPS) return fail(GPT_E_ARG, w + ": more than 2^24 optimiser steps in one call");
+    if (c.n_idx < 1 || c.bb[0] < 0 || c.bb[c.n_steps] > c.n_idx) return fail(GPT_E_ARG, w + ": batch boundaries outside the index array");
+    int bmax = 0;
+    for (int64_t s = 0; s < c.n_steps; ++s) {
+        const int64_t b = c.bb[s + 1] - c.bb[s];
+        if (b < 1 || b > SV_MAX_B) return fail(GPT_E_ARG, w + ": batch " + std::to_string(s) + " has " + std::to_string(b) + " rows (1 .. 1024)");
+        if (b > bmax) bmax = (int)b;
+    }
+    for (int64_t i = c.bb[0]; i < c.bb[c.n_steps]; ++i)
+        if (c.idx[i] < 0 || c.idx[i] >= c.N) return fail(GPT_E_ARG, w + ": schedule index out of range at " + std::to_string(i));
+    if (!std::isfinite(c.lr) || c.lr < 0) return fail(GPT_E_ARG, w + ": lr must be finite and >= 0");
+    const int D = c.D, T = c.T, Zn = c.Zn;
+    if (!finite(c.X, (size_t)c.N * D) || !finite(c.Y, (size_t)c.N * T) || !finite(c.Z, (size_t)Zn * D) || !finite(c.m, (size_t)T * Zn) ||
+        !finite(c.C, (size_t)T * Zn * Zn) || !finite(c.raw_ls, D) || !finite(c.raw_os, T) || !finite(c.raw_noise, T + 1))
+        return fail(GPT_E_ARG, w + ": non-finite input");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
+    SVCHK(hipSetDevice(device));
+
+    const int64_t ZZ = (int64_t)Zn * Zn;
+    const int64_t n_shared = D + (int64_t)Zn * D + 1, task_stride = 2 + Zn + ZZ, n_theta = n_shared + T * task_stride;
+    std::vector<double> th(n_theta);
+    for (int d = 0; d < D; ++d) th[d] = c.raw_ls[d];
+    for (int64_t e = 0; e < (int64_t)Zn * D; ++e) th[D + e] = c.Z[e];
+    th[n_shared - 1] = c.raw_noise[T];
+    for (int t = 0; t < T; ++t) {
+        double* p = th.data() + n_shared + t * task_stride;
+        p[0] = c.raw_os[t];
+        p[1] = c.raw_noise[t];
+        for (int i = 0; i < Zn; ++i) p[2 + i] = c.m[(int64_t)t * Zn + i];
+        for (int64_t e = 0; e < ZZ; ++e) {
+            const int i = (int)(e / Zn), j = (int)(e % Zn);
+            p[2 + Zn + e] = j > i ? 0.0 : c.C[t * ZZ + e];          // the strict upper triangle is not a parameter
+        }
+    }
+    const int64_t i0 = c.bb[0], ni = c.bb[c.n_steps] - i0;
+    std::vector<int> idx32(ni);
+    for (int64_t i = 0; i < ni; ++i) idx32[i] = (int)c.idx[i0 + i];
+
+    SvBuffers buf;
+    SVCHK(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+    SvArgs a{};
+    a.N = (int)c.N; a.D = D; a.T = T; a.Zn = Zn; a.bmax = bmax; a.num_data = (double)c.num_data;
+    a.n_shared = n_shared; a.task_stride = task_stride; a.part_stride = 2 + D + (int64_t)Zn * D;
+    a.ws_stride = 3 * ZZ + 5 * (int64_t)Zn * bmax + (int64_t)bmax * D + bmax;
+    double *dX, *dY, *dth, *dg, *dm1, *dm2, *dpart, *dws, *dloss;
+    int *didx, *dfail;
+    SVCHK(buf.alloc(&dX, (size_t)c.N * D));
+    SVCHK(buf.alloc(&dY, (size_t)c.N * T));
+    SVCHK(buf.alloc(&didx, (size_t)ni));
+    SVCHK(buf.alloc(&dth, (size_t)n_theta));
+    SVCHK(buf.alloc(&dg, (size_t)n_theta));
+    SVCHK(buf.alloc(&dm1, (size_t)n_theta));
+    SVCHK(buf.alloc(&dm2, (size_t)n_theta));
+    SVCHK(buf.alloc(&dpart, (size_t)T * a.part_stride));
+    SVCHK(buf.alloc(&dws, (size_t)T * a.ws_stride));
+    SVCHK(buf.alloc(&dloss, (size_t)c.n_steps));
+    SVCHK(buf.alloc(&dfail, 1));
+    const hipStream_t s = buf.stream;
+    const int nofail = INT_MAX;
+    SVCHK(hipMemcpyAsync(dX, c.X, (size_t)c.N * D * 8, hipMemcpyHostToDevice, s));
+    SVCHK(hipMemcpyAsync(dY, c.Y, (size_t)c.N * T * 8, hipMemcpyHostToDevice, s));
+    SVCHK(hipMemcpyAsync(didx, idx32.data(), (size_t)ni * sizeof(int), hipMemcpyHostToDevice, s));
+    SVCHK(hipMemcpyAsync(dth, th.data(), (size_t)n_theta * 8, hipMemcpyHostToDevice, s));
+    SVCHK(hipMemsetAsync(dm1, 0, (size_t)n_theta * 8, s));
+    SVCHK(hipMemsetAsync(dm2, 0, (size_t)n_theta * 8, s));
+    SVCHK(hipMemcpyAsync(dfail, &nofail, sizeof(int), hipMemcpyHostToDevice, s));
+    a.X = dX; a.Y = dY; a.idx = didx; a.theta = dth; a.grad = dg; a.m1 = dm1; a.m2 = dm2; a.part = dpart; a.ws = dws;
+    a.loss = dloss; a.fail = dfail;
+
+    for (int64_t st = 0; st < c.n_steps; ++st) {
+        const double k = (double)(st + 1);
+        const double bc1 = 1.0 - std::pow(BETA1, k), bc2s = std::sqrt(1.0 - std::pow(BETA2, k));
+        const int b0 = (int)(c.bb[st] - i0), b = (int)(c.bb[st + 1] - c.bb[st]);
+        hipLaunchKernelGGL(svgp_task_step, dim3(T), dim3(NT), 0, s, a, (int)st, b0, b, c.apply, c.lr, bc1, bc2s);
+        hipLaunchKernelGGL(svgp_shared_step, dim3(1), dim3(NT), 0, s, a, (int)st, c.apply, c.lr, bc1, bc2s);
+    }
+    SVCHK(hipGetLastError());
+    int failed = INT_MAX;
+    std::vector<double> loss(c.n_steps), out(n_theta);
+    SVCHK(hipMemcpyAsync(&failed, dfail, sizeof(int), hipMemcpyDeviceToHost, s));
+    SVCHK(hipMemcpyAsync(loss.data(), dloss, (size_t)c.n_steps * 8, hipMemcpyDeviceToHost, s));
+    SVCHK(hipMemcpyAsync(out.data(), c.apply ? dth : dg, (size_t)n_theta * 8, hipMemcpyDeviceToHost, s));
+    SVCHK(hipStreamSynchronize(s));
+    if (failed != INT_MAX)
+        return fail(GPT_E_NOT_PD, w + ": non-positive pivot in chol(K(Z,Z) + eps I) at optimiser step " + std::to_string(failed / 64) +
+                                      " (task " + std::to_string(failed % 64) + "); parameters left as they were passed");
+    if (c.loss_trace)
+        for (int64_t i = 0; i < c.n_steps; ++i) c.loss_trace[i] = loss[i];
+    // scatter the flat vector (parameters, or gradients) back into the caller's arrays
+    double* dst[6] = {c.Z, c.m, c.C, c.raw_ls, c.raw_os, c.raw_noise};
+    if (!c.apply)
+        for (int q = 0; q < 6; ++q) dst[q] = c.grads[q];
+    if (dst[3]) for (int d = 0; d < D; ++d) dst[3][d] = out[d];
+    if (dst[0]) for (int64_t e = 0; e < (int64_t)Zn * D; ++e) dst[0][e] = out[D + e];
+    if (dst[5]) dst[5][T] = out[n_shared - 1];
+    for (int t = 0; t < T; ++t) {
+        const double* p = out.data() + n_shared + t * task_stride;
+        if (dst[4]) dst[4][t] = p[0];
+        if (dst[5]) dst[5][t] = p[1];
+        if (dst[1]) for (int i = 0; i < Zn; ++i) dst[1][(int64_t)t * Zn + i] = p[2 + i];
+        if (dst[2])
+            for (int64_t e = 0; e < ZZ; ++e) {
+                const int i = (int)(e / Zn), j = (int)(e % Zn);
+                if (j <= i || !c.apply) dst[2][t * ZZ + e] = p[2 + Zn + e];      // parameters: the upper triangle stays as passed
+            }
+    }
+    return GPT_OK;
+}
+
+}  // namespace
+
+extern "C" int gpt_svgp_train(int device, const double* X, const double* Y, int64_t N, int D, int T, int n_inducing, double* Z, double* m,
+                              double* C, double* raw_lengthscale, double* raw_outputscale, double* raw_noise, const int64_t* idx, int64_t n_idx,
+                              const int64_t* batch_begin, int64_t n_steps, double lr, double* loss_trace) {
+    SvCall c{};
+    c.X = X; c.Y = Y; c.N = N; c.num_data = N; c.D = D; c.T = T; c.Zn = n_inducing;
+    c.Z = Z; c.m = m; c.C = C; c.raw_ls = raw_lengthscale; c.raw_os = raw_outputscale; c.raw_noise = raw_noise;
+    c.idx = idx; c.bb = batch_begin; c.n_idx = n_idx; c.n_steps = n_steps; c.lr = lr; c.apply = 1; c.loss_trace = loss_trace;
+    return run(device, "gpt_svgp_train", c);
+}
+
+extern "C" int gpt_svgp_elbo_grad(int device, const double* Xb, const double* Yb, int64_t b, int64_t num_data, int D, int T, int n_inducing,
+                                  const double* Z, const double* m, const double* C, const double* raw_lengthscale,
+                                  const double* raw_outputscale, const double* raw_noise, double* loss, double* grad_Z, double* grad_m,
+                                  double* grad_C, double* grad_raw_lengthscale, double* grad_raw_outputscale, double* grad_raw_noise) {
+    if (b < 1 || b > SV_MAX_B) return fail(GPT_E_ARG, "gpt_svgp_elbo_grad: batch size must be 1 .. 1024, got " + std::to_string(b));
+    std::vector<int64_t> idx(b);
+    for (int64_t i = 0; i < b; ++i) idx[i] = i;
+    const int64_t bb[2] = {0, b};
+    SvCall c{};
+    c.X = Xb; c.Y = Yb; c.N = b; c.num_data = num_data; c.D = D; c.T = T; c.Zn = n_inducing;
+    c.Z = const_cast<double*>(Z); c.m = const_cast<double*>(m); c.C = const_cast<double*>(C);
+    c.raw_ls = const_cast<double*>(raw_lengthscale); c.raw_os = const_cast<double*>(raw_outputscale); c.raw_noise = const_cast<double*>(raw_noise);
+    c.idx = idx.data(); c.bb = bb; c.n_idx = b; c.n_steps = 1; c.lr = 0.0; c.apply = 0; c.loss_trace = loss;
+    c.grads[0] = grad_Z; c.grads[1] = grad_m; c.grads[2] = grad_C; c.grads[3] = grad_raw_lengthscale; c.grads[4] = grad_raw_outputscale;
+    c.grads[5] = grad_raw_noise;
+    return run(device, "gpt_svgp_elbo_grad", c);
+}

@@ -8,8 +8,9 @@ the GPU exact-conversion predictor.
     outputs  training_traj, std, training_traj_old, training_delta + var_vel_transported, training_ori,
              affine_transform, gp_delta_map
 
-Differences, all stated: the variational training (:59-60 -> gpytorch) is out of scope, so `fit_transportation`
-takes the trained pseudo-point quantities through `pseudo_points=`; outputs are numpy arrays where the reference
+Differences, all stated: the variational training (:59-60 -> gpytorch) is opt-in — with `variational_training=True`
+`fit_transportation(num_epochs, num_inducing)` trains the SVGP on the GPU (StocasticVariationalGaussianProcess.fit);
+without it, it takes the trained pseudo-point quantities through `pseudo_points=`; outputs are numpy arrays where the reference
 holds torch tensors it converts at once (:68-69, :77-78); the quaternion algebra uses this package's own helpers
 (the reference's `quaternion` package is absent: parity unpinned, as for transport_orientation)."""
 from __future__ import annotations
@@ -24,8 +25,9 @@ from .svgp_exact import StocasticVariationalGaussianProcess
 
 
 class SVGPTransport:
-    def __init__(self, device=0, dtype="float32", verbose=True):
+    def __init__(self, device=0, dtype="float32", verbose=True, variational_training=False):
         self.device, self.dtype, self.verbose = device, dtype, verbose
+        self.variational_training = bool(variational_training)
 
     # ---- data plumbing of the reference (:17-43); files are this package's own pickles of numpy arrays
     def save_distributions(self, directory="distributions"):
@@ -44,8 +46,9 @@ class SVGPTransport:
 
     def fit_transportation(self, num_epochs=20, num_inducing=100, pseudo_points=None):
         """(:46-60)  Affine pre-alignment, residual field, SVGP on (aligned source, residual).  `pseudo_points` =
-        dict(x_inducing, var_inducing, y_inducing, outputscale, lengthscale) of the trained model; without it the
-        call reaches the (unavailable) variational training and raises NotImplementedError."""
+        dict(x_inducing, var_inducing, y_inducing, outputscale, lengthscale) of a model trained elsewhere; without it the
+        call trains the SVGP (num_epochs, num_inducing) when the transport was built with variational_training=True and
+        raises NotImplementedError otherwise."""
         if type(self.target_distribution) != type(self.source_distribution):
             raise TypeError("Both the distribution must be a numpy array.")
         if not isinstance(self.target_distribution, np.ndarray) and not isinstance(self.source_distribution, np.ndarray):
@@ -56,7 +59,7 @@ class SVGPTransport:
         delta_distribution = self.target_distribution - source_distribution
         self.gp_delta_map = StocasticVariationalGaussianProcess(source_distribution, delta_distribution,
                                                                 num_inducing=num_inducing, device=self.device,
-                                                                dtype=self.dtype)
+                                                                dtype=self.dtype, variational_training=self.variational_training)
         if pseudo_points is None:
             self.gp_delta_map.fit(num_epochs=num_epochs)
         else:

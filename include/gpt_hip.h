@@ -120,6 +120,33 @@ int gpt_fit_noise_matrix(gpt_handle* h, const double* X, const double* Y, int64_
 int gpt_fit_svgp(gpt_handle* h, const double* Z, const double* y, const double* Sigma, int64_t N, int D, int T,
                  const double* length_scale, int n_ls, const double* outputscale, double jitter, int dtype);
 
+/* (new) Variational training of the SVGP transport model — replaces StocasticVariationalGaussianProcess.fit
+ * (policy_transportation/models/torch/stocastic_variational_gaussian_process_derivatives.py:168-187: Adam, lr, over
+ * gpytorch's VariationalELBO of the model at :15-63).  fp64 throughout, on `device`, host memory in and out.
+ *   X (N,D), Y (N,T) training data (D 1..15, T 1..32); n_inducing Z 1..1024;
+ *   in / out, updated in place: Z (Z,D) inducing points, m (T,Z) whitened variational means, C (T,Z,Z) variational
+ *   Cholesky factors (lower triangle; the strict upper triangle is ignored and returned as passed), raw_lengthscale (D),
+ *   raw_outputscale (T), raw_noise (T+1: per task, then the global noise) — softplus-constrained as gpytorch's defaults:
+ *   l = softplus(raw), c_t = softplus(raw), noise_t = (1e-4 + softplus(raw_t)) + (1e-4 + softplus(raw_global));
+ *   schedule: step s uses rows idx[batch_begin[s] .. batch_begin[s+1]) (1 .. 1024 rows; idx in [0,N)), n_steps >= 1;
+ *   Adam (betas 0.9, 0.999, eps 1e-8) with learning rate lr, its state zero at the call; loss_trace (n_steps, may be NULL)
+ *   receives each step's negative ELBO (before that step's update).
+ * Every step is enqueued without a host round trip; the result is bit-reproducible.  GPT_E_NOT_PD (message: the optimiser
+ * step) if chol(K(Z,Z) + 1e-4 I) meets a non-positive pivot — the parameters are then left as passed.  GPT_E_ARG for sizes
+ * outside the limits above, an empty schedule or non-finite input. */
+int gpt_svgp_train(int device, const double* X, const double* Y, int64_t N, int D, int T, int n_inducing, double* Z, double* m,
+                   double* C, double* raw_lengthscale, double* raw_outputscale, double* raw_noise, const int64_t* idx, int64_t n_idx,
+                   const int64_t* batch_begin, int64_t n_steps, double lr, double* loss_trace);
+
+/* (new) One minibatch of the same objective without the update — the loss `-mll(output, y_batch)` and its `backward()` of
+ * stocastic_variational_gaussian_process_derivatives.py:180-182: Xb (b,D), Yb (b,T), num_data = N of the KL term's 1/N;
+ * parameters as at gpt_svgp_train (read only); loss (1) and the gradient of every raw parameter, each shaped like its
+ * parameter (grad_C zero above the diagonal).  Gradient pointers may be NULL. */
+int gpt_svgp_elbo_grad(int device, const double* Xb, const double* Yb, int64_t b, int64_t num_data, int D, int T, int n_inducing,
+                       const double* Z, const double* m, const double* C, const double* raw_lengthscale, const double* raw_outputscale,
+                       const double* raw_noise, double* loss, double* grad_Z, double* grad_m, double* grad_C,
+                       double* grad_raw_lengthscale, double* grad_raw_outputscale, double* grad_raw_noise);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */
