@@ -13,11 +13,15 @@ arithmetic: it casts everything with `.float()`) or fp64.  The reference materia
 Training (`variational_training=True`; the reference's :168-187 runs it in gpytorch, which is not a dependency here):
 Adam on the whitened variational ELBO, every optimiser step fused into one HIP launch pair (`gpt_svgp_train`, fp64),
 then the trained q(u) is converted to pseudo-points on the host (`variational_to_pseudo_points`).  The model is a
-restatement of gpytorch's defaults as read (DESIGN "SVGP training"): parity with gpytorch's float32 numbers is unpinned.
+restatement of gpytorch's defaults as read (DESIGN "SVGP training").  Its m / C structure is pinned: at the closed-form
+(Titsias) optimum of q(u) the gradients vanish and the loss is the collapsed bound (tests/test_svgp_anchors.py).  Its
+gpytorch constants (the 1e-4 jitter, the 1e-4 noise floor) and gpytorch's float32 numbers stay unpinned.
 
-PARITY UNPINNED: the reference holds no fixture for this path; the CPU restatement is
-oracle/gp_oracle.py:svgp_exact_oracle.  Where the reference's :142 broadcasts K_inv over the input-dimension axis
-(it only type-checks for T == D), the intended per-task K_inv[t] is used."""
+Parity: the prediction and the pseudo-point conversion are pinned to the reference's fixtures in the homoscedastic case
+(Z = X, Sigma_t = (noise + alpha) I is the sklearn GP of tests/golden/*.npz; tests/test_svgp_anchors.py).  A general
+Sigma_t and gpytorch's float32 numbers stay unpinned; there the yardstick is oracle/gp_oracle.py:svgp_exact_oracle.
+Where the reference's :142 broadcasts K_inv over the input-dimension axis (it only type-checks for T == D), the intended
+per-task K_inv[t] is used."""
 from __future__ import annotations
 
 import numpy as np

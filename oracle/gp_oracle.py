@@ -362,8 +362,9 @@ def svgp_exact_oracle(x, Z, Sigma, y, outputscale, lengthscale):
     alpha = K_inv y), :113-129 (mean = k* alpha, std = sqrt(diag(k** - k* K_inv k*^T)), k** = outputscale),
     :132-153 (J = dk*/dx alpha, var' = outputscale/l_d^2 - diag(dk* K_inv dk*^T)); gpytorch ScaleKernel(RBF ARD):
     outputscale_t exp(-0.5 |(x-z)/l|^2).  K_inv[t] per task (see svgp_exact.py on the reference's :142).
-    PARITY UNPINNED (gpytorch absent, no fixture in the reference).  Returns mean (M,T), std (M,T), J (M,T,D),
-    J_std (M,T,D)."""
+    Pinned to the reference's fixtures in the homoscedastic case (Z = X, Sigma_t = (noise + alpha) I reproduces the sklearn
+    GP of tests/golden/*.npz: tests/test_svgp_anchors.py); unpinned for a general Sigma and against gpytorch's float32
+    numbers (gpytorch absent).  Returns mean (M,T), std (M,T), J (M,T,D), J_std (M,T,D)."""
     ls = np.broadcast_to(np.atleast_1d(np.asarray(lengthscale, np.float64)), (Z.shape[1],))
     T = Sigma.shape[0]
     M, D = x.shape
