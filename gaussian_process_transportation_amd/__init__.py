@@ -6,7 +6,9 @@ from .policy_transportation import PolicyTransportation
 from .gaussian_process_transportation import GaussianProcessTransportation
 from .svgp_exact import StocasticVariationalGaussianProcess, SVGPExactPredictor
 from .svgp_transport import SVGPTransport
+from .svgp_surface import StocasticVariationalGaussianProcess as SurfaceSVGP
 
-# the reference's three exports first; then the duck-typed caller and the SVGP exact-conversion path
+# the reference's three exports first; then the duck-typed caller, the SVGP exact-conversion path and the
+# point-cloud surface SVGP
 __all__ = ["AffineTransform", "GaussianProcessTransportation", "GaussianProcess", "PolicyTransportation",
-           "SVGPTransport", "StocasticVariationalGaussianProcess", "SVGPExactPredictor"]
+           "SVGPTransport", "StocasticVariationalGaussianProcess", "SVGPExactPredictor", "SurfaceSVGP"]

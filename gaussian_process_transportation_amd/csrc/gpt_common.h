@@ -104,6 +104,11 @@ size_t factor_scratch_doubles(int NP);        // gpt_fit_plan.h
 // L = chol(K) in place (lower), W = L^-1; scratch >= factor_scratch_doubles(NP); ev_factored (may be null) is recorded
 // in `s` when L is complete
 void launch_factor_inverse(hipStream_t s, double* K, double* W, int NP, int* info, double* scratch, FitAux* aux, hipEvent_t ev_factored);
+// C (M x N, ldc) = alpha op(A) op(B), fp64 MFMA (k_gemm): at -> op(A) = A^T with A stored (K x M, lda), bt -> op(B) = B^T
+// with B stored (N x K, ldb), not both; lower_only -> C's block lower triangle only (M == N).  M, N, K multiples of 64,
+// leading dimensions and pointers 16-byte aligned.
+void launch_dgemm(hipStream_t s, bool at, bool bt, int M, int N, int K, double alpha, const double* A, long lda, const double* B,
+                  long ldb, double* C, long ldc, bool lower_only);
 void launch_alpha(hipStream_t s, const double* W, const double* Y4, int N, int NP, double* tmp4, double* A4,
                   double* scratch /* >= (NP/512)*NP*4 doubles */);
 // W (row-major fp64, lower) * scale -> tile set `task` of the fragment-ordered stream Wf (element type dtype)

@@ -930,6 +930,18 @@ static void trinv_levels(hipStream_t s, const double* L, double* W, int NP, int 
     }
 }
 
+// Thin entry to launch_gemm for the other units (gpt_common.h).
+void launch_dgemm(hipStream_t s, bool at, bool bt, int M, int N, int K, double alpha, const double* A, long lda, const double* B,
+                  long ldb, double* C, long ldc, bool lower_only) {
+    GemmArgs g{};
+    g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
+    g.M = g.M_last = M; g.N = N; g.K = g.K_last = K; g.nbatch = 1;
+    g.alpha = alpha; g.beta = 0.0; g.lower_only = lower_only ? 1 : 0;
+    if (bt) launch_gemm<true>(s, g);
+    else if (at) launch_gemm<false, true>(s, g);
+    else launch_gemm<false>(s, g);
+}
+
 void fit_aux_release(FitAux& aux) {
     for (auto& e : aux.events) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     if (aux.side) (void)hipStreamDestroy(aux.side);

@@ -103,8 +103,9 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
 
 }  // namespace gpt
 
-// The variational training unit (gpt_svgp_train.hip) is device code end to end and is not part of this build; its entry
-// points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this library too.
+// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip) are device code end to end and are not part of
+// this build; their entry points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this
+// library too.
 #include "../../../include/gpt_hip.h"
 extern "C" int gpt_svgp_train(int, const double*, const double*, int64_t, int, int, int, double*, double*, double*, double*, double*,
                               double*, const int64_t*, int64_t, const int64_t*, int64_t, double, double*) {
@@ -115,5 +116,21 @@ extern "C" int gpt_svgp_elbo_grad(int, const double*, const double*, int64_t, in
                                   const double*, const double*, const double*, const double*, double*, double*, double*, double*,
                                   double*, double*, double*) {
     gpt::set_last_error("gpt_svgp_elbo_grad: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_svgp_surface_train(int, const double*, const double*, int64_t, int, int, int, double*, double*, double*, double*,
+                                      double*, double*, const int64_t*, int64_t, const int64_t*, int64_t, double, double*) {
+    gpt::set_last_error("gpt_svgp_surface_train: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_svgp_surface_elbo_grad(int, const double*, const double*, int64_t, int64_t, int, int, int, const double*,
+                                          const double*, const double*, const double*, const double*, const double*, double*,
+                                          double*, double*, double*, double*, double*, double*) {
+    gpt::set_last_error("gpt_svgp_surface_elbo_grad: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_svgp_surface_predict(int, const double*, const double*, const double*, const double*, const double*, int, int, int,
+                                        const double*, int64_t, double*, double*, double*) {
+    gpt::set_last_error("gpt_svgp_surface_predict: not in the host sanitizer build");
     return GPT_E_HIP;
 }

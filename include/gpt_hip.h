@@ -147,6 +147,42 @@ int gpt_svgp_elbo_grad(int device, const double* Xb, const double* Yb, int64_t b
                        const double* raw_noise, double* loss, double* grad_Z, double* grad_m, double* grad_C,
                        double* grad_raw_lengthscale, double* grad_raw_outputscale, double* grad_raw_noise);
 
+/* (new) Variational training of the point-cloud surface SVGP — replaces StocasticVariationalGaussianProcess.fit of
+ * policy_transportation/models/torch/stocastic_variational_gaussian_process.py:68-89 (Adam on gpytorch's VariationalELBO
+ * of the SVGP at :15-60).  The objective of gpt_svgp_train with a length-scale per task: raw_lengthscale (T,D),
+ * K_t(Z,Z) = c_t k_{l_t}(Z,Z) + 1e-4 I.  Every other argument, the schedule, Adam and the failure contract as at
+ * gpt_svgp_train; limits: n_inducing 1..4096, T 1..32, D 1..15, 1..1024 rows per batch.  Each task's Z x Z work runs
+ * device-wide (blocked Cholesky + inverse, MFMA GEMMs); the result is bit-reproducible.
+ * Failure: after a non-positive pivot every glue kernel returns at once, but the factor and GEMM launches of the steps
+ * already enqueued still run (on stale data; no parameter changes), so a call that fails early costs about as long as
+ * the whole schedule.
+ * Memory, with NP = n_inducing rounded up to a multiple of 512: C is kept padded (NP x NP per task) in the parameters,
+ * gradients and both Adam moments, so one call takes about 32 (T + 1) NP^2 bytes of device memory and 16 T NP^2 bytes of
+ * host memory (T = 1, Z = 1000: 67 MB / 17 MB; T = 32, Z = 4096: 17.7 GB / 8.6 GB). */
+int gpt_svgp_surface_train(int device, const double* X, const double* Y, int64_t N, int D, int T, int n_inducing, double* Z,
+                           double* m, double* C, double* raw_lengthscale, double* raw_outputscale, double* raw_noise,
+                           const int64_t* idx, int64_t n_idx, const int64_t* batch_begin, int64_t n_steps, double lr,
+                           double* loss_trace);
+
+/* (new) One minibatch of the surface objective without the update — `loss = -self.mll(output, y_batch)` and its
+ * `loss.backward()` at stocastic_variational_gaussian_process.py:84-87.  Arguments as at gpt_svgp_elbo_grad, with
+ * raw_lengthscale and grad_raw_lengthscale shaped (T,D).  Gradient pointers may be NULL. */
+int gpt_svgp_surface_elbo_grad(int device, const double* Xb, const double* Yb, int64_t b, int64_t num_data, int D, int T,
+                               int n_inducing, const double* Z, const double* m, const double* C, const double* raw_lengthscale,
+                               const double* raw_outputscale, const double* raw_noise, double* loss, double* grad_Z,
+                               double* grad_m, double* grad_C, double* grad_raw_lengthscale, double* grad_raw_outputscale,
+                               double* grad_raw_noise);
+
+/* (new) The variational predictive of the surface SVGP — replaces `self.gp(x)` in StocasticVariationalGaussianProcess.predict
+ * (stocastic_variational_gaussian_process.py:95-103) and the jacobian of its mean in derivative (:105-111).  Per task,
+ * with a = W_t c_t k_{l_t}(Z, x), W_t = chol(c_t k(Z,Z) + 1e-4 I)^-1: mean (M,T) = a^T m_t; var (M,T, may be NULL) =
+ * c_t - |a|^2 + |C_t^T a|^2 (the latent f, no likelihood noise); J (M,T,D, may be NULL) = d mean / d x.  fp64, host
+ * memory in and out.  GPT_E_NOT_PD if a factor meets a non-positive pivot.  Memory: about 8 (3 NP^2 + 3072 NP) bytes of
+ * device and 16 NP^2 bytes of host memory (NP as at gpt_svgp_surface_train), plus the inputs and outputs. */
+int gpt_svgp_surface_predict(int device, const double* Z, const double* m, const double* C, const double* raw_lengthscale,
+                             const double* raw_outputscale, int n_inducing, int D, int T, const double* Xq, int64_t M,
+                             double* mean, double* var, double* J);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */
