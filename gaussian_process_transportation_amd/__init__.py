@@ -7,8 +7,10 @@ from .gaussian_process_transportation import GaussianProcessTransportation
 from .svgp_exact import StocasticVariationalGaussianProcess, SVGPExactPredictor
 from .svgp_transport import SVGPTransport
 from .svgp_surface import StocasticVariationalGaussianProcess as SurfaceSVGP
+from .gaussian_process_al import ActiveLearningGaussianProcess
 
 # the reference's three exports first; then the duck-typed caller, the SVGP exact-conversion path and the
-# point-cloud surface SVGP
+# point-cloud surface SVGP, and the large-input exact regressor (greedy active-learning subset selection)
 __all__ = ["AffineTransform", "GaussianProcessTransportation", "GaussianProcess", "PolicyTransportation",
-           "SVGPTransport", "StocasticVariationalGaussianProcess", "SVGPExactPredictor", "SurfaceSVGP"]
+           "SVGPTransport", "StocasticVariationalGaussianProcess", "SVGPExactPredictor", "SurfaceSVGP",
+           "ActiveLearningGaussianProcess"]

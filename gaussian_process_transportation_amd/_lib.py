@@ -71,6 +71,8 @@ SIGNATURES = {
     "gpt_svgp_surface_elbo_grad": (C.c_int, [C.c_int, _dp, _dp, _i64, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp,
                                              _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpt_svgp_surface_predict": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _i64, _dp, _dp, _dp]),
+    "gpt_select_greedy": (C.c_int, [C.c_int, _dp, _i64, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(_i64),
+                                    C.c_int, C.c_int, C.POINTER(_i64), _dp, _dp]),
 }
 
 _lib = None
@@ -347,6 +349,40 @@ def svgp_surface_predict(params, Xq, var=False, J=False, device=0):
                                        Zn, D, T, dptr(Xq), M, dptr(mean), dptr(v) if var else None, dptr(j) if J else None),
           "gpt_svgp_surface_predict")
     return mean, v, j
+
+
+def select_greedy(X, length_scale, constant_value, noise_level, alpha, n_total, initial=(), kernel_type=0, device=0,
+                  residual=True):
+    """Greedy maximum-variance selection of n_total pool points (gpt_select_greedy): the `initial` indices first, in their
+    order, then the point of largest posterior variance each time (ties: lowest index).  Returns (selected (n_total,) int64,
+    selection_variance (n_total - len(initial),), residual_variance (N,) or None)."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    if X.ndim != 2:
+        raise ValueError(f"expected a 2-D array, got shape {X.shape}")
+    N, D = X.shape
+    if not 1 <= D <= MAX_D:
+        raise ValueError(f"the pool has {D} features: this GPU path supports input dimension D = 1 .. {MAX_D} only")
+    ls = as_f64(np.atleast_1d(length_scale), 1, "length_scale")
+    if ls.size == 1:
+        ls = np.full(D, ls[0])
+    if ls.size != D:
+        raise ValueError(f"length_scale has {ls.size} entries, the pool {D} features")
+    initial = np.ascontiguousarray(initial, dtype=np.int64).reshape(-1)
+    n_total = int(n_total)
+    if n_total > N:
+        raise ValueError(f"cannot select {n_total} points from a pool of {N}")
+    if n_total < 1 or initial.size > n_total:
+        raise ValueError("need len(initial) <= n_total and n_total >= 1")
+    lib = load()             # the entry point scans the pool for NaN / infinity itself (ValueError)
+    require_gpu()
+    selected = np.zeros(n_total, dtype=np.int64)
+    selvar = np.zeros(max(n_total - initial.size, 1))
+    resid = np.zeros(N) if residual else None
+    ip = C.POINTER(_i64)
+    check(lib.gpt_select_greedy(int(device), dptr(X), N, D, dptr(ls), float(constant_value), float(noise_level), float(alpha),
+                                int(kernel_type), initial.ctypes.data_as(ip) if initial.size else None, initial.size, n_total,
+                                selected.ctypes.data_as(ip), dptr(selvar), dptr(resid)), "gpt_select_greedy")
+    return selected, selvar[:n_total - initial.size], resid
 
 
 class Handle:

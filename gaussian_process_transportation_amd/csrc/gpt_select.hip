@@ -1,0 +1,336 @@
+// Greedy maximum-variance subset selection over a point pool — gpt_select_greedy (include/gpt_hip.h), the device side of
+// ActiveLearningGaussianProcess.  With the hyper-parameters held fixed, "insert the pool point of largest posterior
+// variance, refit, repeat" is a pivoted Cholesky factorisation of the pool's kernel matrix with the diagonal pivot rule:
+// the residual diagonal d is the posterior variance.  One insertion is one new column of the pool factor P (N x mp,
+// row-major: a pool point's row is contiguous):
+//     P[i, j] = (k(x_i, x_p) - P[i, :j] . P[p, :j]) / sqrt(d[p] + alpha),   d[i] -= P[i, j]^2
+// for EVERY pool row i (selected rows included: their d stays sklearn's predictive variance at a training point), and the
+// same pass finds each workgroup's (max d, lowest index) over the rows still alive.  A second one-workgroup launch reduces
+// the partials in a fixed order to the next pivot, which never leaves the device.  A prescribed pivot (the initial
+// subset) runs the same two kernels; the reduction then reads the pivot from the list instead of choosing it.
+//
+// sel_column is a bandwidth kernel: step j streams 8 N j bytes of P.  A group of LPR lanes (8, 16 or 64: short rows would
+// leave most of a wave idle) owns one row at a time and reads it with 16-byte loads against the pivot row's first j
+// entries, staged once per workgroup in LDS (the first SEL_LDS_COLS of them; a longer pivot row's tail is read from
+// global memory, where every group reads the same addresses).  k is evaluated in scaled coordinates (rows of 4 / 8 / 16
+// doubles, gpt_common.h) with the table exp of gpt_exp.h.
+#include "gpt_common.h"
+#include "gpt_exp.h"
+#include "../../include/gpt_hip.h"
+
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace gpt {
+namespace {
+
+constexpr int SEL_NT = 256;              // threads of a sel_column workgroup (4 waves)
+constexpr int SEL_LDS_COLS = 4096;       // pivot-row entries staged in LDS (32 KB); a multiple of 2 * 64
+constexpr int SEL_MAX_WG = 2048;         // sel_column workgroups = partial maxima the reduction reads
+constexpr double SEL_MEMORY_SHARE = 0.8; // of the device's free memory the pool factor may take
+
+struct SelArgs {
+    const double* Xs;        // (N, stride) scaled pool
+    double* P;               // (N, mp) pool factor, zero beyond the columns written so far
+    double* d;               // (N) residual variance, sklearn's y_var convention (white noise included)
+    unsigned char* alive;    // (N) 1 until the row is taken as a pivot
+    int* selected;           // (n_total) pivots in insertion order; the first n_pre are prescribed
+    double* pivd;            // (n_total) d[pivot] at the moment it was taken
+    double* part_d;          // (SEL_MAX_WG) per-workgroup maximum of d over alive rows ...
+    int* part_i;             // ... and the lowest index attaining it
+    int* fail;               // 0, or 1 + the insertion whose pivot was not positive
+    int N, stride, mp, n_pre, ktype;
+    double lnc, base_var, alpha;   // log c; c + noise
+};
+
+__device__ __forceinline__ bool sel_better(const double da, const int ia, const double db, const int ib) {
+    return da > db || (da == db && ia < ib);
+}
+
+__global__ __launch_bounds__(SEL_NT) void sel_scale(const double* __restrict__ X, const double* __restrict__ inv_ls, double* __restrict__ Xs,
+                                                    int N, int D, int stride) {
+    const int64_t e = (int64_t)blockIdx.x * SEL_NT + threadIdx.x;
+    if (e >= (int64_t)N * stride) return;
+    const int i = (int)(e / stride), k = (int)(e % stride);
+    Xs[e] = k < D ? X[(int64_t)i * D + k] * inv_ls[k] : 0.0;
+}
+
+__global__ __launch_bounds__(SEL_NT) void sel_init(SelArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * SEL_NT + threadIdx.x;      // N may lie within SEL_NT of 2^31
+    if (i < a.N) { a.d[i] = a.base_var; a.alive[i] = 1; }
+    if (i == 0) a.pivd[0] = a.base_var;
+}
+
+template <int LPR>
+__global__ __launch_bounds__(SEL_NT) void sel_column(SelArgs a, int j) {
+    __shared__ __attribute__((aligned(16))) double Lrow[SEL_LDS_COLS];
+    __shared__ double T[256];
+    __shared__ double xp[MAX_D];
+    __shared__ double wd[SEL_NT / 64];
+    __shared__ int wi[SEL_NT / 64];
+    if (*a.fail) return;
+    const double piv = a.pivd[j] + a.alpha;
+    if (!(piv > 0.0)) {                       // the same value in every workgroup: all of them leave
+        if (blockIdx.x == 0 && threadIdx.x == 0) *a.fail = j + 1;
+        return;
+    }
+    const int p = a.selected[j], mp = a.mp, N = a.N, stride = a.stride;
+    const double* __restrict__ prow_p = a.P + (size_t)p * mp;
+    const int jl = j < SEL_LDS_COLS ? j : SEL_LDS_COLS;
+    for (int c = threadIdx.x; c < ((jl + 1) & ~1); c += SEL_NT) Lrow[c] = c < j ? prow_p[c] : 0.0;
+    T[threadIdx.x] = g_exp2_table[threadIdx.x];
+    if (threadIdx.x < stride) xp[threadIdx.x] = a.Xs[(size_t)p * stride + threadIdx.x];
+    __syncthreads();
+
+    const double rs = sqrt(piv);
+    constexpr int GROUPS = SEL_NT / LPR;          // rows a workgroup holds at a time
+    const int sub = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    double best_d = -INFINITY;
+    int best_i = INT_MAX;
+    for (int64_t row0 = (int64_t)blockIdx.x * GROUPS; row0 < N; row0 += (int64_t)gridDim.x * GROUPS) {
+        const int64_t i = row0 + grp;
+        const bool valid = i < N;                  // the shuffles below need whole waves in the loop
+        const double* __restrict__ prow = a.P + (size_t)(valid ? i : 0) * mp;
+        const int je = valid ? j : 0, jle = valid ? jl : 0;
+        d2 acc = {0.0, 0.0};
+        int c = 2 * sub;
+#pragma unroll 8
+        for (; c < jle; c += 2 * LPR) {
+            const d2 v = *reinterpret_cast<const d2*>(prow + c);
+            const d2 l = *reinterpret_cast<const d2*>(Lrow + c);
+            acc.x = fma(v.x, l.x, acc.x);
+            acc.y = fma(v.y, l.y, acc.y);
+        }
+#pragma unroll 4
+        for (; c < je; c += 2 * LPR) {            // j > SEL_LDS_COLS: the pivot row's tail from global memory
+            const d2 v = *reinterpret_cast<const d2*>(prow + c);
+            d2 l = *reinterpret_cast<const d2*>(prow_p + c);
+            if (c + 1 >= j) l.y = 0.0;             // column j of row p is being written by its owner
+            acc.x = fma(v.x, l.x, acc.x);
+            acc.y = fma(v.y, l.y, acc.y);
+        }
+        double s = acc.x + acc.y;
+#pragma unroll
+        for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (valid) {
+            const double* __restrict__ xi = a.Xs + (size_t)i * stride;
+            double h = 0.0;
+            for (int k = 0; k < stride; k += 2) {
+                const d2 x = *reinterpret_cast<const d2*>(xi + k);
+                const double u = x.x - xp[k], w = x.y - xp[k + 1];
+                h = fma(u, u, h);
+                h = fma(w, w, h);
+            }
+            h *= 0.5;
+            double kv;
+            switch (a.ktype) {
+                case KT_RBF: kv = kernel_tab<KT_RBF>(h, a.lnc, T); break;
+                case KT_MATERN12: kv = kernel_tab<KT_MATERN12>(h, a.lnc, T); break;
+                case KT_MATERN32: kv = kernel_tab<KT_MATERN32>(h, a.lnc, T); break;
+                default: kv = kernel_tab<KT_MATERN52>(h, a.lnc, T); break;
+            }
+            const double v = (kv - s) / rs;
+            const double dn = a.d[i] - v * v;
+            const bool mine = (int)i == p;
+            if (sub == 0) {
+                a.P[(size_t)i * mp + j] = v;
+                a.d[i] = dn;
+                if (mine) a.alive[i] = 0;
+            }
+            if (!mine && a.alive[i] && sel_better(dn, (int)i, best_d, best_i)) { best_d = dn; best_i = (int)i; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(best_d, o);
+        const int oi = __shfl_xor(best_i, o);
+        if (sel_better(od, oi, best_d, best_i)) { best_d = od; best_i = oi; }
+    }
+    if (threadIdx.x % 64 == 0) { wd[threadIdx.x / 64] = best_d; wi[threadIdx.x / 64] = best_i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SEL_NT / 64; ++w)
+            if (sel_better(wd[w], wi[w], best_d, best_i)) { best_d = wd[w]; best_i = wi[w]; }
+        a.part_d[blockIdx.x] = best_d;
+        a.part_i[blockIdx.x] = best_i;
+    }
+}
+
+// Pivot of insertion j + 1 after column j: prescribed (the list), or the maximum of the n_part partials — every
+// comparison is (larger d, then lower index), so the result does not depend on the order of the reduction.
+__global__ __launch_bounds__(SEL_NT) void sel_next(SelArgs a, int j, int n_part) {
+    __shared__ double wd[SEL_NT / 64];
+    __shared__ int wi[SEL_NT / 64];
+    if (*a.fail) return;
+    if (j + 1 < a.n_pre) {
+        if (threadIdx.x == 0) a.pivd[j + 1] = a.d[a.selected[j + 1]];
+        return;
+    }
+    double best_d = -INFINITY;
+    int best_i = INT_MAX;
+    for (int t = threadIdx.x; t < n_part; t += SEL_NT)
+        if (sel_better(a.part_d[t], a.part_i[t], best_d, best_i)) { best_d = a.part_d[t]; best_i = a.part_i[t]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(best_d, o);
+        const int oi = __shfl_xor(best_i, o);
+        if (sel_better(od, oi, best_d, best_i)) { best_d = od; best_i = oi; }
+    }
+    if (threadIdx.x % 64 == 0) { wd[threadIdx.x / 64] = best_d; wi[threadIdx.x / 64] = best_i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < SEL_NT / 64; ++w)
+            if (sel_better(wd[w], wi[w], best_d, best_i)) { best_d = wd[w]; best_i = wi[w]; }
+        a.selected[j + 1] = best_i;          // n_total <= N: a row is still alive whenever a next pivot is asked for
+        a.pivd[j + 1] = best_d;
+    }
+}
+
+int sel_fail(int code, const std::string& msg) {
+    set_last_error(msg.c_str());
+    return code;
+}
+
+#define SELCHK(expr)                                                                                      \
+    do {                                                                                                  \
+        hipError_t e_ = (expr);                                                                           \
+        if (e_ != hipSuccess) return sel_fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// Device buffers of one call; released on every return path.
+struct SelBuffers {
+    std::vector<void*> ptrs;
+    hipStream_t stream = nullptr;
+    ~SelBuffers() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    template <class T> hipError_t alloc(T** p, size_t count) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
+        if (e == hipSuccess) ptrs.push_back(q);
+        *p = static_cast<T*>(q);
+        return e;
+    }
+};
+
+// lanes per pool row at insertion j: a row has j doubles, a lane reads two at a time
+int sel_lanes(int j) { return j <= 32 ? 8 : (j <= 128 ? 16 : 64); }
+
+}  // namespace
+}  // namespace gpt
+
+using namespace gpt;
+
+extern "C" int gpt_select_greedy(int device, const double* X, int64_t N, int D, const double* length_scale, double c, double noise,
+                                 double alpha, int kernel_type, const int64_t* initial, int n_initial, int n_total, int64_t* selected,
+                                 double* selection_variance, double* residual_variance) {
+    const std::string w = "gpt_select_greedy";
+    if (!X || !length_scale || !selected || (n_initial > 0 && !initial) || (n_total > n_initial && !selection_variance))
+        return sel_fail(GPT_E_ARG, w + ": NULL argument");
+    if (D < 1 || D > MAX_DIMS) return sel_fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
+    if (N < 1 || N > INT_MAX) return sel_fail(GPT_E_ARG, w + ": N must be 1 .. 2^31 - 1");
+    if (n_total < 1 || n_initial < 0 || n_initial > n_total)
+        return sel_fail(GPT_E_ARG, w + ": need 0 <= n_initial <= n_total and n_total >= 1");
+    if (n_total > N)
+        return sel_fail(GPT_E_ARG, w + ": cannot select " + std::to_string(n_total) + " points from a pool of " + std::to_string(N));
+    if (kernel_type < GPT_KERNEL_RBF || kernel_type > GPT_KERNEL_MATERN52) return sel_fail(GPT_E_ARG, w + ": unknown kernel_type");
+    if (!(c > 0) || !std::isfinite(c) || !(noise >= 0) || !std::isfinite(noise) || !(alpha >= 0) || !std::isfinite(alpha))
+        return sel_fail(GPT_E_ARG, w + ": need finite constant_value > 0, noise >= 0, alpha >= 0");
+    double inv_ls[MAX_D] = {};
+    for (int k = 0; k < D; ++k) {
+        if (!(length_scale[k] > 0) || !std::isfinite(length_scale[k])) return sel_fail(GPT_E_ARG, w + ": length_scale must be finite and > 0");
+        inv_ls[k] = 1.0 / length_scale[k];
+    }
+    // sizes first: a pool that cannot fit is refused before it is read
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return sel_fail(GPT_E_ARG, w + ": no such HIP device");
+    SELCHK(hipSetDevice(device));
+
+    const int mp = n_total + (n_total & 1);        // rows of P stay 16-byte aligned
+    const int stride = xs_stride(D);
+    size_t mem_free = 0, mem_total = 0;
+    SELCHK(hipMemGetInfo(&mem_free, &mem_total));
+    // everything the call allocates that grows with N: the pool factor, the raw and the scaled pool, d, the alive mask
+    const double factor = 8.0 * (double)N * mp;
+    const double need = factor + (double)N * (8.0 * D + 8.0 * stride + 8.0 + 1.0) + 16.0 * n_total + 65536.0;
+    if (need > SEL_MEMORY_SHARE * (double)mem_free)
+        return sel_fail(GPT_E_ARG, w + ": the call needs " + std::to_string((long long)(need / 1048576.0)) + " MiB of device memory (pool factor 8 N m = " +
+                                       std::to_string((long long)(factor / 1048576.0)) + " MiB), more than " +
+                                       std::to_string((int)(SEL_MEMORY_SHARE * 100)) + " % of the device's free memory (" +
+                                       std::to_string((long long)(mem_free / 1048576)) + " MiB free)");
+
+    // without an initial subset every point starts at the prior variance and the lowest index wins: pivot 0
+    const int n_pre = n_initial > 0 ? n_initial : 1;
+    std::vector<int> sel32(n_total, 0);
+    {
+        std::vector<unsigned char> seen(N, 0);
+        for (int t = 0; t < n_initial; ++t) {
+            if (initial[t] < 0 || initial[t] >= N) return sel_fail(GPT_E_ARG, w + ": initial index out of range at " + std::to_string(t));
+            if (seen[initial[t]]) return sel_fail(GPT_E_ARG, w + ": initial index " + std::to_string(initial[t]) + " is listed twice");
+            seen[initial[t]] = 1;
+            sel32[t] = (int)initial[t];
+        }
+    }
+    for (size_t e = 0; e < (size_t)N * D; ++e)
+        if (!std::isfinite(X[e])) return sel_fail(GPT_E_ARG, w + ": the pool contains NaN or infinity (row " + std::to_string(e / D) + ")");
+    SelBuffers buf;
+    SELCHK(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+    const hipStream_t s = buf.stream;
+    SelArgs a{};
+    double *dX, *dXs, *dP, *dd, *dpivd, *dpart_d, *dinv;
+    unsigned char* dalive;
+    int *dsel, *dpart_i, *dfail;
+    SELCHK(buf.alloc(&dX, (size_t)N * D));
+    SELCHK(buf.alloc(&dinv, (size_t)MAX_D));
+    SELCHK(buf.alloc(&dXs, (size_t)N * stride));
+    SELCHK(buf.alloc(&dP, (size_t)N * mp));
+    SELCHK(buf.alloc(&dd, (size_t)N));
+    SELCHK(buf.alloc(&dalive, (size_t)N));
+    SELCHK(buf.alloc(&dsel, (size_t)n_total));
+    SELCHK(buf.alloc(&dpivd, (size_t)n_total));
+    SELCHK(buf.alloc(&dpart_d, (size_t)SEL_MAX_WG));
+    SELCHK(buf.alloc(&dpart_i, (size_t)SEL_MAX_WG));
+    SELCHK(buf.alloc(&dfail, 1));
+    SELCHK(hipMemcpyAsync(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice, s));
+    SELCHK(hipMemcpyAsync(dinv, inv_ls, sizeof(inv_ls), hipMemcpyHostToDevice, s));
+    SELCHK(hipMemcpyAsync(dsel, sel32.data(), (size_t)n_total * sizeof(int), hipMemcpyHostToDevice, s));
+    SELCHK(hipMemsetAsync(dP, 0, (size_t)N * mp * 8, s));
+    SELCHK(hipMemsetAsync(dfail, 0, sizeof(int), s));
+    a.Xs = dXs; a.P = dP; a.d = dd; a.alive = dalive; a.selected = dsel; a.pivd = dpivd; a.part_d = dpart_d; a.part_i = dpart_i;
+    a.fail = dfail; a.N = (int)N; a.stride = stride; a.mp = mp; a.n_pre = n_pre; a.ktype = kernel_type;
+    a.lnc = std::log(c); a.base_var = c + noise; a.alpha = alpha;
+
+    const int64_t nxs = N * stride;
+    hipLaunchKernelGGL(sel_scale, dim3((unsigned)((nxs + SEL_NT - 1) / SEL_NT)), dim3(SEL_NT), 0, s, dX, dinv, dXs, (int)N, D, stride);
+    hipLaunchKernelGGL(sel_init, dim3((unsigned)((N + SEL_NT - 1) / SEL_NT)), dim3(SEL_NT), 0, s, a);
+    // the whole schedule, enqueued without a host round trip
+    for (int j = 0; j < n_total; ++j) {
+        const int lpr = sel_lanes(j), groups = SEL_NT / lpr;
+        const int64_t want = (N + groups - 1) / groups;
+        const int G = (int)(want < SEL_MAX_WG ? want : SEL_MAX_WG);
+        if (lpr == 8) hipLaunchKernelGGL(sel_column<8>, dim3(G), dim3(SEL_NT), 0, s, a, j);
+        else if (lpr == 16) hipLaunchKernelGGL(sel_column<16>, dim3(G), dim3(SEL_NT), 0, s, a, j);
+        else hipLaunchKernelGGL(sel_column<64>, dim3(G), dim3(SEL_NT), 0, s, a, j);
+        if (j + 1 < n_total) hipLaunchKernelGGL(sel_next, dim3(1), dim3(SEL_NT), 0, s, a, j, G);
+    }
+    SELCHK(hipGetLastError());
+    int failed = 0;
+    std::vector<double> pivd(n_total);
+    SELCHK(hipMemcpyAsync(&failed, dfail, sizeof(int), hipMemcpyDeviceToHost, s));
+    SELCHK(hipMemcpyAsync(sel32.data(), dsel, (size_t)n_total * sizeof(int), hipMemcpyDeviceToHost, s));
+    SELCHK(hipMemcpyAsync(pivd.data(), dpivd, (size_t)n_total * 8, hipMemcpyDeviceToHost, s));
+    SELCHK(hipStreamSynchronize(s));
+    if (failed)
+        return sel_fail(GPT_E_NOT_PD, w + ": non-positive pivot (residual variance + alpha <= 0) at insertion " + std::to_string(failed - 1) +
+                                          ": the selected points' kernel matrix is not positive definite");
+    if (residual_variance) {
+        SELCHK(hipMemcpyAsync(residual_variance, dd, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+        SELCHK(hipStreamSynchronize(s));
+    }
+    for (int t = 0; t < n_total; ++t) selected[t] = sel32[t];
+    for (int t = n_initial; t < n_total; ++t) selection_variance[t - n_initial] = pivd[t];
+    return GPT_OK;
+}

@@ -183,6 +183,27 @@ int gpt_svgp_surface_predict(int device, const double* Z, const double* m, const
                              const double* raw_outputscale, int n_inducing, int D, int T, const double* Xq, int64_t M,
                              double* mean, double* var, double* J);
 
+/* (new) Greedy active-learning subset selection — replaces the selection loop of the reference's large-input regressor
+ * (policy_transportation/models/gaussian_process_al.py:26-57: start from an initial subset, then repeatedly add the pool
+ * point whose posterior standard deviation is largest and refit) for FIXED hyper-parameters, where that loop is a pivoted
+ * Cholesky factorisation of the pool's kernel matrix with the diagonal pivot rule.  fp64, on `device`, host memory.
+ *   X (N,D) pool, D 1..15; length_scale (D); c constant_value; noise the WhiteKernel level; alpha the jitter;
+ *   kernel_type GPT_KERNEL_*; initial (n_initial distinct pool indices, may be NULL when n_initial == 0): the first pivots,
+ *   prescribed in this order; n_total: points to select in all (n_initial <= n_total <= N);
+ *   selected (n_total): pool indices in insertion order (the initial ones first); selection_variance (n_total - n_initial):
+ *   the posterior variance of each chosen point when it was chosen, in sklearn's convention (kernel diagonal with the white
+ *   noise, minus |L^-1 k*|^2: sklearn/gaussian_process/_gpr.py:472-494), i.e. the square of the std the reference takes
+ *   its argmax over; residual_variance (N, may be NULL): the same variance of every pool point after the last insertion.
+ * Ties go to the lowest pool index (numpy.argmax over the reference's order-preserving pool).  The whole schedule is
+ * enqueued without a host round trip; the result is bit-reproducible.  One insertion streams the pool factor (N x j
+ * doubles), so a call reads about 4 N n_total^2 bytes of device memory.
+ * GPT_E_NOT_PD: a pivot's variance + alpha was not positive (outputs untouched).  GPT_E_ARG: sizes outside the limits
+ * above, a repeated or out-of-range initial index, NaN / infinity in the pool, or device buffers (the pool factor, 8 N n_total
+ * bytes, plus the pool, its scaled copy and the per-point state) above 80 % of the device's free memory at the call. */
+int gpt_select_greedy(int device, const double* X, int64_t N, int D, const double* length_scale, double c, double noise,
+                      double alpha, int kernel_type, const int64_t* initial, int n_initial, int n_total, int64_t* selected,
+                      double* selection_variance, double* residual_variance);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */
