@@ -57,6 +57,8 @@ SIGNATURES = {
     "gpt_debug_var_plan": (C.c_int, [_i64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(C.c_int),
                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gpt_debug_fit_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
+    "gpt_debug_dgemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64, _dp, _i64, _dp, _i64,
+                                  C.c_int, C.POINTER(C.c_int)]),
     "gpt_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "gpt_fit_timings": (C.c_int, [_vp, _dp, C.c_int]),
     "gpt_set_profiling": (C.c_int, [_vp, C.c_int]),
@@ -198,6 +200,25 @@ def debug_fit_plan(n_padded, form=-1, panel=-1, streams=-1):
     check(lib.gpt_debug_fit_plan(n_padded, form, panel, streams, counts, ops.ctypes.data_as(C.POINTER(_i64))))
     return {"arena": counts[1], "form": counts[2], "n_events": counts[3], "allocated": counts[4], "side_eighths": counts[5],
             "ops": ops[:counts[0], :17]}
+
+
+def debug_dgemm(A, B, out, M, N, K, alpha=1.0, at=False, bt=False, lower_only=False, device=0):
+    """One call of the library's fp64 GEMM (gpt_debug_dgemm; tests only): out[:M, :N] = alpha op(A) op(B) in place, where A,
+    B and out are C-contiguous float64 2-D arrays whose row length is the leading dimension (the operands sit in their
+    first rows and columns: A (M, K), or (K, M) with at; B (K, N), or (N, K) with bt).  Returns the tile edge the launcher
+    chose (32, 64 or 128)."""
+    rows = {"A": K if at else M, "B": N if bt else K, "out": M}
+    for name, a in (("A", A), ("B", B), ("out", out)):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.ndim == 2 and a.flags.c_contiguous):
+            raise ValueError(f"debug_dgemm: {name} must be a C-contiguous float64 2-D array")
+        if a.shape[0] < rows[name]:
+            raise ValueError(f"debug_dgemm: {name} has {a.shape[0]} rows, the product uses {rows[name]}")
+    if not out.flags.writeable:
+        raise ValueError("debug_dgemm: out is read-only")
+    edge = C.c_int(0)
+    check(load().gpt_debug_dgemm(device, int(at), int(bt), M, N, K, float(alpha), dptr(A), A.shape[1], dptr(B), B.shape[1], dptr(out),
+                                 out.shape[1], int(lower_only), C.byref(edge)), "gpt_debug_dgemm")
+    return edge.value
 
 
 SVGP_PARAMS = ("Z", "m", "C", "raw_ls", "raw_os", "raw_noise")

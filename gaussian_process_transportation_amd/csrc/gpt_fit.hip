@@ -9,7 +9,10 @@
 #include "gpt_common.h"
 #include "gpt_exp.h"
 #include "gpt_fit_plan.h"
+#include "../../include/gpt_hip.h"
+#include <cstdint>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -815,8 +818,9 @@ static int gemm_tile32_threshold() {
     return thr;
 }
 
-template <bool BT, bool AT = false>
-static void launch_gemm(hipStream_t s, const GemmArgs& g) {
+// Tile edge of a product (32, 64 or 128), by its number of 128-tiles: the one rule behind launch_gemm and what
+// gpt_debug_dgemm reports.
+static int gemm_tile_edge(const GemmArgs& g) {
     const int Mmax = g.nbatch == 1 ? g.M_last : (g.M > g.M_last ? g.M : g.M_last);
     double tiles = (double)g.nbatch * ((Mmax + 127) / 128) * ((g.N + 127) / 128);
     if (g.lower_only) tiles *= 0.5;
@@ -824,9 +828,17 @@ static void launch_gemm(hipStream_t s, const GemmArgs& g) {
     // fill the chip: the N = 2500 inverse went 0.23 -> 0.32 ms and its K^-1 = W^T W 149 -> 209 us.  Few tiles, whatever their depth,
     // want the small tile: profiles/r04_fit_summary.txt)
     const double thr32 = (double)gemm_tile32_threshold();
-    if (4.0 * tiles < thr32 && gemm_body() == 0) launch_gemm_ts<BT, AT, 32>(s, g);
-    else if (tiles < gemm_tile_threshold()) launch_gemm_ts<BT, AT, 64>(s, g);
-    else launch_gemm_ts<BT, AT, 128>(s, g);
+    if (4.0 * tiles < thr32 && gemm_body() == 0) return 32;
+    return tiles < gemm_tile_threshold() ? 64 : 128;
+}
+
+template <bool BT, bool AT = false>
+static void launch_gemm(hipStream_t s, const GemmArgs& g) {
+    switch (gemm_tile_edge(g)) {
+        case 32: launch_gemm_ts<BT, AT, 32>(s, g); break;
+        case 64: launch_gemm_ts<BT, AT, 64>(s, g); break;
+        default: launch_gemm_ts<BT, AT, 128>(s, g); break;
+    }
 }
 
 // =====================================================================================
@@ -931,12 +943,17 @@ static void trinv_levels(hipStream_t s, const double* L, double* W, int NP, int 
 }
 
 // Thin entry to launch_gemm for the other units (gpt_common.h).
-void launch_dgemm(hipStream_t s, bool at, bool bt, int M, int N, int K, double alpha, const double* A, long lda, const double* B,
-                  long ldb, double* C, long ldc, bool lower_only) {
+static GemmArgs dgemm_args(int M, int N, int K, double alpha, const double* A, long lda, const double* B, long ldb, double* C, long ldc,
+                           bool lower_only) {
     GemmArgs g{};
     g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.C = C; g.ldc = ldc;
     g.M = g.M_last = M; g.N = N; g.K = g.K_last = K; g.nbatch = 1;
     g.alpha = alpha; g.beta = 0.0; g.lower_only = lower_only ? 1 : 0;
+    return g;
+}
+void launch_dgemm(hipStream_t s, bool at, bool bt, int M, int N, int K, double alpha, const double* A, long lda, const double* B,
+                  long ldb, double* C, long ldc, bool lower_only) {
+    const GemmArgs g = dgemm_args(M, N, K, alpha, A, lda, B, ldb, C, ldc, lower_only);
     if (bt) launch_gemm<true>(s, g);
     else if (at) launch_gemm<false, true>(s, g);
     else launch_gemm<false>(s, g);
@@ -1444,3 +1461,46 @@ void launch_logdet(hipStream_t s, const double* K, int N, int NP, double* out) {
 }
 
 }  // namespace gpt
+
+// Test hook (include/gpt_hip.h): one launch_dgemm on host operands, and the tile edge launch_gemm chose for it.
+extern "C" int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, double alpha, const double* A, int64_t lda,
+                               const double* B, int64_t ldb, double* C, int64_t ldc, int lower_only, int* tile_edge) {
+    using namespace gpt;
+    auto fail = [](int code, const std::string& msg) { set_last_error(msg.c_str()); return code; };
+    const std::string w = "gpt_debug_dgemm";
+    if (!A || !B || !C || !tile_edge) return fail(GPT_E_ARG, w + ": NULL argument");
+    if (M < 64 || N < 64 || K < 64 || M % 64 || N % 64 || K % 64 || M > (1 << 20) || N > (1 << 20) || K > (1 << 20))
+        return fail(GPT_E_ARG, w + ": M, N, K must be multiples of 64 (64 .. 2^20)");
+    if (at && bt) return fail(GPT_E_ARG, w + ": at and bt together are not supported");
+    if (lower_only && M != N) return fail(GPT_E_ARG, w + ": lower_only needs M == N");
+    // stored shapes: A (M x K), or (K x M) with at; B (K x N), or (N x K) with bt
+    const int64_t a_rows = at ? K : M, a_cols = at ? M : K, b_rows = bt ? N : K, b_cols = bt ? K : N;
+    if (lda < a_cols || ldb < b_cols || ldc < N || lda % 2 || ldb % 2 || ldc % 2 || lda > (1 << 26) || ldb > (1 << 26) || ldc > (1 << 26))
+        return fail(GPT_E_ARG, w + ": a leading dimension is smaller than its row, odd (rows are 16-byte aligned) or above 2^26");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
+    const size_t na = (size_t)a_rows * lda, nb = (size_t)b_rows * ldb, nc = (size_t)M * ldc;
+    double* dev[3] = {nullptr, nullptr, nullptr};
+    hipStream_t s = nullptr;
+    auto run = [&]() -> hipError_t {
+        hipError_t e;
+        if ((e = hipSetDevice(device)) != hipSuccess) return e;
+        if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess) return e;
+        const size_t n[3] = {na, nb, nc};
+        for (int i = 0; i < 3; ++i)
+            if ((e = hipMalloc(reinterpret_cast<void**>(&dev[i]), n[i] * sizeof(double))) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dev[0], A, na * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dev[1], B, nb * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dev[2], C, nc * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+        *tile_edge = gemm_tile_edge(dgemm_args(M, N, K, alpha, dev[0], lda, dev[1], ldb, dev[2], ldc, lower_only != 0));
+        launch_dgemm(s, at != 0, bt != 0, M, N, K, alpha, dev[0], lda, dev[1], ldb, dev[2], ldc, lower_only != 0);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(C, dev[2], nc * sizeof(double), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+        return hipStreamSynchronize(s);
+    };
+    const hipError_t e = run();
+    if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+    for (double* p : dev) if (p) (void)hipFree(p);
+    if (e != hipSuccess) return fail(GPT_E_HIP, w + ": " + hipGetErrorString(e));
+    return GPT_OK;
+}

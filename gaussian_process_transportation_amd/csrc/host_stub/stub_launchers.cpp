@@ -103,7 +103,8 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
 
 }  // namespace gpt
 
-// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip) and the subset selection (gpt_select.hip) are device code end to end and are not part of
+// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip), the subset selection (gpt_select.hip) and the GEMM's
+// test hook (gpt_fit.hip) are device code end to end and are not part of
 // this build; their entry points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this
 // library too.
 #include "../../../include/gpt_hip.h"
@@ -137,5 +138,10 @@ extern "C" int gpt_svgp_surface_predict(int, const double*, const double*, const
 extern "C" int gpt_select_greedy(int, const double*, int64_t, int, const double*, double, double, double, int, const int64_t*, int, int,
                                  int64_t*, double*, double*) {
     gpt::set_last_error("gpt_select_greedy: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
+                               int*) {
+    gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
     return GPT_E_HIP;
 }

@@ -317,6 +317,17 @@ int gpt_debug_var_plan(int64_t n_columns, int n_iblocks, int n_tasks, int n_work
  * -1 = none; FitOpKind and the streams in gpt_fit_plan.h). */
 int gpt_debug_fit_plan(int n_padded, int form, int panel, int streams, int64_t* counts, int64_t* ops);
 
+/* Test hook (needs a GPU): one call of the library's fp64 MFMA GEMM (k_gemm behind launch_dgemm, csrc/gpt_common.h) on host
+ * operands.  C (M x N, ldc) = alpha op(A) op(B): at -> op(A) = A^T with A stored (K x M, lda); bt -> op(B) = B^T with B stored
+ * (N x K, ldb); not both.  lower_only (M == N): only the block lower triangle of C is computed (tiles above the diagonal and
+ * the upper wave quadrants of diagonal tiles are not written).  The WHOLE image of C (M x ldc doubles) goes to the device and
+ * comes back, so that a caller can pre-fill it and look for stray writes; A and B are read as (rows x ld) images too.
+ * tile_edge receives the tile edge the launcher chose for this product (32, 64 or 128).  GPT_E_ARG for what launch_dgemm's
+ * contract excludes: M, N, K not multiples of 64, at && bt, lower_only with M != N, a leading dimension smaller than its row,
+ * odd or above 2^26. */
+int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, double alpha, const double* A, int64_t lda,
+                    const double* B, int64_t ldb, double* C, int64_t ldc, int lower_only, int* tile_edge);
+
 #ifdef __cplusplus
 }
 #endif

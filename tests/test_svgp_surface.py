@@ -19,13 +19,13 @@ CLOUDS = ["distribution", "dustbin_cover", "pan", "white_towelholder", "wood_pla
 NEW_SYMBOLS = ["gpt_svgp_surface_train", "gpt_svgp_surface_elbo_grad", "gpt_svgp_surface_predict"]
 
 
-def _problem(Zn, T, D, N, seed=0):
-    """Smooth multi-output data on [0,1]^D, inducing points drawn from it, a random lower-triangular C, random m and
-    distinct raw length-scales per task."""
+def _problem(Zn, T, D, N, seed=0, distinct=False):
+    """Smooth multi-output data on [0,1]^D, inducing points drawn from it (distinct: without repeats), a random
+    lower-triangular C, random m and distinct raw length-scales per task."""
     rng = np.random.default_rng(seed)
     X = rng.uniform(0, 1, (N, D))
     Y = np.stack([0.3 * np.sin(3 * X @ rng.standard_normal(D) / np.sqrt(D) + t) for t in range(T)], 1)
-    p = ss.init_params(X, Y, rng.choice(N, Zn))
+    p = ss.init_params(X, Y, rng.choice(N, Zn, replace=not distinct))
     p["C"] = np.tril(0.05 * rng.standard_normal((T, Zn, Zn)), -1) + np.eye(Zn) * rng.uniform(0.5, 1.0, (T, 1, Zn))
     p["m"] = 0.1 * rng.standard_normal((T, Zn))
     p["raw_ls"] = rng.uniform(-1.5, -0.5, (T, D)) + np.log(D) / 2
@@ -141,6 +141,235 @@ def test_elbo_grad_matches_autograd(case):
     for k in ss.PARAM_NAMES:
         ref = np.tril(gr[k]) if k == "C" else gr[k]
         assert relmax(gg[k], ref) <= 1e-10, k
+
+
+def _loss_explicit_inverse(tp, Xb, Yb, num_data):
+    """ss.loss written the way the device computes it: W = L^-1 formed explicitly, A = W k(Z, X_b), U = C^T A,
+    v = c + eps + |U_k|^2 - |A_k|^2, tr S = |C|_F^2 (torch fp64 on the CPU).  A second correct fp64 formulation: its
+    disagreement with the restatement is the size of error that conditioning alone explains."""
+    import torch
+    import torch.nn.functional as F
+    Z, m, C = tp["Z"], tp["m"], tp["C"]
+    Zn, T, b = Z.shape[0], m.shape[0], Xb.shape[0]
+    ls, c = F.softplus(tp["raw_ls"]), F.softplus(tp["raw_os"])
+    noise = (ss.NOISE_FLOOR + F.softplus(tp["raw_noise"][:T])) + (ss.NOISE_FLOOR + F.softplus(tp["raw_noise"][T]))
+    eye = torch.eye(Zn, dtype=Z.dtype)
+    total = Z.new_zeros(())
+    for t in range(T):
+        L = torch.linalg.cholesky(c[t] * ss.rbf(Z, Z, ls[t]) + EPS * eye)
+        W = torch.linalg.solve_triangular(L, eye, upper=False)
+        A = W @ (c[t] * ss.rbf(Z, Xb, ls[t]))
+        Ct = torch.tril(C[t])
+        U = Ct.T @ A
+        v = c[t] + EPS + (U * U).sum(0) - (A * A).sum(0)
+        lik = -0.5 * torch.log(2 * np.pi * noise[t]) - ((Yb[:, t] - A.T @ m[t]) ** 2 + v) / (2 * noise[t])
+        kl = 0.5 * ((Ct * Ct).sum() + m[t] @ m[t] - Zn - torch.log(torch.diagonal(Ct) ** 2).sum())
+        total = total - lik.sum() / b + kl / num_data
+    return total
+
+
+def _loss_and_grad_explicit_inverse(p, Xb, Yb, num_data):
+    import torch
+    tp = ss.to_torch(p, requires_grad=True)
+    val = _loss_explicit_inverse(tp, torch.as_tensor(np.asarray(Xb, np.float64)), torch.as_tensor(np.asarray(Yb, np.float64)), num_data)
+    val.backward()
+    return float(val.detach()), {k: tp[k].grad.numpy().copy() for k in ss.PARAM_NAMES}
+
+
+# (Z, T, D, b): every boundary of the padded sizes NP = round_up(Z, 512) and BP = round_up(b, 64) and of the documented
+# limits Z <= 4096, b <= 1024, T <= 32, D <= 15.  From NP = 2048 the NP x NP products run at tile edge 64 (256 tiles), among
+# them the general A^T B ones (U = C^T A needs BP = 1024 as well: 16 x 8 x 2 tiles).
+LIMIT_CASES = [(1, 2, 1, 1), (2, 32, 2, 63), (512, 1, 3, 65), (513, 2, 15, 1000), (1025, 1, 2, 1024), (1600, 2, 3, 200),
+               (2200, 1, 3, 1024), (4096, 1, 2, 100), (64, 4, 15, 1024)]
+FLOOR, SLACK, CAP = 1e-10, 10.0, 1e-8
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", LIMIT_CASES, ids=lambda c: "Z%d_T%d_D%d_b%d" % c)
+def test_elbo_grad_matches_autograd_at_the_size_limits(case):
+    """Loss and gradients against the restatement where K(Z,Z) + 1e-4 I is no longer well conditioned.  The bound per
+    quantity is max(1e-10, 10 d): d is the disagreement, on the CPU, of the explicit-inverse formulation with the restatement
+    (two correct fp64 formulations of one objective); 10x because the device sums in another order again and inverts in
+    blocks.  10 d <= 1e-8 is asserted, so conditioning never loosens a bound by more than two digits (inducing points are
+    drawn without repeats to keep it so)."""
+    from gaussian_process_transportation_amd import _lib
+    Zn, T, D, b = case
+    X, Y, p = _problem(Zn, T, D, max(2 * b, Zn + 50), seed=Zn + D, distinct=True)
+    lr, gr = ss.loss_and_grad(p, X[:b], Y[:b], len(X))
+    li, gi = _loss_and_grad_explicit_inverse(p, X[:b], Y[:b], len(X))
+    lg, gg = _lib.svgp_surface_elbo_grad(X[:b], Y[:b], p, len(X))
+    d = {"loss": abs(li - lr) / abs(lr), **{k: relmax(gi[k], gr[k]) for k in ss.PARAM_NAMES}}
+    err = {"loss": abs(lg - lr) / abs(lr), **{k: relmax(gg[k], np.tril(gr[k]) if k == "C" else gr[k]) for k in ss.PARAM_NAMES}}
+    print(f"{case}: " + ", ".join(f"{k} d {d[k]:.1e} gpu {err[k]:.1e}" for k in d))
+    for k in d:
+        assert SLACK * d[k] <= CAP, (k, d[k])
+    for k in d:
+        assert err[k] <= max(FLOOR, SLACK * d[k]), (k, err[k], d[k])
+
+
+def _uneven_schedule():
+    """T = 2, Z = 300; six batches, the largest first (every later step runs in a workspace wider than its batch), the
+    schedule drawn with replacement (rows repeat inside a batch)."""
+    X, Y, p = _problem(300, 2, 2, 1500, seed=11, distinct=True)
+    sizes = [1024, 7, 64, 65, 1, 130]
+    idx = np.random.default_rng(4).integers(0, 1500, sum(sizes))
+    assert len(np.unique(idx[:1024])) < 1024 and len(np.unique(idx[1024:1031])) <= 7
+    return X, Y, p, idx, np.concatenate([[0], np.cumsum(sizes)])
+
+
+UNEVEN_LR = 1e-4
+
+
+@pytest.mark.gpu
+def test_uneven_batches_match_torch_adam(monkeypatch):
+    """Six steps on batches of 1024, 7, 64, 65, 1 and 130 rows against torch.optim.Adam, to this file's 1e-9.
+    Adam divides each gradient component by its own running magnitude, so a component near zero (d loss / d C_ij of two
+    distant inducing points, 1e-9 against 13 for the largest) turns its rounding error, relative to ITSELF, into a step of
+    lr times that: with inducing points drawn with repeats and lr = 0.01 two correct CPU formulations (the restatement and
+    the explicit-inverse one) already end 7.8e-9 apart in C on this schedule, and with distinct points and lr = 1e-3 still
+    0.65e-10 to 1.3e-10, depending on the machine's BLAS.  The inputs are therefore chosen (distinct inducing points,
+    lr = 1e-4) so that those two agree to 1e-10, a tenth of the bound, with room to spare; that is asserted first.  What
+    this test is for, a stale column of the wider workspace entering a gradient, is an error of the size of the gradient."""
+    from gaussian_process_transportation_amd import _lib
+    X, Y, p, idx, bb = _uneven_schedule()
+    ref, tr_ref = ss.adam_train(p, X, Y, idx, bb, lr=UNEVEN_LR)
+    with monkeypatch.context() as mp:
+        mp.setattr(ss, "loss", _loss_explicit_inverse)
+        alt, tr_alt = ss.adam_train(p, X, Y, idx, bb, lr=UNEVEN_LR)
+    d = {k: relmax(np.tril(alt[k]), np.tril(ref[k])) if k == "C" else relmax(alt[k], ref[k]) for k in ss.PARAM_NAMES}
+    print("CPU formulations: loss trace", f"{relmax(tr_alt, tr_ref):.2e}", {k: f"{v:.1e}" for k, v in d.items()})
+    assert relmax(tr_alt, tr_ref) <= 1e-10 and max(d.values()) <= 1e-10
+    moved = relmax(ref["C"], p["C"])
+    assert moved >= 3e-4, moved             # the steps are 1e5 times the bound: a wrong gradient cannot hide behind the small lr
+    tr = _lib.svgp_surface_train(X, Y, p, idx, bb, lr=UNEVEN_LR)
+    print("loss trace", f"{relmax(tr, tr_ref):.2e}")
+    assert relmax(tr, tr_ref) <= 1e-9
+    for k in ss.PARAM_NAMES:
+        a, b = (np.tril(p[k]), np.tril(ref[k])) if k == "C" else (p[k], ref[k])
+        print(k, f"{relmax(a, b):.2e}")
+        assert relmax(a, b) <= 1e-9, k
+
+
+@pytest.mark.gpu
+def test_uneven_batches_in_a_wide_workspace_equal_batches_sized_by_themselves():
+    """lr = 0 leaves the parameters as they are (p + (-0) x), so the trace of one training call holds the loss of each
+    batch in the workspace sized by the largest one (BP = 1024); gpt_svgp_surface_elbo_grad sizes it by the batch itself.
+    Bit for bit: a column of A, U and the statistics is summed over the inducing points only, in an order that does not
+    depend on the number of columns (same tile edge 32 at NP = 512 whatever BP: at most 32 tiles), and the residual sums run
+    over k < b in the same thread order.  The padding columns must contribute exact zeros."""
+    from gaussian_process_transportation_amd import _lib
+    X, Y, p, idx, bb = _uneven_schedule()
+    q = {k: v.copy() for k, v in p.items()}
+    tr = _lib.svgp_surface_train(X, Y, q, idx, bb, lr=0.0)
+    for k in ss.PARAM_NAMES:
+        a, b = (np.tril(p[k]), np.tril(q[k])) if k == "C" else (p[k], q[k])
+        assert np.array_equal(a, b), k
+    single = []
+    for s in range(len(bb) - 1):
+        rows = idx[bb[s]:bb[s + 1]]
+        single.append(_lib.svgp_surface_elbo_grad(X[rows], Y[rows], p, len(X))[0])
+    print("trace", tr, "single", np.array(single), "difference", tr - np.array(single))
+    assert np.array_equal(tr, np.array(single))
+
+
+def _predict_numpy(p, Xq, explicit_inverse=False):
+    """The variational predictive in plain numpy fp64: a = L^-1 c k(Z, x) by a triangular solve, mean a^T m,
+    var c - |a|^2 + |C^T a|^2, J_d = sum_i beta_i c k(z_i, x) (z_id - x_d) / l_d^2 with beta = L^-T m.
+    explicit_inverse: the same through W = L^-1 formed explicitly (the device's formulation)."""
+    Z, T = p["Z"], p["m"].shape[0]
+    Zn, D = Z.shape
+    mean, var, J = np.empty((len(Xq), T)), np.empty((len(Xq), T)), np.empty((len(Xq), T, D))
+    for t in range(T):
+        ls, c = _softplus(p["raw_ls"][t]), _softplus(p["raw_os"][t])
+        L = np.linalg.cholesky(c * ss_rbf(Z, Z, ls) + EPS * np.eye(Zn))
+        kx = c * ss_rbf(Z, Xq, ls)
+        if explicit_inverse:
+            W = solve_triangular(L, np.eye(Zn), lower=True)
+            a, beta = W @ kx, W.T @ p["m"][t]
+        else:
+            a, beta = solve_triangular(L, kx, lower=True), solve_triangular(L, p["m"][t], lower=True, trans="T")
+        Ct = np.tril(p["C"][t])
+        mean[:, t] = a.T @ p["m"][t]
+        var[:, t] = c - (a * a).sum(0) + ((Ct.T @ a) ** 2).sum(0)
+        f = beta[:, None] * kx
+        for d in range(D):
+            J[:, t, d] = ((Z[:, d][:, None] - Xq[:, d][None, :]) * f).sum(0) / ls[d] ** 2
+    return mean, var, J
+
+
+PREDICT_M = [1, 63, 64, 1023, 1024, 1025, 2500]
+_PREDICT_MODELS = {}
+
+
+def _predict_model(Zn):
+    """(params, Xq (2500, D), reference (mean, var, J), tolerances): T = 3, distinct length-scales, random lower C.
+    The tolerances are 1e-9 (mean and J of the array scale; var, a difference of O(c) terms, absolute against max c_t),
+    widened to 10 d where d, the CPU disagreement of the explicit-inverse formulation with the solve-based one, is above
+    1e-10; 10 d <= 1e-7 is asserted (two digits at the most)."""
+    if Zn not in _PREDICT_MODELS:
+        D = 2 if Zn == 300 else 3
+        X, _, p = _problem(Zn, 3, D, Zn + 50, seed=Zn, distinct=True)
+        assert np.ptp(p["raw_ls"], axis=0).min() > 0
+        Xq = np.random.default_rng(Zn + 1).uniform(-0.05, 1.05, (2500, D))
+        ref = _predict_numpy(p, Xq)
+        inv = _predict_numpy(p, Xq, explicit_inverse=True)
+        cmax = _softplus(p["raw_os"]).max()
+        d = (relmax(inv[0], ref[0]), np.abs(inv[1] - ref[1]).max() / cmax, relmax(inv[2], ref[2]))
+        print(f"Z {Zn}: explicit inverse against solve: mean {d[0]:.1e} var {d[1]:.1e} J {d[2]:.1e}")
+        assert 10 * max(d) <= 1e-7, d
+        _PREDICT_MODELS[Zn] = p, Xq, ref, tuple(max(1e-9, 10 * x) for x in d), cmax
+    return _PREDICT_MODELS[Zn]
+
+
+def _predict_errors(got, ref, cmax):
+    return relmax(got[0], ref[0]), float(np.abs(got[1] - ref[1]).max() / cmax), relmax(got[2], ref[2])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M", PREDICT_M)
+@pytest.mark.parametrize("Zn", [300, 2200])
+def test_predict_chunk_boundaries_match_numpy(Zn, M):
+    """Queries below, at and above the 1024-query chunk, and several chunks plus a tail, T = 3."""
+    from gaussian_process_transportation_amd import _lib
+    p, Xq, ref, tol, cmax = _predict_model(Zn)
+    got = _lib.svgp_surface_predict(p, Xq[:M], var=True, J=True)
+    err = _predict_errors(got, [r[:M] for r in ref], cmax)
+    print(f"Z {Zn} M {M}: mean {err[0]:.2e} var {err[1]:.2e} J {err[2]:.2e} (bounds {tol[0]:.1e} {tol[1]:.1e} {tol[2]:.1e})")
+    for e, bound, what in zip(err, tol, ("mean", "var", "J")):
+        assert e <= bound, what
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Zn", [300, 2200])
+def test_predict_without_var_or_J_returns_the_same_mean(Zn):
+    from gaussian_process_transportation_amd import _lib
+    p, Xq, ref, tol, cmax = _predict_model(Zn)
+    full = _lib.svgp_surface_predict(p, Xq[:1025], var=True, J=True)
+    for var, J in ((False, False), (True, False), (False, True)):
+        got = _lib.svgp_surface_predict(p, Xq[:1025], var=var, J=J)
+        assert np.array_equal(got[0], full[0]), (var, J)
+        assert (got[1] is None) == (not var) and (got[2] is None) == (not J)
+        if var:
+            assert np.array_equal(got[1], full[1])
+        if J:
+            assert np.array_equal(got[2], full[2])
+    # the paths without var / J against the reference too, not only against each other
+    assert relmax(full[0], ref[0][:1025]) <= tol[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Zn", [300, 2200])
+def test_predict_slices_agree_with_the_full_call(Zn):
+    """Xq[a:b] alone against rows a:b of the 2500-query call, for slices that straddle the chunk boundaries 1024 and 2048
+    (the slice runs in a chunk of another width)."""
+    from gaussian_process_transportation_amd import _lib
+    p, Xq, ref, tol, cmax = _predict_model(Zn)
+    full = _lib.svgp_surface_predict(p, Xq, var=True, J=True)
+    for a, b in ((1000, 1100), (2040, 2056), (1023, 1025), (900, 2100)):
+        part = _lib.svgp_surface_predict(p, Xq[a:b], var=True, J=True)
+        err = _predict_errors(part, [f[a:b] for f in full], cmax)
+        print(f"Z {Zn} slice {a}:{b}: mean {err[0]:.2e} var {err[1]:.2e} J {err[2]:.2e}")
+        assert max(err) <= 1e-12, (a, b)
 
 
 @pytest.mark.gpu
