@@ -222,130 +222,90 @@ def debug_dgemm(A, B, out, M, N, K, alpha=1.0, at=False, bt=False, lower_only=Fa
 
 
 SVGP_PARAMS = ("Z", "m", "C", "raw_ls", "raw_os", "raw_noise")
-
-
-def _svgp_params(params, D, T):
-    """Validated C-contiguous float64 copies of the SVGP training parameters (see gpt_svgp_train)."""
-    p = {k: np.ascontiguousarray(params[k], dtype=np.float64).copy() for k in SVGP_PARAMS}
-    Zn = p["Z"].shape[0] if p["Z"].ndim == 2 else -1
-    shapes = {"Z": (Zn, D), "m": (T, Zn), "C": (T, Zn, Zn), "raw_ls": (D,), "raw_os": (T,), "raw_noise": (T + 1,)}
-    for k, shp in shapes.items():
-        if p[k].shape != shp:
-            raise ValueError(f"SVGP parameter {k} has shape {p[k].shape}, expected {shp}")
-    return p, Zn
-
-
-def svgp_train(X, Y, params, idx, batch_begin, lr=0.01, device=0):
-    """Adam on the SVGP's negative ELBO over the schedule (gpt_svgp_train).  `params` (dict of SVGP_PARAMS) is updated in
-    place; returns the per-step loss (n_steps,)."""
-    lib = load()
-    require_gpu()
-    X = as_f64(X, 2, "X")
-    Y = as_f64(Y, 2, "y")
-    (N, D), T = X.shape, Y.shape[1]
-    if Y.shape[0] != N:
-        raise ValueError("X and Y have different numbers of rows")
-    p, Zn = _svgp_params(params, D, T)
-    idx = np.ascontiguousarray(idx, dtype=np.int64)
-    bb = np.ascontiguousarray(batch_begin, dtype=np.int64)
-    n_steps = max(bb.size - 1, 0)
-    trace = np.zeros(max(n_steps, 1))
-    ip = C.POINTER(_i64)
-    check(lib.gpt_svgp_train(int(device), dptr(X), dptr(Y), N, D, T, Zn, dptr(p["Z"]), dptr(p["m"]), dptr(p["C"]), dptr(p["raw_ls"]),
-                             dptr(p["raw_os"]), dptr(p["raw_noise"]), idx.ctypes.data_as(ip), idx.size, bb.ctypes.data_as(ip),
-                             n_steps, float(lr), dptr(trace)), "gpt_svgp_train")
-    for k in SVGP_PARAMS:
-        params[k] = p[k]
-    return trace[:n_steps]
-
-
-def svgp_elbo_grad(Xb, Yb, params, num_data, device=0):
-    """(loss, {name: gradient}) of one minibatch (gpt_svgp_elbo_grad)."""
-    lib = load()
-    require_gpu()
-    Xb = as_f64(Xb, 2, "X")
-    Yb = as_f64(Yb, 2, "y")
-    (b, D), T = Xb.shape, Yb.shape[1]
-    if Yb.shape[0] != b:
-        raise ValueError("X and Y have different numbers of rows")
-    p, Zn = _svgp_params(params, D, T)
-    g = {k: np.zeros_like(p[k]) for k in SVGP_PARAMS}
-    loss = C.c_double()
-    check(lib.gpt_svgp_elbo_grad(int(device), dptr(Xb), dptr(Yb), b, int(num_data), D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
-                                 C.byref(loss), *(dptr(g[k]) for k in SVGP_PARAMS)), "gpt_svgp_elbo_grad")
-    return loss.value, g
-
-
 SURFACE_MAX_INDUCING = 4096     # gpt_svgp_surface_* limits (include/gpt_hip.h)
 SURFACE_MAX_TASKS = 32
 SURFACE_MAX_BATCH = 1024
+# entry-point prefix -> (name in messages, a length-scale vector per task, limits (inducing points, tasks, rows per batch))
+_SVGP_MODELS = {"gpt_svgp": ("SVGP", False, (1024, 32, 1024)),
+                "gpt_svgp_surface": ("surface SVGP", True, (SURFACE_MAX_INDUCING, SURFACE_MAX_TASKS, SURFACE_MAX_BATCH))}
 
 
-def _surface_params(params, D, T):
-    """Validated C-contiguous float64 copies of the surface SVGP's parameters: those of gpt_svgp_train with raw_ls (T,D)."""
+def _svgp_params(params, D, T, who, per_task_ls, limits):
+    """Validated C-contiguous float64 copies of the SVGP training parameters (gpt_svgp_train; per_task_ls: raw_ls (T,D)), within `limits`."""
     p = {k: np.ascontiguousarray(params[k], dtype=np.float64).copy() for k in SVGP_PARAMS}
     Zn = p["Z"].shape[0] if p["Z"].ndim == 2 else -1
-    shapes = {"Z": (Zn, D), "m": (T, Zn), "C": (T, Zn, Zn), "raw_ls": (T, D), "raw_os": (T,), "raw_noise": (T + 1,)}
+    shapes = {"Z": (Zn, D), "m": (T, Zn), "C": (T, Zn, Zn), "raw_ls": (T, D) if per_task_ls else (D,), "raw_os": (T,),
+              "raw_noise": (T + 1,)}
     for k, shp in shapes.items():
         if p[k].shape != shp:
-            raise ValueError(f"surface SVGP parameter {k} has shape {p[k].shape}, expected {shp}")
-    if not 1 <= Zn <= SURFACE_MAX_INDUCING:
-        raise ValueError(f"surface SVGP: inducing points must be 1 .. {SURFACE_MAX_INDUCING}, got {Zn}")
-    if not 1 <= T <= SURFACE_MAX_TASKS:
-        raise ValueError(f"surface SVGP: T (tasks) must be 1 .. {SURFACE_MAX_TASKS}, got {T}")
-    if not 1 <= D <= MAX_D:
-        raise ValueError(f"surface SVGP: D must be 1 .. {MAX_D}, got {D}")
+            raise ValueError(f"{who} parameter {k} has shape {p[k].shape}, expected {shp}")
+    for what, n, most in (("inducing points", Zn, limits[0]), ("T (tasks)", T, limits[1]), ("D", D, MAX_D)):
+        if not 1 <= n <= most:
+            raise ValueError(f"{who}: {what} must be 1 .. {most}, got {n}")
     return p, Zn
 
 
-def svgp_surface_train(X, Y, params, idx, batch_begin, lr=0.01, device=0):
-    """Adam on the surface SVGP's negative ELBO over the schedule (gpt_svgp_surface_train).  `params` (dict of SVGP_PARAMS,
-    raw_ls (T,D)) is updated in place; returns the per-step loss (n_steps,)."""
+def svgp_train(X, Y, params, idx, batch_begin, lr=0.01, device=0, model="gpt_svgp"):
+    """Adam on the SVGP's negative ELBO over the schedule (gpt_svgp_train).  `params` (dict of SVGP_PARAMS) is updated in
+    place; returns the per-step loss (n_steps,).  Every refusal that needs no device comes before the library is loaded."""
+    who, per_task_ls, limits = _SVGP_MODELS[model]
     X = as_f64(X, 2, "X")
     Y = as_f64(Y, 2, "y")
     (N, D), T = X.shape, Y.shape[1]
     if Y.shape[0] != N:
         raise ValueError("X and Y have different numbers of rows")
-    p, Zn = _surface_params(params, D, T)
+    p, Zn = _svgp_params(params, D, T, who, per_task_ls, limits)
     idx = np.ascontiguousarray(idx, dtype=np.int64)
     bb = np.ascontiguousarray(batch_begin, dtype=np.int64)
     n_steps = max(bb.size - 1, 0)
     if n_steps < 1:
-        raise ValueError("surface SVGP: empty schedule (no optimiser step)")
+        raise ValueError(f"{who}: empty schedule (no optimiser step)")
     sizes = np.diff(bb)
-    if sizes.min() < 1 or sizes.max() > SURFACE_MAX_BATCH:
-        raise ValueError(f"surface SVGP: every batch must have 1 .. {SURFACE_MAX_BATCH} rows")
+    if sizes.min() < 1 or sizes.max() > limits[2]:
+        raise ValueError(f"{who}: every batch must have 1 .. {limits[2]} rows")
     if bb[0] < 0 or bb[-1] > idx.size or idx[bb[0]:bb[-1]].min() < 0 or idx[bb[0]:bb[-1]].max() >= N:
-        raise ValueError("surface SVGP: schedule indices must lie in [0, N)")
+        raise ValueError(f"{who}: schedule indices must lie in [0, N)")
     lib = load()
     require_gpu()
     trace = np.zeros(n_steps)
     ip = C.POINTER(_i64)
-    check(lib.gpt_svgp_surface_train(int(device), dptr(X), dptr(Y), N, D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
-                                     idx.ctypes.data_as(ip), idx.size, bb.ctypes.data_as(ip), n_steps, float(lr), dptr(trace)),
-          "gpt_svgp_surface_train")
+    check(getattr(lib, model + "_train")(int(device), dptr(X), dptr(Y), N, D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
+                                         idx.ctypes.data_as(ip), idx.size, bb.ctypes.data_as(ip), n_steps, float(lr), dptr(trace)),
+          model + "_train")
     for k in SVGP_PARAMS:
         params[k] = p[k]
     return trace
 
 
-def svgp_surface_elbo_grad(Xb, Yb, params, num_data, device=0):
-    """(loss, {name: gradient}) of one minibatch of the surface SVGP (gpt_svgp_surface_elbo_grad)."""
+def svgp_elbo_grad(Xb, Yb, params, num_data, device=0, model="gpt_svgp"):
+    """(loss, {name: gradient}) of one minibatch (gpt_svgp_elbo_grad)."""
+    who, per_task_ls, limits = _SVGP_MODELS[model]
     Xb = as_f64(Xb, 2, "X")
     Yb = as_f64(Yb, 2, "y")
     (b, D), T = Xb.shape, Yb.shape[1]
     if Yb.shape[0] != b:
         raise ValueError("X and Y have different numbers of rows")
-    if not 1 <= b <= SURFACE_MAX_BATCH:
-        raise ValueError(f"surface SVGP: batch size must be 1 .. {SURFACE_MAX_BATCH}, got {b}")
-    p, Zn = _surface_params(params, D, T)
+    if not 1 <= b <= limits[2]:
+        raise ValueError(f"{who}: batch size must be 1 .. {limits[2]}, got {b}")
+    p, Zn = _svgp_params(params, D, T, who, per_task_ls, limits)
     lib = load()
     require_gpu()
     g = {k: np.zeros_like(p[k]) for k in SVGP_PARAMS}
     loss = C.c_double()
-    check(lib.gpt_svgp_surface_elbo_grad(int(device), dptr(Xb), dptr(Yb), b, int(num_data), D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
-                                         C.byref(loss), *(dptr(g[k]) for k in SVGP_PARAMS)), "gpt_svgp_surface_elbo_grad")
+    check(getattr(lib, model + "_elbo_grad")(int(device), dptr(Xb), dptr(Yb), b, int(num_data), D, T, Zn, *(dptr(p[k]) for k in SVGP_PARAMS),
+                                             C.byref(loss), *(dptr(g[k]) for k in SVGP_PARAMS)), model + "_elbo_grad")
     return loss.value, g
+
+
+def svgp_surface_train(X, Y, params, idx, batch_begin, lr=0.01, device=0):
+    """Adam on the surface SVGP's negative ELBO over the schedule (gpt_svgp_surface_train).  `params` (dict of SVGP_PARAMS,
+    raw_ls (T,D)) is updated in place; returns the per-step loss (n_steps,)."""
+    return svgp_train(X, Y, params, idx, batch_begin, lr, device, model="gpt_svgp_surface")
+
+
+def svgp_surface_elbo_grad(Xb, Yb, params, num_data, device=0):
+    """(loss, {name: gradient}) of one minibatch of the surface SVGP (gpt_svgp_surface_elbo_grad)."""
+    return svgp_elbo_grad(Xb, Yb, params, num_data, device, model="gpt_svgp_surface")
 
 
 def svgp_surface_predict(params, Xq, var=False, J=False, device=0):
@@ -357,7 +317,7 @@ def svgp_surface_predict(params, Xq, var=False, J=False, device=0):
     T = np.asarray(params["m"]).shape[0]
     if Xq.shape[1] != D:
         raise ValueError(f"queries have {Xq.shape[1]} columns, the model {D}")
-    p, _ = _surface_params(dict(params, raw_noise=np.zeros(T + 1)), D, T)
+    p, _ = _svgp_params(dict(params, raw_noise=np.zeros(T + 1)), D, T, *_SVGP_MODELS["gpt_svgp_surface"])
     M = Xq.shape[0]
     if M < 1:
         raise ValueError("no query points")

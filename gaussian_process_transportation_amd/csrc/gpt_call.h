@@ -1,0 +1,61 @@
+// Host helpers of a one-shot C entry point (internal header): a call without a handle, which validates host arrays, opens a
+// stream, allocates, enqueues its whole schedule, reads back and frees.  Used by gpt_svgp_train.hip, gpt_svgp_surface.hip,
+// gpt_select.hip and gpt_debug_dgemm (gpt_fit.hip); gpt_api.hip keeps its own (the sanitizer build compiles it against
+// host_stub/, which this header is not written for).
+#pragma once
+#include "gpt_common.h"
+#include "../../include/gpt_hip.h"
+
+#include <climits>
+#include <cmath>
+#include <string>
+#include <vector>
+
+namespace gpt {
+
+// Sets the calling thread's gpt_last_error() text; returns the code.
+inline int fail(int code, const std::string& msg) {
+    set_last_error(msg.c_str());
+    return code;
+}
+
+// Returns GPT_E_HIP from the enclosing function if a hipError_t expression fails.
+#define CALLCHK(expr)                                                                                          \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return gpt::fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// Stream and device buffers of one call; synchronised and released on every return path.
+struct CallBuffers {
+    std::vector<void*> ptrs;
+    hipStream_t stream = nullptr;
+    ~CallBuffers() {
+        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+    hipError_t open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking); }
+    template <class T> hipError_t alloc(T** p, size_t count) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
+        if (e == hipSuccess) ptrs.push_back(q);
+        *p = static_cast<T*>(q);
+        return e;
+    }
+};
+
+inline bool all_finite(const double* p, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+
+// Makes `device` the calling thread's device; GPT_E_ARG if there is no such device.
+inline int use_device(const std::string& who, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, who + ": no such HIP device");
+    CALLCHK(hipSetDevice(device));
+    return GPT_OK;
+}
+
+}  // namespace gpt

@@ -6,10 +6,9 @@
 // What is replaced (reference, all CPU/LAPACK): sklearn/_gpr.py:346-364 (kernel_(X), +alpha on
 // the diagonal, cholesky, cho_solve) and models/gaussian_process.py:42-43 (explicit K^-1, here
 // kept as its triangular factor W = L^-1 so that k^T K^-1 k = |W k|^2).
-#include "gpt_common.h"
+#include "gpt_call.h"
 #include "gpt_exp.h"
 #include "gpt_fit_plan.h"
-#include "../../include/gpt_hip.h"
 #include <cstdint>
 #include <cstdlib>
 #include <string>
@@ -1466,7 +1465,6 @@ void launch_logdet(hipStream_t s, const double* K, int N, int NP, double* out) {
 extern "C" int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, double alpha, const double* A, int64_t lda,
                                const double* B, int64_t ldb, double* C, int64_t ldc, int lower_only, int* tile_edge) {
     using namespace gpt;
-    auto fail = [](int code, const std::string& msg) { set_last_error(msg.c_str()); return code; };
     const std::string w = "gpt_debug_dgemm";
     if (!A || !B || !C || !tile_edge) return fail(GPT_E_ARG, w + ": NULL argument");
     if (M < 64 || N < 64 || K < 64 || M % 64 || N % 64 || K % 64 || M > (1 << 20) || N > (1 << 20) || K > (1 << 20))
@@ -1477,30 +1475,22 @@ extern "C" int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, 
     const int64_t a_rows = at ? K : M, a_cols = at ? M : K, b_rows = bt ? N : K, b_cols = bt ? K : N;
     if (lda < a_cols || ldb < b_cols || ldc < N || lda % 2 || ldb % 2 || ldc % 2 || lda > (1 << 26) || ldb > (1 << 26) || ldc > (1 << 26))
         return fail(GPT_E_ARG, w + ": a leading dimension is smaller than its row, odd (rows are 16-byte aligned) or above 2^26");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
+    if (int rc = use_device(w, device)) return rc;
     const size_t na = (size_t)a_rows * lda, nb = (size_t)b_rows * ldb, nc = (size_t)M * ldc;
-    double* dev[3] = {nullptr, nullptr, nullptr};
-    hipStream_t s = nullptr;
-    auto run = [&]() -> hipError_t {
-        hipError_t e;
-        if ((e = hipSetDevice(device)) != hipSuccess) return e;
-        if ((e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) != hipSuccess) return e;
-        const size_t n[3] = {na, nb, nc};
-        for (int i = 0; i < 3; ++i)
-            if ((e = hipMalloc(reinterpret_cast<void**>(&dev[i]), n[i] * sizeof(double))) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(dev[0], A, na * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(dev[1], B, nb * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(dev[2], C, nc * sizeof(double), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-        *tile_edge = gemm_tile_edge(dgemm_args(M, N, K, alpha, dev[0], lda, dev[1], ldb, dev[2], ldc, lower_only != 0));
-        launch_dgemm(s, at != 0, bt != 0, M, N, K, alpha, dev[0], lda, dev[1], ldb, dev[2], ldc, lower_only != 0);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(C, dev[2], nc * sizeof(double), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
-        return hipStreamSynchronize(s);
-    };
-    const hipError_t e = run();
-    if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    for (double* p : dev) if (p) (void)hipFree(p);
-    if (e != hipSuccess) return fail(GPT_E_HIP, w + ": " + hipGetErrorString(e));
+    CallBuffers buf;
+    CALLCHK(buf.open());
+    const hipStream_t s = buf.stream;
+    double *dA, *dB, *dC;
+    CALLCHK(buf.alloc(&dA, na));
+    CALLCHK(buf.alloc(&dB, nb));
+    CALLCHK(buf.alloc(&dC, nc));
+    CALLCHK(hipMemcpyAsync(dA, A, na * sizeof(double), hipMemcpyHostToDevice, s));
+    CALLCHK(hipMemcpyAsync(dB, B, nb * sizeof(double), hipMemcpyHostToDevice, s));
+    CALLCHK(hipMemcpyAsync(dC, C, nc * sizeof(double), hipMemcpyHostToDevice, s));
+    *tile_edge = gemm_tile_edge(dgemm_args(M, N, K, alpha, dA, lda, dB, ldb, dC, ldc, lower_only != 0));
+    launch_dgemm(s, at != 0, bt != 0, M, N, K, alpha, dA, lda, dB, ldb, dC, ldc, lower_only != 0);
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipMemcpyAsync(C, dC, nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }

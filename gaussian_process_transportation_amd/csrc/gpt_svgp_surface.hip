@@ -22,27 +22,15 @@
 // Every GEMM has M, N, K multiples of 64 (k_gemm's tiles): the inducing points are padded to NP (a multiple of 512, the
 // factor's padding), the minibatch to BP (a multiple of 64); padding is zero, or identity on the diagonal of K and W.
 // No floating-point atomics: two runs with the same inputs are bit-identical.  Notation: DESIGN.md "SVGP training".
-#include "gpt_common.h"
-#include "../../include/gpt_hip.h"
-
-#include <climits>
-#include <cmath>
-#include <string>
-#include <vector>
+#include "gpt_svgp_common.h"
 
 using namespace gpt;
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int SF_MAX_Z = 4096, SF_MAX_T = 32, SF_MAX_B = 1024;
-constexpr int64_t SF_MAX_STEPS = 1 << 24;    // the failure code packs (step, task) into one int
+constexpr SvgpLimits SF_LIMITS{4096, 32, 1024};
 constexpr int SF_HDR = 32;                   // per-task header: [raw_os, raw_noise_t, raw_ls (D), pad]; keeps m and C 16-byte aligned
 constexpr int SF_PRED_CHUNK = 1024;          // queries per prediction chunk
-constexpr double JITTER = 1e-4;              // gpytorch's float32 Cholesky jitter (as read)
-constexpr double NOISE_FLOOR = 1e-4;         // GreaterThan(1e-4) on each likelihood noise
-constexpr double BETA1 = 0.9, BETA2 = 0.999, ADAM_EPS = 1e-8;
-constexpr double LOG_2PI = 1.8378770664093453;
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -64,32 +52,10 @@ struct SfArgs {
     double num_data;
 };
 
-__device__ inline double softplus(double x) { return x > 20.0 ? x : log1p(exp(x)); }
-__device__ inline double softplus_grad(double x) { if (x > 20.0) return 1.0; double z = exp(x); return z / (z + 1.0); }
-
-__device__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __device__ inline double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-__device__ inline void adam(double& p, double g, double& a, double& b, double lr, double bc1, double bc2s) {
-    a = a + (1.0 - BETA1) * (g - a);
-    b = b * BETA2 + (1.0 - BETA2) * g * g;
-    p = p + (-(lr / bc1)) * (a / (sqrt(b) / bc2s + ADAM_EPS));
 }
 
 __device__ inline bool failed(const SfArgs& a) { return *a.fail != INT_MAX; }
@@ -397,39 +363,6 @@ __global__ __launch_bounds__(NT) void sf_pred_cols(const double* Aq, const doubl
     if (J) for (int d = 0; d < D; ++d) J[(q * T + t) * D + d] = jd[d];
 }
 
-int fail(int code, const std::string& msg) {
-    set_last_error(msg.c_str());
-    return code;
-}
-
-#define SFCHK(expr)                                                                               \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct SfBuffers {
-    std::vector<void*> ptrs;
-    hipStream_t stream = nullptr;
-    ~SfBuffers() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <class T> hipError_t alloc(T** p, size_t count) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = static_cast<T*>(q);
-        return e;
-    }
-};
-
-bool finite(const double* p, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
 double host_softplus(double x) { return x > 20.0 ? x : std::log1p(std::exp(x)); }
 
 unsigned grid_for(int64_t n) {
@@ -437,51 +370,12 @@ unsigned grid_for(int64_t n) {
     return (unsigned)(g < 4096 ? (g > 0 ? g : 1) : 4096);
 }
 
-struct SfCall {
-    const double *X, *Y;
-    int64_t N, num_data;
-    int D, T, Zn;
-    double *Z, *m, *C, *raw_ls, *raw_os, *raw_noise;       // in / out (out only when apply)
-    const int64_t *idx, *bb;
-    int64_t n_idx, n_steps;
-    double lr;
-    int apply;
-    double* loss_trace;
-    double* grads[6];                                       // gZ, gm, gC, g_raw_ls, g_raw_os, g_raw_noise (apply = 0)
-};
-
-int check_model(const std::string& w, int D, int T, int Zn) {
-    if (D < 1 || D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
-    if (T < 1 || T > SF_MAX_T) return fail(GPT_E_ARG, w + ": T (tasks) must be 1 .. 32, got " + std::to_string(T));
-    if (Zn < 1 || Zn > SF_MAX_Z) return fail(GPT_E_ARG, w + ": inducing points must be 1 .. 4096, got " + std::to_string(Zn));
-    return GPT_OK;
-}
-
-int run(int device, const char* who, const SfCall& c) {
+int run(int device, const char* who, const SvgpCall& c) {
     const std::string w = who;
-    if (!c.X || !c.Y || !c.Z || !c.m || !c.C || !c.raw_ls || !c.raw_os || !c.raw_noise || !c.idx || !c.bb)
-        return fail(GPT_E_ARG, w + ": NULL argument");
-    if (int rc = check_model(w, c.D, c.T, c.Zn)) return rc;
-    if (c.N < 1 || c.N > INT_MAX || c.num_data < 1) return fail(GPT_E_ARG, w + ": N must be >= 1");
-    if (c.n_steps < 1) return fail(GPT_E_ARG, w + ": empty schedule (no optimiser step)");
-    if (c.n_steps > SF_MAX_STEPS) return fail(GPT_E_ARG, w + ": more than 2^24 optimiser steps in one call");
-    if (c.n_idx < 1 || c.bb[0] < 0 || c.bb[c.n_steps] > c.n_idx) return fail(GPT_E_ARG, w + ": batch boundaries outside the index array");
     int bmax = 0;
-    for (int64_t s = 0; s < c.n_steps; ++s) {
-        const int64_t b = c.bb[s + 1] - c.bb[s];
-        if (b < 1 || b > SF_MAX_B) return fail(GPT_E_ARG, w + ": batch " + std::to_string(s) + " has " + std::to_string(b) + " rows (1 .. 1024)");
-        if (b > bmax) bmax = (int)b;
-    }
-    for (int64_t i = c.bb[0]; i < c.bb[c.n_steps]; ++i)
-        if (c.idx[i] < 0 || c.idx[i] >= c.N) return fail(GPT_E_ARG, w + ": schedule index out of range [0, N) at " + std::to_string(i));
-    if (!std::isfinite(c.lr) || c.lr < 0) return fail(GPT_E_ARG, w + ": lr must be finite and >= 0");
+    if (int rc = svgp_validate(w, c, SF_LIMITS, (size_t)c.T * c.D, &bmax)) return rc;
+    if (int rc = use_device(w, device)) return rc;
     const int D = c.D, T = c.T, Zn = c.Zn;
-    if (!finite(c.X, (size_t)c.N * D) || !finite(c.Y, (size_t)c.N * T) || !finite(c.Z, (size_t)Zn * D) || !finite(c.m, (size_t)T * Zn) ||
-        !finite(c.C, (size_t)T * Zn * Zn) || !finite(c.raw_ls, (size_t)T * D) || !finite(c.raw_os, T) || !finite(c.raw_noise, T + 1))
-        return fail(GPT_E_ARG, w + ": non-finite input");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
-    SFCHK(hipSetDevice(device));
 
     const int NP = (int)round_up(Zn, PAD_N), BP = (int)round_up(bmax, 64);
     const int64_t ZZ = (int64_t)Zn * Zn, NN = (int64_t)NP * NP, NB_ = (int64_t)NP * BP;
@@ -498,53 +392,33 @@ int run(int device, const char* who, const SfCall& c) {
         for (int i = 0; i < Zn; ++i)
             for (int j = 0; j <= i; ++j) p[SF_HDR + NP + (int64_t)i * NP + j] = c.C[t * ZZ + (int64_t)i * Zn + j];   // the strict upper triangle is not a parameter
     }
-    const int64_t i0 = c.bb[0], ni = c.bb[c.n_steps] - i0;
-    std::vector<int> idx32(ni);
-    for (int64_t i = 0; i < ni; ++i) idx32[i] = (int)c.idx[i0 + i];
-
-    SfBuffers buf;
-    SFCHK(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+    std::vector<int> idx32;
+    CallBuffers buf;
+    CALLCHK(buf.open());
+    const hipStream_t s = buf.stream;
+    SvgpDevice dev;
+    if (int rc = svgp_upload(buf, c, th, &idx32, &dev)) return rc;
     SfArgs a{};
+    a.X = dev.X; a.Y = dev.Y; a.idx = dev.idx; a.loss = dev.loss; a.fail = dev.fail;
+    a.theta = dev.theta; a.grad = dev.grad; a.m1 = dev.m1; a.m2 = dev.m2;
     a.N = (int)c.N; a.D = D; a.T = T; a.Zn = Zn; a.NP = NP; a.BP = BP; a.num_data = (double)c.num_data;
     a.SH = SH; a.task_stride = task_stride; a.part_stride = 2 + nz;
-    double *dX, *dY;
-    int* didx;
-    SFCHK(buf.alloc(&dX, (size_t)c.N * D));
-    SFCHK(buf.alloc(&dY, (size_t)c.N * T));
-    SFCHK(buf.alloc(&didx, (size_t)ni));
-    SFCHK(buf.alloc(&a.theta, (size_t)n_theta));
-    SFCHK(buf.alloc(&a.grad, (size_t)n_theta));
-    SFCHK(buf.alloc(&a.m1, (size_t)n_theta));
-    SFCHK(buf.alloc(&a.m2, (size_t)n_theta));
-    SFCHK(buf.alloc(&a.part, (size_t)T * a.part_stride));
-    SFCHK(buf.alloc(&a.loss, (size_t)c.n_steps));
-    for (double** p : {&a.K, &a.W, &a.Q, &a.M2}) SFCHK(buf.alloc(p, (size_t)NN));
-    for (double** p : {&a.Kx, &a.A, &a.U, &a.CU, &a.Ab, &a.B}) SFCHK(buf.alloc(p, (size_t)NB_));
-    SFCHK(buf.alloc(&a.scr, factor_scratch_doubles(NP)));
-    SFCHK(buf.alloc(&a.stat, (size_t)3 * BP));
-    SFCHK(buf.alloc(&a.rbuf, (size_t)BP));
-    SFCHK(buf.alloc(&a.klrow, (size_t)NP));
-    SFCHK(buf.alloc(&a.rowpart, (size_t)NP * (1 + D)));
-    SFCHK(buf.alloc(&a.sc, 8));
-    SFCHK(buf.alloc(&a.info, (size_t)T));
-    SFCHK(buf.alloc(&a.fail, 1));
-    const hipStream_t s = buf.stream;
-    const int nofail = INT_MAX;
-    SFCHK(hipMemcpyAsync(dX, c.X, (size_t)c.N * D * 8, hipMemcpyHostToDevice, s));
-    SFCHK(hipMemcpyAsync(dY, c.Y, (size_t)c.N * T * 8, hipMemcpyHostToDevice, s));
-    SFCHK(hipMemcpyAsync(didx, idx32.data(), (size_t)ni * sizeof(int), hipMemcpyHostToDevice, s));
-    SFCHK(hipMemcpyAsync(a.theta, th.data(), (size_t)n_theta * 8, hipMemcpyHostToDevice, s));
-    SFCHK(hipMemsetAsync(a.grad, 0, (size_t)n_theta * 8, s));
-    SFCHK(hipMemsetAsync(a.m1, 0, (size_t)n_theta * 8, s));
-    SFCHK(hipMemsetAsync(a.m2, 0, (size_t)n_theta * 8, s));
-    SFCHK(hipMemsetAsync(a.info, 0, (size_t)T * sizeof(int), s));
-    SFCHK(hipMemcpyAsync(a.fail, &nofail, sizeof(int), hipMemcpyHostToDevice, s));
-    a.X = dX; a.Y = dY; a.idx = didx;
+    CALLCHK(buf.alloc(&a.part, (size_t)T * a.part_stride));
+    for (double** p : {&a.K, &a.W, &a.Q, &a.M2}) CALLCHK(buf.alloc(p, (size_t)NN));
+    for (double** p : {&a.Kx, &a.A, &a.U, &a.CU, &a.Ab, &a.B}) CALLCHK(buf.alloc(p, (size_t)NB_));
+    CALLCHK(buf.alloc(&a.scr, factor_scratch_doubles(NP)));
+    CALLCHK(buf.alloc(&a.stat, (size_t)3 * BP));
+    CALLCHK(buf.alloc(&a.rbuf, (size_t)BP));
+    CALLCHK(buf.alloc(&a.klrow, (size_t)NP));
+    CALLCHK(buf.alloc(&a.rowpart, (size_t)NP * (1 + D)));
+    CALLCHK(buf.alloc(&a.sc, 8));
+    CALLCHK(buf.alloc(&a.info, (size_t)T));
+    CALLCHK(hipMemsetAsync(a.grad, 0, (size_t)n_theta * 8, s));
+    CALLCHK(hipMemsetAsync(a.info, 0, (size_t)T * sizeof(int), s));
 
     for (int64_t st = 0; st < c.n_steps; ++st) {
-        const double k = (double)(st + 1);
-        const double bc1 = 1.0 - std::pow(BETA1, k), bc2s = std::sqrt(1.0 - std::pow(BETA2, k));
-        const int b0 = (int)(c.bb[st] - i0), b = (int)(c.bb[st + 1] - c.bb[st]);
+        const AdamBias bc = adam_bias((double)(st + 1));
+        const int b0 = (int)(c.bb[st] - c.bb[0]), b = (int)(c.bb[st + 1] - c.bb[st]);
         for (int t = 0; t < T; ++t) {
             double* Cp = a.theta + SH + t * task_stride + SF_HDR + NP;
             double* gC = a.grad + SH + t * task_stride + SF_HDR + NP;
@@ -566,25 +440,13 @@ int run(int device, const char* who, const SfCall& c) {
             launch_dgemm(s, true, false, NP, NP, NP, 1.0, a.W, NP, a.M2, NP, a.K, NP, false);         // Kbar = W^T Q W
             hipLaunchKernelGGL(sf_partials, dim3((Zn + 3) / 4), dim3(NT), 0, s, a, t, b0, b);
             hipLaunchKernelGGL(sf_task_final, dim3(1), dim3(NT), 0, s, a, t);
-            if (c.apply) hipLaunchKernelGGL(sf_adam_task, dim3(grid_for(task_stride)), dim3(NT), 0, s, a, t, c.lr, bc1, bc2s);
+            if (c.apply) hipLaunchKernelGGL(sf_adam_task, dim3(grid_for(task_stride)), dim3(NT), 0, s, a, t, c.lr, bc.bc1, bc.bc2s);
         }
-        hipLaunchKernelGGL(sf_shared, dim3(grid_for(nz + 1)), dim3(NT), 0, s, a, (int)st, c.apply, c.lr, bc1, bc2s);
+        hipLaunchKernelGGL(sf_shared, dim3(grid_for(nz + 1)), dim3(NT), 0, s, a, (int)st, c.apply, c.lr, bc.bc1, bc.bc2s);
     }
-    SFCHK(hipGetLastError());
-    int failed_at = INT_MAX;
-    std::vector<double> loss(c.n_steps), out(n_theta);
-    SFCHK(hipMemcpyAsync(&failed_at, a.fail, sizeof(int), hipMemcpyDeviceToHost, s));
-    SFCHK(hipMemcpyAsync(loss.data(), a.loss, (size_t)c.n_steps * 8, hipMemcpyDeviceToHost, s));
-    SFCHK(hipMemcpyAsync(out.data(), c.apply ? a.theta : a.grad, (size_t)n_theta * 8, hipMemcpyDeviceToHost, s));
-    SFCHK(hipStreamSynchronize(s));
-    if (failed_at != INT_MAX)
-        return fail(GPT_E_NOT_PD, w + ": non-positive pivot in chol(c_t k(Z,Z) + eps I) at optimiser step " + std::to_string(failed_at / 64) +
-                                      " (task " + std::to_string(failed_at % 64) + "); parameters left as they were passed");
-    if (c.loss_trace)
-        for (int64_t i = 0; i < c.n_steps; ++i) c.loss_trace[i] = loss[i];
-    double* dst[6] = {c.Z, c.m, c.C, c.raw_ls, c.raw_os, c.raw_noise};
-    if (!c.apply)
-        for (int q = 0; q < 6; ++q) dst[q] = c.grads[q];
+    std::vector<double> out(n_theta);
+    double* dst[6];
+    if (int rc = svgp_read_back(w, s, c, dev, &out, dst)) return rc;
     if (dst[0]) for (int64_t e = 0; e < nz; ++e) dst[0][e] = out[e];
     if (dst[5]) dst[5][T] = out[nz];
     for (int t = 0; t < T; ++t) {
@@ -607,7 +469,7 @@ extern "C" int gpt_svgp_surface_train(int device, const double* X, const double*
                                       double* m, double* C, double* raw_lengthscale, double* raw_outputscale, double* raw_noise,
                                       const int64_t* idx, int64_t n_idx, const int64_t* batch_begin, int64_t n_steps, double lr,
                                       double* loss_trace) {
-    SfCall c{};
+    SvgpCall c{};
     c.X = X; c.Y = Y; c.N = N; c.num_data = N; c.D = D; c.T = T; c.Zn = n_inducing;
     c.Z = Z; c.m = m; c.C = C; c.raw_ls = raw_lengthscale; c.raw_os = raw_outputscale; c.raw_noise = raw_noise;
     c.idx = idx; c.bb = batch_begin; c.n_idx = n_idx; c.n_steps = n_steps; c.lr = lr; c.apply = 1; c.loss_trace = loss_trace;
@@ -619,18 +481,9 @@ extern "C" int gpt_svgp_surface_elbo_grad(int device, const double* Xb, const do
                                           const double* raw_outputscale, const double* raw_noise, double* loss, double* grad_Z,
                                           double* grad_m, double* grad_C, double* grad_raw_lengthscale, double* grad_raw_outputscale,
                                           double* grad_raw_noise) {
-    if (b < 1 || b > SF_MAX_B) return fail(GPT_E_ARG, "gpt_svgp_surface_elbo_grad: batch size must be 1 .. 1024, got " + std::to_string(b));
-    std::vector<int64_t> idx(b);
-    for (int64_t i = 0; i < b; ++i) idx[i] = i;
-    const int64_t bb[2] = {0, b};
-    SfCall c{};
-    c.X = Xb; c.Y = Yb; c.N = b; c.num_data = num_data; c.D = D; c.T = T; c.Zn = n_inducing;
-    c.Z = const_cast<double*>(Z); c.m = const_cast<double*>(m); c.C = const_cast<double*>(C);
-    c.raw_ls = const_cast<double*>(raw_lengthscale); c.raw_os = const_cast<double*>(raw_outputscale); c.raw_noise = const_cast<double*>(raw_noise);
-    c.idx = idx.data(); c.bb = bb; c.n_idx = b; c.n_steps = 1; c.lr = 0.0; c.apply = 0; c.loss_trace = loss;
-    c.grads[0] = grad_Z; c.grads[1] = grad_m; c.grads[2] = grad_C; c.grads[3] = grad_raw_lengthscale; c.grads[4] = grad_raw_outputscale;
-    c.grads[5] = grad_raw_noise;
-    return run(device, "gpt_svgp_surface_elbo_grad", c);
+    const double* params[6] = {Z, m, C, raw_lengthscale, raw_outputscale, raw_noise};
+    double* grads[6] = {grad_Z, grad_m, grad_C, grad_raw_lengthscale, grad_raw_outputscale, grad_raw_noise};
+    return svgp_elbo_grad(run, "gpt_svgp_surface_elbo_grad", SF_LIMITS, device, Xb, Yb, b, num_data, D, T, n_inducing, params, loss, grads);
 }
 
 extern "C" int gpt_svgp_surface_predict(int device, const double* Z, const double* m, const double* C, const double* raw_lengthscale,
@@ -639,42 +492,40 @@ extern "C" int gpt_svgp_surface_predict(int device, const double* Z, const doubl
     const std::string w = "gpt_svgp_surface_predict";
     if (!Z || !m || !C || !raw_lengthscale || !raw_outputscale || !Xq || !mean) return fail(GPT_E_ARG, w + ": NULL argument");
     const int Zn = n_inducing;
-    if (int rc = check_model(w, D, T, Zn)) return rc;
+    if (int rc = svgp_check_model(w, SF_LIMITS, D, T, Zn)) return rc;
     if (M < 1 || M > ((int64_t)1 << 40)) return fail(GPT_E_ARG, w + ": M (queries) must be >= 1");
     const int64_t ZZ = (int64_t)Zn * Zn;
-    if (!finite(Z, (size_t)Zn * D) || !finite(m, (size_t)T * Zn) || !finite(C, (size_t)T * ZZ) || !finite(raw_lengthscale, (size_t)T * D) ||
-        !finite(raw_outputscale, T) || !finite(Xq, (size_t)M * D))
+    if (!all_finite(Z, (size_t)Zn * D) || !all_finite(m, (size_t)T * Zn) || !all_finite(C, (size_t)T * ZZ) ||
+        !all_finite(raw_lengthscale, (size_t)T * D) || !all_finite(raw_outputscale, T) || !all_finite(Xq, (size_t)M * D))
         return fail(GPT_E_ARG, w + ": non-finite input");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
-    SFCHK(hipSetDevice(device));
+    if (int rc = use_device(w, device)) return rc;
     const int NP = (int)round_up(Zn, PAD_N);
     const int MC = (int)(M < SF_PRED_CHUNK ? round_up(M, 64) : SF_PRED_CHUNK);
     const int64_t NN = (int64_t)NP * NP, NM = (int64_t)NP * MC;
 
-    SfBuffers buf;
-    SFCHK(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+    CallBuffers buf;
+    CALLCHK(buf.open());
     const hipStream_t s = buf.stream;
     double *dZ, *dX, *dK, *dW, *dC, *dm, *dbeta, *dKq, *dAq, *dVq, *dscr, *dil, *dmean, *dvar = nullptr, *dJ = nullptr;
     int* dinfo;
-    SFCHK(buf.alloc(&dZ, (size_t)Zn * D));
-    SFCHK(buf.alloc(&dX, (size_t)M * D));
-    SFCHK(buf.alloc(&dK, (size_t)NN));
-    SFCHK(buf.alloc(&dW, (size_t)NN));
-    SFCHK(buf.alloc(&dC, (size_t)NN));
-    SFCHK(buf.alloc(&dm, (size_t)NP));
-    SFCHK(buf.alloc(&dbeta, (size_t)NP));
-    SFCHK(buf.alloc(&dKq, (size_t)NM));
-    SFCHK(buf.alloc(&dAq, (size_t)NM));
-    SFCHK(buf.alloc(&dVq, (size_t)NM));
-    SFCHK(buf.alloc(&dscr, factor_scratch_doubles(NP)));
-    SFCHK(buf.alloc(&dil, (size_t)MAX_D));
-    SFCHK(buf.alloc(&dinfo, 1));
-    SFCHK(buf.alloc(&dmean, (size_t)M * T));
-    if (var) SFCHK(buf.alloc(&dvar, (size_t)M * T));
-    if (J) SFCHK(buf.alloc(&dJ, (size_t)M * T * D));
-    SFCHK(hipMemcpyAsync(dZ, Z, (size_t)Zn * D * 8, hipMemcpyHostToDevice, s));
-    SFCHK(hipMemcpyAsync(dX, Xq, (size_t)M * D * 8, hipMemcpyHostToDevice, s));
+    CALLCHK(buf.alloc(&dZ, (size_t)Zn * D));
+    CALLCHK(buf.alloc(&dX, (size_t)M * D));
+    CALLCHK(buf.alloc(&dK, (size_t)NN));
+    CALLCHK(buf.alloc(&dW, (size_t)NN));
+    CALLCHK(buf.alloc(&dC, (size_t)NN));
+    CALLCHK(buf.alloc(&dm, (size_t)NP));
+    CALLCHK(buf.alloc(&dbeta, (size_t)NP));
+    CALLCHK(buf.alloc(&dKq, (size_t)NM));
+    CALLCHK(buf.alloc(&dAq, (size_t)NM));
+    CALLCHK(buf.alloc(&dVq, (size_t)NM));
+    CALLCHK(buf.alloc(&dscr, factor_scratch_doubles(NP)));
+    CALLCHK(buf.alloc(&dil, (size_t)MAX_D));
+    CALLCHK(buf.alloc(&dinfo, 1));
+    CALLCHK(buf.alloc(&dmean, (size_t)M * T));
+    if (var) CALLCHK(buf.alloc(&dvar, (size_t)M * T));
+    if (J) CALLCHK(buf.alloc(&dJ, (size_t)M * T * D));
+    CALLCHK(hipMemcpyAsync(dZ, Z, (size_t)Zn * D * 8, hipMemcpyHostToDevice, s));
+    CALLCHK(hipMemcpyAsync(dX, Xq, (size_t)M * D * 8, hipMemcpyHostToDevice, s));
 
     std::vector<double> Kh(NN), Ch(NN), mh(NP), il(MAX_D, 0.0);
     for (int t = 0; t < T; ++t) {
@@ -694,16 +545,16 @@ extern "C" int gpt_svgp_surface_predict(int device, const double* Z, const doubl
                 Ch[(int64_t)i * NP + j] = C[t * ZZ + (int64_t)i * Zn + j];
             }
         }
-        SFCHK(hipMemcpyAsync(dK, Kh.data(), (size_t)NN * 8, hipMemcpyHostToDevice, s));
-        SFCHK(hipMemcpyAsync(dC, Ch.data(), (size_t)NN * 8, hipMemcpyHostToDevice, s));
-        SFCHK(hipMemcpyAsync(dm, mh.data(), (size_t)NP * 8, hipMemcpyHostToDevice, s));
-        SFCHK(hipMemcpyAsync(dil, il.data(), (size_t)MAX_D * 8, hipMemcpyHostToDevice, s));
-        SFCHK(hipMemsetAsync(dW, 0, (size_t)NN * 8, s));
-        SFCHK(hipMemsetAsync(dinfo, 0, sizeof(int), s));
+        CALLCHK(hipMemcpyAsync(dK, Kh.data(), (size_t)NN * 8, hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(dC, Ch.data(), (size_t)NN * 8, hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(dm, mh.data(), (size_t)NP * 8, hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(dil, il.data(), (size_t)MAX_D * 8, hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemsetAsync(dW, 0, (size_t)NN * 8, s));
+        CALLCHK(hipMemsetAsync(dinfo, 0, sizeof(int), s));
         launch_factor_inverse(s, dK, dW, NP, dinfo, dscr, nullptr, nullptr);
         int info = 0;
-        SFCHK(hipMemcpyAsync(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
-        SFCHK(hipStreamSynchronize(s));
+        CALLCHK(hipMemcpyAsync(&info, dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        CALLCHK(hipStreamSynchronize(s));
         if (info != 0)
             return fail(GPT_E_NOT_PD, w + ": non-positive pivot " + std::to_string(info) + " in chol(c_t k(Z,Z) + eps I) of task " + std::to_string(t));
         hipLaunchKernelGGL(sf_wtm, dim3((NP + NT - 1) / NT), dim3(NT), 0, s, dW, dm, NP, dbeta);
@@ -714,12 +565,12 @@ extern "C" int gpt_svgp_surface_predict(int device, const double* Z, const doubl
             hipLaunchKernelGGL(sf_pred_cols, dim3((MC + NT - 1) / NT), dim3(NT), 0, s, dAq, dVq, dKq, dm, dbeta, dZ, dX, dil, Zn, D, T, t, MC,
                                q0, M, c, dmean, dvar, dJ);
         }
-        SFCHK(hipGetLastError());
-        SFCHK(hipStreamSynchronize(s));       // the host images are rewritten for the next task
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipStreamSynchronize(s));       // the host images are rewritten for the next task
     }
-    SFCHK(hipMemcpyAsync(mean, dmean, (size_t)M * T * 8, hipMemcpyDeviceToHost, s));
-    if (var) SFCHK(hipMemcpyAsync(var, dvar, (size_t)M * T * 8, hipMemcpyDeviceToHost, s));
-    if (J) SFCHK(hipMemcpyAsync(J, dJ, (size_t)M * T * D * 8, hipMemcpyDeviceToHost, s));
-    SFCHK(hipStreamSynchronize(s));
+    CALLCHK(hipMemcpyAsync(mean, dmean, (size_t)M * T * 8, hipMemcpyDeviceToHost, s));
+    if (var) CALLCHK(hipMemcpyAsync(var, dvar, (size_t)M * T * 8, hipMemcpyDeviceToHost, s));
+    if (J) CALLCHK(hipMemcpyAsync(J, dJ, (size_t)M * T * D * 8, hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }

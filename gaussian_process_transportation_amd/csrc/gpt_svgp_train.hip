@@ -10,25 +10,14 @@
 //                                   on the shared parameters, loss trace
 // Every reduction runs in a fixed order (no floating-point atomics): two runs with the same inputs are bit-identical.
 // Notation and the derivation of the backward: DESIGN.md "SVGP training".
-#include "gpt_common.h"
-#include "../../include/gpt_hip.h"
-
-#include <climits>
-#include <cmath>
-#include <string>
-#include <vector>
+#include "gpt_svgp_common.h"
 
 using namespace gpt;
 
 namespace {
 
-constexpr int NT = 256;                      // threads per workgroup (16 x 16 in the Cholesky's trailing update)
-constexpr int SV_MAX_Z = 1024, SV_MAX_T = 32, SV_MAX_B = 1024;
-constexpr int64_t SV_MAX_STEPS = 1 << 24;    // the failure code packs (step, task) into one int
-constexpr double JITTER = 1e-4;              // gpytorch's float32 Cholesky jitter (as read)
-constexpr double NOISE_FLOOR = 1e-4;         // GreaterThan(1e-4) on each likelihood noise
-constexpr double BETA1 = 0.9, BETA2 = 0.999, ADAM_EPS = 1e-8;
-constexpr double LOG_2PI = 1.8378770664093453;
+constexpr int SV_MAX_Z = 1024, SV_MAX_B = 1024;              // sizes of svgp_task_step's LDS arrays
+constexpr SvgpLimits SV_LIMITS{SV_MAX_Z, 32, SV_MAX_B};
 
 struct SvArgs {
     const double* X;      // (N, D) training inputs
@@ -46,30 +35,6 @@ struct SvArgs {
     int N, D, T, Zn, bmax;
     double num_data;      // N of the ELBO's KL scaling
 };
-
-__device__ inline double softplus(double x) { return x > 20.0 ? x : log1p(exp(x)); }
-__device__ inline double softplus_grad(double x) { if (x > 20.0) return 1.0; double z = exp(x); return z / (z + 1.0); }
-
-// Fixed-order sum over the workgroup (every thread returns the total).
-__device__ double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// torch.optim.Adam's update of one element (single-tensor path): bc1 = 1 - beta1^k, bc2s = sqrt(1 - beta2^k).
-__device__ inline void adam(double& p, double g, double& a, double& b, double lr, double bc1, double bc2s) {
-    a = a + (1.0 - BETA1) * (g - a);
-    b = b * BETA2 + (1.0 - BETA2) * g * g;
-    p = p + (-(lr / bc1)) * (a / (sqrt(b) / bc2s + ADAM_EPS));
-}
 
 // ---- one task's forward, backward and own-parameter update --------------------------------------------------------
 // Workspace (doubles): M0, M1, M2 (Zn x Zn each), Kx, A, U, Ab, B (Zn x bmax each, row stride b), Xb (bmax x D), yb (bmax).
@@ -339,81 +304,13 @@ __global__ __launch_bounds__(NT) void svgp_shared_step(SvArgs a, int step, int a
     }
 }
 
-int fail(int code, const std::string& msg) {
-    set_last_error(msg.c_str());
-    return code;
-}
-
-#define SVCHK(expr)                                                                               \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess) return fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// Device buffers of one call; released on every return path.
-struct SvBuffers {
-    std::vector<void*> ptrs;
-    hipStream_t stream = nullptr;
-    ~SvBuffers() {
-        if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    template <class T> hipError_t alloc(T** p, size_t count) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, count * sizeof(T) > 0 ? count * sizeof(T) : 8);
-        if (e == hipSuccess) ptrs.push_back(q);
-        *p = static_cast<T*>(q);
-        return e;
-    }
-};
-
-bool finite(const double* p, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(p[i])) return false;
-    return true;
-}
-
 // The whole schedule: shared by gpt_svgp_train (apply = 1) and gpt_svgp_elbo_grad (one step, apply = 0).
-struct SvCall {
-    const double *X, *Y;
-    int64_t N, num_data;
-    int D, T, Zn;
-    double *Z, *m, *C, *raw_ls, *raw_os, *raw_noise;       // in / out (out only when apply)
-    const int64_t *idx, *bb;
-    int64_t n_idx, n_steps;
-    double lr;
-    int apply;
-    double* loss_trace;                                     // n_steps
-    double* grads[6];                                       // gZ, gm, gC, g_raw_ls, g_raw_os, g_raw_noise (apply = 0)
-};
-
-int run(int device, const char* who, const SvCall& c) {
+int run(int device, const char* who, const SvgpCall& c) {
     const std::string w = who;
-    if (!c.X || !c.Y || !c.Z || !c.m || !c.C || !c.raw_ls || !c.raw_os || !c.raw_noise || !c.idx || !c.bb)
-        return fail(GPT_E_ARG, w + ": NULL argument");
-    if (c.D < 1 || c.D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(c.D));
-    if (c.T < 1 || c.T > SV_MAX_T) return fail(GPT_E_ARG, w + ": T (tasks) must be 1 .. 32, got " + std::to_string(c.T));
-    if (c.Zn < 1 || c.Zn > SV_MAX_Z) return fail(GPT_E_ARG, w + ": inducing points must be 1 .. 1024, got " + std::to_string(c.Zn));
-    if (c.N < 1 || c.N > INT_MAX || c.num_data < 1) return fail(GPT_E_ARG, w + ": N must be >= 1");
-    if (c.n_steps < 1) return fail(GPT_E_ARG, w + ": empty schedule (no optimiser step)");
-    if (c.n_steps > SV_MAX_STEPS) return fail(GPT_E_ARG, w + ": more than 2^24 optimiser steps in one call");
-    if (c.n_idx < 1 || c.bb[0] < 0 || c.bb[c.n_steps] > c.n_idx) return fail(GPT_E_ARG, w + ": batch boundaries outside the index array");
     int bmax = 0;
-    for (int64_t s = 0; s < c.n_steps; ++s) {
-        const int64_t b = c.bb[s + 1] - c.bb[s];
-        if (b < 1 || b > SV_MAX_B) return fail(GPT_E_ARG, w + ": batch " + std::to_string(s) + " has " + std::to_string(b) + " rows (1 .. 1024)");
-        if (b > bmax) bmax = (int)b;
-    }
-    for (int64_t i = c.bb[0]; i < c.bb[c.n_steps]; ++i)
-        if (c.idx[i] < 0 || c.idx[i] >= c.N) return fail(GPT_E_ARG, w + ": schedule index out of range at " + std::to_string(i));
-    if (!std::isfinite(c.lr) || c.lr < 0) return fail(GPT_E_ARG, w + ": lr must be finite and >= 0");
+    if (int rc = svgp_validate(w, c, SV_LIMITS, c.D, &bmax)) return rc;
+    if (int rc = use_device(w, device)) return rc;
     const int D = c.D, T = c.T, Zn = c.Zn;
-    if (!finite(c.X, (size_t)c.N * D) || !finite(c.Y, (size_t)c.N * T) || !finite(c.Z, (size_t)Zn * D) || !finite(c.m, (size_t)T * Zn) ||
-        !finite(c.C, (size_t)T * Zn * Zn) || !finite(c.raw_ls, D) || !finite(c.raw_os, T) || !finite(c.raw_noise, T + 1))
-        return fail(GPT_E_ARG, w + ": non-finite input");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(GPT_E_ARG, w + ": no such HIP device");
-    SVCHK(hipSetDevice(device));
 
     const int64_t ZZ = (int64_t)Zn * Zn;
     const int64_t n_shared = D + (int64_t)Zn * D + 1, task_stride = 2 + Zn + ZZ, n_theta = n_shared + T * task_stride;
@@ -431,64 +328,31 @@ int run(int device, const char* who, const SvCall& c) {
             p[2 + Zn + e] = j > i ? 0.0 : c.C[t * ZZ + e];          // the strict upper triangle is not a parameter
         }
     }
-    const int64_t i0 = c.bb[0], ni = c.bb[c.n_steps] - i0;
-    std::vector<int> idx32(ni);
-    for (int64_t i = 0; i < ni; ++i) idx32[i] = (int)c.idx[i0 + i];
-
-    SvBuffers buf;
-    SVCHK(hipStreamCreateWithFlags(&buf.stream, hipStreamNonBlocking));
+    std::vector<int> idx32;
+    CallBuffers buf;
+    CALLCHK(buf.open());
+    const hipStream_t s = buf.stream;
+    SvgpDevice dev;
+    if (int rc = svgp_upload(buf, c, th, &idx32, &dev)) return rc;
     SvArgs a{};
+    a.X = dev.X; a.Y = dev.Y; a.idx = dev.idx; a.loss = dev.loss; a.fail = dev.fail;
+    a.theta = dev.theta; a.grad = dev.grad; a.m1 = dev.m1; a.m2 = dev.m2;
     a.N = (int)c.N; a.D = D; a.T = T; a.Zn = Zn; a.bmax = bmax; a.num_data = (double)c.num_data;
     a.n_shared = n_shared; a.task_stride = task_stride; a.part_stride = 2 + D + (int64_t)Zn * D;
     a.ws_stride = 3 * ZZ + 5 * (int64_t)Zn * bmax + (int64_t)bmax * D + bmax;
-    double *dX, *dY, *dth, *dg, *dm1, *dm2, *dpart, *dws, *dloss;
-    int *didx, *dfail;
-    SVCHK(buf.alloc(&dX, (size_t)c.N * D));
-    SVCHK(buf.alloc(&dY, (size_t)c.N * T));
-    SVCHK(buf.alloc(&didx, (size_t)ni));
-    SVCHK(buf.alloc(&dth, (size_t)n_theta));
-    SVCHK(buf.alloc(&dg, (size_t)n_theta));
-    SVCHK(buf.alloc(&dm1, (size_t)n_theta));
-    SVCHK(buf.alloc(&dm2, (size_t)n_theta));
-    SVCHK(buf.alloc(&dpart, (size_t)T * a.part_stride));
-    SVCHK(buf.alloc(&dws, (size_t)T * a.ws_stride));
-    SVCHK(buf.alloc(&dloss, (size_t)c.n_steps));
-    SVCHK(buf.alloc(&dfail, 1));
-    const hipStream_t s = buf.stream;
-    const int nofail = INT_MAX;
-    SVCHK(hipMemcpyAsync(dX, c.X, (size_t)c.N * D * 8, hipMemcpyHostToDevice, s));
-    SVCHK(hipMemcpyAsync(dY, c.Y, (size_t)c.N * T * 8, hipMemcpyHostToDevice, s));
-    SVCHK(hipMemcpyAsync(didx, idx32.data(), (size_t)ni * sizeof(int), hipMemcpyHostToDevice, s));
-    SVCHK(hipMemcpyAsync(dth, th.data(), (size_t)n_theta * 8, hipMemcpyHostToDevice, s));
-    SVCHK(hipMemsetAsync(dm1, 0, (size_t)n_theta * 8, s));
-    SVCHK(hipMemsetAsync(dm2, 0, (size_t)n_theta * 8, s));
-    SVCHK(hipMemcpyAsync(dfail, &nofail, sizeof(int), hipMemcpyHostToDevice, s));
-    a.X = dX; a.Y = dY; a.idx = didx; a.theta = dth; a.grad = dg; a.m1 = dm1; a.m2 = dm2; a.part = dpart; a.ws = dws;
-    a.loss = dloss; a.fail = dfail;
+    CALLCHK(buf.alloc(&a.part, (size_t)T * a.part_stride));
+    CALLCHK(buf.alloc(&a.ws, (size_t)T * a.ws_stride));
 
     for (int64_t st = 0; st < c.n_steps; ++st) {
-        const double k = (double)(st + 1);
-        const double bc1 = 1.0 - std::pow(BETA1, k), bc2s = std::sqrt(1.0 - std::pow(BETA2, k));
-        const int b0 = (int)(c.bb[st] - i0), b = (int)(c.bb[st + 1] - c.bb[st]);
-        hipLaunchKernelGGL(svgp_task_step, dim3(T), dim3(NT), 0, s, a, (int)st, b0, b, c.apply, c.lr, bc1, bc2s);
-        hipLaunchKernelGGL(svgp_shared_step, dim3(1), dim3(NT), 0, s, a, (int)st, c.apply, c.lr, bc1, bc2s);
+        const AdamBias bc = adam_bias((double)(st + 1));
+        const int b0 = (int)(c.bb[st] - c.bb[0]), b = (int)(c.bb[st + 1] - c.bb[st]);
+        hipLaunchKernelGGL(svgp_task_step, dim3(T), dim3(NT), 0, s, a, (int)st, b0, b, c.apply, c.lr, bc.bc1, bc.bc2s);
+        hipLaunchKernelGGL(svgp_shared_step, dim3(1), dim3(NT), 0, s, a, (int)st, c.apply, c.lr, bc.bc1, bc.bc2s);
     }
-    SVCHK(hipGetLastError());
-    int failed = INT_MAX;
-    std::vector<double> loss(c.n_steps), out(n_theta);
-    SVCHK(hipMemcpyAsync(&failed, dfail, sizeof(int), hipMemcpyDeviceToHost, s));
-    SVCHK(hipMemcpyAsync(loss.data(), dloss, (size_t)c.n_steps * 8, hipMemcpyDeviceToHost, s));
-    SVCHK(hipMemcpyAsync(out.data(), c.apply ? dth : dg, (size_t)n_theta * 8, hipMemcpyDeviceToHost, s));
-    SVCHK(hipStreamSynchronize(s));
-    if (failed != INT_MAX)
-        return fail(GPT_E_NOT_PD, w + ": non-positive pivot in chol(K(Z,Z) + eps I) at optimiser step " + std::to_string(failed / 64) +
-                                      " (task " + std::to_string(failed % 64) + "); parameters left as they were passed");
-    if (c.loss_trace)
-        for (int64_t i = 0; i < c.n_steps; ++i) c.loss_trace[i] = loss[i];
+    std::vector<double> out(n_theta);
+    double* dst[6];
+    if (int rc = svgp_read_back(w, s, c, dev, &out, dst)) return rc;
     // scatter the flat vector (parameters, or gradients) back into the caller's arrays
-    double* dst[6] = {c.Z, c.m, c.C, c.raw_ls, c.raw_os, c.raw_noise};
-    if (!c.apply)
-        for (int q = 0; q < 6; ++q) dst[q] = c.grads[q];
     if (dst[3]) for (int d = 0; d < D; ++d) dst[3][d] = out[d];
     if (dst[0]) for (int64_t e = 0; e < (int64_t)Zn * D; ++e) dst[0][e] = out[D + e];
     if (dst[5]) dst[5][T] = out[n_shared - 1];
@@ -511,7 +375,7 @@ int run(int device, const char* who, const SvCall& c) {
 extern "C" int gpt_svgp_train(int device, const double* X, const double* Y, int64_t N, int D, int T, int n_inducing, double* Z, double* m,
                               double* C, double* raw_lengthscale, double* raw_outputscale, double* raw_noise, const int64_t* idx, int64_t n_idx,
                               const int64_t* batch_begin, int64_t n_steps, double lr, double* loss_trace) {
-    SvCall c{};
+    SvgpCall c{};
     c.X = X; c.Y = Y; c.N = N; c.num_data = N; c.D = D; c.T = T; c.Zn = n_inducing;
     c.Z = Z; c.m = m; c.C = C; c.raw_ls = raw_lengthscale; c.raw_os = raw_outputscale; c.raw_noise = raw_noise;
     c.idx = idx; c.bb = batch_begin; c.n_idx = n_idx; c.n_steps = n_steps; c.lr = lr; c.apply = 1; c.loss_trace = loss_trace;
@@ -522,16 +386,7 @@ extern "C" int gpt_svgp_elbo_grad(int device, const double* Xb, const double* Yb
                                   const double* Z, const double* m, const double* C, const double* raw_lengthscale,
                                   const double* raw_outputscale, const double* raw_noise, double* loss, double* grad_Z, double* grad_m,
                                   double* grad_C, double* grad_raw_lengthscale, double* grad_raw_outputscale, double* grad_raw_noise) {
-    if (b < 1 || b > SV_MAX_B) return fail(GPT_E_ARG, "gpt_svgp_elbo_grad: batch size must be 1 .. 1024, got " + std::to_string(b));
-    std::vector<int64_t> idx(b);
-    for (int64_t i = 0; i < b; ++i) idx[i] = i;
-    const int64_t bb[2] = {0, b};
-    SvCall c{};
-    c.X = Xb; c.Y = Yb; c.N = b; c.num_data = num_data; c.D = D; c.T = T; c.Zn = n_inducing;
-    c.Z = const_cast<double*>(Z); c.m = const_cast<double*>(m); c.C = const_cast<double*>(C);
-    c.raw_ls = const_cast<double*>(raw_lengthscale); c.raw_os = const_cast<double*>(raw_outputscale); c.raw_noise = const_cast<double*>(raw_noise);
-    c.idx = idx.data(); c.bb = bb; c.n_idx = b; c.n_steps = 1; c.lr = 0.0; c.apply = 0; c.loss_trace = loss;
-    c.grads[0] = grad_Z; c.grads[1] = grad_m; c.grads[2] = grad_C; c.grads[3] = grad_raw_lengthscale; c.grads[4] = grad_raw_outputscale;
-    c.grads[5] = grad_raw_noise;
-    return run(device, "gpt_svgp_elbo_grad", c);
+    const double* params[6] = {Z, m, C, raw_lengthscale, raw_outputscale, raw_noise};
+    double* grads[6] = {grad_Z, grad_m, grad_C, grad_raw_lengthscale, grad_raw_outputscale, grad_raw_noise};
+    return svgp_elbo_grad(run, "gpt_svgp_elbo_grad", SV_LIMITS, device, Xb, Yb, b, num_data, D, T, n_inducing, params, loss, grads);
 }

@@ -1,0 +1,46 @@
+"""Check that a host-only change left the device code alone: compile units of two csrc trees to gfx950 assembly (the Makefile's
+CXXFLAGS plus --cuda-device-only -S), drop .file / .ident, source-path lines and comment-only lines, and compare kernel by
+kernel: every .amdhsa_kernel symbol present under the same name on both sides, instruction stream and kernel descriptor
+identical.  The other tree needs ../../include/gpt_hip.h next to it, as in a checkout.
+usage: python tools/device_isa_diff.py OTHER_CSRC [unit.hip ...]   (CPU only; hipcc cross-compiles; exit 1 on any difference)"""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc", "--cuda-device-only", "-S"]
+
+
+def kernels(csrc, unit, out):
+    """{kernel symbol: (instruction stream, descriptor)} of one unit, normalised."""
+    subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + [os.path.join(csrc, unit), "-o", out], check=True, stderr=subprocess.DEVNULL)
+    lines = [x.rstrip() for x in open(out)]
+    lines = [x for x in lines if x.strip() and not x.lstrip().startswith((";", "//", ".file", ".ident")) and csrc not in x]
+    s = "\n".join(re.sub(r"\s*;.*$", "", x) for x in lines)
+    found = {}
+    for name in re.findall(r"^\s*\.amdhsa_kernel (\S+)$", s, flags=re.M):
+        i = s.index("\n" + name + ":\n")
+        body = s[i:s.index(".Lfunc_end", i)]
+        j = s.index(".amdhsa_kernel " + name + "\n")
+        found[name] = (body, s[j:s.index(".end_amdhsa_kernel", j)])
+    return found
+
+
+def main():
+    other = os.path.abspath(sys.argv[1])
+    units = sys.argv[2:] or ["gpt_svgp_train.hip", "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_fit.hip"]
+    bad = 0
+    with tempfile.TemporaryDirectory() as d:
+        for unit in units:
+            a, b = kernels(other, unit, os.path.join(d, "a.s")), kernels(CSRC, unit, os.path.join(d, "b.s"))
+            diff = sorted(set(a) ^ set(b)) + sorted(k for k in set(a) & set(b) if a[k] != b[k])
+            print(f"{unit}: {len(b)} kernels, " + ("identical" if not diff else "DIFFERENT: " + ", ".join(diff)))
+            bad += len(diff)
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
