@@ -1,7 +1,7 @@
 // C ABI of libgpt_hip (see include/gpt_hip.h).  Host-side orchestration only: owns the device
 // buffers, prepares scaled/padded inputs, sequences the kernels of gpt_fit.hip / gpt_predict.hip
 // on one HIP stream and maps failures to error codes.
-#include "gpt_common.h"
+#include "gpt_call.h"
 #include "gpt_plan.h"
 #include "gpt_fit_plan.h"
 #include "../../include/gpt_hip.h"
@@ -18,18 +18,6 @@ using namespace gpt;
 namespace {
 
 thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return fail(GPT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));            \
-    } while (0)
 
 constexpr double MAGIC = 1196446770.0;   // "GPT2": header layout of this version
 constexpr int HDR_DOUBLES = 64;
@@ -86,13 +74,7 @@ int var_workgroups() {
 
 static int var_cols_per_query(const KernelParams& p, int ncomp) { return gpt::var_cols_per_query(p.D, ncomp); }   // codes: gpt_common.h
 
-void var_release(VarWorkspace& ws) {
-    for (void** pp : {&ws.slab, &ws.vslab, &ws.bscratch, &ws.plan_dev}) { if (*pp) (void)hipFree(*pp); *pp = nullptr; }
-    ws.slab_bytes = ws.vslab_bytes = ws.bscratch_bytes = ws.plan_bytes = 0;
-    delete ws.plan;
-    ws.plan = nullptr;
-    ws.key_cols = -1;
-}
+VarWorkspace::~VarWorkspace() = default;
 
 hipError_t var_prepare(VarWorkspace& ws, hipStream_t s, const KernelParams& p, int64_t M, int ncomp) {
     const size_t esz = p.dtype == DT_F32 ? sizeof(float) : sizeof(double);
@@ -100,47 +82,43 @@ hipError_t var_prepare(VarWorkspace& ws, hipStream_t s, const KernelParams& p, i
     const int nbi = p.NP / WT;
     const int64_t ncols = M * var_cols_per_query(p, ncomp);
     bool synced = false;
-    auto grow = [&](void*& buf, size_t& have, size_t need) -> hipError_t {
-        if (need <= have) return hipSuccess;
-        if (!synced) { if (hipError_t e = hipStreamSynchronize(s)) return e; synced = true; }   // work in flight may still use the old buffers
-        if (buf) (void)hipFree(buf);
-        buf = nullptr; have = 0;
-        if (hipError_t e = hipMalloc(&buf, need)) return e;
-        have = need;
-        ++ws.allocs;
-        return hipSuccess;
+    auto grow = [&](DevBuf<void>& buf, size_t need) -> hipError_t {
+        if (need <= buf.bytes) return hipSuccess;
+        const hipError_t e = reserve(buf, need, synced ? nullptr : s);   // work in flight may still use the old buffers: one wait per call
+        synced = true;
+        return e;
     };
     const bool same = ws.plan && ws.key_cols == ncols && ws.key_nbi == nbi && ws.key_ntask == p.ntask && ws.key_P == P;
     if (!same) {
         int order_env = -1;                                  // diagnostic override of the tail order (README)
         if (const char* e = getenv("GPT_VAR_TAIL_ORDER")) order_env = atoi(e);
-        VarPlanHost* np = new VarPlanHost(build_var_plan(ncols, nbi, p.ntask, P, order_env));
+        auto np = std::make_unique<VarPlanHost>(build_var_plan(ncols, nbi, p.ntask, P, order_env));
         // device image: [item_begin (P+1) | items | fin | splits], each part 16-byte aligned
         auto al = [](size_t b) { return (b + 15) / 16 * 16; };
         const size_t b0 = al((size_t)(P + 1) * sizeof(int)), b1 = al(np->items.size() * sizeof(VarItem)),
                      b2 = al(np->fin.size() * sizeof(int)), b3 = al(np->splits.size() * sizeof(VarSplit));
         const size_t total = b0 + b1 + b2 + b3 + 16;
         // the previous plan may still be read by a launch in flight: wait before overwriting it
-        if (!synced) { if (hipError_t e = hipStreamSynchronize(s)) { delete np; return e; } synced = true; }
-        if (hipError_t e = grow(ws.plan_dev, ws.plan_bytes, total)) { delete np; return e; }
+        if (hipError_t e = hipStreamSynchronize(s)) return e;
+        synced = true;
+        if (hipError_t e = grow(ws.plan_dev, total)) return e;
         std::vector<unsigned char> img(total, 0);
         memcpy(img.data(), np->item_begin.data(), (size_t)(P + 1) * sizeof(int));
         if (!np->items.empty()) memcpy(img.data() + b0, np->items.data(), np->items.size() * sizeof(VarItem));
         if (!np->fin.empty()) memcpy(img.data() + b0 + b1, np->fin.data(), np->fin.size() * sizeof(int));
         if (!np->splits.empty()) memcpy(img.data() + b0 + b1 + b2, np->splits.data(), np->splits.size() * sizeof(VarSplit));
-        if (hipError_t e = hipMemcpy(ws.plan_dev, img.data(), total, hipMemcpyHostToDevice)) { delete np; return e; }
-        unsigned char* base = static_cast<unsigned char*>(ws.plan_dev);
+        if (hipError_t e = hipMemcpy(ws.plan_dev, img.data(), total, hipMemcpyHostToDevice)) return e;
+        unsigned char* base = static_cast<unsigned char*>(ws.plan_dev.p);
         np->d.item_begin = reinterpret_cast<const int*>(base);
         np->d.items = reinterpret_cast<const VarItem*>(base + b0);
         np->d.fin = reinterpret_cast<const int*>(base + b0 + b1);
         np->d.splits = reinterpret_cast<const VarSplit*>(base + b0 + b1 + b2);
-        delete ws.plan;
-        ws.plan = np;
+        ws.plan = std::move(np);
         ws.key_cols = ncols; ws.key_nbi = nbi; ws.key_ntask = p.ntask; ws.key_P = P;
     }
-    if (hipError_t e = grow(ws.slab, ws.slab_bytes, (size_t)(ws.plan->n_slots + 1) * VAR_SLOT * esz)) return e;
-    if (hipError_t e = grow(ws.vslab, ws.vslab_bytes, (size_t)ws.plan->n_vslots * VAR_VSLOT * esz)) return e;
-    if (hipError_t e = grow(ws.bscratch, ws.bscratch_bytes, (size_t)P * p.NP * VAR_COLS * esz)) return e;
+    if (hipError_t e = grow(ws.slab, (size_t)(ws.plan->n_slots + 1) * VAR_SLOT * esz)) return e;
+    if (hipError_t e = grow(ws.vslab, (size_t)ws.plan->n_vslots * VAR_VSLOT * esz)) return e;
+    if (hipError_t e = grow(ws.bscratch, (size_t)P * p.NP * VAR_COLS * esz)) return e;
     return hipSuccess;
 }
 
@@ -150,22 +128,25 @@ struct gpt_handle {
     int device = 0;
     int dtype_next = DT_F64;       // element type of models fitted from now on (gpt_set_dtype)
     bool matern_derivatives = false;   // derivatives of Matern 3/2 / 5/2 models enabled (gpt_set_matern_derivatives)
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    Stream own_stream;
+    hipStream_t stream = nullptr;  // own_stream, or the caller's (gpt_set_stream)
     // model blob
-    unsigned char* blob = nullptr;
+    DevBuf<unsigned char> blob;
     Layout lay{};
     bool have_layout = false, committed = false;
     KernelParams p{};
     double jitter = 0, ls[MAX_D] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
     int n_ls = 1;
-    // fit workspace (fp64)
-    double *dK = nullptr, *dW = nullptr, *dY4 = nullptr, *dT4 = nullptr, *dTa = nullptr, *dXs64 = nullptr, *dA64 = nullptr, *dscal = nullptr;
-    double* dXraw = nullptr;       // the raw (N, D) sources as uploaded; scaled on the device for every new set of length-scales
-    double* dScr = nullptr;        // arena of the factor + inverse (gpt_fit_plan.h) and scratch of alpha's backward pass
-    size_t scr_doubles = 0;        // its capacity
-    int* dinfo = nullptr;
-    int64_t ws_np = 0;
-    int ws_npass = 0;
+    // fit workspace (fp64), allocated and replaced as a whole (ensure_workspace) for one NP and up to `npass` passes
+    struct Workspace {
+        DevBuf<double> dK, dW, dY4, dT4, dTa, dXs64, dA64, dscal;
+        DevBuf<double> dXraw;      // the raw (N, D) sources as uploaded; scaled on the device for every new set of length-scales
+        DevBuf<double> dScr;       // arena of the factor + inverse (gpt_fit_plan.h) and scratch of alpha's backward pass (grow-only)
+        DevBuf<int> dinfo;
+        int64_t np = 0;
+        int npass = 0;
+    };
+    std::unique_ptr<Workspace> ws = std::make_unique<Workspace>();
     bool have_L = false;           // dK holds L of the committed model (gpt_export, gpt_lml)
     bool have_W = false;           // dW holds L^-1 of the committed model (gpt_predict_cov, gpt_lml_gradient, gpt_export_inverse_factor)
     bool objective_ready = false;  // gpt_lml_objective: factor and alpha in the workspace, no committed model
@@ -178,58 +159,51 @@ struct gpt_handle {
     int host_info = 0;
     // staging of the host-pointer API, grow-only per buffer
     // (two sets: while the results of one chunk travel to the host on `copy_stream`, the next chunk computes)
-    struct Staging { void* buf[ST_COUNT] = {}; size_t bytes[ST_COUNT] = {}; } st[2];
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_done[2] = {}, ev_copied[2] = {};   // chunk computed / chunk's outputs copied out, per staging set
+    struct Staging { DevBuf<void> buf[ST_COUNT]; } st[2];
+    Stream copy_stream;
+    Event ev_done[2], ev_copied[2];   // chunk computed / chunk's outputs copied out, per staging set
     double fit_ms[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t ev[7] = {};
+    Event ev[7];
     // per-kernel timing of the last predict (gpt_set_profiling)
     bool profiling = false, pred_mj = false, pred_var = false;
     VarWorkspace vws;              // scratch + cached plan of the variance kernel
     FitAux fit_aux;                // CU-masked streams + events of the factor + inverse plan (gpt_fit_plan.h)
-    double* lml_partial = nullptr; // partial sums of the LML gradient (grow-only)
-    size_t lml_partial_cap = 0;
-    unsigned char* cov_buf = nullptr;   // scratch of gpt_predict_cov (grow-only)
-    size_t cov_cap = 0;
-    hipEvent_t pev[4] = {};
+    DevBuf<double> lml_partial;    // partial sums of the LML gradient (grow-only)
+    DevBuf<unsigned char> cov_buf; // scratch of gpt_predict_cov (grow-only)
+    Event pev[4];
+
+    ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
 
     void* dXs() const { return blob + lay.off_xs; }
     void* dA4() const { return blob + lay.off_a4; }
     void* dWf() const { return blob + lay.off_wf; }
-    const double* dHdr() const { return reinterpret_cast<const double*>(blob); }
+    const double* dHdr() const { return reinterpret_cast<const double*>(blob.p); }
 };
 
 namespace {
 
 int set_device(gpt_handle* h) {
-    HIPCHK(hipSetDevice(h->device));
+    CALLCHK(hipSetDevice(h->device));
     return GPT_OK;
 }
 
-void free_staging(gpt_handle* h) {
-    for (auto& t : h->st)
-        for (int i = 0; i < ST_COUNT; ++i) { if (t.buf[i]) (void)hipFree(t.buf[i]); t.buf[i] = nullptr; t.bytes[i] = 0; }
+// No model, no factors: what the call that follows leaves behind is all the handle holds.
+void invalidate_model(gpt_handle* h) {
+    h->committed = false;
+    h->have_L = h->have_W = false;
+    h->objective_ready = false;
 }
 
-void free_workspace(gpt_handle* h) {
-    double** ptrs[] = {&h->dK, &h->dW, &h->dY4, &h->dT4, &h->dTa, &h->dXs64, &h->dA64, &h->dscal, &h->dScr, &h->dXraw};
-    h->hostX.clear(); h->hostY.clear();
-    for (auto pp : ptrs) { if (*pp) (void)hipFree(*pp); *pp = nullptr; }
-    if (h->dinfo) (void)hipFree(h->dinfo);
-    h->dinfo = nullptr;
-    h->ws_np = 0; h->ws_npass = 0; h->have_L = h->have_W = false;
-    h->scr_doubles = 0;
-}
-
+// the blob keeps its address as long as the model keeps its shape (gpt_factor_blob), and is replaced when the shape changes
 int ensure_blob(gpt_handle* h, const Layout& l) {
     if (h->blob && h->have_layout && h->lay.same_shape(l)) {
         h->lay = l;
         return GPT_OK;
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->blob) { (void)hipFree(h->blob); h->blob = nullptr; }
+    CALLCHK(hipStreamSynchronize(h->stream));
+    h->blob.release();
     h->have_layout = false;
-    HIPCHK(hipMalloc(&h->blob, l.total));
+    CALLCHK(reserve(h->blob, l.total, nullptr));
     h->lay = l;
     h->have_layout = true;
     return GPT_OK;
@@ -239,54 +213,44 @@ int ensure_blob(gpt_handle* h, const Layout& l) {
 // process may change between two fits of one handle)
 int ensure_scratch(gpt_handle* h, int64_t NP) {
     const size_t a = factor_scratch_doubles((int)NP), b = (size_t)(NP / 512) * NP * 4;
-    const size_t need = a > b ? a : b;
-    if (h->dScr && h->scr_doubles >= need) return GPT_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->dScr) (void)hipFree(h->dScr);
-    h->dScr = nullptr; h->scr_doubles = 0;
-    HIPCHK(hipMalloc(&h->dScr, need * sizeof(double)));
-    h->scr_doubles = need;
+    CALLCHK(reserve(h->ws->dScr, (a > b ? a : b) * sizeof(double), h->stream));
     return GPT_OK;
 }
 
 int ensure_workspace(gpt_handle* h, int64_t NP, int npass) {
-    if (h->ws_np == NP && h->ws_npass >= npass && h->dK) return ensure_scratch(h, NP);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    free_workspace(h);
-    HIPCHK(hipMalloc(&h->dK, (size_t)NP * NP * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dW, (size_t)NP * NP * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dY4, (size_t)npass * NP * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dA64, (size_t)npass * NP * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dT4, (size_t)NP * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dTa, (size_t)NP * 4 * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dXs64, (size_t)NP * MAX_D * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dXraw, (size_t)NP * MAX_D * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dscal, (2 + LML_TERMS + 4) * sizeof(double)));
-    HIPCHK(hipMalloc(&h->dinfo, sizeof(int)));
+    if (h->ws->np == NP && h->ws->npass >= npass && h->ws->dK) return ensure_scratch(h, NP);
+    CALLCHK(hipStreamSynchronize(h->stream));
+    h->ws = std::make_unique<gpt_handle::Workspace>();      // the old one is freed here, before anything new is allocated,
+    h->hostX.clear(); h->hostY.clear();                     // and with it goes what the mirrors and the factor flags stood for
+    h->have_L = h->have_W = false;
+    gpt_handle::Workspace& w = *h->ws;
+    CALLCHK(reserve(w.dK, (size_t)NP * NP * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dW, (size_t)NP * NP * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dY4, (size_t)npass * NP * 4 * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dA64, (size_t)npass * NP * 4 * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dT4, (size_t)NP * 4 * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dTa, (size_t)NP * 4 * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dXs64, (size_t)NP * MAX_D * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dXraw, (size_t)NP * MAX_D * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dscal, (2 + LML_TERMS + 4) * sizeof(double), nullptr));
+    CALLCHK(reserve(w.dinfo, sizeof(int), nullptr));
     if (int rc = ensure_scratch(h, NP)) return rc;
-    h->ws_np = NP; h->ws_npass = npass;
+    w.np = NP; w.npass = npass;
     return GPT_OK;
 }
 
 // one staging buffer of one set, grow-only; only what a call asks for is ever allocated
 int ensure_stage(gpt_handle* h, int set, int which, size_t bytes) {
-    gpt_handle::Staging& t = h->st[set];
-    if (t.bytes[which] >= bytes) return GPT_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->copy_stream) HIPCHK(hipStreamSynchronize(h->copy_stream));
-    if (t.buf[which]) (void)hipFree(t.buf[which]);
-    t.buf[which] = nullptr; t.bytes[which] = 0;
-    HIPCHK(hipMalloc(&t.buf[which], bytes));
-    t.bytes[which] = bytes;
+    CALLCHK(reserve(h->st[set].buf[which], bytes, h->stream, h->copy_stream));
     return GPT_OK;
 }
 
 int ensure_copy_stream(gpt_handle* h) {
     if (h->copy_stream) return GPT_OK;
-    HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+    CALLCHK(hipStreamCreateWithFlags(&h->copy_stream.h, hipStreamNonBlocking));
     for (int i = 0; i < 2; ++i) {
-        HIPCHK(hipEventCreateWithFlags(&h->ev_done[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_copied[i], hipEventDisableTiming));
+        CALLCHK(hipEventCreateWithFlags(&h->ev_done[i].h, hipEventDisableTiming));
+        CALLCHK(hipEventCreateWithFlags(&h->ev_copied[i].h, hipEventDisableTiming));
     }
     return GPT_OK;
 }
@@ -333,12 +297,12 @@ int upload_sources(gpt_handle* h, const Layout& l, const double* X, std::vector<
     hipStream_t s = h->stream;
     const size_t nx = (size_t)l.N * l.D;
     if (h->hostX.size() != nx || h->hostX_D != l.D || memcmp(h->hostX.data(), X, nx * sizeof(double)) != 0) {
-        HIPCHK(hipStreamSynchronize(s));     // (a copy out of the old mirror that an aborted call left in flight)
+        CALLCHK(hipStreamSynchronize(s));     // (a copy out of the old mirror that an aborted call left in flight)
         h->hostX.assign(X, X + nx);          // the mirror is also the source of the asynchronous copy: it outlives the call
         h->hostX_D = l.D;
-        HIPCHK(hipMemcpyAsync(h->dXraw, h->hostX.data(), nx * sizeof(double), hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(h->ws->dXraw, h->hostX.data(), nx * sizeof(double), hipMemcpyHostToDevice, s));
     }
-    launch_scale_x(s, h->dXraw, (int)l.N, (int)l.NP, l.D, h->p.inv_ls, h->dXs64, model ? h->dXs() : nullptr, l.dtype);
+    launch_scale_x(s, h->ws->dXraw, (int)l.N, (int)l.NP, l.D, h->p.inv_ls, h->ws->dXs64, model ? h->dXs() : nullptr, l.dtype);
     return GPT_OK;
 }
 
@@ -346,30 +310,30 @@ int upload_sources(gpt_handle* h, const Layout& l, const double* X, std::vector<
 int upload_targets(gpt_handle* h, const Layout& l, const double* Y) {
     const size_t ny = (size_t)l.N * l.O, NP = (size_t)l.NP;
     if (h->hostY.size() == ny && h->hostY_O == l.O && memcmp(h->hostY.data(), Y, ny * sizeof(double)) == 0) return GPT_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     h->hostY.assign(Y, Y + ny);
     h->hostY_O = l.O;
     h->hostY4.assign((size_t)l.npass * NP * 4, 0.0);
     for (int64_t i = 0; i < l.N; ++i)
         for (int o = 0; o < l.O; ++o) h->hostY4[((size_t)(o / 4) * NP + i) * 4 + (o % 4)] = Y[i * l.O + o];
-    HIPCHK(hipMemcpyAsync(h->dY4, h->hostY4.data(), h->hostY4.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CALLCHK(hipMemcpyAsync(h->ws->dY4, h->hostY4.data(), h->hostY4.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     return GPT_OK;
 }
 
 // K -> L (in dK), W = L^-1 (in dW); K's Gram part from dXs64, optional dense SPD addend Sigma (host, N x N)
 int factorise(gpt_handle* h, int64_t N, int NP, int kernel_type, double c, double diag_add, const double* Sigma) {
     hipStream_t s = h->stream;
-    HIPCHK(hipMemsetAsync(h->dinfo, 0, sizeof(int), s));
-    HIPCHK(hipMemsetAsync(h->dW, 0, (size_t)NP * NP * sizeof(double), s));
-    launch_gram(s, h->dXs64, h->p.D, (int)N, NP, kernel_type, c, diag_add, h->dK);
+    CALLCHK(hipMemsetAsync(h->ws->dinfo, 0, sizeof(int), s));
+    CALLCHK(hipMemsetAsync(h->ws->dW, 0, (size_t)NP * NP * sizeof(double), s));
+    launch_gram(s, h->ws->dXs64, h->p.D, (int)N, NP, kernel_type, c, diag_add, h->ws->dK);
     if (Sigma) {      // K += Sigma: staged through dW (not in use until the factorisation starts)
-        HIPCHK(hipMemcpyAsync(h->dW, Sigma, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, s));
-        launch_add_lower(s, h->dK, h->dW, (int)N, NP);
-        HIPCHK(hipMemsetAsync(h->dW, 0, (size_t)NP * NP * sizeof(double), s));
+        CALLCHK(hipMemcpyAsync(h->ws->dW, Sigma, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_add_lower(s, h->ws->dK, h->ws->dW, (int)N, NP);
+        CALLCHK(hipMemsetAsync(h->ws->dW, 0, (size_t)NP * NP * sizeof(double), s));
     }
-    HIPCHK(hipEventRecord(h->ev[1], s));
-    launch_factor_inverse(s, h->dK, h->dW, NP, h->dinfo, h->dScr, &h->fit_aux, h->ev[2]);
-    HIPCHK(hipEventRecord(h->ev[3], s));
+    CALLCHK(hipEventRecord(h->ev[1], s));
+    launch_factor_inverse(s, h->ws->dK, h->ws->dW, NP, h->ws->dinfo, h->ws->dScr, &h->fit_aux, h->ev[2]);
+    CALLCHK(hipEventRecord(h->ev[3], s));
     return GPT_OK;
 }
 
@@ -392,21 +356,17 @@ int gpt_create(gpt_handle** out, int device) {
     if (!out) return fail(GPT_E_ARG, "gpt_create: out is NULL");
     int n = gpt_device_count();
     if (device < 0 || device >= n || device >= MAX_DEVICES) return fail(GPT_E_ARG, "gpt_create: no such HIP device");
-    HIPCHK(hipSetDevice(device));
-    gpt_handle* h = new gpt_handle();
+    CALLCHK(hipSetDevice(device));
+    auto h = std::make_unique<gpt_handle>();           // a failure below releases whatever exists by then
     h->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail(GPT_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e)); }
+    hipError_t e = hipStreamCreateWithFlags(&h->own_stream.h, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(GPT_E_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
     h->stream = h->own_stream;
-    for (auto& ev : h->ev) {
-        e = hipEventCreate(&ev);
-        if (e != hipSuccess) { delete h; return fail(GPT_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-    }
-    for (auto& ev : h->pev) {
-        e = hipEventCreate(&ev);
-        if (e != hipSuccess) { delete h; return fail(GPT_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-    }
-    *out = h;
+    for (Event& ev : h->ev)
+        if ((e = hipEventCreate(&ev.h)) != hipSuccess) return fail(GPT_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    for (Event& ev : h->pev)
+        if ((e = hipEventCreate(&ev.h)) != hipSuccess) return fail(GPT_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+    *out = h.release();
     return GPT_OK;
 }
 
@@ -415,19 +375,6 @@ void gpt_destroy(gpt_handle* h) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-    free_staging(h);
-    free_workspace(h);
-    var_release(h->vws);
-    fit_aux_release(h->fit_aux);
-    if (h->blob) (void)hipFree(h->blob);
-    if (h->lml_partial) (void)hipFree(h->lml_partial);
-    if (h->cov_buf) (void)hipFree(h->cov_buf);
-    for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->pev) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->ev_done) if (ev) (void)hipEventDestroy(ev);
-    for (auto& ev : h->ev_copied) if (ev) (void)hipEventDestroy(ev);
-    if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-    if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     delete h;
 }
 
@@ -440,7 +387,7 @@ int gpt_set_stream(gpt_handle* h, void* hip_stream) {
 int gpt_synchronize(gpt_handle* h) {
     if (!h) return fail(GPT_E_ARG, "gpt_synchronize: NULL handle");
     if (int rc = set_device(h)) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     return GPT_OK;
 }
 
@@ -483,10 +430,10 @@ int gpt_fit_noise_matrix(gpt_handle* h, const double* X, const double* Y, int64_
 static int read_fit_times(gpt_handle* h) {
     float ms = 0;
     for (int i = 1; i <= 5; ++i) {
-        HIPCHK(hipEventElapsedTime(&ms, h->ev[i - 1], h->ev[i]));
+        CALLCHK(hipEventElapsedTime(&ms, h->ev[i - 1], h->ev[i]));
         h->fit_ms[i] = ms;
     }
-    HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5]));
+    CALLCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[5]));
     h->fit_ms[0] = ms;
     return GPT_OK;
 }
@@ -503,9 +450,7 @@ static int fit_enqueue(gpt_handle* h, const double* X, const double* Y, int64_t 
     if (!(constant_value > 0.0) || !(noise_level >= 0.0) || !(alpha_jitter >= 0.0))
         return fail(GPT_E_ARG, "gpt_fit: constant_value > 0, noise_level >= 0, alpha >= 0 required");
     if (int rc = set_device(h)) return rc;
-    h->committed = false;
-    h->have_L = h->have_W = false;
-    h->objective_ready = false;
+    invalidate_model(h);
     const Layout l = make_layout(N, D, O, 1, h->dtype_next);
     if (int rc = ensure_blob(h, l)) return rc;
     if (int rc = ensure_workspace(h, l.NP, l.npass)) return rc;
@@ -519,25 +464,25 @@ static int fit_enqueue(gpt_handle* h, const double* X, const double* Y, int64_t 
     if (model) {
         hdr[HDR_TASK_C] = constant_value;
         memcpy(h->host_hdr, hdr.data(), sizeof h->host_hdr);          // a member: the source of an asynchronous copy
-        HIPCHK(hipMemcpyAsync(h->blob, h->host_hdr, sizeof h->host_hdr, hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(h->blob, h->host_hdr, sizeof h->host_hdr, hipMemcpyHostToDevice, s));
     }
 
     // ---- device pipeline
-    HIPCHK(hipEventRecord(h->ev[0], s));
+    CALLCHK(hipEventRecord(h->ev[0], s));
     if (int rc = factorise(h, N, NP, kernel_type, constant_value, noise_level + alpha_jitter, Sigma)) return rc;
     for (int ps = 0; ps < l.npass; ++ps) {
-        double* a64 = h->dA64 + (size_t)ps * NP * 4;
-        launch_alpha(s, h->dW, h->dY4 + (size_t)ps * NP * 4, (int)N, NP, h->dT4, a64, h->dScr);
+        double* a64 = h->ws->dA64 + (size_t)ps * NP * 4;
+        launch_alpha(s, h->ws->dW, h->ws->dY4 + (size_t)ps * NP * 4, (int)N, NP, h->ws->dT4, a64, h->ws->dScr);
         if (model) launch_store4(s, a64, NP, static_cast<unsigned char*>(h->dA4()) + (size_t)ps * NP * 4 * l.esz, l.dtype, 0, 0, 4, 1.0);
     }
-    HIPCHK(hipEventRecord(h->ev[4], s));
+    CALLCHK(hipEventRecord(h->ev[4], s));
     if (model) {
-        launch_pack_w(s, h->dW, (int)N, NP, h->dWf(), l.dtype, 0, 1.0);
-        HIPCHK(hipMemsetAsync(static_cast<unsigned char*>(h->dWf()) + wf_elems(NP) * l.esz, 0, wf_overrun_elems() * l.esz, s));
+        launch_pack_w(s, h->ws->dW, (int)N, NP, h->dWf(), l.dtype, 0, 1.0);
+        CALLCHK(hipMemsetAsync(static_cast<unsigned char*>(h->dWf()) + wf_elems(NP) * l.esz, 0, wf_overrun_elems() * l.esz, s));
     }
-    HIPCHK(hipEventRecord(h->ev[5], s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&h->host_info, h->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipEventRecord(h->ev[5], s));
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipMemcpyAsync(&h->host_info, h->ws->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
     return GPT_OK;
 }
 
@@ -558,7 +503,7 @@ static int fit_impl(gpt_handle* h, const double* X, const double* Y, int64_t N, 
                     const double* length_scale, int n_ls, double constant_value, double noise_level,
                     double alpha_jitter, int kernel_type, const double* Sigma, bool model) {
     if (int rc = fit_enqueue(h, X, Y, N, D, O, length_scale, n_ls, constant_value, noise_level, alpha_jitter, kernel_type, Sigma, model)) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     if (int rc = read_fit_times(h)) return rc;
     return fit_finish(h, model);
 }
@@ -566,25 +511,18 @@ static int fit_impl(gpt_handle* h, const double* X, const double* Y, int64_t N, 
 // ---- log-marginal likelihood and its gradient: device-side reductions into dscal, one read-back
 //   dscal[0] = sum_i log L_ii, dscal[1] = sum_o y_o^T alpha_o, dscal[2 ..] = the LML_TERMS traces of the gradient
 static void enqueue_lml_scalars(gpt_handle* h) {
-    launch_logdet(h->stream, h->dK, h->p.N, h->p.NP, h->dscal);
-    launch_dot(h->stream, h->dY4, h->dA64, (int64_t)h->lay.npass * h->p.NP * 4, h->dscal + 1);
+    launch_logdet(h->stream, h->ws->dK, h->p.N, h->p.NP, h->ws->dscal);
+    launch_dot(h->stream, h->ws->dY4, h->ws->dA64, (int64_t)h->lay.npass * h->p.NP * 4, h->ws->dscal + 1);
 }
 
 static int enqueue_gradient_terms(gpt_handle* h) {
     const int64_t NP = h->p.NP;
     hipStream_t s = h->stream;
     // K^-1 (lower) into dK, per-tile partial sums into their own scratch
-    const size_t need = (size_t)(NP / 64) * (NP / 64) * LML_PARTIAL_STRIDE;
-    if (need > h->lml_partial_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (h->lml_partial) (void)hipFree(h->lml_partial);
-        h->lml_partial = nullptr; h->lml_partial_cap = 0;
-        HIPCHK(hipMalloc(&h->lml_partial, need * sizeof(double)));
-        h->lml_partial_cap = need;
-    }
-    launch_kinv(s, h->dW, (int)NP, h->dK);
-    launch_lml_terms(s, h->dXs64, h->p.D, h->dA64, h->lay.npass, h->dK, h->p.N, (int)NP, h->p.O, h->p.ktype, h->p.c, h->lml_partial, h->dscal + 2);
-    HIPCHK(hipGetLastError());
+    CALLCHK(reserve(h->lml_partial, (size_t)(NP / 64) * (NP / 64) * LML_PARTIAL_STRIDE * sizeof(double), s));
+    launch_kinv(s, h->ws->dW, (int)NP, h->ws->dK);
+    launch_lml_terms(s, h->ws->dXs64, h->p.D, h->ws->dA64, h->lay.npass, h->ws->dK, h->p.N, (int)NP, h->p.O, h->p.ktype, h->p.c, h->lml_partial, h->ws->dscal + 2);
+    CALLCHK(hipGetLastError());
     return GPT_OK;
 }
 
@@ -618,8 +556,8 @@ int gpt_lml_objective(gpt_handle* h, const double* X, const double* Y, int64_t N
     hipStream_t s = h->stream;
     enqueue_lml_scalars(h);                                   // reads diag(L) in dK before the gradient overwrites it
     if (int rc = enqueue_gradient_terms(h)) return rc;
-    HIPCHK(hipMemcpyAsync(h->host_scal, h->dscal, (2 + LML_TERMS) * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    CALLCHK(hipMemcpyAsync(h->host_scal, h->ws->dscal, (2 + LML_TERMS) * sizeof(double), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
     if (int rc = fit_finish(h, false)) return rc;             // not positive definite: whatever ran behind the factor is discarded
     h->have_L = false;                                        // dK holds K^-1 now
     *lml = lml_from_scalars(h, h->host_scal);
@@ -637,9 +575,7 @@ int gpt_fit_svgp(gpt_handle* h, const double* Z, const double* y, const double* 
         if (!(outputscale[t] > 0.0)) return fail(GPT_E_ARG, "gpt_fit_svgp: outputscale must be > 0");
     if (!(jitter >= 0.0)) return fail(GPT_E_ARG, "gpt_fit_svgp: jitter >= 0 required");
     if (int rc = set_device(h)) return rc;
-    h->committed = false;
-    h->have_L = h->have_W = false;
-    h->objective_ready = false;
+    invalidate_model(h);
     const Layout l = make_layout(N, D, T, T, dtype);
     if (int rc = ensure_blob(h, l)) return rc;
     if (int rc = ensure_workspace(h, l.NP, l.npass)) return rc;
@@ -650,33 +586,33 @@ int gpt_fit_svgp(gpt_handle* h, const double* Z, const double* y, const double* 
     std::vector<double> hdr;
     if (int rc = upload_sources(h, l, Z, hdr, length_scale, n_ls, 1.0, 0.0, jitter, GPT_KERNEL_RBF, true)) return rc;
     for (int t = 0; t < T; ++t) hdr[HDR_TASK_C + t] = outputscale[t];
-    HIPCHK(hipMemcpyAsync(h->blob, hdr.data(), HDR_DOUBLES * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(h->dA4(), 0, (size_t)l.npass * NP * 4 * l.esz, s));
-    HIPCHK(hipMemsetAsync(h->dA64, 0, (size_t)l.npass * NP * 4 * sizeof(double), s));
-    HIPCHK(hipStreamSynchronize(s));
+    CALLCHK(hipMemcpyAsync(h->blob, hdr.data(), HDR_DOUBLES * sizeof(double), hipMemcpyHostToDevice, s));
+    CALLCHK(hipMemsetAsync(h->dA4(), 0, (size_t)l.npass * NP * 4 * l.esz, s));
+    CALLCHK(hipMemsetAsync(h->ws->dA64, 0, (size_t)l.npass * NP * 4 * sizeof(double), s));
+    CALLCHK(hipStreamSynchronize(s));
     h->hostY.clear();
     std::vector<double> y4((size_t)NP * 4);
-    HIPCHK(hipEventRecord(h->ev[0], s));
+    CALLCHK(hipEventRecord(h->ev[0], s));
     int info = 0, bad_task = -1;
     for (int t = 0; t < T && info == 0; ++t) {
         std::fill(y4.begin(), y4.end(), 0.0);
         for (int64_t i = 0; i < N; ++i) y4[(size_t)i * 4] = y[(size_t)t * N + i];
-        HIPCHK(hipMemcpyAsync(h->dY4, y4.data(), y4.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        CALLCHK(hipMemcpyAsync(h->ws->dY4, y4.data(), y4.size() * sizeof(double), hipMemcpyHostToDevice, s));
         if (int rc = factorise(h, N, NP, GPT_KERNEL_RBF, outputscale[t], jitter, Sigma + (size_t)t * N * N)) return rc;
-        launch_alpha(s, h->dW, h->dY4, (int)N, NP, h->dT4, h->dTa, h->dScr);
+        launch_alpha(s, h->ws->dW, h->ws->dY4, (int)N, NP, h->ws->dT4, h->ws->dTa, h->ws->dScr);
         const size_t col_off = (size_t)(t / 4) * NP * 4;
-        launch_store4(s, h->dTa, NP, h->dA64 + col_off, DT_F64, 0, t % 4, 1, 1.0);
-        launch_store4(s, h->dTa, NP, static_cast<unsigned char*>(h->dA4()) + col_off * l.esz, l.dtype, 0, t % 4, 1, outputscale[t]);
-        launch_pack_w(s, h->dW, (int)N, NP, h->dWf(), l.dtype, t, outputscale[t]);
-        HIPCHK(hipMemcpyAsync(&info, h->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));           // y4 is reused; the pivot check of this task
+        launch_store4(s, h->ws->dTa, NP, h->ws->dA64 + col_off, DT_F64, 0, t % 4, 1, 1.0);
+        launch_store4(s, h->ws->dTa, NP, static_cast<unsigned char*>(h->dA4()) + col_off * l.esz, l.dtype, 0, t % 4, 1, outputscale[t]);
+        launch_pack_w(s, h->ws->dW, (int)N, NP, h->dWf(), l.dtype, t, outputscale[t]);
+        CALLCHK(hipMemcpyAsync(&info, h->ws->dinfo, sizeof(int), hipMemcpyDeviceToHost, s));
+        CALLCHK(hipStreamSynchronize(s));           // y4 is reused; the pivot check of this task
         if (info != 0) bad_task = t;
     }
-    HIPCHK(hipMemsetAsync(static_cast<unsigned char*>(h->dWf()) + (size_t)T * wf_elems(NP) * l.esz, 0, wf_overrun_elems() * l.esz, s));
-    HIPCHK(hipEventRecord(h->ev[4], s));
-    HIPCHK(hipEventRecord(h->ev[5], s));
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(s));
+    CALLCHK(hipMemsetAsync(static_cast<unsigned char*>(h->dWf()) + (size_t)T * wf_elems(NP) * l.esz, 0, wf_overrun_elems() * l.esz, s));
+    CALLCHK(hipEventRecord(h->ev[4], s));
+    CALLCHK(hipEventRecord(h->ev[5], s));
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipStreamSynchronize(s));
     if (int rc = read_fit_times(h)) return rc;
     if (info != 0) {
         char buf[200];
@@ -693,7 +629,7 @@ int gpt_reserve(gpt_handle* h, int64_t M, int jacobian_variance) {
     if (M < 0) return fail(GPT_E_ARG, "gpt_reserve: bad query count");
     if (int rc = set_device(h)) return rc;
     if (M == 0) return GPT_OK;
-    HIPCHK(var_prepare(h->vws, h->stream, h->p, M, jacobian_variance ? var_fused_cols(h->p.D) : 1));
+    CALLCHK(var_prepare(h->vws, h->stream, h->p, M, jacobian_variance ? var_fused_cols(h->p.D) : 1));
     return GPT_OK;
 }
 
@@ -717,21 +653,21 @@ int gpt_predict_all_dev(gpt_handle* h, const void* Xq, int64_t M, void* mean, vo
     h->pred_mj = (mean || J);
     h->pred_var = (var || Jvar || dvar);
     if (h->pred_mj) {
-        if (prof) HIPCHK(hipEventRecord(h->pev[0], s));
+        if (prof) CALLCHK(hipEventRecord(h->pev[0], s));
         launch_mean_jac(s, h->p, h->dXs(), h->dA4(), Xq, M, mean, J);
-        if (prof) HIPCHK(hipEventRecord(h->pev[1], s));
+        if (prof) CALLCHK(hipEventRecord(h->pev[1], s));
     }
     if (h->pred_var) {
         // fused: k* and the D derivative columns of a query side by side; 3: Jacobian variance alone (no k* column, D <= 3)
         const int fused = var_fused_cols(h->p.D);
         const int alone = h->p.D <= 3 ? 3 : (h->p.D == 4 ? VAR_NCOMP_DERIV4 : (h->p.D == 8 ? VAR_NCOMP_DERIV8 : fused));
         const int ncomp = dvar ? fused : (Jvar ? (var ? fused : alone) : 1);
-        HIPCHK(var_prepare(h->vws, s, h->p, M, ncomp));
-        if (prof) HIPCHK(hipEventRecord(h->pev[2], s));
+        CALLCHK(var_prepare(h->vws, s, h->p, M, ncomp));
+        if (prof) CALLCHK(hipEventRecord(h->pev[2], s));
         launch_var(s, h->p, h->vws, h->dXs(), h->dWf(), Xq, M, ncomp, var, ncomp == 1 ? nullptr : Jvar, ncomp == 1 ? nullptr : dvar, h->dHdr());
-        if (prof) HIPCHK(hipEventRecord(h->pev[3], s));
+        if (prof) CALLCHK(hipEventRecord(h->pev[3], s));
     }
-    HIPCHK(hipGetLastError());
+    CALLCHK(hipGetLastError());
     return GPT_OK;
 }
 
@@ -765,27 +701,27 @@ int gpt_predict_all(gpt_handle* h, const void* Xq_, int64_t M, void* mean_, void
         const int b = (int)(i & 1);
         const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
         gpt_handle::Staging& t = h->st[b];
-        if (i >= 2) HIPCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
-        HIPCHK(hipMemcpyAsync(t.buf[ST_Q], Xq + (size_t)off * D * esz, (size_t)m * D * esz, hipMemcpyHostToDevice, s));
-        if (int rc = gpt_predict_all_dev(h, t.buf[ST_Q], m, mean ? t.buf[ST_MEAN] : nullptr, var ? t.buf[ST_VAR] : nullptr,
-                                         J ? t.buf[ST_J] : nullptr, Jvar ? t.buf[ST_JVAR] : nullptr, dvar ? t.buf[ST_DVAR] : nullptr))
+        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
+        CALLCHK(hipMemcpyAsync(t.buf[ST_Q], Xq + (size_t)off * D * esz, (size_t)m * D * esz, hipMemcpyHostToDevice, s));
+        if (int rc = gpt_predict_all_dev(h, t.buf[ST_Q], m, mean ? t.buf[ST_MEAN].p : nullptr, var ? t.buf[ST_VAR].p : nullptr,
+                                         J ? t.buf[ST_J].p : nullptr, Jvar ? t.buf[ST_JVAR].p : nullptr, dvar ? t.buf[ST_DVAR].p : nullptr))
             return rc;
-        if (!single) HIPCHK(hipEventRecord(h->ev_done[b], s));
+        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
         return GPT_OK;
     };
     auto copy_out = [&](int64_t i) -> int {
         const int b = (int)(i & 1);
         const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
         const gpt_handle::Staging& t = h->st[b];
-        if (!single) HIPCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
+        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
         unsigned char* const dst[ST_COUNT] = {nullptr, mean, var, J, Jvar, nullptr};
         for (int k = ST_MEAN; k <= ST_JVAR; ++k)
-            if (dst[k]) HIPCHK(hipMemcpyAsync(dst[k] + (size_t)off * per[k] * esz, t.buf[k], (size_t)m * per[k] * esz, hipMemcpyDeviceToHost, cs));
+            if (dst[k]) CALLCHK(hipMemcpyAsync(dst[k] + (size_t)off * per[k] * esz, t.buf[k], (size_t)m * per[k] * esz, hipMemcpyDeviceToHost, cs));
         if (dvar)
             for (size_t d = 0; d < D; ++d)   // device chunk is (D, m); host result is (D, M)
-                HIPCHK(hipMemcpyAsync(dvar + (d * (size_t)M + (size_t)off) * esz, static_cast<unsigned char*>(t.buf[ST_DVAR]) + d * (size_t)m * esz,
+                CALLCHK(hipMemcpyAsync(dvar + (d * (size_t)M + (size_t)off) * esz, static_cast<unsigned char*>(t.buf[ST_DVAR].p) + d * (size_t)m * esz,
                                       (size_t)m * esz, hipMemcpyDeviceToHost, cs));
-        if (!single) HIPCHK(hipEventRecord(h->ev_copied[b], cs));
+        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
         return GPT_OK;
     };
     if (int rc = enqueue(0)) return rc;
@@ -793,8 +729,8 @@ int gpt_predict_all(gpt_handle* h, const void* Xq_, int64_t M, void* mean_, void
         if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
         if (int rc = copy_out(i)) return rc;
     }
-    if (!single) HIPCHK(hipStreamSynchronize(cs));
-    HIPCHK(hipStreamSynchronize(s));
+    if (!single) CALLCHK(hipStreamSynchronize(cs));
+    CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }
 
@@ -816,16 +752,16 @@ static int fetch_alpha(gpt_handle* h, std::vector<double>& a4) {
     const size_t n = (size_t)h->lay.npass * NP * 4;
     a4.resize(n);
     if (h->have_W) {
-        HIPCHK(hipMemcpyAsync(a4.data(), h->dA64, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        CALLCHK(hipMemcpyAsync(a4.data(), h->ws->dA64, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CALLCHK(hipStreamSynchronize(h->stream));
     } else if (h->lay.dtype == DT_F32) {
         std::vector<float> af(n);
-        HIPCHK(hipMemcpyAsync(af.data(), h->dA4(), n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        CALLCHK(hipMemcpyAsync(af.data(), h->dA4(), n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        CALLCHK(hipStreamSynchronize(h->stream));
         for (size_t i = 0; i < n; ++i) a4[i] = af[i];
     } else {
-        HIPCHK(hipMemcpyAsync(a4.data(), h->dA4(), n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
+        CALLCHK(hipMemcpyAsync(a4.data(), h->dA4(), n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        CALLCHK(hipStreamSynchronize(h->stream));
     }
     return GPT_OK;
 }
@@ -836,10 +772,10 @@ int gpt_export(gpt_handle* h, double* L, double* alpha) {
     if (int rc = set_device(h)) return rc;
     const int64_t N = h->p.N, NP = h->p.NP;
     const int O = h->p.O;
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     if (L) {
         if (!h->have_L) return fail(GPT_E_STATE, "gpt_export: L is only available on the handle that ran gpt_fit (and before gpt_lml_gradient)");
-        HIPCHK(hipMemcpy2D(L, (size_t)N * sizeof(double), h->dK, (size_t)NP * sizeof(double), (size_t)N * sizeof(double),
+        CALLCHK(hipMemcpy2D(L, (size_t)N * sizeof(double), h->ws->dK, (size_t)NP * sizeof(double), (size_t)N * sizeof(double),
                            (size_t)N, hipMemcpyDeviceToHost));
         for (int64_t i = 0; i < N; ++i)
             for (int64_t j = i + 1; j < N; ++j) L[i * N + j] = 0.0;
@@ -859,8 +795,8 @@ int gpt_export_inverse_factor(gpt_handle* h, double* W) {
     if (!h->committed || !h->have_W) return fail(GPT_E_STATE, "gpt_export_inverse_factor: no factor on this handle");
     if (int rc = set_device(h)) return rc;
     const int64_t N = h->p.N, NP = h->p.NP;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy2D(W, (size_t)N * sizeof(double), h->dW, (size_t)NP * sizeof(double), (size_t)N * sizeof(double),
+    CALLCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipMemcpy2D(W, (size_t)N * sizeof(double), h->ws->dW, (size_t)NP * sizeof(double), (size_t)N * sizeof(double),
                        (size_t)N, hipMemcpyDeviceToHost));
     return GPT_OK;
 }
@@ -870,8 +806,8 @@ int gpt_lml(gpt_handle* h, double* lml) {
     if (!(h->committed || h->objective_ready) || !h->have_L || !h->have_W) return fail(GPT_E_STATE, "gpt_lml: needs the handle that ran gpt_fit");
     if (int rc = set_device(h)) return rc;
     enqueue_lml_scalars(h);
-    HIPCHK(hipMemcpyAsync(h->host_scal, h->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipMemcpyAsync(h->host_scal, h->ws->dscal, 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     *lml = lml_from_scalars(h, h->host_scal);
     return GPT_OK;
 }
@@ -894,24 +830,18 @@ int gpt_predict_cov(gpt_handle* h, const double* Xq, int64_t M, double* mean, do
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t b_q = al((size_t)M * D * sizeof(double)), b_k = al((size_t)NP * Mp * sizeof(double)),
                  b_vv = al((size_t)Mp * Mp * sizeof(double)), b_c = al((size_t)M * M * sizeof(double));
-    const size_t need = b_q + 2 * b_k + b_vv + b_c;
-    if (need > h->cov_cap) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (h->cov_buf) (void)hipFree(h->cov_buf);
-        h->cov_buf = nullptr; h->cov_cap = 0;
-        HIPCHK(hipMalloc(&h->cov_buf, need));
-        h->cov_cap = need;
-    }
-    double* dq = reinterpret_cast<double*>(h->cov_buf);
-    double* KsT = reinterpret_cast<double*>(h->cov_buf + b_q);
-    double* V = reinterpret_cast<double*>(h->cov_buf + b_q + b_k);
-    double* VtV = reinterpret_cast<double*>(h->cov_buf + b_q + 2 * b_k);
-    double* dcov = reinterpret_cast<double*>(h->cov_buf + b_q + 2 * b_k + b_vv);
-    HIPCHK(hipMemcpyAsync(dq, Xq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, s));
-    launch_cov(s, h->p, h->dXs64, h->dW, dq, M, Mp, KsT, V, VtV, dcov);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(cov, dcov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    CALLCHK(reserve(h->cov_buf, b_q + 2 * b_k + b_vv + b_c, s));
+    unsigned char* const cb = h->cov_buf;
+    double* dq = reinterpret_cast<double*>(cb);
+    double* KsT = reinterpret_cast<double*>(cb + b_q);
+    double* V = reinterpret_cast<double*>(cb + b_q + b_k);
+    double* VtV = reinterpret_cast<double*>(cb + b_q + 2 * b_k);
+    double* dcov = reinterpret_cast<double*>(cb + b_q + 2 * b_k + b_vv);
+    CALLCHK(hipMemcpyAsync(dq, Xq, (size_t)M * D * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_cov(s, h->p, h->ws->dXs64, h->ws->dW, dq, M, Mp, KsT, V, VtV, dcov);
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipMemcpyAsync(cov, dcov, (size_t)M * M * sizeof(double), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }
 
@@ -922,8 +852,8 @@ int gpt_lml_gradient(gpt_handle* h, double* lml, double* grad) {
     enqueue_lml_scalars(h);                                      // uses diag(L) in dK before it is overwritten
     h->have_L = false;                                           // L is gone: gpt_export(L) needs a new gpt_fit (W stays valid)
     if (int rc = enqueue_gradient_terms(h)) return rc;
-    HIPCHK(hipMemcpyAsync(h->host_scal, h->dscal, (2 + LML_TERMS) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipMemcpyAsync(h->host_scal, h->ws->dscal, (2 + LML_TERMS) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CALLCHK(hipStreamSynchronize(h->stream));
     *lml = lml_from_scalars(h, h->host_scal);
     gradient_from_scalars(h, h->host_scal + 2, grad);
     return GPT_OK;
@@ -942,9 +872,7 @@ int gpt_factor_alloc_model(gpt_handle* h, int64_t N, int D, int O, int n_tasks, 
     if (N < 1 || D < 1 || D > MAX_DIMS || O < 1 || n_tasks < 1 || n_tasks > MAX_TASKS || (dtype != GPT_F64 && dtype != GPT_F32))
         return fail(GPT_E_ARG, "gpt_factor_alloc: bad geometry");
     if (int rc = set_device(h)) return rc;
-    h->committed = false;
-    h->have_L = h->have_W = false;
-    h->objective_ready = false;
+    invalidate_model(h);
     if (int rc = ensure_blob(h, make_layout(N, D, O, n_tasks, dtype))) return rc;
     *dev_ptr = h->blob;
     *bytes = h->lay.total;
@@ -960,8 +888,8 @@ int gpt_factor_commit(gpt_handle* h) {
     if (!h->blob || !h->have_layout) return fail(GPT_E_STATE, "gpt_factor_commit: no model storage");
     if (int rc = set_device(h)) return rc;
     double hdr[HDR_DOUBLES];
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(hdr, h->blob, sizeof hdr, hipMemcpyDeviceToHost));
+    CALLCHK(hipStreamSynchronize(h->stream));
+    CALLCHK(hipMemcpy(hdr, h->blob, sizeof hdr, hipMemcpyDeviceToHost));
     if (hdr[0] != MAGIC) return fail(GPT_E_STATE, "gpt_factor_commit: blob has no model header (broadcast missing?)");
     if ((int64_t)hdr[1] != h->lay.N || (int)hdr[3] != h->lay.D || (int)hdr[4] != h->lay.O || (int64_t)hdr[2] != h->lay.NP ||
         (int)hdr[14] != h->lay.ntask || (int)hdr[15] != h->lay.dtype)
@@ -977,18 +905,16 @@ int gpt_factor_copy(gpt_handle* dst, gpt_handle* src) {
     if (!src->committed || !src->blob) return fail(GPT_E_STATE, "gpt_factor_copy: source handle holds no fitted model");
     // the source's kernels (fit, pack) have to be done before another device reads the blob
     if (int rc = set_device(src)) return rc;
-    HIPCHK(hipStreamSynchronize(src->stream));
+    CALLCHK(hipStreamSynchronize(src->stream));
     double hdr[HDR_DOUBLES];
-    HIPCHK(hipMemcpy(hdr, src->blob, sizeof hdr, hipMemcpyDeviceToHost));
+    CALLCHK(hipMemcpy(hdr, src->blob, sizeof hdr, hipMemcpyDeviceToHost));
     if (hdr[0] != MAGIC) return fail(GPT_E_STATE, "gpt_factor_copy: source blob has no model header");
     const Layout l = src->lay;
     if (int rc = set_device(dst)) return rc;
-    dst->committed = false;
-    dst->have_L = dst->have_W = false;
-    dst->objective_ready = false;
+    invalidate_model(dst);
     if (int rc = ensure_blob(dst, l)) return rc;
     if (dst->device == src->device) {
-        HIPCHK(hipMemcpyAsync(dst->blob, src->blob, l.total, hipMemcpyDeviceToDevice, dst->stream));
+        CALLCHK(hipMemcpyAsync(dst->blob, src->blob, l.total, hipMemcpyDeviceToDevice, dst->stream));
     } else {
         // device to device over xGMI (peer access is enabled on demand; without it the runtime stages through the host)
         int can = 0;
@@ -997,9 +923,9 @@ int gpt_factor_copy(gpt_handle* dst, gpt_handle* src) {
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
             else (void)hipGetLastError();
         }
-        HIPCHK(hipMemcpyPeerAsync(dst->blob, dst->device, src->blob, src->device, l.total, dst->stream));
+        CALLCHK(hipMemcpyPeerAsync(dst->blob, dst->device, src->blob, src->device, l.total, dst->stream));
     }
-    HIPCHK(hipStreamSynchronize(dst->stream));
+    CALLCHK(hipStreamSynchronize(dst->stream));
     fill_params(dst, hdr);
     dst->committed = true;
     return GPT_OK;
@@ -1036,13 +962,13 @@ int gpt_predict_timings(gpt_handle* h, double* ms_out) {
     ms_out[0] = ms_out[1] = 0.0;
     float ms = 0;
     if (h->pred_mj) {
-        HIPCHK(hipEventSynchronize(h->pev[1]));
-        HIPCHK(hipEventElapsedTime(&ms, h->pev[0], h->pev[1]));
+        CALLCHK(hipEventSynchronize(h->pev[1]));
+        CALLCHK(hipEventElapsedTime(&ms, h->pev[0], h->pev[1]));
         ms_out[0] = ms;
     }
     if (h->pred_var) {
-        HIPCHK(hipEventSynchronize(h->pev[3]));
-        HIPCHK(hipEventElapsedTime(&ms, h->pev[2], h->pev[3]));
+        CALLCHK(hipEventSynchronize(h->pev[3]));
+        CALLCHK(hipEventElapsedTime(&ms, h->pev[2], h->pev[3]));
         ms_out[1] = ms;
     }
     return GPT_OK;

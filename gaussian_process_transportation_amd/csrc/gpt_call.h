@@ -1,7 +1,8 @@
-// Host helpers of a one-shot C entry point (internal header): a call without a handle, which validates host arrays, opens a
-// stream, allocates, enqueues its whole schedule, reads back and frees.  Used by gpt_svgp_train.hip, gpt_svgp_surface.hip,
-// gpt_select.hip and gpt_debug_dgemm (gpt_fit.hip); gpt_api.hip keeps its own (the sanitizer build compiles it against
-// host_stub/, which this header is not written for).
+// Host helpers of the C entry points (internal header).  fail() and CALLCHK serve every unit, gpt_api.hip included (so this
+// header also compiles under g++ against host_stub/, the sanitizer build).  The rest is for a one-shot call without a handle,
+// which validates host arrays, opens a stream, allocates, enqueues its whole schedule, reads back and frees: gpt_svgp_train.hip,
+// gpt_svgp_surface.hip, gpt_select.hip and gpt_debug_dgemm (gpt_fit.hip).  A handle's long-lived resources have owners of
+// their own: DevBuf, Stream and Event in gpt_common.h.
 #pragma once
 #include "gpt_common.h"
 #include "../../include/gpt_hip.h"

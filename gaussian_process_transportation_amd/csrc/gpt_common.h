@@ -5,6 +5,7 @@
 #include <mutex>
 #include <cstdint>
 #include <cstddef>
+#include <memory>
 
 namespace gpt {
 
@@ -63,6 +64,44 @@ struct PerDeviceOnce {
     // restarts) wait until it has finished, so nobody launches a kernel before its attributes are set
     template <class F> void run(F&& f) { std::call_once(flags[current_device()], f); }
 };
+
+// ---- owners of device resources: whoever holds one releases it, on every path ---------
+// Device memory: pointer + size in bytes, freed by the destructor.  Reads as a T* wherever one is expected.
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+    operator T*() const { return p; }
+};
+// Makes `buf` hold at least `need` bytes (contents are not kept).  Nothing happens when it already does; otherwise the
+// streams whose work may still use the old memory are synchronised (a null stream: the caller has already waited), the old
+// memory is freed and the new allocated.  After a failed allocation the buffer is empty.
+template <class T> hipError_t reserve(DevBuf<T>& buf, size_t need, hipStream_t stream, hipStream_t stream2 = nullptr) {
+    if (need <= buf.bytes) return hipSuccess;
+    for (hipStream_t s : {stream, stream2})
+        if (s) { if (hipError_t e = hipStreamSynchronize(s)) return e; }
+    buf.release();
+    void* q = nullptr;
+    if (hipError_t e = hipMalloc(&q, need)) return e;
+    buf.p = static_cast<T*>(q);
+    buf.bytes = need;
+    return hipSuccess;
+}
+// A stream or an event, destroyed with its owner; reads as the plain handle.
+template <class H, hipError_t (*destroy)(H)> struct Owned {
+    H h = nullptr;
+    Owned() = default;
+    Owned(const Owned&) = delete;
+    Owned& operator=(const Owned&) = delete;
+    ~Owned() { if (h) (void)destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
 
 // The calling thread's gpt_last_error() text (gpt_api.hip), for the C entry points of the other units.
 void set_last_error(const char* msg);
@@ -131,11 +170,10 @@ void launch_mean_jac(hipStream_t s, const KernelParams& p, const void* Xs, const
 // Scratch of the variance kernel, owned by a handle (grow-only) and the cached work plan of the last launch shape.
 struct VarPlanHost;
 struct VarWorkspace {
-    void *slab = nullptr, *vslab = nullptr, *bscratch = nullptr, *plan_dev = nullptr;
-    size_t slab_bytes = 0, vslab_bytes = 0, bscratch_bytes = 0, plan_bytes = 0;
-    VarPlanHost* plan = nullptr;            // host copy of the plan resident in plan_dev
+    DevBuf<void> slab, vslab, bscratch, plan_dev;
+    std::unique_ptr<VarPlanHost> plan;      // host copy of the plan resident in plan_dev
     int64_t key_cols = -1; int key_nbi = 0, key_ntask = 0, key_P = 0;
-    int64_t allocs = 0;                     // number of (re)allocations so far (tests / gpt_reserve)
+    ~VarWorkspace();                        // gpt_api.hip, where VarPlanHost is complete
 };
 // Builds (or re-uses) the plan for M queries x `ncomp` columns and makes every buffer large enough; may synchronise
 // `s` and reallocate.  Call before launch_var with the same arguments.
@@ -143,7 +181,6 @@ hipError_t var_prepare(VarWorkspace& ws, hipStream_t s, const KernelParams& p, i
 // hdr: the model blob's header (device), hdr[16 + t] = prior variance of task t.
 void launch_var(hipStream_t s, const KernelParams& p, const VarWorkspace& ws, const void* Xs, const void* Wf,
                 const void* Xq, int64_t M, int ncomp, void* var, void* Jvar, void* dvar, const double* hdr);
-void var_release(VarWorkspace& ws);
 int var_workgroups();
 
 size_t wf_elems(int NP);          // elements of ONE task's tile set (+ prefetch overrun after the last task: wf_overrun_elems)

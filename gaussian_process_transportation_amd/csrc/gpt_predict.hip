@@ -353,9 +353,9 @@ static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspac
     const VarPlanDev& pl_all = ws.plan->d;
     constexpr size_t lds = var_lds_bytes<T>();
     var_kernel_setup<T>();
-    T* slab = static_cast<T*>(ws.slab);
-    T* vslab = static_cast<T*>(ws.vslab);
-    T* bscr = static_cast<T*>(ws.bscratch);
+    T* slab = static_cast<T*>(ws.slab.p);
+    T* vslab = static_cast<T*>(ws.vslab.p);
+    T* bscr = static_cast<T*>(ws.bscratch.p);
     const dim3 grid((unsigned)pl_all.P), fgrid((unsigned)pl_all.ncb), cgrid((unsigned)pl_all.n_splits * VAR_SPLIT_SLOTS);
     const bool wide = p.D > 3, wide16 = p.D > WIDE_D;
     const bool cross = ncomp >= 4 && dvar != nullptr;

@@ -74,28 +74,26 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
     const VarPlanHost& pl = *ws.plan;
     touch_r(Xs, (size_t)p.NP * xs_stride(p.D) * e); touch_r(Xq, (size_t)M * p.D * e); touch_r(hdr, (16 + p.ntask) * 8);
     touch_r(Wf, ((size_t)p.ntask * wf_elems(p.NP) + wf_overrun_elems()) * e);
-    unsigned char* base = static_cast<unsigned char*>(ws.plan_dev);                   // the uploaded image, as the kernels index it
     const int* item_begin = pl.d.item_begin;
     touch_r(item_begin, (size_t)(pl.d.P + 1) * 4);
-    (void)base;
     for (int q = 0; q < pl.d.P; ++q) {
-        touch_w(static_cast<unsigned char*>(ws.bscratch) + (size_t)q * p.NP * VAR_COLS * e, (size_t)p.NP * VAR_COLS * e);
+        touch_w(static_cast<unsigned char*>(ws.bscratch.p) + (size_t)q * p.NP * VAR_COLS * e, (size_t)p.NP * VAR_COLS * e);
         for (int i = item_begin[q]; i < item_begin[q + 1]; ++i) {
             const VarItem it = pl.d.items[i];
-            if (it.vslot >= 0) touch_w(static_cast<unsigned char*>(ws.vslab) + (size_t)it.vslot * VAR_VSLOT * e, (size_t)VAR_VSLOT * e);
-            if (it.slot >= 0) touch_w(static_cast<unsigned char*>(ws.slab) + (size_t)it.slot * VAR_SLOT * e, (size_t)VAR_SLOT * e);
+            if (it.vslot >= 0) touch_w(static_cast<unsigned char*>(ws.vslab.p) + (size_t)it.vslot * VAR_VSLOT * e, (size_t)VAR_VSLOT * e);
+            if (it.slot >= 0) touch_w(static_cast<unsigned char*>(ws.slab.p) + (size_t)it.slot * VAR_SLOT * e, (size_t)VAR_SLOT * e);
         }
     }
     touch_w(ws.slab, (size_t)pl.d.nfull * p.ntask * VAR_SLOT * e);
     for (int i = 0; i < pl.d.n_splits; ++i) {
         const VarSplit sp = pl.d.splits[i];
-        touch_r(static_cast<unsigned char*>(ws.vslab) + (size_t)sp.v_begin * VAR_VSLOT * e, (size_t)(sp.v_end - sp.v_begin) * VAR_VSLOT * e);
-        touch_w(static_cast<unsigned char*>(ws.slab) + (size_t)sp.slot * VAR_SLOT * e, (size_t)VAR_SPLIT_SLOTS * VAR_SLOT * e);
+        touch_r(static_cast<unsigned char*>(ws.vslab.p) + (size_t)sp.v_begin * VAR_VSLOT * e, (size_t)(sp.v_end - sp.v_begin) * VAR_VSLOT * e);
+        touch_w(static_cast<unsigned char*>(ws.slab.p) + (size_t)sp.slot * VAR_SLOT * e, (size_t)VAR_SPLIT_SLOTS * VAR_SLOT * e);
     }
     for (int64_t c = 0; c < pl.d.ncb - pl.d.nfull; ++c)
         for (int t = 0; t < p.ntask; ++t) {
             const int b = pl.d.fin[2 * (c * p.ntask + t)], en = pl.d.fin[2 * (c * p.ntask + t) + 1];
-            touch_r(static_cast<unsigned char*>(ws.slab) + (size_t)b * VAR_SLOT * e, (size_t)(en - b) * VAR_SLOT * e);
+            touch_r(static_cast<unsigned char*>(ws.slab.p) + (size_t)b * VAR_SLOT * e, (size_t)(en - b) * VAR_SLOT * e);
         }
     (void)var_cols_per_query(p.D, ncomp);
     touch_w(var, (size_t)M * p.ntask * e); touch_w(Jvar, (size_t)M * p.ntask * p.D * e); touch_w(dvar, (size_t)M * p.D * e);
@@ -108,6 +106,8 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
 // this build; their entry points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this
 // library too.
 #include "../../../include/gpt_hip.h"
+// Stub only: allocations, streams and events created and not yet released (tests/asan_driver.py).
+extern "C" long gpt_stub_live_objects(void) { return stub_live_objects; }
 extern "C" int gpt_svgp_train(int, const double*, const double*, int64_t, int, int, int, double*, double*, double*, double*, double*,
                               double*, const int64_t*, int64_t, const int64_t*, int64_t, double, double*) {
     gpt::set_last_error("gpt_svgp_train: not in the host sanitizer build");

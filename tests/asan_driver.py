@@ -2,6 +2,9 @@
 C ABI's host orchestration (GPT_HIP_LIB = csrc/build/libgpt_host_asan.so: g++ -fsanitize=address,undefined, inert HIP
 runtime and kernel stand-ins that touch the memory the real kernels would) through its argument checks, state
 machine, staging, hand-off and work-plan paths.  Outputs are meaningless; AddressSanitizer / UBSan abort on a finding."""
+import ctypes
+import gc
+
 import numpy as np
 
 from gaussian_process_transportation_amd import _lib
@@ -9,7 +12,12 @@ from gaussian_process_transportation_amd import _lib
 rng = np.random.default_rng(0)
 lib = _lib.load()
 assert b"gfx950" in lib.gpt_version()
+lib.gpt_stub_live_objects.restype = ctypes.c_long       # allocations, streams and events alive in the stand-in runtime
+assert lib.gpt_stub_live_objects() == 0
 h = _lib.Handle(0)
+live = lib.gpt_stub_live_objects()
+_lib.Handle(0).close()                                  # an unused handle gives back everything it created
+assert lib.gpt_stub_live_objects() == live, (lib.gpt_stub_live_objects(), live)
 for bad in (lambda: _lib.Handle(3), lambda: h.predict_all(np.zeros((2, 3)), mean=True), lambda: h.export(), lambda: h.reserve(10),
             lambda: h.fit(np.zeros((3, 2)), np.zeros((4, 2)), [1.0], 1.0, 0.1, 0.0),
             lambda: h.fit(np.zeros((3, 2)), np.zeros((3, 2)), [1.0, 1.0, 1.0], 1.0, 0.1, 0.0),
@@ -107,7 +115,6 @@ for dtype in (_lib.GPT_F32, _lib.GPT_F64):
     src, nbytes = h.factor_blob()
     dst, nbytes2 = h2.factor_alloc(Z, D, T, T, dtype)
     assert nbytes == nbytes2
-    import ctypes
     ctypes.memmove(dst, src, nbytes)
     h2.factor_commit()
     assert h2.model_info() == (T, dtype) and h2.info() == h.info()
@@ -122,4 +129,6 @@ except ValueError:
 pl = _lib.debug_var_plan(123_456, 7, 3, 256)
 assert pl["n_items"] > 0
 h.close()
+gc.collect()                                            # the handles that were only ever temporaries
+assert lib.gpt_stub_live_objects() == 0, f"{lib.gpt_stub_live_objects()} device objects outlive their handles"
 print("ASAN_DRIVER_OK")
