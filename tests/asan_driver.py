@@ -71,6 +71,42 @@ for N, D, O in ((1, 1, 1), (700, 3, 3), (1100, 2, 6), (530, 5, 5), (200, 8, 2), 
         h.fit_timings()
 h.set_dtype(_lib.GPT_F64)
 
+# one handle through the fits of tests/test_covariance_and_handle_reuse.py (its steps 1 - 3, 6, 11, 13 and 14, in this order): the
+# grow / keep / rebuild decisions on the workspace and the blob, the mirror compares and the frees, with every output read once
+def reuse_fit(N, D, O, X=None, noise=1e-2, jitter=1e-10):
+    X = rng.uniform(0, 1, (N, D)) if X is None else X
+    Y = rng.standard_normal((N, O))
+    try:
+        h.fit(X, Y, np.full(D, 0.3), 1.3, noise, jitter)
+    except np.linalg.LinAlgError:                       # (the stand-in factorisation reports no pivot; the device does)
+        return X
+    h.export(); h.export_inverse_factor(); h.lml()
+    for M in (700, 70):
+        h.predict_all(rng.uniform(0, 1, (M, D)), mean=True, var=True, J=True, Jvar=True, dvar=True)
+    h.predict_cov(rng.uniform(0, 1, (130, D)))
+    h.lml_gradient(D)
+    return X
+
+reuse_fit(600, 3, 5)                                    # padded size past 512, two output passes
+reuse_fit(300, 3, 5)                                    # smaller padded size: the workspace is rebuilt
+X3 = reuse_fit(280, 3, 2)                               # same padded size, fewer passes: the workspace is kept
+reuse_fit(420, 2, 2, X=np.ascontiguousarray(X3.reshape(420, 2)))     # as many doubles, other N and D: the X mirror must miss
+Sig3 = 1e-2 * np.eye(280) * np.ones((3, 1, 1))
+h.fit_svgp(X3, rng.standard_normal((3, 280)), Sig3, np.full(3, 0.3), np.ones(3))
+h.predict_all(rng.uniform(0, 1, (700, 3)), mean=True, var=True, J=True, Jvar=True)
+Xdup = X3.copy(); Xdup[200:] = Xdup[:80]
+reuse_fit(280, 3, 2, X=Xdup, noise=0.0, jitter=0.0)     # singular on the device (GPT_E_NOT_PD)
+reuse_fit(280, 3, 2, X=X3)
+reuse_fit(280, 12, 2)                                   # source rows of 16 at the same padded size
+reuse_fit(280, 3, 2, X=X3)
+for M in (385, 12, 385, 0):                             # the grow-only covariance scratch, laid out per call
+    h.predict_cov(rng.uniform(0, 1, (M, 3)))
+live_before = lib.gpt_stub_live_objects()
+one = np.zeros(1)
+rc = lib.gpt_predict_cov(h._h, _lib.dptr(np.zeros((16385, 3))), 16385, None, _lib.dptr(one))
+assert rc == _lib.GPT_E_ARG, rc                         # refused before anything is allocated or written
+assert lib.gpt_stub_live_objects() == live_before
+
 # a size the multi-stream forms of the factor + inverse run at (csrc/gpt_fit_plan.h): the stand-in replays every scratch region of
 # the plan inside the arena the orchestration allocated — with the plan changing under the handle between two fits
 import os
