@@ -50,7 +50,7 @@ inline int var_fused_cols(int D) { return D <= 3 ? 4 : (D <= 7 ? 8 : 16); }
 constexpr int VAR_NCOMP_DERIV4 = 104, VAR_NCOMP_DERIV8 = 108;
 inline int var_cols_per_query(int D, int ncomp) { return ncomp == 3 ? D : (ncomp > 100 ? ncomp - 100 : ncomp); }
 
-// Per-device one-time setup (hipFuncSetAttribute opt-ins, CU counts): a process may hold handles on several devices
+// Per-device one-time setup (the dynamic-LDS opt-in of launch_lds, gpt_dispatch.h; CU counts): a process may hold handles on several devices
 // (gpt_create takes a device), so "done once" has to mean once per device, not once per process.
 constexpr int MAX_DEVICES = 64;
 inline int current_device() {

@@ -7,6 +7,7 @@
 // the diagonal, cholesky, cho_solve) and models/gaussian_process.py:42-43 (explicit K^-1, here
 // kept as its triangular factor W = L^-1 so that k^T K^-1 k = |W k|^2).
 #include "gpt_call.h"
+#include "gpt_dispatch.h"
 #include "gpt_exp.h"
 #include "gpt_fit_plan.h"
 #include <cstdint>
@@ -74,9 +75,7 @@ __global__ __launch_bounds__(256) void k_gram(const double* __restrict__ Xs, int
 
 void launch_gram(hipStream_t s, const double* Xs, int D, int N, int NP, int ktype, double c, double diag_add, double* K) {
     dim3 grid(NP / 64, NP / 64);
-    if (D <= 3) hipLaunchKernelGGL(k_gram<3>, grid, dim3(256), 0, s, Xs, N, NP, ktype, c, diag_add, K);
-    else if (D <= WIDE_D) hipLaunchKernelGGL(k_gram<WIDE_D>, grid, dim3(256), 0, s, Xs, N, NP, ktype, c, diag_add, K);
-    else hipLaunchKernelGGL(k_gram<MAX_D>, grid, dim3(256), 0, s, Xs, N, NP, ktype, c, diag_add, K);
+    with_coord_width(D, [&](auto dw) { hipLaunchKernelGGL(k_gram<decltype(dw)::value>, grid, dim3(256), 0, s, Xs, N, NP, ktype, c, diag_add, K); });
 }
 
 // Xs[i][d] = X[i][d] / l_d for i < N, d < D, zero elsewhere (rows of 4 or 8: xs_stride): the fp64 image the fit kernels
@@ -100,8 +99,9 @@ void launch_scale_x(hipStream_t s, const double* X, int N, int NP, int D, const 
     InvLs il;
     for (int d = 0; d < MAX_D; ++d) il.v[d] = inv_ls[d];
     const dim3 grid((NP + 255) / 256);
-    if (dtype == DT_F32) hipLaunchKernelGGL(k_scale_x<float>, grid, dim3(256), 0, s, X, N, NP, D, xs_stride(D), il, Xs64, static_cast<float*>(Xm));
-    else hipLaunchKernelGGL(k_scale_x<double>, grid, dim3(256), 0, s, X, N, NP, D, xs_stride(D), il, Xs64, static_cast<double*>(Xm));
+    with_elem_type(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_scale_x<decltype(t)>, grid, dim3(256), 0, s, X, N, NP, D, xs_stride(D), il, Xs64, static_cast<decltype(t)*>(Xm));
+    });
 }
 
 // out[0] = sum_i a[i] b[i], one workgroup, fixed order (deterministic): sum_o y_o^T alpha_o of the LML over the padded
@@ -792,9 +792,7 @@ static void launch_gemm_ts(hipStream_t s, const GemmArgs& g) {
         if (gemm_body() != 0) { launch_gemm_variant<BT, AT, TS>(s, g, q, lds); return; }
     }
 #endif
-    static PerDeviceOnce once;
-    once.run([&] { hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm<BT, AT, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    hipLaunchKernelGGL((k_gemm<BT, AT, TS>), dim3(q.nvid), dim3(256), lds, s, g, q.TM, q.TN, q.G, q.fold_tm);
+    launch_lds<k_gemm<BT, AT, TS>>(dim3(q.nvid), dim3(256), lds, s, g, q.TM, q.TN, q.G, q.fold_tm);
 }
 
 // 64-tiles below this many 128-tiles (measured: equal within noise from 2500 up, tools/gpu_fit_ab.sh; a 4096^3 product runs at 64.6 vs 66.3 TFLOP/s)
@@ -871,12 +869,6 @@ static void potrf_groups(hipStream_t s, double* K, double* W, int NP, int* info,
     const int nb = row_blk_end;
     const int ob = potrf_outer_blocks();
     constexpr size_t step_lds = (size_t)(2 * NB * PS) * sizeof(double);
-    constexpr size_t fin_lds = (size_t)(2 * NB * DS) * sizeof(double);
-    static PerDeviceOnce once;
-    once.run([&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_potrf_finish), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds);
-    });
     // Third level: panels are grouped by `grp`.  Inside a group a panel's own columns receive the group's earlier panels
     // just before its steps (a thin GEMM, K = up to (grp-1) panels); everything behind the group is updated once per
     // group with K = grp panels — the read-modify-write of the trailing matrix, which bounds the rank-128 update
@@ -892,7 +884,7 @@ static void potrf_groups(hipStream_t s, double* K, double* W, int NP, int* info,
             const int pend = p0 + ob < gend ? p0 + ob : gend;
             if (p0 > g0) syrk(p0 * NB, (pend - p0) * NB, g0 * NB, (p0 - g0) * NB);   // this panel's columns <- earlier panels of the group
             for (int kb = p0; kb < pend; ++kb)
-                hipLaunchKernelGGL(k_potrf_step, dim3(nb - kb), dim3(256), step_lds, s, K, W, NP, kb, p0, info GPT_TRACE_NULL);
+                launch_lds<k_potrf_step>(dim3(nb - kb), dim3(256), step_lds, s, K, W, NP, kb, p0, info GPT_TRACE_NULL);
         }
         syrk(gend * NB, nb * NB - gend * NB, g0 * NB, (gend - g0) * NB);             // everything behind the group
     }
@@ -901,7 +893,7 @@ static void potrf_groups(hipStream_t s, double* K, double* W, int NP, int* info,
 // diagonal blocks [b0, b1): parked L_kk from W into K, inv(L_kk) into W (the seeds of the triangular inverse)
 static void potrf_finish(hipStream_t s, double* K, double* W, int NP, int b0, int b1) {
     constexpr size_t fin_lds = (size_t)(2 * NB * DS) * sizeof(double);
-    if (b1 > b0) hipLaunchKernelGGL(k_potrf_finish, dim3(b1 - b0), dim3(256), fin_lds, s, K, W, NP, b0);
+    if (b1 > b0) launch_lds<k_potrf_finish>(dim3(b1 - b0), dim3(256), fin_lds, s, K, W, NP, b0);
 }
 
 // =====================================================================================
@@ -1222,15 +1214,11 @@ __global__ __launch_bounds__(256) void k_pack_w(const double* __restrict__ W, in
 void launch_pack_w(hipStream_t s, const double* W, int N, int NP, void* Wf, int dtype, int task, double scale) {
     const int nbt = NP / WT;
     const size_t lds = (size_t)PKR * PK_S * sizeof(double);
-    static PerDeviceOnce once;
-    once.run([&] {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_pack_w<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(k_pack_w<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    });
     const dim3 grid(nbt * (WT / PKC), nbt * (WT / PKR));
     const size_t off = (size_t)task * wf_elems(NP);
-    if (dtype == DT_F32) hipLaunchKernelGGL(k_pack_w<float>, grid, dim3(256), lds, s, W, N, NP, static_cast<float*>(Wf) + off, scale);
-    else hipLaunchKernelGGL(k_pack_w<double>, grid, dim3(256), lds, s, W, N, NP, static_cast<double*>(Wf) + off, scale);
+    with_elem_type(dtype, [&](auto t) {
+        launch_lds<k_pack_w<decltype(t)>>(grid, dim3(256), lds, s, W, N, NP, static_cast<decltype(t)*>(Wf) + off, scale);
+    });
 }
 
 // dst[r][dst_col0 + c] = src[r][src_col0 + c] * scale for c < ncol: moves alpha columns from the fp64 fit workspace into
@@ -1246,8 +1234,9 @@ __global__ __launch_bounds__(256) void k_store4(const double* __restrict__ src4,
 
 void launch_store4(hipStream_t s, const double* src4, int rows, void* dst4, int dtype, int src_col0, int dst_col0, int ncol, double scale) {
     const dim3 grid((rows + 255) / 256);
-    if (dtype == DT_F32) hipLaunchKernelGGL(k_store4<float>, grid, dim3(256), 0, s, src4, rows, static_cast<float*>(dst4), src_col0, dst_col0, ncol, scale);
-    else hipLaunchKernelGGL(k_store4<double>, grid, dim3(256), 0, s, src4, rows, static_cast<double*>(dst4), src_col0, dst_col0, ncol, scale);
+    with_elem_type(dtype, [&](auto t) {
+        hipLaunchKernelGGL(k_store4<decltype(t)>, grid, dim3(256), 0, s, src4, rows, static_cast<decltype(t)*>(dst4), src_col0, dst_col0, ncol, scale);
+    });
 }
 
 // =====================================================================================
@@ -1367,16 +1356,11 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__
 void launch_lml_terms(hipStream_t s, const double* Xs, int D, const double* A4, int npass, const double* Kinv, int N, int NP,
                       int O, int ktype, double c, double* partial, double* out) {
     const int nb = NP / 64;
-    if (D <= 3) {
-        hipLaunchKernelGGL(k_lml_terms<3>, dim3(nb, nb), dim3(256), 0, s, Xs, A4, npass, Kinv, N, NP, O, ktype, c, partial);
-        hipLaunchKernelGGL(k_sum_partials<3>, dim3(1), dim3(256), 0, s, partial, nb * nb, out);
-    } else if (D <= WIDE_D) {
-        hipLaunchKernelGGL(k_lml_terms<WIDE_D>, dim3(nb, nb), dim3(256), 0, s, Xs, A4, npass, Kinv, N, NP, O, ktype, c, partial);
-        hipLaunchKernelGGL(k_sum_partials<WIDE_D>, dim3(1), dim3(256), 0, s, partial, nb * nb, out);
-    } else {
-        hipLaunchKernelGGL(k_lml_terms<MAX_D>, dim3(nb, nb), dim3(256), 0, s, Xs, A4, npass, Kinv, N, NP, O, ktype, c, partial);
-        hipLaunchKernelGGL(k_sum_partials<MAX_D>, dim3(1), dim3(256), 0, s, partial, nb * nb, out);
-    }
+    with_coord_width(D, [&](auto dw) {
+        constexpr int DW = decltype(dw)::value;
+        hipLaunchKernelGGL(k_lml_terms<DW>, dim3(nb, nb), dim3(256), 0, s, Xs, A4, npass, Kinv, N, NP, O, ktype, c, partial);
+        hipLaunchKernelGGL(k_sum_partials<DW>, dim3(1), dim3(256), 0, s, partial, nb * nb, out);
+    });
 }
 
 // =====================================================================================

@@ -3,6 +3,7 @@
 // build compiles the two at the same time).
 #pragma once
 #include "gpt_common.h"
+#include "gpt_dispatch.h"
 #include "gpt_exp.h"
 #include "gpt_plan.h"
 #include <type_traits>
@@ -927,9 +928,43 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
 #endif
 }
 
+// The one choice of k_var's instantiation <T, NCOMP, CROSS, KT, DW, KSTAR, HALF>, and its launch with arguments `a`.  A unit
+// instantiates one side of it per kernel type: DERIV = false, k* alone (ncomp == 1: every kernel type, gpt_predict.hip), or DERIV =
+// true, the derivative-column shapes (the other `ncomp` codes of gpt_common.h: RBF in gpt_predict.hip, Matern 3/2 and 5/2 in
+// gpt_predict_matern.hip; Matern 1/2 has none, the API refuses its derivatives).  diag_half: launch_var_t.
+template <typename T, int KT, bool DERIV, class... A>
+void launch_kvar(int ncomp, bool cross, int D, bool diag_half, dim3 grid, hipStream_t s, A... a) {
+    auto one = [&](auto nc, auto cr, auto dw, auto kstar) {
+        constexpr int NC = decltype(nc)::value, DW = decltype(dw)::value;
+        constexpr bool CR = decltype(cr)::value, KS = decltype(kstar)::value;
+        // HALF exists for fp64 alone (launch_var_t), and not: at ncomp == 3 (at the register limit it keeps a spilled pointer inside
+        // the lock-step loop), for rows of 16, without the k* column, for Matern derivatives (the plain kernel runs at every model size)
+        if constexpr (std::is_same<T, double>::value && NC != 3 && DW != MAX_D && KS && (NC == 1 || KT == KT_RBF)) {
+            if (diag_half) { launch_lds<k_var<T, NC, CR, KT, DW, KS, true>>(grid, dim3(512), var_lds_bytes<T>(), s, a...); return; }
+        }
+        launch_lds<k_var<T, NC, CR, KT, DW, KS, false>>(grid, dim3(512), var_lds_bytes<T>(), s, a...);
+    };
+    constexpr Bool<true> yes{};
+    constexpr Bool<false> no{};
+    if constexpr (!DERIV) {
+        with_coord_width(D, [&](auto dw) { one(Int<1>{}, no, dw, yes); });
+    } else {
+        static_assert(KT != KT_MATERN12, "Matern 1/2 has no derivative columns");
+        // a fused layout (k*, dk_0 .. dk_{D-1} per query), with the cross products k* . dk_d for d var or without
+        auto fused = [&](auto nc, auto dw) { if (cross) one(nc, yes, dw, yes); else one(nc, no, dw, yes); };
+        if (ncomp == 3) one(Int<3>{}, no, Int<3>{}, yes);                           // Jacobian variance alone, D <= 3: D columns per query
+        else if (ncomp == VAR_NCOMP_DERIV4) one(Int<4>{}, no, Int<WIDE_D>{}, no);   // Jacobian variance alone, D = 4: dk_0 .. dk_3
+        else if (ncomp == VAR_NCOMP_DERIV8) one(Int<8>{}, no, Int<WIDE_D>{}, no);   // Jacobian variance alone, D = 8
+        else if (ncomp == 4) fused(Int<4>{}, Int<3>{});                             // D <= 3
+        else if (ncomp == 8) fused(Int<8>{}, Int<WIDE_D>{});                        // D = 4 .. 7
+        else if (D <= WIDE_D) fused(Int<16>{}, Int<WIDE_D>{});                      // D = 8
+        else fused(Int<16>{}, Int<MAX_D>{});                                        // D = 9 .. 15
+    }
+}
+
 // gpt_predict_matern.hip: k_var launches with derivative columns (ncomp > 1) of a Matern 3/2 or 5/2 model
 template <typename T>
-void launch_var_matern(hipStream_t s, const KernelParams& p, const VarPlanDev& pl, int ncomp, bool cross, dim3 grid, size_t lds,
+void launch_var_matern(hipStream_t s, const KernelParams& p, const VarPlanDev& pl, int ncomp, bool cross, dim3 grid,
                        const T* Xs, const T* Wf, const T* Xq, int64_t M, T* slab, T* vslab, T* bscr);
 
 }  // namespace gpt

@@ -172,49 +172,32 @@ static void launch_mean_jac_t(hipStream_t s, const KernelParams& p, const T* Xs,
         const int cnt = (p.O - ob) < 4 ? (p.O - ob) : 4;
         const T* a4 = A4 + (size_t)(ob / 4) * p.NP * 4;
         const dim3 grid((unsigned)blocks);
-#define GPT_MJ(OC_, KT_)                                                                                                          \
-        do {                                                                                                                      \
-            if (J) hipLaunchKernelGGL((k_mean_jac<T, QPW, OC_, KT_, DW, true>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J); \
-            else if (many) hipLaunchKernelGGL((k_mean_jac<T, QPW_M, OC_, KT_, DW, false>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J); \
-            else hipLaunchKernelGGL((k_mean_jac<T, QPW, OC_, KT_, DW, false>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J);  \
-        } while (0)
-#define GPT_MJ_K(OC_)                                     \
-        switch (p.ktype) {                                 \
-            case KT_MATERN12: GPT_MJ(OC_, KT_MATERN12); break; \
-            case KT_MATERN32: GPT_MJ(OC_, KT_MATERN32); break; \
-            case KT_MATERN52: GPT_MJ(OC_, KT_MATERN52); break; \
-            default: GPT_MJ(OC_, KT_RBF);                  \
-        }
-        switch (cnt) {
-            case 1: GPT_MJ_K(1); break;
-            case 2: GPT_MJ_K(2); break;
-            case 3: GPT_MJ_K(3); break;
-            default: GPT_MJ_K(4);
-        }
-#undef GPT_MJ_K
-#undef GPT_MJ
+        auto go = [&](auto kt, auto oc) {
+            constexpr int KT = decltype(kt)::value, OC = decltype(oc)::value;
+            if (J) hipLaunchKernelGGL((k_mean_jac<T, QPW, OC, KT, DW, true>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J);
+            else if (many) hipLaunchKernelGGL((k_mean_jac<T, QPW_M, OC, KT, DW, false>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J);
+            else hipLaunchKernelGGL((k_mean_jac<T, QPW, OC, KT, DW, false>), grid, dim3(256), 0, s, p, Xs, a4, Xq, M, ob, mean, J);
+        };
+        with_kernel_type(p.ktype, [&](auto kt) {
+            switch (cnt) {
+                case 1: go(kt, Int<1>{}); break;
+                case 2: go(kt, Int<2>{}); break;
+                case 3: go(kt, Int<3>{}); break;
+                default: go(kt, Int<4>{});
+            }
+        });
     }
 }
 
 void launch_mean_jac(hipStream_t s, const KernelParams& p, const void* Xs, const void* A4,
                      const void* Xq, int64_t M, void* mean, void* J) {
     if (M <= 0 || (!mean && !J)) return;
-    if (p.D <= 3) {
-        if (p.dtype == DT_F32)
-            launch_mean_jac_t<float, 3>(s, p, (const float*)Xs, (const float*)A4, (const float*)Xq, M, (float*)mean, (float*)J);
-        else
-            launch_mean_jac_t<double, 3>(s, p, (const double*)Xs, (const double*)A4, (const double*)Xq, M, (double*)mean, (double*)J);
-    } else if (p.D <= WIDE_D) {
-        if (p.dtype == DT_F32)
-            launch_mean_jac_t<float, WIDE_D>(s, p, (const float*)Xs, (const float*)A4, (const float*)Xq, M, (float*)mean, (float*)J);
-        else
-            launch_mean_jac_t<double, WIDE_D>(s, p, (const double*)Xs, (const double*)A4, (const double*)Xq, M, (double*)mean, (double*)J);
-    } else {
-        if (p.dtype == DT_F32)
-            launch_mean_jac_t<float, MAX_D>(s, p, (const float*)Xs, (const float*)A4, (const float*)Xq, M, (float*)mean, (float*)J);
-        else
-            launch_mean_jac_t<double, MAX_D>(s, p, (const double*)Xs, (const double*)A4, (const double*)Xq, M, (double*)mean, (double*)J);
-    }
+    with_elem_type(p.dtype, [&](auto t) {
+        using T = decltype(t);
+        with_coord_width(p.D, [&](auto dw) {
+            launch_mean_jac_t<T, decltype(dw)::value>(s, p, (const T*)Xs, (const T*)A4, (const T*)Xq, M, (T*)mean, (T*)J);
+        });
+    });
 }
 
 // A sweep the work split cut along k: add its parts' partial products in part order, then square / reduce as the
@@ -307,39 +290,6 @@ __global__ __launch_bounds__(64) void k_var_finalize(KernelParams p, VarPlanDev 
     }
 }
 
-// Dynamic LDS beyond the default limit is an opt-in per kernel and device.
-template <typename T>
-static void var_kernel_setup() {
-    static PerDeviceOnce once;
-    once.run([] {
-    const void* fns[] = {reinterpret_cast<const void*>(k_var<T, 1, false, KT_RBF>), reinterpret_cast<const void*>(k_var<T, 4, true, KT_RBF>),
-                         reinterpret_cast<const void*>(k_var<T, 4, false, KT_RBF>), reinterpret_cast<const void*>(k_var<T, 3, false, KT_RBF>),
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN12>),
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN32>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN52>),
-                         // D = 4 .. 8
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_RBF, WIDE_D>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN12, WIDE_D>),
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN32, WIDE_D>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN52, WIDE_D>),
-                         reinterpret_cast<const void*>(k_var<T, 8, true, KT_RBF, WIDE_D>), reinterpret_cast<const void*>(k_var<T, 8, false, KT_RBF, WIDE_D>),
-                         reinterpret_cast<const void*>(k_var<T, 16, true, KT_RBF, WIDE_D>), reinterpret_cast<const void*>(k_var<T, 16, false, KT_RBF, WIDE_D>),
-                         reinterpret_cast<const void*>(k_var<T, 4, false, KT_RBF, WIDE_D, false>), reinterpret_cast<const void*>(k_var<T, 8, false, KT_RBF, WIDE_D, false>),
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_RBF, MAX_D>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN12, MAX_D>),
-                         reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN32, MAX_D>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN52, MAX_D>),
-                         reinterpret_cast<const void*>(k_var<T, 16, true, KT_RBF, MAX_D>), reinterpret_cast<const void*>(k_var<T, 16, false, KT_RBF, MAX_D>)};
-    for (const void* f : fns) hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var_lds_bytes<T>());
-    if constexpr (std::is_same<T, double>::value) {       // the small-model instantiations (HALF): launch_var_t
-        const void* hf[] = {reinterpret_cast<const void*>(k_var<T, 1, false, KT_RBF, 3, true, true>), reinterpret_cast<const void*>(k_var<T, 4, true, KT_RBF, 3, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 4, false, KT_RBF, 3, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN12, 3, true, true>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN32, 3, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN52, 3, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 1, false, KT_RBF, WIDE_D, true, true>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN12, WIDE_D, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN32, WIDE_D, true, true>), reinterpret_cast<const void*>(k_var<T, 1, false, KT_MATERN52, WIDE_D, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 8, true, KT_RBF, WIDE_D, true, true>), reinterpret_cast<const void*>(k_var<T, 8, false, KT_RBF, WIDE_D, true, true>),
-                            reinterpret_cast<const void*>(k_var<T, 16, true, KT_RBF, WIDE_D, true, true>), reinterpret_cast<const void*>(k_var<T, 16, false, KT_RBF, WIDE_D, true, true>)};
-        for (const void* f : hf) hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var_lds_bytes<T>());
-    }
-    });
-}
-
 // rounds of whole column blocks per launch of k_var (0: all in one launch); see launch_var_t
 static int var_rounds_per_launch() {
     const char* e = getenv("GPT_VAR_ROUNDS_PER_LAUNCH");          // read per call: tests compare settings in one process
@@ -351,13 +301,10 @@ template <typename T>
 static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspace& ws, const T* Xs, const T* Wf,
                          const T* Xq, int64_t M, int ncomp, T* var, T* Jvar, T* dvar, const double* hdr) {
     const VarPlanDev& pl_all = ws.plan->d;
-    constexpr size_t lds = var_lds_bytes<T>();
-    var_kernel_setup<T>();
     T* slab = static_cast<T*>(ws.slab.p);
     T* vslab = static_cast<T*>(ws.vslab.p);
     T* bscr = static_cast<T*>(ws.bscratch.p);
     const dim3 grid((unsigned)pl_all.P), fgrid((unsigned)pl_all.ncb), cgrid((unsigned)pl_all.n_splits * VAR_SPLIT_SLOTS);
-    const bool wide = p.D > 3, wide16 = p.D > WIDE_D;
     const bool cross = ncomp >= 4 && dvar != nullptr;
     // The persistent workgroups are not synchronised between rounds and drift apart; once they are further apart than a W
     // tile stays in L2 each fetches its own copy of the W stream (mode J+Jvar, 122 rounds in one launch: 155 MB fetched per
@@ -383,55 +330,17 @@ static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspac
     pl.rnd_begin = r0;
     pl.rnd_end = r0 + rpl < rounds ? r0 + rpl : rounds;
     pl.with_tail = pl.rnd_end >= rounds ? 1 : 0;
-#define GPT_KVAR(NC_, CR_, KT_, DW_)                                                                                                      \
-    do {                                                                                                                                 \
-        if (diag_half) hipLaunchKernelGGL((k_var<T, NC_, CR_, KT_, DW_, true, HALF_OK>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr); \
-        else hipLaunchKernelGGL((k_var<T, NC_, CR_, KT_, DW_>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);       \
-    } while (0)
-#define GPT_KVAR1(DW_)                                                  \
-        switch (p.ktype) {                                               \
-            case KT_MATERN12: GPT_KVAR(1, false, KT_MATERN12, DW_); break; \
-            case KT_MATERN32: GPT_KVAR(1, false, KT_MATERN32, DW_); break; \
-            case KT_MATERN52: GPT_KVAR(1, false, KT_MATERN52, DW_); break; \
-            default: GPT_KVAR(1, false, KT_RBF, DW_); break;             \
-        }
-    if (ncomp != 1 && (p.ktype == KT_MATERN32 || p.ktype == KT_MATERN52)) {
-        // derivative columns of a Matern model (the API refuses Matern 1/2): gpt_predict_matern.hip
-        launch_var_matern<T>(s, p, pl, ncomp, cross, grid, lds, Xs, Wf, Xq, M, slab, vslab, bscr);
-    } else if (ncomp == VAR_NCOMP_DERIV4) {          // D = 4, Jacobian variance alone: dk_0 .. dk_3
-        hipLaunchKernelGGL((k_var<T, 4, false, KT_RBF, WIDE_D, false>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);
-    } else if (ncomp == VAR_NCOMP_DERIV8) {   // D = 8
-        hipLaunchKernelGGL((k_var<T, 8, false, KT_RBF, WIDE_D, false>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);
-    } else if (ncomp == 1) {
-        if (wide16) {             // D = 9 .. 15: rows of 16 (no HALF instantiations)
-#define GPT_KVAR16(NC_, CR_, KT_) hipLaunchKernelGGL((k_var<T, NC_, CR_, KT_, MAX_D>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr)
-            switch (p.ktype) {
-                case KT_MATERN12: GPT_KVAR16(1, false, KT_MATERN12); break;
-                case KT_MATERN32: GPT_KVAR16(1, false, KT_MATERN32); break;
-                case KT_MATERN52: GPT_KVAR16(1, false, KT_MATERN52); break;
-                default: GPT_KVAR16(1, false, KT_RBF); break;
-            }
-        } else if (wide) { GPT_KVAR1(WIDE_D) } else { GPT_KVAR1(3) }
-    } else if (ncomp == 3) {      // Jacobian variance alone: D columns per query (D <= 3)
-        // (no HALF instantiation: at the register limit it keeps a spilled pointer inside the lock-step loop)
-        hipLaunchKernelGGL((k_var<T, 3, false, KT_RBF, 3>), grid, dim3(512), lds, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);
-    } else if (ncomp == 4) {      // Jacobian variance / d var, RBF (Matern: above)
-        if (cross) GPT_KVAR(4, true, KT_RBF, 3);
-        else GPT_KVAR(4, false, KT_RBF, 3);
-    } else if (ncomp == 8) {      // D = 4 .. 7
-        if (cross) GPT_KVAR(8, true, KT_RBF, WIDE_D);
-        else GPT_KVAR(8, false, KT_RBF, WIDE_D);
-    } else if (wide16) {          // D = 9 .. 15
-        if (cross) GPT_KVAR16(16, true, KT_RBF);
-        else GPT_KVAR16(16, false, KT_RBF);
-    } else {                      // D = 8
-        if (cross) GPT_KVAR(16, true, KT_RBF, WIDE_D);
-        else GPT_KVAR(16, false, KT_RBF, WIDE_D);
+    // which instantiation: launch_kvar (gpt_kvar.h).  k* alone: every kernel type, in this unit; derivative columns: RBF in this unit,
+    // Matern 3/2 and 5/2 in gpt_predict_matern.hip (Matern 1/2 has none: the API refuses its derivatives before a launch is reached)
+    if (ncomp == 1)
+        with_kernel_type(p.ktype, [&](auto kt) {
+            launch_kvar<T, decltype(kt)::value, false>(ncomp, cross, p.D, diag_half, grid, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);
+        });
+    else if (p.ktype == KT_MATERN32 || p.ktype == KT_MATERN52)
+        launch_var_matern<T>(s, p, pl, ncomp, cross, grid, Xs, Wf, Xq, M, slab, vslab, bscr);
+    else
+        launch_kvar<T, KT_RBF, true>(ncomp, cross, p.D, diag_half, grid, s, p, pl, Xs, Wf, Xq, M, slab, vslab, bscr);
     }
-    }
-#undef GPT_KVAR16
-#undef GPT_KVAR1
-#undef GPT_KVAR
     const VarPlanDev& pl = pl_all;
     if (pl.n_splits > 0) {
         if (!cross) hipLaunchKernelGGL((k_var_combine<T, false>), cgrid, dim3(256), 0, s, pl, vslab, slab);
@@ -453,10 +362,10 @@ static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspac
 void launch_var(hipStream_t s, const KernelParams& p, const VarWorkspace& ws, const void* Xs, const void* Wf,
                 const void* Xq, int64_t M, int ncomp, void* var, void* Jvar, void* dvar, const double* hdr) {
     if (M <= 0 || !ws.plan) return;
-    if (p.dtype == DT_F32)
-        launch_var_t<float>(s, p, ws, (const float*)Xs, (const float*)Wf, (const float*)Xq, M, ncomp, (float*)var, (float*)Jvar, (float*)dvar, hdr);
-    else
-        launch_var_t<double>(s, p, ws, (const double*)Xs, (const double*)Wf, (const double*)Xq, M, ncomp, (double*)var, (double*)Jvar, (double*)dvar, hdr);
+    with_elem_type(p.dtype, [&](auto t) {
+        using T = decltype(t);
+        launch_var_t<T>(s, p, ws, (const T*)Xs, (const T*)Wf, (const T*)Xq, M, ncomp, (T*)var, (T*)Jvar, (T*)dvar, hdr);
+    });
 }
 
 }  // namespace gpt

@@ -1,5 +1,6 @@
 """Check that a host-only change left the device code alone: compile units of two csrc trees to gfx950 assembly (the Makefile's
-CXXFLAGS plus --cuda-device-only -S), drop .file / .ident, source-path lines and comment-only lines, and compare kernel by
+CXXFLAGS plus --cuda-device-only -S), drop .file / .ident, source-path lines and comment-only lines, take the function's position
+in its unit out of the local labels (.LBB<position>_<block>: it moves with the order of instantiation), and compare kernel by
 kernel: every .amdhsa_kernel symbol present under the same name on both sides, instruction stream and kernel descriptor
 identical.  The other tree needs ../../include/gpt_hip.h next to it, as in a checkout.
 usage: python tools/device_isa_diff.py OTHER_CSRC [unit.hip ...]   (CPU only; hipcc cross-compiles; exit 1 on any difference)"""
@@ -8,6 +9,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
@@ -20,6 +22,7 @@ def kernels(csrc, unit, out):
     lines = [x.rstrip() for x in open(out)]
     lines = [x for x in lines if x.strip() and not x.lstrip().startswith((";", "//", ".file", ".ident")) and csrc not in x]
     s = "\n".join(re.sub(r"\s*;.*$", "", x) for x in lines)
+    s = re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", s)
     found = {}
     for name in re.findall(r"^\s*\.amdhsa_kernel (\S+)$", s, flags=re.M):
         i = s.index("\n" + name + ":\n")
@@ -31,11 +34,14 @@ def kernels(csrc, unit, out):
 
 def main():
     other = os.path.abspath(sys.argv[1])
-    units = sys.argv[2:] or ["gpt_svgp_train.hip", "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_fit.hip"]
+    units = sys.argv[2:] or ["gpt_api.hip", "gpt_fit.hip", "gpt_predict.hip", "gpt_predict_matern.hip", "gpt_svgp_train.hip",
+                             "gpt_svgp_surface.hip", "gpt_select.hip"]
     bad = 0
-    with tempfile.TemporaryDirectory() as d:
+    with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as ex:
+        jobs = {(side, unit): ex.submit(kernels, csrc, unit, os.path.join(d, f"{side}_{unit}.s"))
+                for unit in units for side, csrc in (("a", other), ("b", CSRC))}
         for unit in units:
-            a, b = kernels(other, unit, os.path.join(d, "a.s")), kernels(CSRC, unit, os.path.join(d, "b.s"))
+            a, b = jobs["a", unit].result(), jobs["b", unit].result()
             diff = sorted(set(a) ^ set(b)) + sorted(k for k in set(a) & set(b) if a[k] != b[k])
             print(f"{unit}: {len(b)} kernels, " + ("identical" if not diff else "DIFFERENT: " + ", ".join(diff)))
             bad += len(diff)
