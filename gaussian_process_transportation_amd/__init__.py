@@ -8,9 +8,12 @@ from .svgp_exact import StocasticVariationalGaussianProcess, SVGPExactPredictor
 from .svgp_transport import SVGPTransport
 from .svgp_surface import StocasticVariationalGaussianProcess as SurfaceSVGP
 from .gaussian_process_al import ActiveLearningGaussianProcess
+from .gaussian_process_batch import GaussianProcessBatch
+from .batch_transportation import GaussianProcessTransportationBatch
 
 # the reference's three exports first; then the duck-typed caller, the SVGP exact-conversion path and the
-# point-cloud surface SVGP, and the large-input exact regressor (greedy active-learning subset selection)
+# point-cloud surface SVGP, the large-input exact regressor (greedy active-learning subset selection), and the batch of small
+# models (one workgroup each) with its transport protocol
 __all__ = ["AffineTransform", "GaussianProcessTransportation", "GaussianProcess", "PolicyTransportation",
            "SVGPTransport", "StocasticVariationalGaussianProcess", "SVGPExactPredictor", "SurfaceSVGP",
-           "ActiveLearningGaussianProcess"]
+           "ActiveLearningGaussianProcess", "GaussianProcessBatch", "GaussianProcessTransportationBatch"]

@@ -75,6 +75,12 @@ SIGNATURES = {
     "gpt_svgp_surface_predict": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _i64, _dp, _dp, _dp]),
     "gpt_select_greedy": (C.c_int, [C.c_int, _dp, _i64, C.c_int, _dp, C.c_double, C.c_double, C.c_double, C.c_int, C.POINTER(_i64),
                                     C.c_int, C.c_int, C.POINTER(_i64), _dp, _dp]),
+    "gpt_batch_lml_objective": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double,
+                                          C.c_int, _dp, _dp, C.POINTER(C.c_int)]),
+    "gpt_batch_fit": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int,
+                                _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "gpt_batch_predict": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double,
+                                    C.c_int, _dp, C.POINTER(_i64), _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -364,6 +370,136 @@ def select_greedy(X, length_scale, constant_value, noise_level, alpha, n_total, 
                                 int(kernel_type), initial.ctypes.data_as(ip) if initial.size else None, initial.size, n_total,
                                 selected.ctypes.data_as(ip), dptr(selvar), dptr(resid)), "gpt_select_greedy")
     return selected, selvar[:n_total - initial.size], resid
+
+
+BATCH_MAX_N = 128          # gpt_batch_* limits (include/gpt_hip.h)
+BATCH_MAX_O = 16
+BATCH_MAX_B = 1 << 20
+
+
+def batch_pack(Xs, Ys, who="batch"):
+    """The ragged layout of the gpt_batch_* entry points from sequences of (n_b, D) / (n_b, O) arrays: (X (sum n, D),
+    Y (sum n, O), n_begin (B + 1) int64).  Every refusal that needs no device is made here, before the library is loaded."""
+    Xs = [as_f64(x, 2, "X") for x in Xs]
+    Ys = [as_f64(y, 2, "y") for y in Ys]
+    B = len(Xs)
+    if len(Ys) != B:
+        raise ValueError(f"{who}: {B} inputs but {len(Ys)} targets")
+    if not 1 <= B <= BATCH_MAX_B:
+        raise ValueError(f"{who}: a batch holds 1 .. 2^20 models, got {B}")
+    D, O = Xs[0].shape[1], Ys[0].shape[1]
+    for b, (x, y) in enumerate(zip(Xs, Ys)):
+        if x.shape[1] != D or y.shape[1] != O:
+            raise ValueError(f"{who}: every model of a batch must share D and O; model {b} has D = {x.shape[1]}, O = {y.shape[1]}, "
+                             f"model 0 has D = {D}, O = {O}")
+        if y.shape[0] != x.shape[0]:
+            raise ValueError(f"{who}: model {b}: X and Y have different numbers of rows")
+        if not 1 <= x.shape[0] <= BATCH_MAX_N:
+            raise ValueError(f"{who}: model {b} has {x.shape[0]} rows; a batch member holds 1 .. {BATCH_MAX_N} points "
+                             "(larger models: GaussianProcess)")
+    if not 1 <= D <= MAX_D:
+        raise ValueError(f"{who}: X has {D} features: this GPU path supports input dimension D = 1 .. {MAX_D} only")
+    if not 1 <= O <= BATCH_MAX_O:
+        raise ValueError(f"{who}: y has {O} outputs: a batch supports O = 1 .. {BATCH_MAX_O}")
+    n_begin = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum([x.shape[0] for x in Xs], out=n_begin[1:])
+    return np.concatenate(Xs), np.concatenate(Ys), n_begin
+
+
+def _batch_hyper(B, D, length_scale, constant_value, noise_level, who):
+    ls = as_f64(length_scale, None, "length_scale")
+    if ls.ndim == 1:
+        ls = ls[:, None]
+    if ls.ndim != 2 or ls.shape[0] != B or ls.shape[1] not in (1, D):
+        raise ValueError(f"{who}: length_scale must be (B, 1) or (B, D), got {ls.shape}")
+    c = as_f64(constant_value, 1, "constant_value")
+    noise = as_f64(noise_level, 1, "noise_level")
+    if c.shape != (B,) or noise.shape != (B,):
+        raise ValueError(f"{who}: constant_value and noise_level must have one entry per model")
+    return np.ascontiguousarray(ls), c, noise
+
+
+def _split(a, begin):
+    return [a[begin[b]:begin[b + 1]] for b in range(len(begin) - 1)]
+
+
+def batch_lml_objective_packed(X, Y, n_begin, length_scale, constant_value, noise_level, alpha, kernel_type=0, device=0):
+    """gpt_batch_lml_objective on arrays already in the ragged layout (batch_pack): (lml (B,), grad (B, 2 + n_ls), status (B,)).
+    A model whose status is GPT_E_NOT_PD has NaN in its lml and gradient."""
+    B, D = n_begin.size - 1, X.shape[1]
+    ls, c, noise = _batch_hyper(B, D, length_scale, constant_value, noise_level, "batch_lml_objective")
+    lib = load()
+    require_gpu()
+    lml = np.full(B, np.nan)
+    grad = np.full((B, 2 + ls.shape[1]), np.nan)
+    status = np.zeros(B, dtype=np.int32)
+    check(lib.gpt_batch_lml_objective(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(C.POINTER(_i64)), B, D, Y.shape[1], dptr(ls),
+                                      ls.shape[1], dptr(c), dptr(noise), float(alpha), int(kernel_type), dptr(lml), dptr(grad),
+                                      status.ctypes.data_as(C.POINTER(C.c_int))), "gpt_batch_lml_objective")
+    return lml, grad, status
+
+
+def batch_lml_objective(Xs, Ys, length_scale, constant_value, noise_level, alpha, kernel_type=0, device=0):
+    """LML and its gradient with respect to log [c, l.., noise] of B independent small models in one launch
+    (gpt_batch_lml_objective).  Xs, Ys: sequences of (n_b, D) / (n_b, O) arrays; length_scale (B, 1 or D), constant_value (B,),
+    noise_level (B,).  Returns (lml (B,), grad (B, 2 + n_ls), status (B,))."""
+    X, Y, n_begin = batch_pack(Xs, Ys, "batch_lml_objective")
+    return batch_lml_objective_packed(X, Y, n_begin, length_scale, constant_value, noise_level, alpha, kernel_type, device)
+
+
+def batch_fit(Xs, Ys, length_scale, constant_value, noise_level, alpha, kernel_type=0, device=0, want_L=True):
+    """sklearn's fitted attributes of B independent small models (gpt_batch_fit): (L list of (n_b, n_b) or None, alpha list of
+    (n_b, O), lml (B,), status (B,)); the arrays of a model that is not PD hold NaN."""
+    X, Y, n_begin = batch_pack(Xs, Ys, "batch_fit")
+    B, D = n_begin.size - 1, X.shape[1]
+    ls, c, noise = _batch_hyper(B, D, length_scale, constant_value, noise_level, "batch_fit")
+    lib = load()
+    require_gpu()
+    sizes = np.diff(n_begin)
+    l_begin = np.concatenate([[0], np.cumsum(sizes * sizes)])
+    L = np.full(l_begin[-1], np.nan) if want_L else None
+    a = np.full(Y.shape, np.nan)
+    lml = np.full(B, np.nan)
+    status = np.zeros(B, dtype=np.int32)
+    check(lib.gpt_batch_fit(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(C.POINTER(_i64)), B, D, Y.shape[1], dptr(ls), ls.shape[1],
+                            dptr(c), dptr(noise), float(alpha), int(kernel_type), dptr(L), dptr(a), dptr(lml),
+                            status.ctypes.data_as(C.POINTER(C.c_int))), "gpt_batch_fit")
+    Ls = [L[l_begin[b]:l_begin[b + 1]].reshape(sizes[b], sizes[b]) for b in range(B)] if want_L else None
+    return Ls, _split(a, n_begin), lml, status
+
+
+def batch_predict(Xs, Ys, length_scale, constant_value, noise_level, alpha, xqs, kernel_type=0, device=0, mean=False, var=False, J=False,
+                  Jvar=False, dvar=False):
+    """The fused posterior of B independent small models, each at its own queries xqs[b] (M_b, D), M_b >= 0
+    (gpt_batch_predict).  Returns ({name: list of per-model arrays} for the outputs asked for — mean (M_b, O), var (M_b,),
+    J (M_b, O, D), Jvar (M_b, D), dvar (M_b, D) — and status (B,)); a model that is not PD has NaN in its arrays."""
+    X, Y, n_begin = batch_pack(Xs, Ys, "batch_predict")
+    B, D, O = n_begin.size - 1, X.shape[1], Y.shape[1]
+    ls, c, noise = _batch_hyper(B, D, length_scale, constant_value, noise_level, "batch_predict")
+    xqs = [as_f64(x, 2, "X") for x in xqs]
+    if len(xqs) != B:
+        raise ValueError(f"batch_predict: {B} models but {len(xqs)} query arrays")
+    for b, x in enumerate(xqs):
+        if x.shape[1] != D:
+            raise ValueError(f"batch_predict: the queries of model {b} have {x.shape[1]} features, the models {D}")
+    q_begin = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum([x.shape[0] for x in xqs], out=q_begin[1:])
+    M = int(q_begin[-1])
+    if M >= 2 ** 31:
+        raise ValueError("batch_predict: the queries of one call must number fewer than 2^31")
+    Xq = np.concatenate(xqs) if M else np.zeros((0, D))
+    lib = load()
+    require_gpu()
+    shapes = {"mean": (M, O), "var": (M,), "J": (M, O, D), "Jvar": (M, D), "dvar": (M, D)}
+    want = {"mean": mean, "var": var, "J": J, "Jvar": Jvar, "dvar": dvar}
+    out = {k: (np.full(shapes[k], np.nan) if want[k] else None) for k in shapes}
+    status = np.zeros(B, dtype=np.int32)
+    ip = C.POINTER(_i64)
+    check(lib.gpt_batch_predict(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(ip), B, D, O, dptr(ls), ls.shape[1], dptr(c),
+                                dptr(noise), float(alpha), int(kernel_type), dptr(Xq), q_begin.ctypes.data_as(ip), dptr(out["mean"]),
+                                dptr(out["var"]), dptr(out["J"]), dptr(out["Jvar"]), dptr(out["dvar"]),
+                                status.ctypes.data_as(C.POINTER(C.c_int))), "gpt_batch_predict")
+    return {k: _split(v, q_begin) for k, v in out.items() if v is not None}, status
 
 
 class Handle:

@@ -101,7 +101,7 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
 
 }  // namespace gpt
 
-// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip), the subset selection (gpt_select.hip) and the GEMM's
+// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip), the subset selection (gpt_select.hip), the batch of small models (gpt_batch.hip) and the GEMM's
 // test hook (gpt_fit.hip) are device code end to end and are not part of
 // this build; their entry points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this
 // library too.
@@ -138,6 +138,22 @@ extern "C" int gpt_svgp_surface_predict(int, const double*, const double*, const
 extern "C" int gpt_select_greedy(int, const double*, int64_t, int, const double*, double, double, double, int, const int64_t*, int, int,
                                  int64_t*, double*, double*) {
     gpt::set_last_error("gpt_select_greedy: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_batch_lml_objective(int, const double*, const double*, const int64_t*, int64_t, int, int, const double*, int,
+                                       const double*, const double*, double, int, double*, double*, int*) {
+    gpt::set_last_error("gpt_batch_lml_objective: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_batch_fit(int, const double*, const double*, const int64_t*, int64_t, int, int, const double*, int, const double*,
+                             const double*, double, int, double*, double*, double*, int*) {
+    gpt::set_last_error("gpt_batch_fit: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_batch_predict(int, const double*, const double*, const int64_t*, int64_t, int, int, const double*, int,
+                                 const double*, const double*, double, int, const double*, const int64_t*, double*, double*, double*,
+                                 double*, double*, int*) {
+    gpt::set_last_error("gpt_batch_predict: not in the host sanitizer build");
     return GPT_E_HIP;
 }
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,

@@ -204,6 +204,46 @@ int gpt_select_greedy(int device, const double* X, int64_t N, int D, const doubl
                       double alpha, int kernel_type, const int64_t* initial, int n_initial, int n_total, int64_t* selected,
                       double* selection_variance, double* residual_variance);
 
+/* (new) A batch of independent small exact GPs, each handled by one workgroup and the whole batch by one launch per operation
+ * and size class (n <= 32, n <= 128) — the three entry points below.  They share:
+ *   layout: B models, ragged.  X (sum n_b, D) and Y (sum n_b, O) are the models' rows concatenated, n_begin (B + 1) their
+ *   offsets (n_begin[0] = 0); queries Xq (sum M_b, D) with q_begin (B + 1) likewise, outputs concatenated by the same offsets;
+ *   hyper-parameters per model: length_scale (B, n_ls), n_ls 1 or D for the whole batch, constant_value (B), noise_level (B);
+ *   alpha_jitter and kernel_type (GPT_KERNEL_*) are shared.  fp64, on `device`, host memory in and out.
+ *   limits (GPT_E_ARG, the message names the limit): 1 <= n_b <= 128, D 1..15, O 1..16, 1 <= B <= 2^20, M_b >= 0 and
+ *   sum M_b < 2^31, increasing offsets, no NaN / infinity, length_scale and constant_value > 0, noise_level >= 0.
+ *   status (B): GPT_OK, or GPT_E_NOT_PD for a model whose Cholesky met a pivot <= 0 (sklearn's LinAlgError); that model's
+ *   outputs are left untouched and every other model is computed as usual.  The return value is GPT_OK whenever the batch ran.
+ *   Every sum over a model's points runs in a fixed order: a model's results do not depend on the batch around it, and a
+ *   query's not on the other queries, bit for bit.
+ *
+ * gpt_batch_lml_objective — log_marginal_likelihood(theta, eval_gradient=True) (sklearn/_gpr.py:537-652) for B (data, theta)
+ * pairs at once: what the optimiser of every GaussianProcess.fit in the reference's per-frame loop
+ * (example/comparisons/multi_reference_frames/models/model_gpt.py:74-83, a transport fitted on 10 points per frame pair)
+ * evaluates a few hundred times.  lml (B); grad (B, 2 + n_ls) with respect to log [c, l.., noise], as gpt_lml_objective;
+ * all four kernel types. */
+int gpt_batch_lml_objective(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O,
+                            const double* length_scale, int n_ls, const double* constant_value, const double* noise_level,
+                            double alpha_jitter, int kernel_type, double* lml, double* grad, int* status);
+
+/* (new) gpt_batch_fit — GaussianProcess.fit at fixed hyper-parameters (models/gaussian_process.py:25-43 ->
+ * sklearn/_gpr.py:346-364) for every model of the batch, the fits of model_gpt.py:74-83 in one call: L (sum n_b^2: each
+ * model's n_b x n_b factor, zeros above the diagonal; may be NULL), alpha (sum n_b, O), lml (B; may be NULL). */
+int gpt_batch_fit(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O,
+                  const double* length_scale, int n_ls, const double* constant_value, const double* noise_level,
+                  double alpha_jitter, int kernel_type, double* L, double* alpha, double* lml, int* status);
+
+/* (new) gpt_batch_predict — the fused posterior of every model at its own queries: GaussianProcess.predict and .derivative
+ * (gaussian_process.py:46-55, 63-102) and .derivative_of_variance (:104-126) as model_gpt.py:74-83 calls them per frame.
+ * Stateless: the models are factored again inside the call (microseconds at these sizes).  Any output may be NULL:
+ * mean (sum M, O); var (sum M) = max(c + noise - |W k*|^2, 0) as gpt_predict; J (sum M, O, D); Jvar (sum M, D) = c / l_d^2 -
+ * |W dk_d|^2; dvar (sum M, D) = -2 (W dk_d).(W k*), W = L^-1.  J, Jvar and dvar are RBF only (GPT_E_ARG on a Matern batch).
+ * Device memory: the inputs and outputs plus 4 n_b (n_b + 1) bytes per model. */
+int gpt_batch_predict(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O,
+                      const double* length_scale, int n_ls, const double* constant_value, const double* noise_level,
+                      double alpha_jitter, int kernel_type, const double* Xq, const int64_t* q_begin, double* mean, double* var,
+                      double* J, double* Jvar, double* dvar, int* status);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */

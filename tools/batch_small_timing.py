@@ -1,0 +1,135 @@
+"""Timing of the batch of small models -> profiles/batch_small_models.txt.
+
+  python tools/batch_small_timing.py --resources        (CPU only: hipcc -save-temps, the factor kernel's resource summary)
+  timeout 900 python tools/batch_small_timing.py --gpu  (on an MI355X: the measurements)
+  Each run replaces its own section of the file and keeps the other; --out FILE names another file than the profile.
+
+Objective: the median of 20 runs of one gpt_batch_lml_objective at B = 64, n = 20, D = 2, O = 2 against 64 sequential
+Handle.lml_objective calls on one handle; the batched call must take no longer than 8 of the sequential calls (one launch
+and one small copy each way against at least eight dependent launches per call: a worse ratio means the batch does not run
+as one launch).  End to end: examples/multi_frame_batch.py's workload at 8 and 160 pairs — batch class, per-pair loop of
+GaussianProcessTransportation, scikit-learn on the host CPU."""
+import os
+import re
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OUT = os.path.join(ROOT, "profiles", "batch_small_models.txt")
+CSRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
+
+
+def resources():
+    lines = []
+    with tempfile.TemporaryDirectory() as d:
+        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc",
+                        "-save-temps", "-c", os.path.join(CSRC, "gpt_batch.hip"), "-o", os.path.join(d, "gpt_batch.o")], check=True, cwd=d,
+                       stderr=subprocess.DEVNULL)
+        asm = open([os.path.join(d, f) for f in os.listdir(d) if f.endswith(".s") and "amdgcn" in f][0]).read()
+    from gaussian_process_transportation_amd import _lib  # noqa: F401  (only to fail early if the tree is broken)
+    for m in re.finditer(r"\.amdhsa_kernel (\S*bat_factor\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S):
+        def field(k):
+            r = re.search(r"\.amdhsa_" + k + r"\s+(\S+)", m.group(2))
+            return r.group(1) if r else "?"
+        t = re.search(r"bat_factorILi(\d+)ELi(\d)ELb(\d)", m.group(1))
+        nmax, kt, obj = int(t.group(1)), int(t.group(2)), int(t.group(3))
+        dyn = (nmax * (nmax + 1) + nmax * 16 + nmax) * 8
+        lines.append(f"bat_factor<NMAX={nmax}, KT={kt}, OBJ={obj}>: VGPRs {field('next_free_vgpr')}, SGPRs {field('next_free_sgpr')}, "
+                     f"static LDS {field('group_segment_fixed_size')} B, dynamic LDS (computed) {dyn} B, scratch {field('private_segment_fixed_size')} B")
+    return lines
+
+
+def gpu():
+    from examples.multi_frame_batch import frame_pairs, kernel, run_batch, run_loop
+    from gaussian_process_transportation_amd import _lib
+    lines = []
+    rng = np.random.default_rng(0)
+    B = 64
+    Xs = [rng.uniform(0, 1, (20, 2)) for _ in range(B)]
+    Ys = [np.sin(3 * x) + 0.01 * rng.standard_normal(x.shape) for x in Xs]
+    X, Y, nb = _lib.batch_pack(Xs, Ys)
+    ls, c, noise = np.full((B, 2), 0.3), np.ones(B), np.full(B, 1e-3)
+    h = _lib.Handle(0)
+    for _ in range(3):
+        _lib.batch_lml_objective_packed(X, Y, nb, ls, c, noise, 1e-10)
+        h.lml_objective(Xs[0], Ys[0], ls[0], 1.0, 1e-3, 1e-10)
+    tb, ts = [], []
+    for _ in range(20):
+        t0 = time.perf_counter()
+        _lib.batch_lml_objective_packed(X, Y, nb, ls, c, noise, 1e-10)
+        tb.append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        for b in range(B):
+            h.lml_objective(Xs[b], Ys[b], ls[b], 1.0, 1e-3, 1e-10)
+        ts.append(time.perf_counter() - t0)
+    tb, ts = float(np.median(tb)), float(np.median(ts))
+    ratio = tb / (ts / B)
+    lines.append(f"objective, B = 64, n = 20, D = 2, O = 2 (median of 20): batched call {1e6 * tb:.0f} us; 64 sequential Handle.lml_objective "
+                 f"calls {1e6 * ts:.0f} us ({1e6 * ts / B:.0f} us each); the batched call costs {ratio:.2f} sequential calls "
+                 f"(requirement: <= 8) -> {'met' if ratio <= 8 else 'NOT MET'}")
+    from sklearn.gaussian_process import GaussianProcessRegressor
+    from gaussian_process_transportation_amd.affine_transform import AffineTransform
+    run_batch(frame_pairs(2))
+    for n_pairs in (8, 160):
+        pairs = frame_pairs(n_pairs)
+        t0 = time.perf_counter()
+        res = run_batch(pairs)
+        t_batch = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        run_loop(pairs)
+        t_loop = time.perf_counter() - t0
+        np.random.seed(0)
+        t0 = time.perf_counter()
+        for source, target, traj, vel in pairs:        # the reference's fit + predict on the CPU (the derivative algebra left out)
+            aff = AffineTransform(verbose=False).fit(source, target)
+            src = aff.predict(source)
+            gp = GaussianProcessRegressor(kernel=kernel(), alpha=1e-10, n_restarts_optimizer=5).fit(src, target - src)
+            gp.predict(aff.predict(traj), return_std=True)
+        t_cpu = time.perf_counter() - t0
+        lines.append(f"end to end, {n_pairs} pairs (n = 10, M = 200, optimiser on, 5 restarts): batch class {t_batch:.3f} s "
+                     f"({res.regressor.optimizer_stats_['calls']} batched objective calls for {res.regressor.optimizer_stats_['runs']} runs), "
+                     f"loop of GaussianProcessTransportation {t_loop:.3f} s, scikit-learn on the CPU (fit + predict with std only) {t_cpu:.3f} s")
+    return lines, ratio
+
+
+HEADS = {"resources": "# resources of bat_factor (hipcc --offload-arch=gfx950 -save-temps: VGPRs, SGPRs, static LDS and scratch from the "
+                      "compiler's kernel descriptor; the dynamic LDS is what the launch asks for, computed here as BatCfg::factor_lds does)",
+         "measurements": "# measurements on an MI355X (tools/batch_small_timing.py --gpu)"}
+
+
+def write_section(path, name, lines):
+    """Replaces one section of the profile (a HEADS line and what follows it up to the next one) and keeps the other."""
+    sections = {k: [] for k in HEADS}
+    current = None
+    if os.path.exists(path):
+        for line in open(path).read().splitlines():
+            hit = [k for k, h in HEADS.items() if line.split(" (")[0] == h.split(" (")[0]]
+            if hit:
+                current = hit[0]
+            elif current:
+                sections[current].append(line)
+    sections[name] = list(lines)
+    with open(path, "w") as f:
+        for k, h in HEADS.items():
+            if sections[k]:
+                f.write("\n".join([h] + sections[k]) + "\n")
+
+
+def main():
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
+    if "--resources" in sys.argv:
+        write_section(out, "resources", resources())
+    if "--gpu" in sys.argv:
+        lines, ratio = gpu()
+        write_section(out, "measurements", lines)
+        print("\n".join(lines))
+        sys.exit(0 if ratio <= 8 else 1)
+
+
+if __name__ == "__main__":
+    main()
