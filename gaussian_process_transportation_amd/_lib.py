@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("GPT_HIP_LIB") or os.path.join(_HERE, "libgpt_hip.so")
 
 GPT_OK, GPT_E_HIP, GPT_E_NOT_PD, GPT_E_ARG, GPT_E_STATE = 0, -1, -2, -3, -4
 GPT_F64, GPT_F32 = 0, 1
+INV_CONVERGED, INV_MAX_PASSES, INV_SINGULAR, INV_STALLED = 0, 1, 2, 3      # GPT_INV_*: per-query status of inverse_map
+INV_STATUS_NAMES = ("CONVERGED", "MAX_PASSES", "SINGULAR", "STALLED")
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -41,6 +43,8 @@ SIGNATURES = {
     "gpt_dvariance": (C.c_int, [_vp, _vp, _i64, _vp]),
     "gpt_predict_all": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gpt_predict_all_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "gpt_inverse_map_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "gpt_inverse_map": (C.c_int, [_vp, _dp, _dp, _i64, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -658,6 +662,35 @@ class Handle:
         mean, cov = np.empty((M, O)), np.empty((M, M))
         check(self.lib.gpt_predict_cov(self._h, dptr(Xq), M, dptr(mean), dptr(cov)), "gpt_predict_cov")
         return mean, cov
+
+    # ---- inverse of the displacement map
+    def inverse_map(self, y, z0=None, rtol=1e-10, max_passes=64):
+        """The z (M,D) with z + mean(z) = y for each row of y, by damped Newton on the device (gpt_inverse_map), started at
+        z0 (default: y).  Returns (z, info): info["status"] (M,) int32 INV_*, info["passes"] (M,) int32, info["residual"] (M,)
+        = |z + mean(z) - y| and info["det"] (M,) = det(I + J(z)) at the returned point."""
+        N, D, O, _ = self.info()
+        y = as_f64(y, 2, "y")
+        if y.shape[1] != D:
+            raise ValueError(f"y has {y.shape[1]} columns, model was fitted with {D} features")
+        if z0 is not None:
+            z0 = as_f64(z0, 2, "z0")
+            if z0.shape != y.shape:
+                raise ValueError(f"z0 has shape {z0.shape}, y {y.shape}")
+        M = y.shape[0]
+        z = np.empty((M, D))
+        info = {"status": np.empty(M, dtype=np.int32), "passes": np.empty(M, dtype=np.int32), "residual": np.empty(M),
+                "det": np.empty(M)}
+        ip = C.POINTER(C.c_int)
+        check(self.lib.gpt_inverse_map(self._h, dptr(y), dptr(z0), M, float(rtol), int(max_passes), dptr(z), dptr(info["residual"]),
+                                       dptr(info["det"]), info["passes"].ctypes.data_as(ip), info["status"].ctypes.data_as(ip)),
+              "gpt_inverse_map")
+        return z, info
+
+    def inverse_map_dev(self, y_ptr, M, z_ptr, status_ptr, z0_ptr=0, residual_ptr=0, det_ptr=0, passes_ptr=0, rtol=1e-10, max_passes=64):
+        """The same on device pointers (float64 / int32), asynchronous on the handle's stream (gpt_inverse_map_dev)."""
+        check(self.lib.gpt_inverse_map_dev(self._h, _vp(y_ptr), _vp(z0_ptr or None), int(M), float(rtol), int(max_passes), _vp(z_ptr),
+                                           _vp(residual_ptr or None), _vp(det_ptr or None), _vp(passes_ptr or None), _vp(status_ptr)),
+              "gpt_inverse_map_dev")
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -47,6 +47,11 @@ class AffineTransform:
         x = np.asarray(x, dtype=np.float64)
         return self.scale * ((x - self.S_centroid) @ self.rotation_matrix.T) + self.T_centroid
 
+    def inverse_predict(self, z):
+        """The x with predict(x) = z, scale included (the reference has no inverse; its scale quirk lives in derivative only)."""
+        z = np.asarray(z, dtype=np.float64)
+        return (z - self.T_centroid) @ self.rotation_matrix / self.scale + self.S_centroid
+
     def derivative(self, x):
         # the reference ignores `scale` here (affine_trasformation.py:55-57); preserved
         return np.broadcast_to(self.rotation_matrix, (np.shape(x)[0],) + self.rotation_matrix.shape).copy()

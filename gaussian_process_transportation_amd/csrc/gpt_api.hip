@@ -170,6 +170,7 @@ struct gpt_handle {
     FitAux fit_aux;                // CU-masked streams + events of the factor + inverse plan (gpt_fit_plan.h)
     DevBuf<double> lml_partial;    // partial sums of the LML gradient (grow-only)
     DevBuf<unsigned char> cov_buf; // scratch of gpt_predict_cov (grow-only)
+    DevBuf<unsigned char> inv_buf; // device images of gpt_inverse_map's host arrays (grow-only)
     Event pev[4];
 
     ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
@@ -744,6 +745,74 @@ int gpt_derivative(gpt_handle* h, const void* Xq, int64_t M, void* J, void* Jvar
 
 int gpt_dvariance(gpt_handle* h, const void* Xq, int64_t M, void* g) {
     return gpt_predict_all(h, Xq, M, nullptr, nullptr, nullptr, nullptr, g);
+}
+
+static_assert(GPT_INV_CONVERGED == INV_CONVERGED && GPT_INV_MAX_PASSES == INV_MAX_PASSES && GPT_INV_SINGULAR == INV_SINGULAR &&
+              GPT_INV_STALLED == INV_STALLED, "status codes of the header and of the kernel");
+
+// what both inverse entry points refuse, in the order of the header's list
+static int inverse_check(gpt_handle* h, const char* who, const double* Y, int64_t M, double rtol, int max_passes, const double* Z,
+                         const int* status) {
+    const std::string w(who);
+    if (!h) return fail(GPT_E_ARG, w + ": NULL handle");
+    if (!h->committed) return fail(GPT_E_STATE, w + ": model is not fitted");
+    const KernelParams& p = h->p;
+    if (p.D != p.O || p.D > 3)
+        return fail(GPT_E_ARG, w + ": the inverse needs a map of a space onto itself, D == O, with D <= 3 (this model: D = " +
+                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
+    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (this model was fitted with GPT_F32)");
+    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (this model is a multi-task gpt_fit_svgp model)");
+    if (p.ktype == GPT_KERNEL_MATERN12)
+        return fail(GPT_E_ARG, w + ": Matern 1/2 (nu = 0.5) is not differentiable at the training points: Newton has no Jacobian; "
+                                   "use RBF, Matern 3/2 or Matern 5/2");
+    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
+        return fail(GPT_E_ARG, w + ": the inverse of a Matern model uses the analytic derivatives of its posterior; "
+                                   "gpt_set_matern_derivatives(h, 1) enables them");
+    if (!(rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
+    if (max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
+    if (M < 0 || M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
+    if (M > 0 && (!Y || !Z || !status)) return fail(GPT_E_ARG, w + ": Y, Z and status must not be NULL");
+    return GPT_OK;
+}
+
+int gpt_inverse_map_dev(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
+                        double* residual, double* det, int* passes, int* status) {
+    if (int rc = inverse_check(h, "gpt_inverse_map_dev", Y, M, rtol, max_passes, Z, status)) return rc;
+    if (M == 0) return GPT_OK;
+    if (int rc = set_device(h)) return rc;
+    const InverseArgs a{Y, Z0, M, rtol, max_passes, Z, residual, det, passes, status};
+    launch_inverse_newton(h->stream, h->p, static_cast<const double*>(h->dXs()), static_cast<const double*>(h->dA4()), a);
+    CALLCHK(hipGetLastError());
+    return GPT_OK;
+}
+
+int gpt_inverse_map(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
+                    double* residual, double* det, int* passes, int* status) {
+    if (int rc = inverse_check(h, "gpt_inverse_map", Y, M, rtol, max_passes, Z, status)) return rc;
+    if (M == 0) return GPT_OK;
+    const size_t D = h->p.D, nv = (size_t)M * D;
+    if (!all_finite(Y, nv) || (Z0 && !all_finite(Z0, nv))) return fail(GPT_E_ARG, "gpt_inverse_map: Y / Z0 contain NaN or infinity");
+    if (int rc = set_device(h)) return rc;
+    hipStream_t s = h->stream;
+    // one grow-only image: [Y | Z0 | Z | residual | det | passes | status]
+    const size_t bv = nv * sizeof(double), bs = (size_t)M * sizeof(double), bi = ((size_t)M * sizeof(int) + 15) / 16 * 16;
+    CALLCHK(reserve(h->inv_buf, 3 * bv + 2 * bs + 2 * bi, s));
+    unsigned char* const b = h->inv_buf;
+    double *dY = reinterpret_cast<double*>(b), *dZ0 = reinterpret_cast<double*>(b + bv), *dZ = reinterpret_cast<double*>(b + 2 * bv),
+           *dres = reinterpret_cast<double*>(b + 3 * bv), *ddet = reinterpret_cast<double*>(b + 3 * bv + bs);
+    int *dpass = reinterpret_cast<int*>(b + 3 * bv + 2 * bs), *dstat = reinterpret_cast<int*>(b + 3 * bv + 2 * bs + bi);
+    CALLCHK(hipMemcpyAsync(dY, Y, bv, hipMemcpyHostToDevice, s));
+    if (Z0) CALLCHK(hipMemcpyAsync(dZ0, Z0, bv, hipMemcpyHostToDevice, s));
+    if (int rc = gpt_inverse_map_dev(h, dY, Z0 ? dZ0 : nullptr, M, rtol, max_passes, dZ, residual ? dres : nullptr, det ? ddet : nullptr,
+                                     passes ? dpass : nullptr, dstat))
+        return rc;
+    CALLCHK(hipMemcpyAsync(Z, dZ, bv, hipMemcpyDeviceToHost, s));
+    if (residual) CALLCHK(hipMemcpyAsync(residual, dres, bs, hipMemcpyDeviceToHost, s));
+    if (det) CALLCHK(hipMemcpyAsync(det, ddet, bs, hipMemcpyDeviceToHost, s));
+    if (passes) CALLCHK(hipMemcpyAsync(passes, dpass, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipMemcpyAsync(status, dstat, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
+    return GPT_OK;
 }
 
 // alpha as (N,O) fp64 host array: from the fp64 workspace when this handle ran the fit, else converted from the blob

@@ -167,6 +167,23 @@ void launch_lml_terms(hipStream_t s, const double* Xs, int D, const double* A4, 
 void launch_mean_jac(hipStream_t s, const KernelParams& p, const void* Xs, const void* A4,
                      const void* Xq, int64_t M, void* mean, void* J);
 
+// inverse of the displacement map (gpt_inverse.hip): z + mean(z) = y for M targets, damped Newton, one wave per query, one launch.
+// fp64 single-task models with D == O <= 3, RBF / Matern 3/2 / Matern 5/2 (the caller has checked).  Per-query status codes:
+constexpr int INV_CONVERGED = 0, INV_MAX_PASSES = 1, INV_SINGULAR = 2, INV_STALLED = 3;       // = GPT_INV_* of include/gpt_hip.h
+struct InverseArgs {
+    const double* Y;         // (M, D) targets
+    const double* Z0;        // (M, D) start points, or null: start at y
+    int64_t M;
+    double rtol;             // converged when |z + mean(z) - y| <= rtol (1 + |y|)
+    int max_passes;          // source contractions per query, >= 1
+    double* Z;               // (M, D) the last accepted point
+    double* residual;        // (M) |z + mean(z) - y| there; may be null
+    double* det;             // (M) det(I + J(z)) there; may be null
+    int* passes;             // (M) may be null
+    int* status;             // (M)
+};
+void launch_inverse_newton(hipStream_t s, const KernelParams& p, const double* Xs, const double* A4, const InverseArgs& a);
+
 // Scratch of the variance kernel, owned by a handle (grow-only) and the cached work plan of the last launch shape.
 struct VarPlanHost;
 struct VarWorkspace {

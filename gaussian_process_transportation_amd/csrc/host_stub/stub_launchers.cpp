@@ -67,6 +67,12 @@ void launch_mean_jac(hipStream_t, const KernelParams& p, const void* Xs, const v
     touch_r(Xs, (size_t)p.NP * xs_stride(p.D) * e); touch_r(A4, (size_t)((p.O + 3) / 4) * p.NP * 4 * e); touch_r(Xq, (size_t)M * p.D * e);
     touch_w(mean, (size_t)M * p.O * e); touch_w(J, (size_t)M * p.O * p.D * e);
 }
+void launch_inverse_newton(hipStream_t, const KernelParams& p, const double* Xs, const double* A4, const InverseArgs& a) {
+    if (a.M <= 0) return;
+    const size_t M = (size_t)a.M, D = (size_t)p.D;
+    touch_r(Xs, (size_t)p.NP * 4 * 8); touch_r(A4, (size_t)p.NP * 4 * 8); touch_r(a.Y, M * D * 8); touch_r(a.Z0, M * D * 8);
+    touch_w(a.Z, M * D * 8); touch_w(a.residual, M * 8); touch_w(a.det, M * 8); touch_w(a.passes, M * 4); touch_w(a.status, M * 4);
+}
 void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, const void* Xs, const void* Wf, const void* Xq, int64_t M,
                 int ncomp, void* var, void* Jvar, void* dvar, const double* hdr) {
     if (M <= 0 || !ws.plan) return;

@@ -240,6 +240,40 @@ class GaussianProcess:
         self._require_derivatives("derivative_of_variance")
         return self._handle.predict_all(x, dvar=True)["dvar"]
 
+    # ------------------------------------------------------------------ inverse of the displacement map
+    def invert_displacement(self, y, x0=None, rtol=1e-10, max_passes=64, return_info=False):
+        """The z (M,D) with z + predict(z) = y: the map x -> x + predict(x) that PolicyTransportation.transport applies
+        after its affine part, inverted by damped Newton on the device, every query in one wave of one launch
+        (_lib.Handle.inverse_map; the reference only approximates this with a second transport fitted backwards,
+        example/2D/surface_generalization_heteroschedastic _inverse_mapping.py:88-127).  x0 (M,D): start points (default y).
+        A query stops when |z + predict(z) - y| <= rtol (1 + |y|) or after max_passes evaluations of the model.
+        With return_info also a dict: status (M,) (_lib.INV_CONVERGED / INV_MAX_PASSES / INV_SINGULAR / INV_STALLED), passes
+        (M,), residual (M,), det (M,) = det(I + derivative(z)) — not positive where the map folds and the solution is one
+        of several.  Needs n_outputs == n_features <= 3, float64, and for a Matern model matern_derivatives=True.  With
+        devices=[...] it runs on the device that holds the fit."""
+        self._require_fit()
+        if self.n_outputs != self.n_features or self.n_features > 3:
+            raise NotImplementedError(f"invert_displacement(): the inverse needs a map of a space onto itself with at most 3 "
+                                      f"dimensions (this model: {self.n_features} features, {self.n_outputs} outputs)")
+        if self._dtype != _lib.GPT_F64:
+            raise NotImplementedError("invert_displacement(): float64 models only (this one was built with dtype='float32')")
+        self._require_derivatives("invert_displacement")
+        if not float(rtol) > 0.0:
+            raise ValueError("invert_displacement(): rtol must be > 0")
+        if int(max_passes) < 1:
+            raise ValueError("invert_displacement(): max_passes must be >= 1")
+        y = _lib.as_f64(y, 2, "y")
+        if y.shape[1] != self.n_features:
+            raise ValueError(f"y has {y.shape[1]} columns, the model {self.n_features} features")
+        if x0 is not None:
+            x0 = _lib.as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
+        if y.shape[0] >= 2 ** 31:
+            raise ValueError("invert_displacement(): fewer than 2^31 points per call")
+        z, info = self._handle.inverse_map(y, x0, rtol=rtol, max_passes=max_passes)
+        return (z, info) if return_info else z
+
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):
         """Everything predict(x, return_std=True) and derivative(x, return_var=True) return, computed in ONE pass over

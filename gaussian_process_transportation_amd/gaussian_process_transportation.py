@@ -58,6 +58,11 @@ class GaussianProcessTransportation:
         if orientations is not _MISSING:
             self.training_ori = self.method.transport_orientation(before, orientations)
 
+    def inverse_transport(self, points, x0=None, return_info=False, **solver):
+        """The points that fit_transportation()'s map sends to `points` (an addition: PolicyTransportation.inverse_transport);
+        x0: a guess of them, return_info: also status / passes / residual / det per point, solver: rtol, max_passes."""
+        return self.method.inverse_transport(points, x0=x0, return_info=return_info, **solver)
+
     def sample_transportation(self):
         """Posterior draws of the moved demonstration, at the positions of the last apply_transportation() (:29-30)."""
         return self.method.sample_transportation(self._input("training_traj_old"))

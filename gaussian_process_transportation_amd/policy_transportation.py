@@ -1,6 +1,7 @@
 """PolicyTransportation — Phi(x) = gamma(x) + Psi(gamma(x)) with gamma an AffineTransform and Psi
 any `delta_map` exposing fit / predict / derivative / samples (duck-typed plugin slot of the
-reference, policy_transportation/transportation/policy_transportation.py:11-84)."""
+reference, policy_transportation/transportation/policy_transportation.py:11-84); `inverse_transport` (an addition) needs a
+delta_map that also has `invert_displacement`."""
 import numpy as np
 
 from .affine_transform import AffineTransform
@@ -38,6 +39,29 @@ class PolicyTransportation:
         else:
             delta_mean, delta_std = self.delta_map.predict(pos_rotated, return_std=False), None
         return pos_rotated + delta_mean, delta_std
+
+    def inverse_transport(self, pos, x0=None, return_info=False, **solver):
+        """The x with transport(x) = pos: Phi^-1 = gamma^-1 o (id + Psi)^-1.  The displacement part is solved by the
+        delta_map (`invert_displacement`, e.g. GaussianProcess: damped Newton on the device; `solver` passes rtol /
+        max_passes on), started at gamma(x0) when x0 (a guess of the preimage) is given; the affine part is closed form.
+        With return_info also the delta_map's dict (status, passes, residual, det per point).  The reference has no inverse:
+        its inverse-mapping example (example/2D/surface_generalization_heteroschedastic _inverse_mapping.py:88-127) fits a
+        second transport backwards instead."""
+        invert = getattr(self.delta_map, "invert_displacement", None)
+        if invert is None:
+            raise NotImplementedError(f"inverse_transport(): the delta_map ({type(self.delta_map).__name__}) has no "
+                                      "invert_displacement(y, x0, ..., return_info=True); GaussianProcess provides one")
+        z0 = None if x0 is None else self.affine_transform.predict(x0)
+        z, info = invert(np.asarray(pos, dtype=np.float64), z0, return_info=True, **solver)
+        if self.verbose:
+            from ._lib import INV_CONVERGED, INV_STATUS_NAMES
+            status = np.asarray(info["status"])
+            counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(INV_STATUS_NAMES))
+            solved = status == INV_CONVERGED
+            print(f"Inverse of the map: {counts}; det(I + J_psi) <= 0 at {int(np.sum(np.asarray(info['det'])[solved] <= 0))} "
+                  f"of {int(np.sum(solved))} solutions (the map folds there: not a diffeomorphism)")
+        x = self.affine_transform.inverse_predict(z)
+        return (x, info) if return_info else x
 
     def transport_velocity(self, pos, vel, return_var=True):
         """Push velocities through the Jacobian of Phi; variance from the Jacobian variance (:37-59)."""

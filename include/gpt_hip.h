@@ -273,6 +273,35 @@ int gpt_predict_all_dev(gpt_handle* h, const void* Xq_dev, int64_t M, void* mean
  * jacobian_variance != 0 for the 4-column path), so that the first such call does not allocate. */
 int gpt_reserve(gpt_handle* h, int64_t M, int jacobian_variance);
 
+/* (new) Inverse of the displacement map: for each of M targets y (M,D) the z with  z + mean(z) = y,  mean the posterior mean
+ * of gpt_predict — the map of PolicyTransportation.transport (transportation/policy_transportation.py:30-35) after its affine
+ * part, taken backwards.  The reference has no inverse: example/2D/surface_generalization_heteroschedastic _inverse_mapping.py:88-127
+ * fits a SECOND transport with source and target swapped and walks a grid through it in a Python loop, and
+ * GaussianProcessTransportationDiffeo.check_invertibility (transportation/gaussian_process_transportation_diffeomorphic.py:109-121)
+ * measures how far that surrogate misses.  Here the equation itself is solved, damped Newton, every query in one wave of ONE launch:
+ *   z <- Z0 (y when Z0 is NULL); r = z + mean(z) - y; A = I + J(z); rho = |r|_2; tol = rtol (1 + |y|_2); t = 1; passes = 1; repeat:
+ *     rho <= tol -> GPT_INV_CONVERGED;  passes == max_passes -> GPT_INV_MAX_PASSES;  |det A| <= 2^-40 |A|_F^D -> GPT_INV_SINGULAR;
+ *     z' = z - t A^-1 r, one more pass there; rho' < rho: z' is accepted and t = min(1, 2t); else t = t/2 and below 2^-20
+ *     -> GPT_INV_STALLED.
+ * Z (M,D): the last accepted point; residual (M): rho there; det (M): det(I + J) there — <= 0 where the map folds, the honest
+ * form of the "locally diffeomorphic?" print of policy_transportation.py:52; passes (M): contractions over the sources spent;
+ * status (M): GPT_INV_*.  residual, det and passes may be NULL.  A query's result does not depend on M or on the other queries,
+ * bit for bit.  The return value is GPT_OK whenever the launch ran: a query that did not converge says so in its status.
+ * GPT_E_STATE: no model.  GPT_E_ARG (the message names the limit): D != O or D > 3; a GPT_F32 or multi-task (gpt_fit_svgp) model;
+ * Matern 1/2, or Matern 3/2 / 5/2 without gpt_set_matern_derivatives; rtol <= 0; max_passes < 1; M < 0 or M >= 2^31.  M = 0 does
+ * nothing.  Device memory, asynchronous on the handle's stream; the model and the handle's scratch are left as they were. */
+#define GPT_INV_CONVERGED 0
+#define GPT_INV_MAX_PASSES 1
+#define GPT_INV_SINGULAR 2
+#define GPT_INV_STALLED 3
+int gpt_inverse_map_dev(gpt_handle* h, const double* Y_dev, const double* Z0_dev, int64_t M, double rtol, int max_passes,
+                        double* Z_dev, double* residual_dev, double* det_dev, int* passes_dev, int* status_dev);
+/* (new) The same with every pointer in host memory (the 100 x 100 grid of the inverse-mapping example :110-127, the trajectory of
+ * check_invertibility :109-121); also GPT_E_ARG for NaN / infinity in Y or Z0.  The device images belong to the handle.  Returns
+ * when every output is in place. */
+int gpt_inverse_map(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
+                    double* residual, double* det, int* passes, int* status);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);
