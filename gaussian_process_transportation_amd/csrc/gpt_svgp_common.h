@@ -1,6 +1,7 @@
-// What the two SVGP trainers share (internal header; gpt_svgp_train.hip, gpt_svgp_surface.hip): the model family's constants,
-// the device helpers of the whitened ELBO and of Adam, and the host side of a training call that does not depend on a unit's
-// theta layout.  Each unit keeps its args struct, its theta layout (pack / unpack), its workspace and its per-step enqueue.
+// What the two SVGP trainers share (internal header; gpt_svgp_train*.hip, gpt_svgp_surface*.hip): the model family's constants
+// and the host side of a training call that does not depend on a unit's theta layout.  Each unit keeps its args struct, its
+// theta layout (pack / unpack), its workspace and its per-step enqueue.  Plain C++ (the sanitizer build compiles it with g++);
+// the device helpers of the whitened ELBO and of Adam are in gpt_svgp_device.h.
 #pragma once
 #include "gpt_call.h"
 
@@ -12,33 +13,6 @@ constexpr double JITTER = 1e-4;              // gpytorch's float32 Cholesky jitt
 constexpr double NOISE_FLOOR = 1e-4;         // GreaterThan(1e-4) on each likelihood noise
 constexpr double BETA1 = 0.9, BETA2 = 0.999, ADAM_EPS = 1e-8;
 constexpr double LOG_2PI = 1.8378770664093453;
-
-__device__ inline double softplus(double x) { return x > 20.0 ? x : log1p(exp(x)); }
-__device__ inline double softplus_grad(double x) { if (x > 20.0) return 1.0; double z = exp(x); return z / (z + 1.0); }
-
-// Fixed-order sum over the workgroup (every thread returns the total).
-__device__ inline double block_sum(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = NT / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// torch.optim.Adam's update of one element (single-tensor path): bc1 = 1 - beta1^k, bc2s = sqrt(1 - beta2^k).
-__device__ inline void adam(double& p, double g, double& a, double& b, double lr, double bc1, double bc2s) {
-    a = a + (1.0 - BETA1) * (g - a);
-    b = b * BETA2 + (1.0 - BETA2) * g * g;
-    p = p + (-(lr / bc1)) * (a / (sqrt(b) / bc2s + ADAM_EPS));
-}
-
-struct AdamBias { double bc1, bc2s; };       // 1 - beta1^k and sqrt(1 - beta2^k) of optimiser step k = 1, 2, ...
-inline AdamBias adam_bias(double k) { return {1.0 - std::pow(BETA1, k), std::sqrt(1.0 - std::pow(BETA2, k))}; }
 
 struct SvgpLimits { int max_z, max_t, max_b; };    // inducing points, tasks, rows per batch
 

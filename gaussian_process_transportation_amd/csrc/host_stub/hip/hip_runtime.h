@@ -1,5 +1,6 @@
-// Host-only stand-in for <hip/hip_runtime.h>, used ONLY by the sanitizer build of the C-ABI's host orchestration
-// (`make host-asan`: gpt_api.hip compiled by g++ with -fsanitize=address,undefined against host_stub/).  "Device"
+// Host-only stand-in for <hip/hip_runtime.h>, used ONLY by the sanitizer builds of the C-ABI's host orchestration
+// (`make host-asan`, `make host-oneshot-asan`: gpt_api.hip and the *_host.hip halves of the one-shot units compiled by g++ with
+// -fsanitize=address,undefined against host_stub/).  "Device"
 // memory is malloc'ed host memory, so AddressSanitizer sees every staging copy, header read and plan upload the
 // orchestration makes; streams and events are inert; kernels are replaced by host_stub/stub_launchers.cpp.
 // Every live allocation, stream and event is counted (stub_live_objects), so that the driver of the sanitizer run can check
@@ -46,6 +47,7 @@ static inline hipError_t hipMalloc(T** p, size_t bytes) {
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 static inline hipError_t hipFree(void* p) { stub_delete(p); return hipSuccess; }
+static inline hipError_t hipMemGetInfo(size_t* free_bytes, size_t* total) { *free_bytes = *total = (size_t)1 << 36; return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t) { memcpy(d, s, n); return hipSuccess; }

@@ -1,0 +1,401 @@
+// Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
+// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip) and gpt_inverse_map (gpt_api.hip) on the stand-in "device" memory of
+// host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
+// array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
+// The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
+// holds zeros from end to end, and one that was not, or that belongs to a failed member or a failed call, still holds the
+// sentinel.  After every call nothing allocated may be left (stub_live_objects); after a call on a handle, nothing but what the
+// handle held before it.  One line per case, then ONESHOT_DRIVER_OK.
+#include <hip/hip_runtime.h>
+#include "../../../include/gpt_hip.h"
+
+#include <algorithm>
+#include <array>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+namespace gpt {
+extern int stub_fail_model;      // stub_launchers.cpp
+extern bool stub_fail_flag;
+}
+
+namespace {
+
+constexpr double SENT = -7.25e300;
+constexpr int ISENT = -77;
+
+#define CHECK(cond)                                                                                                   \
+    do {                                                                                                              \
+        if (!(cond)) {                                                                                                \
+            fprintf(stderr, "FAILED %s: %s (line %d; last error: %s)\n", g_case.c_str(), #cond, __LINE__, gpt_last_error()); \
+            exit(1);                                                                                                  \
+        }                                                                                                             \
+    } while (0)
+
+std::string g_case;
+int g_cases = 0;
+
+// An array of exactly n elements (n = 0 included: still a pointer of its own).
+template <class T> struct Arr {
+    size_t n;
+    T* p;
+    Arr(size_t n_, T v) : n(n_), p(new T[n_]) { std::fill(p, p + n, v); }
+    Arr(std::initializer_list<T> l) : n(l.size()), p(new T[l.size()]) { std::copy(l.begin(), l.end(), p); }
+    Arr(const Arr& o) : n(o.n), p(new T[o.n]) { std::copy(o.p, o.p + n, p); }
+    Arr& operator=(const Arr&) = delete;
+    ~Arr() { delete[] p; }
+    bool all(T v, size_t b, size_t e) const { return std::all_of(p + b, p + e, [v](T x) { return x == v; }); }
+    bool all(T v) const { return all(v, 0, n); }
+    bool same(const Arr& o) const { return n == o.n && std::equal(p, p + n, o.p); }
+};
+using D = Arr<double>;
+
+// inputs: finite, positive, distinct enough that no check refuses them
+D ramp(size_t n, double first = 0.25, double step = 0.125) {
+    D a(n, 0.0);
+    for (size_t i = 0; i < n; ++i) a.p[i] = first + step * (double)(i % 17);
+    return a;
+}
+
+void begin(const std::string& name) { g_case = name; }
+void done(int rc, int want) {
+    CHECK(rc == want);
+    CHECK(stub_live_objects == 0);
+    printf("ok  %s\n", g_case.c_str());
+    ++g_cases;
+}
+
+// ---- batch --------------------------------------------------------------------------------------------------------------------
+struct BatchShape {
+    std::vector<int> n;
+    int Dm, n_ls, O;
+    int64_t B() const { return (int64_t)n.size(); }
+    std::string name() const {
+        std::string s = "B=" + std::to_string(B()) + " n={";
+        for (int v : n) s += std::to_string(v) + ",";
+        return s + "} D=" + std::to_string(Dm) + " n_ls=" + std::to_string(n_ls) + " O=" + std::to_string(O);
+    }
+};
+
+struct BatchInputs {
+    Arr<int64_t> n_begin, l_begin;
+    D ls, c, noise;
+    explicit BatchInputs(const BatchShape& s)
+        : n_begin(s.n.size() + 1, 0), l_begin(s.n.size() + 1, 0), ls(ramp(s.n.size() * s.n_ls, 0.5)), c(ramp(s.n.size(), 1.0)),
+          noise(ramp(s.n.size(), 0.01, 0.01)) {
+        for (size_t b = 0; b < s.n.size(); ++b) { n_begin.p[b + 1] = n_begin.p[b] + s.n[b]; l_begin.p[b + 1] = l_begin.p[b] + s.n[b] * s.n[b]; }
+    }
+};
+
+// slices [begin[b] * width, begin[b + 1] * width) hold zeros for a member that ran and the sentinel for the failed one
+void check_slices(const D& out, const Arr<int64_t>& begin, size_t width, int failed) {
+    for (size_t b = 0; b + 1 < begin.n; ++b)
+        CHECK(out.all((int)b == failed ? SENT : 0.0, (size_t)begin.p[b] * width, (size_t)begin.p[b + 1] * width));
+}
+void check_status(const Arr<int>& status, int failed) {
+    for (size_t b = 0; b < status.n; ++b) CHECK(status.p[b] == ((int)b == failed ? GPT_E_NOT_PD : GPT_OK));
+}
+
+void batch_cases(const BatchShape& s, const std::vector<int>& queries, int failed) {
+    const int64_t B = s.B();
+    BatchInputs in(s);
+    const size_t rows = (size_t)in.n_begin.p[B];
+    D X = ramp(rows * s.Dm), Y = ramp(rows * s.O);
+    Arr<int64_t> one_each(B + 1, 0);
+    for (int64_t b = 0; b <= B; ++b) one_each.p[b] = b;
+    const std::string tag = s.name() + (failed >= 0 ? " failed=" + std::to_string(failed) : "");
+    gpt::stub_fail_model = failed;
+    {
+        begin("gpt_batch_lml_objective " + tag);
+        D lml(B, SENT), grad(B * (2 + s.n_ls), SENT);
+        Arr<int> status(B, ISENT);
+        done(gpt_batch_lml_objective(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, in.ls.p, s.n_ls, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, lml.p,
+                                     grad.p, status.p), GPT_OK);
+        check_status(status, failed);
+        check_slices(lml, one_each, 1, failed);
+        check_slices(grad, one_each, 2 + s.n_ls, failed);
+    }
+    for (int mask : {0, 3, 1, 2}) {                                      // neither optional output, both, L alone, lml alone
+        begin("gpt_batch_fit " + tag + (mask & 1 ? " L" : " L=NULL") + (mask & 2 ? " lml" : " lml=NULL"));
+        D L((size_t)in.l_begin.p[B], SENT), alpha(rows * s.O, SENT), lml(B, SENT);
+        Arr<int> status(B, ISENT);
+        done(gpt_batch_fit(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, in.ls.p, s.n_ls, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_MATERN32,
+                           mask & 1 ? L.p : nullptr, alpha.p, mask & 2 ? lml.p : nullptr, status.p), GPT_OK);
+        check_status(status, failed);
+        check_slices(alpha, in.n_begin, s.O, failed);
+        if (mask & 1) check_slices(L, in.l_begin, 1, failed);
+        else CHECK(L.all(SENT));
+        if (mask & 2) check_slices(lml, one_each, 1, failed);
+        else CHECK(lml.all(SENT));
+    }
+    Arr<int64_t> q_begin(B + 1, 0);
+    for (int64_t b = 0; b < B; ++b) q_begin.p[b + 1] = q_begin.p[b] + queries[b];
+    const size_t M = (size_t)q_begin.p[B];
+    D Xq = ramp(M * s.Dm);
+    const size_t widths[5] = {(size_t)s.O, 1, (size_t)s.O * s.Dm, (size_t)s.Dm, (size_t)s.Dm};
+    for (int mask : {31, 1, 2, 4, 8, 16}) {
+        begin("gpt_batch_predict " + tag + " M=" + std::to_string(M) + " outputs=" + std::to_string(mask));
+        std::vector<D> out;
+        double* ptr[5];
+        for (int k = 0; k < 5; ++k) out.emplace_back(M * widths[k], SENT);
+        for (int k = 0; k < 5; ++k) ptr[k] = (mask >> k & 1) ? out[k].p : nullptr;
+        Arr<int> status(B, ISENT);
+        done(gpt_batch_predict(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, in.ls.p, s.n_ls, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF,
+                               M ? Xq.p : nullptr, q_begin.p, ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], status.p), GPT_OK);
+        check_status(status, failed);
+        for (int k = 0; k < 5; ++k) {
+            if (ptr[k]) check_slices(out[k], q_begin, widths[k], failed);
+            else CHECK(out[k].all(SENT));
+        }
+    }
+    gpt::stub_fail_model = -1;
+}
+
+void batch_refusals() {
+    BatchShape s{{1, 32, 33}, 3, 3, 3};
+    BatchInputs in(s);
+    D X = ramp(66 * 3), Y = ramp(66 * 3), lml(3, SENT), grad(3 * 5, SENT), alpha(66 * 3, SENT), Xq = ramp(3 * 3), mean(3 * 3, SENT);
+    Arr<int> status(3, ISENT);
+    Arr<int64_t> q_begin{0, 1, 2, 3};
+    auto objective = [&](const double* x, const int64_t* nb, int64_t B, int Dm, int n_ls) {
+        return gpt_batch_lml_objective(0, x, Y.p, nb, B, Dm, 3, in.ls.p, n_ls, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, lml.p, grad.p, status.p);
+    };
+    begin("gpt_batch_lml_objective refuses X = NULL"); done(objective(nullptr, in.n_begin.p, 3, 3, 3), GPT_E_ARG);
+    begin("gpt_batch_lml_objective refuses B = 0"); done(objective(X.p, in.n_begin.p, 0, 3, 3), GPT_E_ARG);
+    begin("gpt_batch_lml_objective refuses D = 16"); done(objective(X.p, in.n_begin.p, 3, 16, 1), GPT_E_ARG);
+    Arr<int64_t> too_many{0, 129};
+    D X129 = ramp(129 * 3), Y129 = ramp(129 * 3);
+    begin("gpt_batch_fit refuses n_b = 129");
+    done(gpt_batch_fit(0, X129.p, Y129.p, too_many.p, 1, 3, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, nullptr, alpha.p, nullptr,
+                       status.p), GPT_E_ARG);
+    begin("gpt_batch_fit refuses alpha = NULL");
+    done(gpt_batch_fit(0, X.p, Y.p, in.n_begin.p, 3, 3, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, nullptr, nullptr, nullptr,
+                       status.p), GPT_E_ARG);
+    begin("gpt_batch_predict refuses q_begin = NULL");
+    done(gpt_batch_predict(0, X.p, Y.p, in.n_begin.p, 3, 3, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, Xq.p, nullptr, mean.p, nullptr,
+                           nullptr, nullptr, nullptr, status.p), GPT_E_ARG);
+    begin("gpt_batch_predict refuses J of a Matern batch");
+    done(gpt_batch_predict(0, X.p, Y.p, in.n_begin.p, 3, 3, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_MATERN52, Xq.p, q_begin.p, nullptr,
+                           nullptr, mean.p, nullptr, nullptr, status.p), GPT_E_ARG);
+    CHECK(lml.all(SENT) && grad.all(SENT) && alpha.all(SENT) && mean.all(SENT) && status.all(ISENT));
+}
+
+// ---- select -------------------------------------------------------------------------------------------------------------------
+void select_cases() {
+    const int64_t N = 5;
+    for (int Dm : {1, 3, 4, 9})
+        for (int n_total : {1, 4, 5})
+            for (int n_initial : {0, 2, n_total})
+                for (int with_residual = 0; with_residual < 2; ++with_residual)
+                    for (int failing = 0; failing < 2; ++failing) {
+                        if (n_initial > n_total || (failing && (with_residual || n_initial == 2))) continue;
+                        begin("gpt_select_greedy D=" + std::to_string(Dm) + " n_total=" + std::to_string(n_total) + " n_initial=" +
+                              std::to_string(n_initial) + (with_residual ? " residual" : "") + (failing ? " failure flag" : ""));
+                        D X = ramp(N * Dm), ls = ramp(Dm, 0.5), selvar(n_total - n_initial, SENT), residual(N, SENT);
+                        Arr<int64_t> initial(n_initial, 0), selected(n_total, ISENT);
+                        for (int t = 0; t < n_initial; ++t) initial.p[t] = N - 1 - t;
+                        gpt::stub_fail_flag = failing;
+                        done(gpt_select_greedy(0, X.p, N, Dm, ls.p, 1.0, 0.01, 1e-10, GPT_KERNEL_MATERN52, n_initial ? initial.p : nullptr, n_initial,
+                                               n_total, selected.p, n_initial == n_total ? nullptr : selvar.p, with_residual ? residual.p : nullptr),
+                             failing ? GPT_E_NOT_PD : GPT_OK);
+                        gpt::stub_fail_flag = false;
+                        if (failing) { CHECK(selected.all(ISENT) && selvar.all(SENT) && residual.all(SENT)); continue; }
+                        std::vector<int> seen(N, 0);
+                        for (int t = 0; t < n_total; ++t) {
+                            CHECK(selected.p[t] >= 0 && selected.p[t] < N && !seen[selected.p[t]]++);
+                            if (t < n_initial) CHECK(selected.p[t] == initial.p[t]);
+                        }
+                        CHECK(std::none_of(selvar.p, selvar.p + selvar.n, [](double v) { return v == SENT; }));
+                        CHECK(with_residual ? std::none_of(residual.p, residual.p + N, [](double v) { return v == SENT; }) : residual.all(SENT));
+                    }
+    D X = ramp(N * 3), ls = ramp(3, 0.5), selvar(5, SENT);
+    Arr<int64_t> selected(5, ISENT), bad_initial{1, 5}, twice{2, 2};
+    auto select = [&](const double* x, int Dm, const int64_t* initial, int n_initial, int n_total) {
+        return gpt_select_greedy(0, x, N, Dm, ls.p, 1.0, 0.01, 1e-10, GPT_KERNEL_RBF, initial, n_initial, n_total, selected.p, selvar.p, nullptr);
+    };
+    begin("gpt_select_greedy refuses X = NULL"); done(select(nullptr, 3, nullptr, 0, 2), GPT_E_ARG);
+    begin("gpt_select_greedy refuses D = 16"); done(select(X.p, 16, nullptr, 0, 2), GPT_E_ARG);
+    begin("gpt_select_greedy refuses n_total > N"); done(select(X.p, 3, nullptr, 0, 6), GPT_E_ARG);
+    begin("gpt_select_greedy refuses an initial index out of range"); done(select(X.p, 3, bad_initial.p, 2, 3), GPT_E_ARG);
+    begin("gpt_select_greedy refuses an initial index listed twice"); done(select(X.p, 3, twice.p, 2, 3), GPT_E_ARG);
+    CHECK(selected.all(ISENT) && selvar.all(SENT));
+}
+
+// ---- SVGP trainers ------------------------------------------------------------------------------------------------------------
+using TrainFn = int (*)(int, const double*, const double*, int64_t, int, int, int, double*, double*, double*, double*, double*, double*,
+                        const int64_t*, int64_t, const int64_t*, int64_t, double, double*);
+using GradFn = int (*)(int, const double*, const double*, int64_t, int64_t, int, int, int, const double*, const double*, const double*,
+                       const double*, const double*, const double*, double*, double*, double*, double*, double*, double*, double*);
+
+struct SvgpParams {
+    D Z, m, C, raw_ls, raw_os, raw_noise;
+    SvgpParams(int T, int Zn, int Dm, size_t n_ls, double fill)
+        : Z(Zn * Dm, fill), m(T * Zn, fill), C((size_t)T * Zn * Zn, fill), raw_ls(n_ls, fill), raw_os(T, fill), raw_noise(T + 1, fill) {}
+    D& at(int q) { D* a[6] = {&Z, &m, &C, &raw_ls, &raw_os, &raw_noise}; return *a[q]; }
+};
+constexpr double UPPER = 77.0;       // the strict upper triangle of C: not a parameter, returned as passed
+
+SvgpParams svgp_params(int T, int Zn, int Dm, size_t n_ls) {
+    SvgpParams p(T, Zn, Dm, n_ls, 0.0);
+    for (int q = 0; q < 6; ++q)
+        for (size_t i = 0; i < p.at(q).n; ++i) p.at(q).p[i] = 0.25 + 0.125 * (double)(i % 13);
+    for (int t = 0; t < T; ++t)
+        for (int i = 0; i < Zn; ++i)
+            for (int j = i + 1; j < Zn; ++j) p.C.p[((size_t)t * Zn + i) * Zn + j] = UPPER;
+    return p;
+}
+
+void svgp_cases(const std::string& unit, TrainFn train, GradFn elbo_grad, bool ls_per_task) {
+    const int64_t N = 7;
+    for (auto [T, Zn, Dm] : {std::array<int, 3>{1, 1, 1}, std::array<int, 3>{3, 5, 2}}) {
+        const size_t n_ls = ls_per_task ? (size_t)T * Dm : (size_t)Dm;
+        const std::string shape = " T=" + std::to_string(T) + " Z=" + std::to_string(Zn) + " D=" + std::to_string(Dm);
+        D X = ramp(N * Dm), Y = ramp(N * T);
+        // the schedule starts past idx[0], which is no row of X (an upload that is not offset by batch_begin[0] hands it to the
+        // stand-in kernels, which refuse it); batches of 3, 1 and 2 rows
+        Arr<int64_t> idx{99, 0, 3, 5, 2, 6, 1}, bb{1, 4, 5, 7};
+        for (int failing = 0; failing < 2; ++failing) {
+            begin(unit + "_train" + shape + (failing ? " failure flag" : ""));
+            SvgpParams p = svgp_params(T, Zn, Dm, n_ls);
+            SvgpParams passed = svgp_params(T, Zn, Dm, n_ls);
+            D loss(3, SENT);
+            gpt::stub_fail_flag = failing;
+            done(train(0, X.p, Y.p, N, Dm, T, Zn, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, p.raw_noise.p, idx.p, (int64_t)idx.n, bb.p, 3, 0.01,
+                       loss.p), failing ? GPT_E_NOT_PD : GPT_OK);
+            gpt::stub_fail_flag = false;
+            if (failing) {
+                for (int q = 0; q < 6; ++q) CHECK(p.at(q).same(passed.at(q)));
+                CHECK(loss.all(SENT));
+                continue;
+            }
+            CHECK(loss.all(0.0) && p.Z.all(0.0) && p.m.all(0.0) && p.raw_ls.all(0.0) && p.raw_os.all(0.0) && p.raw_noise.all(0.0));
+            for (int t = 0; t < T; ++t)
+                for (int i = 0; i < Zn; ++i)
+                    for (int j = 0; j < Zn; ++j) CHECK(p.C.p[((size_t)t * Zn + i) * Zn + j] == (j <= i ? 0.0 : UPPER));
+        }
+        for (int mask : {63, 21, 42}) {                                  // all gradients; every second one NULL, either way round
+            begin(unit + "_elbo_grad" + shape + " gradients=" + std::to_string(mask));
+            SvgpParams p = svgp_params(T, Zn, Dm, n_ls), g(T, Zn, Dm, n_ls, SENT);
+            D loss(1, SENT), Xb = ramp(3 * Dm), Yb = ramp(3 * T);
+            double* gp[6];
+            for (int q = 0; q < 6; ++q) gp[q] = (mask >> q & 1) ? g.at(q).p : nullptr;
+            done(elbo_grad(0, Xb.p, Yb.p, 3, N, Dm, T, Zn, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, p.raw_noise.p, loss.p, gp[0], gp[1], gp[2],
+                           gp[3], gp[4], gp[5]), GPT_OK);
+            CHECK(loss.all(0.0));
+            for (int q = 0; q < 6; ++q) CHECK(g.at(q).all(gp[q] ? 0.0 : SENT));
+        }
+    }
+    D X = ramp(N * 2), Y = ramp(N * 3), loss(1, SENT);
+    SvgpParams p = svgp_params(3, 5, 2, ls_per_task ? 6 : 2);
+    Arr<int64_t> idx{0, 1, 7}, bb{0, 3};
+    auto run = [&](const double* x, int Dm, int64_t last) {
+        return train(0, x, Y.p, N, Dm, 3, 5, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, p.raw_noise.p, idx.p, 3, bb.p, last, 0.01, loss.p);
+    };
+    begin(unit + "_train refuses X = NULL"); done(run(nullptr, 2, 1), GPT_E_ARG);
+    begin(unit + "_train refuses D = 16"); done(run(X.p, 16, 1), GPT_E_ARG);
+    begin(unit + "_train refuses an empty schedule"); done(run(X.p, 2, 0), GPT_E_ARG);
+    begin(unit + "_train refuses a schedule index out of range"); done(run(X.p, 2, 1), GPT_E_ARG);
+    begin(unit + "_elbo_grad refuses b = 0");
+    done(elbo_grad(0, X.p, Y.p, 0, N, 2, 3, 5, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, p.raw_noise.p, loss.p, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, nullptr), GPT_E_ARG);
+    CHECK(loss.all(SENT));
+}
+
+void surface_predict_cases() {
+    for (auto [T, Zn, Dm] : {std::array<int, 3>{1, 1, 1}, std::array<int, 3>{3, 5, 2}}) {
+        const SvgpParams p = svgp_params(T, Zn, Dm, (size_t)T * Dm);
+        for (int64_t M : {(int64_t)1, (int64_t)64, (int64_t)65, (int64_t)1025})      // 1025: one query past a whole prediction chunk
+            for (int mask : {0, 3, 1, 2})
+                for (int failing = 0; failing < 2; ++failing) {
+                    if (failing && (mask != 3 || M != 65)) continue;
+                    begin("gpt_svgp_surface_predict T=" + std::to_string(T) + " Z=" + std::to_string(Zn) + " D=" + std::to_string(Dm) + " M=" +
+                          std::to_string(M) + (mask & 1 ? " var" : "") + (mask & 2 ? " J" : "") + (failing ? " failure flag" : ""));
+                    D Xq = ramp(M * Dm), mean(M * T, SENT), var(M * T, SENT), J((size_t)M * T * Dm, SENT);
+                    gpt::stub_fail_flag = failing;
+                    done(gpt_svgp_surface_predict(0, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, Zn, Dm, T, Xq.p, M, mean.p, mask & 1 ? var.p : nullptr,
+                                                  mask & 2 ? J.p : nullptr), failing ? GPT_E_NOT_PD : GPT_OK);
+                    gpt::stub_fail_flag = false;
+                    CHECK(mean.all(failing ? SENT : 0.0));
+                    CHECK(var.all(!failing && (mask & 1) ? 0.0 : SENT) && J.all(!failing && (mask & 2) ? 0.0 : SENT));
+                }
+    }
+    const SvgpParams p = svgp_params(3, 5, 2, 6);
+    D Xq = ramp(2), mean(3, SENT);
+    auto predict = [&](const double* xq, int Dm, int64_t M) {
+        return gpt_svgp_surface_predict(0, p.Z.p, p.m.p, p.C.p, p.raw_ls.p, p.raw_os.p, 5, Dm, 3, xq, M, mean.p, nullptr, nullptr);
+    };
+    begin("gpt_svgp_surface_predict refuses Xq = NULL"); done(predict(nullptr, 2, 1), GPT_E_ARG);
+    begin("gpt_svgp_surface_predict refuses D = 16"); done(predict(Xq.p, 16, 1), GPT_E_ARG);
+    begin("gpt_svgp_surface_predict refuses M = 0"); done(predict(Xq.p, 2, 0), GPT_E_ARG);
+    CHECK(mean.all(SENT));
+}
+
+// ---- inverse map (gpt_api.hip): one image carved into Y | Z0 | Z | residual | det | passes | status ----------------------------
+void inverse_map_cases() {
+    const int64_t N = 5;
+    D X = ramp(N * 2), Y = ramp(N * 2, 0.01, 0.01), ls{0.5, 0.75};
+    gpt_handle* h = nullptr;
+    begin("gpt_inverse_map setup");
+    CHECK(gpt_create(&h, 0) == GPT_OK);
+    // the handle keeps its own buffers, so a case ends with as many live objects as `held`, not with none
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    D Y1 = ramp(2), Z1(2, SENT);
+    Arr<int> status1(1, ISENT);
+    auto refused = [&](gpt_handle* hh, const double* y, int64_t M, double rtol, int max_passes, double* z) {
+        return gpt_inverse_map(hh, y, nullptr, M, rtol, max_passes, z, nullptr, nullptr, nullptr, status1.p);
+    };
+    begin("gpt_inverse_map refuses a handle without a model"); done_held(refused(h, Y1.p, 1, 1e-10, 50, Z1.p), GPT_E_STATE);
+    CHECK(gpt_fit(h, X.p, Y.p, N, 2, 2, ls.p, 2, 1.0, 0.01, 1e-10) == GPT_OK);
+    held = stub_live_objects;
+    begin("gpt_inverse_map refuses a NULL handle"); done_held(refused(nullptr, Y1.p, 1, 1e-10, 50, Z1.p), GPT_E_ARG);
+    begin("gpt_inverse_map refuses Y = NULL"); done_held(refused(h, nullptr, 1, 1e-10, 50, Z1.p), GPT_E_ARG);
+    begin("gpt_inverse_map refuses Z = NULL"); done_held(refused(h, Y1.p, 1, 1e-10, 50, nullptr), GPT_E_ARG);
+    begin("gpt_inverse_map refuses M = -1"); done_held(refused(h, Y1.p, -1, 1e-10, 50, Z1.p), GPT_E_ARG);
+    begin("gpt_inverse_map refuses rtol = 0"); done_held(refused(h, Y1.p, 1, 0.0, 50, Z1.p), GPT_E_ARG);
+    begin("gpt_inverse_map refuses max_passes = 0"); done_held(refused(h, Y1.p, 1, 1e-10, 0, Z1.p), GPT_E_ARG);
+    CHECK(Z1.all(SENT) && status1.all(ISENT));
+    for (int64_t M : {(int64_t)1, (int64_t)3})                          // growing: each call gets an image of its exact size
+        for (int mask : {0, 15, 5, 10}) {
+            begin("gpt_inverse_map M=" + std::to_string(M) + " optional=" + std::to_string(mask));
+            D Yt = ramp(M * 2), Z0 = ramp(M * 2), Z(M * 2, SENT), residual(M, SENT), det(M, SENT);
+            Arr<int> passes(M, ISENT), status(M, ISENT);
+            const int rc = gpt_inverse_map(h, Yt.p, mask & 1 ? Z0.p : nullptr, M, 1e-10, 50, Z.p, mask & 2 ? residual.p : nullptr,
+                                           mask & 4 ? det.p : nullptr, mask & 8 ? passes.p : nullptr, status.p);
+            if (M == 1 && mask == 0) { CHECK(stub_live_objects == held + 1); held = stub_live_objects; }   // the one image, kept and regrown
+            done_held(rc, GPT_OK);
+            CHECK(Z.all(0.0) && status.all(0) && residual.all(mask & 2 ? 0.0 : SENT) && det.all(mask & 4 ? 0.0 : SENT));
+            CHECK(passes.all(mask & 8 ? 0 : ISENT));
+        }
+    begin("gpt_inverse_map teardown");
+    gpt_destroy(h);
+    done(GPT_OK, GPT_OK);
+}
+
+}  // namespace
+
+int main() {
+    const std::vector<int> sizes3{1, 32, 33}, sizes4{128, 2, 32, 33};      // both size classes in one call, each at its edge
+    for (auto [Dm, n_ls, O] : {std::array<int, 3>{1, 1, 1}, std::array<int, 3>{3, 3, 3}, std::array<int, 3>{15, 1, 16}}) {
+        batch_cases({sizes3, Dm, n_ls, O}, {0, 64, 65}, -1);               // an empty member, a full tile, one query past it
+        batch_cases({sizes4, Dm, n_ls, O}, {65, 0, 64, 65}, -1);
+    }
+    batch_cases({sizes3, 3, 3, 3}, {0, 0, 0}, -1);                         // no query at all
+    batch_cases({sizes3, 3, 3, 3}, {65, 64, 65}, 1);                       // the middle member is not positive definite
+    batch_cases({sizes4, 15, 1, 16}, {65, 64, 0, 65}, 1);
+    batch_refusals();
+    select_cases();
+    svgp_cases("gpt_svgp", gpt_svgp_train, gpt_svgp_elbo_grad, false);
+    svgp_cases("gpt_svgp_surface", gpt_svgp_surface_train, gpt_svgp_surface_elbo_grad, true);
+    surface_predict_cases();
+    inverse_map_cases();
+    printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
+    return 0;
+}

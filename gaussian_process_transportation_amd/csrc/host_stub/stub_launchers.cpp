@@ -1,4 +1,4 @@
-// Kernel launchers of the sanitizer build (see host_stub/hip/hip_runtime.h): no arithmetic — each stand-in TOUCHES the
+// Kernel launchers of the sanitizer builds (see host_stub/hip/hip_runtime.h): no arithmetic — each stand-in TOUCHES the
 // memory its kernel would read and write, with the sizes the kernel derives from its arguments, so that AddressSanitizer
 // checks the buffer sizing of the host orchestration (staging, model blob, slab / vslab / scratch of the variance plan).
 #include "../gpt_common.h"
@@ -107,13 +107,15 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
 
 }  // namespace gpt
 
-// The variational training units (gpt_svgp_train.hip, gpt_svgp_surface.hip), the subset selection (gpt_select.hip), the batch of small models (gpt_batch.hip) and the GEMM's
-// test hook (gpt_fit.hip) are device code end to end and are not part of
-// this build; their entry points exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this
-// library too.
 #include "../../../include/gpt_hip.h"
 // Stub only: allocations, streams and events created and not yet released (tests/asan_driver.py).
 extern "C" long gpt_stub_live_objects(void) { return stub_live_objects; }
+
+#ifdef GPT_STUB_ENTRY_POINTS
+// The library of `make host-asan` holds the handle API alone (gpt_api.hip).  The one-shot units (gpt_svgp_train, gpt_svgp_surface,
+// gpt_select, gpt_batch) and the GEMM's test hook (gpt_debug_dgemm, inside gpt_fit.hip) are not part of it; their entry points
+// exist so that the ctypes loader, which binds every symbol of include/gpt_hip.h, loads this library too.  The host halves of
+// the one-shot units run under the sanitizers in a program of their own: `make host-oneshot-asan`, the #else branch below.
 extern "C" int gpt_svgp_train(int, const double*, const double*, int64_t, int, int, int, double*, double*, double*, double*, double*,
                               double*, const int64_t*, int64_t, const int64_t*, int64_t, double, double*) {
     gpt::set_last_error("gpt_svgp_train: not in the host sanitizer build");
@@ -167,3 +169,183 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+
+#else
+// The program of `make host-oneshot-asan` (oneshot_driver.cpp) links the real entry points of the one-shot units (gpt_*_host.hip);
+// what follows stands in for their launchers (gpt_batch.h, gpt_select.h, gpt_svgp_train.h, gpt_svgp_surface.h).  As above, each
+// walks the memory its kernels would read and write, deriving every offset and size from its arguments the way the kernels do,
+// and writes the words the host reads back: status GPT_OK, failure flag and info untouched (no failure).  A layout the kernels
+// rely on and no memory access shows (a task's workspace running into the next one's, a model in the wrong size class) ends
+// the program through stub_check.
+#include "../gpt_batch.h"
+#include "../gpt_select.h"
+#include "../gpt_svgp_train.h"
+#include "../gpt_svgp_surface.h"
+#include <cstdio>
+
+namespace gpt {
+
+// Test only (oneshot_driver.cpp): the batch member whose factor reports GPT_E_NOT_PD (-1: none), and whether the selection and
+// the SVGP schedules stop on a non-positive pivot at their first step.
+int stub_fail_model = -1;
+bool stub_fail_flag = false;
+
+#define stub_check(cond)                                                                          \
+    do {                                                                                          \
+        if (!(cond)) { fprintf(stderr, "stub_check failed: %s (%s:%d)\n", #cond, __FILE__, __LINE__); abort(); } \
+    } while (0)
+
+// ---- gpt_batch.hip ------------------------------------------------------------------------------------------------------------
+void launch_bat_factor(hipStream_t, int, bool obj, int n_small, int n_large, const BatArgs& a) {
+    for (int k = 0; k < n_small + n_large; ++k) {
+        const int b = a.list[k];
+        const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0;
+        stub_check(n >= 1 && n <= (k < n_small ? BAT_SMALL_N : BAT_MAX_N));      // the LDS image of the size class
+        touch_r(a.X + n0 * a.D, n * a.D * 8); touch_r(a.Y + n0 * a.O, n * a.O * 8);
+        touch_r(a.ls + (int64_t)b * a.n_ls, a.n_ls * 8); touch_r(a.c + b, 8); touch_r(a.noise + b, 8);
+        if (b == stub_fail_model) { a.status[b] = GPT_E_NOT_PD; continue; }       // bat_factor leaves before it writes anything else
+        if (obj) touch_w(a.grad + (int64_t)b * (2 + a.n_ls), (2 + a.n_ls) * 8);
+        else {
+            touch_w(a.alpha + n0 * a.O, n * a.O * 8);
+            if (a.L) touch_w(a.L + a.l_begin[b], n * n * 8);
+            if (a.Wp) touch_w(a.Wp + a.w_begin[b], n * (n + 1) / 2 * 8);
+        }
+        if (a.lml) touch_w(a.lml + b, 8);
+        a.status[b] = GPT_OK;
+    }
+}
+void launch_bat_predict(hipStream_t, int, bool der, int tiles_small, int tiles_large, const BatPredArgs& a) {
+    for (int t = 0; t < tiles_small + tiles_large; ++t) {
+        const int b = a.tile_model[t];
+        if (a.status[b] != GPT_OK) continue;
+        const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0, qb = a.q_begin[b], Mb = a.q_begin[b + 1] - qb, q0 = a.tile_q0[t];
+        stub_check(n >= 1 && n <= (t < tiles_small ? BAT_SMALL_N : BAT_MAX_N));
+        stub_check(q0 >= 0 && q0 < Mb && q0 % BAT_QT == 0);
+        const int64_t row = qb + q0, nq = (Mb - q0 < BAT_QT ? Mb - q0 : BAT_QT);
+        touch_r(a.X + n0 * a.D, n * a.D * 8); touch_r(a.ls + (int64_t)b * a.n_ls, a.n_ls * 8); touch_r(a.c + b, 8); touch_r(a.noise + b, 8);
+        touch_r(a.alpha + n0 * a.O, n * a.O * 8); touch_r(a.Wp + a.w_begin[b], n * (n + 1) / 2 * 8); touch_r(a.Xq + row * a.D, nq * a.D * 8);
+        touch_w(a.mean ? a.mean + row * a.O : nullptr, nq * a.O * 8); touch_w(a.var ? a.var + row : nullptr, nq * 8);
+        if (!der) continue;
+        touch_w(a.J ? a.J + row * a.O * a.D : nullptr, nq * a.O * a.D * 8);
+        touch_w(a.Jvar ? a.Jvar + row * a.D : nullptr, nq * a.D * 8); touch_w(a.dvar ? a.dvar + row * a.D : nullptr, nq * a.D * 8);
+    }
+}
+
+// ---- gpt_select.hip -----------------------------------------------------------------------------------------------------------
+void launch_sel_schedule(hipStream_t, const SelArgs& a, const double* X, const double* inv_ls, double* Xs, int D, int n_total) {
+    const size_t N = a.N, mp = a.mp, stride = a.stride;
+    stub_check(a.Xs == Xs && mp % 2 == 0 && (int)mp >= n_total && stride % 2 == 0 && (int)stride >= D);   // sel_column's 16-byte loads
+    touch_r(X, N * D * 8); touch_r(inv_ls, D * 8); touch_w(Xs, N * stride * 8);
+    touch_w(a.d, N * 8); memset(a.alive, 1, N); a.pivd[0] = a.base_var;
+    for (int j = 0; j < n_total; ++j) {
+        if (*a.fail) return;
+        if (stub_fail_flag) { *a.fail = j + 1; return; }
+        const int p = a.selected[j], lpr = j <= 32 ? 8 : (j <= 128 ? 16 : 64), groups = SEL_NT / lpr;
+        stub_check(p >= 0 && (size_t)p < N);
+        const size_t want = (N + groups - 1) / groups, G = want < (size_t)SEL_MAX_WG ? want : (size_t)SEL_MAX_WG;
+        touch_r(a.pivd + j, 8); touch_r(a.Xs + p * stride, stride * 8);
+        for (size_t i = 0; i < N; ++i) {                      // a row's first j entries in pairs, then column j
+            touch_r(a.P + i * mp, (size_t)((j + 1) & ~1) * 8); touch_r(a.Xs + i * stride, stride * 8);
+            touch_w(a.P + i * mp + j, 8); touch_w(a.d + i, 8);
+        }
+        a.alive[p] = 0;
+        touch_w(a.part_d, G * 8); touch_w(a.part_i, G * 4);
+        if (j + 1 == n_total) break;
+        if (j + 1 >= a.n_pre) {                               // sel_next: the lowest row still alive stands in for the maximum
+            size_t i = 0;
+            while (i < N && !a.alive[i]) ++i;
+            stub_check(i < N);
+            a.selected[j + 1] = (int)i;
+        }
+        a.pivd[j + 1] = a.d[a.selected[j + 1]];
+    }
+}
+
+// ---- gpt_svgp_train.hip, gpt_svgp_surface.hip ---------------------------------------------------------------------------------
+// the rows of one step's batch: X and Y through the schedule
+static void touch_batch(const double* X, const double* Y, const int* idx, int N, int D, int T, int b0, int b) {
+    for (int k = 0; k < b; ++k) {
+        const int row = idx[b0 + k];
+        stub_check(row >= 0 && row < N);
+        touch_r(X + (size_t)row * D, D * 8); touch_r(Y + (size_t)row * T, T * 8);
+    }
+}
+void launch_svgp_steps(hipStream_t, const SvArgs& a, const int64_t* bb, int64_t n_steps, int apply, double) {
+    const int64_t D = a.D, T = a.T, Zn = a.Zn, ZZ = Zn * Zn, ZB = Zn * a.bmax;
+    stub_check(a.n_shared == D + Zn * D + 1 && a.task_stride == 2 + Zn + ZZ && a.part_stride == 2 + D + Zn * D);
+    stub_check(Zn <= SV_MAX_Z && a.bmax <= SV_MAX_B);
+    for (int64_t st = 0; st < n_steps; ++st) {
+        if (*a.fail != INT_MAX) return;
+        if (stub_fail_flag) { *a.fail = (int)st * 64; return; }
+        const int b0 = (int)(bb[st] - bb[0]), b = (int)(bb[st + 1] - bb[st]);
+        stub_check(b >= 1 && b <= a.bmax);
+        touch_batch(a.X, a.Y, a.idx, a.N, a.D, a.T, b0, b);
+        // svgp_shared_step: the shared head of theta and its gradient; svgp_task_step: task t's own slice of each
+        touch_r(a.theta, a.n_shared * 8); touch_w(a.grad, a.n_shared * 8);
+        if (apply) for (double* v : {a.theta, a.m1, a.m2}) touch_w(v, a.n_shared * 8);
+        for (int64_t t = 0; t < T; ++t) {
+            const int64_t th0 = a.n_shared + t * a.task_stride, th_n = 2 + Zn + ZZ;   // raw_os, raw_noise_t, m, C
+            touch_r(a.theta + th0, th_n * 8); touch_w(a.grad + th0, th_n * 8);
+            if (apply) for (double* v : {a.theta, a.m1, a.m2}) touch_w(v + th0, th_n * 8);
+            double* w = a.ws + t * a.ws_stride;                      // M0, M1, M2 | Kx, A, U, Ab, B | Xb | yb, as svgp_task_step carves them
+            for (int q = 0; q < 3; ++q, w += ZZ) touch_w(w, ZZ * 8);
+            for (int q = 0; q < 5; ++q, w += ZB) touch_w(w, Zn * b * 8);
+            touch_w(w, b * D * 8); w += a.bmax * D;
+            touch_w(w, b * 8); w += a.bmax;
+            stub_check(w - (a.ws + t * a.ws_stride) <= a.ws_stride);
+            touch_w(a.part + t * a.part_stride, (2 + D + Zn * D) * 8);
+        }
+        touch_w(a.loss + st, 8);
+    }
+}
+
+void launch_sf_train(hipStream_t s, const SfArgs& a, const int64_t* bb, int64_t n_steps, int apply, double) {
+    const int64_t D = a.D, T = a.T, Zn = a.Zn, NP = a.NP, BP = a.BP, NN = NP * NP, NB_ = NP * BP, nz = Zn * D;
+    stub_check(NP % PAD_N == 0 && NP >= Zn && BP % 64 == 0 && 2 + D <= SF_HDR);
+    stub_check(a.SH >= nz + 1 && a.SH % 2 == 0 && a.task_stride == SF_HDR + NP + NN && a.part_stride == 2 + nz);
+    for (int64_t st = 0; st < n_steps; ++st) {
+        if (*a.fail != INT_MAX) return;
+        const int b0 = (int)(bb[st] - bb[0]), b = (int)(bb[st + 1] - bb[st]);
+        stub_check(b >= 1 && b <= BP);
+        touch_batch(a.X, a.Y, a.idx, a.N, a.D, a.T, b0, b);
+        touch_r(a.theta, a.SH * 8); touch_w(a.grad, a.SH * 8);                    // the shared head: Z, raw_noise_global, pad to SH
+        if (apply) for (double* v : {a.theta, a.m1, a.m2}) touch_w(v, a.SH * 8);
+        for (int64_t t = 0; t < T; ++t) {
+            const int64_t th0 = a.SH + t * a.task_stride;                         // task t: header (SF_HDR), m (NP), C (NP x NP)
+            touch_r(a.theta + th0, (SF_HDR + NP) * 8); touch_w(a.grad + th0, (SF_HDR + NP) * 8);
+            if (apply) for (double* v : {a.theta, a.m1, a.m2}) touch_w(v + th0, a.task_stride * 8);
+            launch_factor_inverse(s, a.K, a.W, (int)NP, a.info + t, a.scr, nullptr, nullptr);
+            if (stub_fail_flag) { a.info[t] = 1; *a.fail = (int)(st * 64 + t); return; }
+            for (double* p : {a.Q, a.M2, a.theta + a.SH + t * a.task_stride + SF_HDR + NP, a.grad + a.SH + t * a.task_stride + SF_HDR + NP})
+                touch_w(p, NN * 8);
+            for (double* p : {a.Kx, a.A, a.U, a.CU, a.Ab, a.B}) touch_w(p, NB_ * 8);
+            touch_w(a.stat, 3 * b * 8); touch_w(a.rbuf, BP * 8);
+            touch_w(a.klrow, Zn * 8); touch_w(a.rowpart, Zn * (1 + D) * 8);          // one entry per inducing row (the host sizes both with NP)
+            touch_w(a.sc, 4 * 8); touch_w(a.part + t * a.part_stride, (2 + nz) * 8);
+        }
+        touch_w(a.loss + st, 8);
+    }
+}
+void launch_sf_pred_factor(hipStream_t s, const SfPredArgs& p) {
+    launch_factor_inverse(s, p.K, p.W, p.NP, p.info, p.scr, nullptr, nullptr);
+    if (stub_fail_flag) *p.info = 1;
+}
+void launch_sf_pred_chunks(hipStream_t, const SfPredArgs& p, int t, double) {
+    const size_t NP = p.NP, MC = p.MC, D = p.D, T = p.T;
+    stub_check(MC % 64 == 0 && MC <= (size_t)SF_PRED_CHUNK && t >= 0 && t < p.T);
+    touch_r(p.W, NP * NP * 8); touch_r(p.C, NP * NP * 8); touch_r(p.m, NP * 8); touch_r(p.il, D * 8); touch_r(p.Z, p.Zn * D * 8);
+    touch_w(p.beta, NP * 8);
+    for (int64_t q0 = 0; q0 < p.M; q0 += MC) {
+        const size_t nq = (size_t)(p.M - q0 < (int64_t)MC ? p.M - q0 : MC);
+        touch_r(p.Xq + q0 * D, nq * D * 8);
+        for (double* panel : {p.Kq, p.Aq, p.Vq}) touch_w(panel, NP * MC * 8);
+        for (size_t q = q0; q < q0 + nq; ++q) {                // column t of the (M, T) outputs
+            touch_w(p.mean + q * T + t, 8);
+            if (p.var) touch_w(p.var + q * T + t, 8);
+            if (p.J) touch_w(p.J + (q * T + t) * D, D * 8);
+        }
+    }
+}
+
+}  // namespace gpt
+#endif

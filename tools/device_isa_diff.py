@@ -2,10 +2,14 @@
 CXXFLAGS plus --cuda-device-only -S), drop .file / .ident, source-path lines and comment-only lines, take the function's position
 in its unit out of the local labels (.LBB<position>_<block>: it moves with the order of instantiation), and compare kernel by
 kernel: every .amdhsa_kernel symbol present under the same name on both sides, instruction stream and kernel descriptor
-identical.  The other tree needs ../../include/gpt_hip.h next to it, as in a checkout.
+identical.  "The same name" is the demangled one (c++filt) without its namespace qualifiers: a kernel's argument struct that moves
+from the unit's anonymous namespace into a header both halves of the unit include changes the mangled symbol and nothing else.
+Two kernels of a unit that reduce to one such name are an error.  The other tree needs ../../include/gpt_hip.h next to it, as in
+a checkout.  The *_host.hip halves of the one-shot units hold no kernel and are not in the default list.
 usage: python tools/device_isa_diff.py OTHER_CSRC [unit.hip ...]   (CPU only; hipcc cross-compiles; exit 1 on any difference)"""
 import os
 import re
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -24,18 +28,26 @@ def kernels(csrc, unit, out):
     s = "\n".join(re.sub(r"\s*;.*$", "", x) for x in lines)
     s = re.sub(r"\.L(BB|JTI|CPI)\d+_", r".L\1_", s)
     found = {}
-    for name in re.findall(r"^\s*\.amdhsa_kernel (\S+)$", s, flags=re.M):
+    names = re.findall(r"^\s*\.amdhsa_kernel (\S+)$", s, flags=re.M)
+    if not shutil.which("c++filt"):
+        sys.exit("device_isa_diff: c++filt (binutils) is needed to compare kernels by their demangled names")
+    plain = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    for name, demangled in zip(names, plain):
+        key = re.sub(r"\(anonymous namespace\)::|\bgpt::", "", demangled)
+        if key in found:                   # two kernels of a unit under one key: one would drop out of the comparison unseen
+            sys.exit(f"device_isa_diff: {unit}: two kernels reduce to the name {key}")
         i = s.index("\n" + name + ":\n")
         body = s[i:s.index(".Lfunc_end", i)]
         j = s.index(".amdhsa_kernel " + name + "\n")
-        found[name] = (body, s[j:s.index(".end_amdhsa_kernel", j)])
+        found[key] = (body.replace(name, key), s[j:s.index(".end_amdhsa_kernel", j)].replace(name, key))
+    assert len(found) == len(names), (unit, len(found), len(names))
     return found
 
 
 def main():
     other = os.path.abspath(sys.argv[1])
     units = sys.argv[2:] or ["gpt_api.hip", "gpt_fit.hip", "gpt_predict.hip", "gpt_predict_matern.hip", "gpt_svgp_train.hip",
-                             "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_batch.hip"]
+                             "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_batch.hip", "gpt_inverse.hip"]
     bad = 0
     with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(max_workers=os.cpu_count() or 1) as ex:
         jobs = {(side, unit): ex.submit(kernels, csrc, unit, os.path.join(d, f"{side}_{unit}.s"))
