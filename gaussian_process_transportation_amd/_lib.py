@@ -16,6 +16,9 @@ GPT_OK, GPT_E_HIP, GPT_E_NOT_PD, GPT_E_ARG, GPT_E_STATE = 0, -1, -2, -3, -4
 GPT_F64, GPT_F32 = 0, 1
 INV_CONVERGED, INV_MAX_PASSES, INV_SINGULAR, INV_STALLED = 0, 1, 2, 3      # GPT_INV_*: per-query status of inverse_map
 INV_STATUS_NAMES = ("CONVERGED", "MAX_PASSES", "SINGULAR", "STALLED")
+# outputs of gpt_transport_policy, in the order of its arguments
+TRANSPORT_OUTPUTS = ("pos_rot", "pos_out", "var", "vel_out", "vel_var", "det_vel", "ori_out", "det_ori", "ori_gap",
+                     "post_mean", "post_J", "post_Jvar", "post_J_ori")
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -45,6 +48,8 @@ SIGNATURES = {
     "gpt_predict_all_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "gpt_inverse_map_dev": (C.c_int, [_vp, _vp, _vp, _i64, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "gpt_inverse_map": (C.c_int, [_vp, _dp, _dp, _i64, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gpt_transport_policy_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, C.c_double] + [_vp] * 16),
+    "gpt_transport_policy": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp, C.c_double] + [_dp] * 16),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -691,6 +696,62 @@ class Handle:
         check(self.lib.gpt_inverse_map_dev(self._h, _vp(y_ptr), _vp(z0_ptr or None), int(M), float(rtol), int(max_passes), _vp(z_ptr),
                                            _vp(residual_ptr or None), _vp(det_ptr or None), _vp(passes_ptr or None), _vp(status_ptr)),
               "gpt_inverse_map_dev")
+
+    # ---- transport: affine part, posterior and push-forward in one call
+    def transport_policy(self, pos, R, c_src, c_dst, scale=1.0, R_jac=None, vel=None, ori=None, outputs=TRANSPORT_OUTPUTS):
+        """gpt_transport_policy on host arrays: pos (M,D) through gamma(x) = scale R (x - c_src) + c_dst and the fitted
+        displacement, velocities vel (M,D) and orientations ori (M,4; w,x,y,z) along.  R_jac: the Jacobian of gamma as the
+        caller defines it (default R).  `outputs`: names out of TRANSPORT_OUTPUTS; pos_out always comes, vel_out / vel_var
+        are left out without vel and ori_out without ori; ori_gap needs no ori (it is a property of the Jacobian at pos) and
+        is left out only where there is no quaternion to speak of, D != 3 (orientations GIVEN to a model with D != 3:
+        ValueError from the library).  Returns a dict."""
+        N, D, O, _ = self.info()
+        pos = as_f64(pos, 2, "pos")
+        if pos.shape[1] != D:
+            raise ValueError(f"pos has {pos.shape[1]} columns, model was fitted with {D} features")
+        M = pos.shape[0]
+        R = as_f64(R, 2, "R")
+        R_jac = R if R_jac is None else as_f64(R_jac, 2, "R_jac")
+        c_src, c_dst = as_f64(c_src, 1, "c_src"), as_f64(c_dst, 1, "c_dst")
+        if R.shape != (D, D) or R_jac.shape != (D, D) or c_src.shape != (D,) or c_dst.shape != (D,):
+            raise ValueError(f"the affine part of a {D}-dimensional model is R ({D},{D}), R_jac ({D},{D}), c_src ({D},), c_dst ({D},)")
+        if vel is not None:
+            vel = as_f64(vel, 2, "vel")
+            if vel.shape != pos.shape:
+                raise ValueError(f"vel has shape {vel.shape}, pos {pos.shape}")
+        if ori is not None:
+            ori = as_f64(ori, 2, "ori")
+            if ori.shape != (M, 4):
+                raise ValueError(f"ori has shape {ori.shape}, expected ({M}, 4)")
+        unknown = set(outputs) - set(TRANSPORT_OUTPUTS)
+        if unknown:
+            raise ValueError(f"transport_policy: unknown outputs {sorted(unknown)}")
+        shapes = {"pos_rot": (M, D), "pos_out": (M, D), "var": (M,), "vel_out": (M, D), "vel_var": (M,), "det_vel": (M,),
+                  "ori_out": (M, 4), "det_ori": (M,), "ori_gap": (M,), "post_mean": (M, D), "post_J": (M, D, D),
+                  "post_Jvar": (M, D), "post_J_ori": (M, D, D)}
+        missing = set()
+        if vel is None:
+            missing |= {"vel_out", "vel_var"}
+        if ori is None:
+            missing |= {"ori_out"} | ({"ori_gap"} if D != 3 else set())
+        want = [k for k in TRANSPORT_OUTPUTS if k == "pos_out" or (k in outputs and k not in missing)]
+        out = {k: np.empty(shapes[k]) for k in want}
+        check(self.lib.gpt_transport_policy(self._h, dptr(pos), M, dptr(R), dptr(c_src), dptr(c_dst), float(scale), dptr(R_jac),
+                                            dptr(vel), dptr(ori), *(dptr(out.get(k)) for k in TRANSPORT_OUTPUTS)),
+              "gpt_transport_policy")
+        return out
+
+    def transport_policy_dev(self, pos_ptr, M, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr, pos_out_ptr, vel_ptr=0, ori_ptr=0, **out_ptrs):
+        """The same on device pointers (float64, the affine part included), asynchronous on the handle's stream
+        (gpt_transport_policy_dev).  out_ptrs: <name>_ptr for the further names of TRANSPORT_OUTPUTS."""
+        ptrs = dict(out_ptrs, pos_out_ptr=pos_out_ptr)
+        unknown = set(ptrs) - {k + "_ptr" for k in TRANSPORT_OUTPUTS}
+        if unknown:
+            raise TypeError(f"transport_policy_dev: unknown arguments {sorted(unknown)}")
+        check(self.lib.gpt_transport_policy_dev(self._h, _vp(pos_ptr or None), int(M), _vp(R_ptr or None), _vp(c_src_ptr or None),
+                                                _vp(c_dst_ptr or None), float(scale), _vp(R_jac_ptr or None), _vp(vel_ptr or None),
+                                                _vp(ori_ptr or None), *(_vp(ptrs.get(k + "_ptr") or None) for k in TRANSPORT_OUTPUTS)),
+              "gpt_transport_policy_dev")
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -4,8 +4,10 @@
 #include "gpt_call.h"
 #include "gpt_plan.h"
 #include "gpt_fit_plan.h"
+#include "gpt_transport.h"
 #include "../../include/gpt_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -51,6 +53,11 @@ Layout make_layout(int64_t N, int D, int O, int ntask, int dtype) {
 }
 
 enum { ST_Q = 0, ST_MEAN, ST_VAR, ST_J, ST_JVAR, ST_DVAR, ST_COUNT };
+// arrays of gpt_transport_policy, in the order of its arguments: inputs, outputs, the posterior the epilogue consumed
+enum { TP_POS = 0, TP_VEL, TP_ORI, TP_POS_ROT, TP_POS_OUT, TP_VAR, TP_VEL_OUT, TP_VEL_VAR, TP_DET_VEL, TP_ORI_OUT, TP_DET_ORI, TP_ORI_GAP,
+       TP_MEAN, TP_J, TP_JVAR, TP_J_ORI, TP_COUNT };
+constexpr int TP_INPUTS = 3;             // TP_POS .. TP_ORI travel to the device, the rest from it
+constexpr int TP_AFFINE_DOUBLES = 24;    // device image of the host call's affine part: R (9) | R_jac (9) | c_src (3) | c_dst (3)
 
 }  // namespace
 
@@ -171,6 +178,12 @@ struct gpt_handle {
     DevBuf<double> lml_partial;    // partial sums of the LML gradient (grow-only)
     DevBuf<unsigned char> cov_buf; // scratch of gpt_predict_cov (grow-only)
     DevBuf<unsigned char> inv_buf; // device images of gpt_inverse_map's host arrays (grow-only)
+    // gpt_transport_policy: what the epilogue reads and the caller did not ask for (gamma(pos), mean, J, Jvar, J at pos), the two
+    // staging sets of the host call and its affine part; each grow-only, each its own owner
+    DevBuf<double> tp_scratch[5];
+    struct TransportStaging { DevBuf<double> buf[TP_COUNT]; } tp_st[2];
+    DevBuf<double> tp_affine;
+    double tp_affine_host[TP_AFFINE_DOUBLES] = {};
     Event pev[4];
 
     ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
@@ -811,6 +824,168 @@ int gpt_inverse_map(gpt_handle* h, const double* Y, const double* Z0, int64_t M,
     if (det) CALLCHK(hipMemcpyAsync(det, ddet, bs, hipMemcpyDeviceToHost, s));
     if (passes) CALLCHK(hipMemcpyAsync(passes, dpass, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
     CALLCHK(hipMemcpyAsync(status, dstat, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
+    CALLCHK(hipStreamSynchronize(s));
+    return GPT_OK;
+}
+
+// ---- transport of positions, velocities and orientations: affine part, posterior, push-forward, all on the device
+namespace {
+
+// the arguments of both transport entry points (host or device pointers alike), indexed by TP_*
+struct TransportCall {
+    int64_t M = 0;
+    double scale = 1.0;
+    const double *R = nullptr, *c_src = nullptr, *c_dst = nullptr, *R_jac = nullptr;
+    double* arr[TP_COUNT] = {};          // (the inputs TP_POS .. TP_ORI are only read)
+};
+
+// what both entry points refuse, in the order of the header's list
+int transport_check(gpt_handle* h, const char* who, const TransportCall& c) {
+    const std::string w(who);
+    if (!h) return fail(GPT_E_ARG, w + ": NULL handle");
+    if (!h->committed) return fail(GPT_E_STATE, w + ": model is not fitted");
+    const KernelParams& p = h->p;
+    if (p.D != p.O || p.D > 3)
+        return fail(GPT_E_ARG, w + ": the transport needs a map of a space onto itself, D == O, with D <= 3 (this model: D = " +
+                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
+    if ((c.arr[TP_ORI] || c.arr[TP_ORI_OUT] || c.arr[TP_ORI_GAP]) && p.D != 3)
+        return fail(GPT_E_ARG, w + ": orientations (ori, ori_out, ori_gap) need D == 3: the rotation closest to a " + std::to_string(p.D) +
+                                   " x " + std::to_string(p.D) + " Jacobian is no quaternion");
+    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (this model was fitted with GPT_F32)");
+    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (this model is a multi-task gpt_fit_svgp model)");
+    if (p.ktype == GPT_KERNEL_MATERN12)
+        return fail(GPT_E_ARG, w + ": Matern 1/2 (nu = 0.5) is not differentiable at the training points: the map has no Jacobian to "
+                                   "push velocities and orientations through; use RBF, Matern 3/2 or Matern 5/2");
+    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
+        return fail(GPT_E_ARG, w + ": the transport through a Matern model uses the analytic derivatives of its posterior; "
+                                   "gpt_set_matern_derivatives(h, 1) enables them");
+    if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
+    if ((c.arr[TP_VEL_OUT] || c.arr[TP_VEL_VAR]) && !c.arr[TP_VEL])
+        return fail(GPT_E_ARG, w + ": vel_out and vel_var need vel (the velocities to push forward)");
+    if (c.arr[TP_ORI_OUT] && !c.arr[TP_ORI]) return fail(GPT_E_ARG, w + ": ori_out needs ori (the orientations to rotate)");
+    if (c.M > 0 && (!c.arr[TP_POS] || !c.arr[TP_POS_OUT] || !c.R || !c.c_src || !c.c_dst || !c.R_jac))
+        return fail(GPT_E_ARG, w + ": pos, pos_out, R, c_src, c_dst and R_jac must not be NULL");
+    return GPT_OK;
+}
+
+int transport_dev(gpt_handle* h, const TransportCall& c) {
+    if (int rc = set_device(h)) return rc;
+    hipStream_t s = h->stream;
+    const int64_t M = c.M;
+    const size_t D = h->p.D;
+    double* const* u = c.arr;
+    // which posterior quantities the outputs asked for consume
+    const bool need_J = u[TP_VEL_OUT] || u[TP_DET_VEL] || u[TP_J];
+    const bool need_Jvar = u[TP_VEL_VAR] || u[TP_JVAR];
+    const bool need_J_ori = u[TP_ORI_OUT] || u[TP_DET_ORI] || u[TP_ORI_GAP] || u[TP_J_ORI];
+    // each lives in the caller's array when there is one, else in the handle's scratch
+    const struct { int which; bool need; size_t per; } mid[5] = {
+        {TP_POS_ROT, true, D}, {TP_MEAN, true, D}, {TP_J, need_J, D * D}, {TP_JVAR, need_Jvar, D}, {TP_J_ORI, need_J_ori, D * D}};
+    double* at[5];
+    for (int k = 0; k < 5; ++k) {
+        at[k] = mid[k].need ? u[mid[k].which] : nullptr;
+        if (mid[k].need && !at[k]) {
+            CALLCHK(reserve(h->tp_scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
+            at[k] = h->tp_scratch[k];
+        }
+    }
+    TransportArgs a{};
+    a.M = M; a.scale = c.scale; a.R = c.R; a.c_src = c.c_src; a.c_dst = c.c_dst; a.R_jac = c.R_jac;
+    a.pos = u[TP_POS]; a.vel = u[TP_VEL]; a.ori = u[TP_ORI];
+    a.pos_rot = at[0]; a.mean = at[1]; a.J = at[2]; a.Jvar = at[3]; a.J_ori = at[4];
+    a.pos_out = u[TP_POS_OUT]; a.vel_out = u[TP_VEL_OUT]; a.vel_var = u[TP_VEL_VAR]; a.det_vel = u[TP_DET_VEL];
+    a.ori_out = u[TP_ORI_OUT]; a.det_ori = u[TP_DET_ORI]; a.ori_gap = u[TP_ORI_GAP];
+    launch_transport_affine(s, (int)D, a);
+    // the Jacobian at the un-rotated positions (the reference's transport_orientation), then the posterior at gamma(pos): the
+    // launches, query image and choice of variance path of gpt_predict_all_dev itself
+    if (need_J_ori) launch_mean_jac(s, h->p, h->dXs(), h->dA4(), a.pos, M, nullptr, at[4]);
+    if (int rc = gpt_predict_all_dev(h, a.pos_rot, M, at[1], u[TP_VAR], at[2], at[3], nullptr)) return rc;
+    launch_transport_push(s, (int)D, a);
+    CALLCHK(hipGetLastError());
+    return GPT_OK;
+}
+
+}  // namespace
+
+#define TRANSPORT_CALL(c)                                                                                                          \
+    TransportCall c;                                                                                                               \
+    c.M = M; c.scale = scale; c.R = R; c.c_src = c_src; c.c_dst = c_dst; c.R_jac = R_jac;                                          \
+    {                                                                                                                              \
+        double* const all[TP_COUNT] = {const_cast<double*>(pos), const_cast<double*>(vel), const_cast<double*>(ori), pos_rot, pos_out, var, \
+                                       vel_out, vel_var, det_vel, ori_out, det_ori, ori_gap, post_mean, post_J, post_Jvar, post_J_ori}; \
+        for (int k = 0; k < TP_COUNT; ++k) c.arr[k] = all[k];                                                                      \
+    }
+
+int gpt_transport_policy_dev(gpt_handle* h, const double* pos, int64_t M, const double* R, const double* c_src, const double* c_dst,
+                             double scale, const double* R_jac, const double* vel, const double* ori, double* pos_rot, double* pos_out,
+                             double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
+                             double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori) {
+    TRANSPORT_CALL(c);
+    if (int rc = transport_check(h, "gpt_transport_policy_dev", c)) return rc;
+    if (M == 0) return GPT_OK;
+    return transport_dev(h, c);
+}
+
+int gpt_transport_policy(gpt_handle* h, const double* pos, int64_t M, const double* R, const double* c_src, const double* c_dst,
+                         double scale, const double* R_jac, const double* vel, const double* ori, double* pos_rot, double* pos_out,
+                         double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
+                         double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori) {
+    TRANSPORT_CALL(c);
+    if (int rc = transport_check(h, "gpt_transport_policy", c)) return rc;
+    if (M == 0) return GPT_OK;
+    const size_t D = h->p.D;
+    if (!all_finite(pos, (size_t)M * D) || (vel && !all_finite(vel, (size_t)M * D)) || (ori && !all_finite(ori, (size_t)M * 4)) ||
+        !all_finite(R, D * D) || !all_finite(R_jac, D * D) || !all_finite(c_src, D) || !all_finite(c_dst, D) || !std::isfinite(scale))
+        return fail(GPT_E_ARG, "gpt_transport_policy: pos / vel / ori / the affine part contain NaN or infinity");
+    if (int rc = set_device(h)) return rc;
+    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
+    const int64_t nchunks = (M + cap - 1) / cap;
+    const size_t per[TP_COUNT] = {D, D, 4, D, D, 1, D, 1, 1, 4, 1, 1, D, D * D, D, D * D};       // doubles per query, by TP_*
+    const bool single = nchunks == 1;
+    if (!single) { if (int rc = ensure_copy_stream(h)) return rc; }
+    hipStream_t s = h->stream, cs = single ? h->stream : h->copy_stream;
+    // only what the caller asked for is staged and crosses the bus; the rest of what the epilogue reads stays in the handle's scratch
+    for (int b = 0; b < (single ? 1 : 2); ++b)
+        for (int k = 0; k < TP_COUNT; ++k)
+            if (c.arr[k]) CALLCHK(reserve(h->tp_st[b].buf[k], (size_t)cap * per[k] * sizeof(double), s, h->copy_stream));
+    CALLCHK(reserve(h->tp_affine, sizeof h->tp_affine_host, s));
+    double* ah = h->tp_affine_host;            // a member: the source of an asynchronous copy
+    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
+    std::fill(ah, ah + TP_AFFINE_DOUBLES, 0.0);
+    memcpy(ah, R, D * D * sizeof(double)); memcpy(ah + 9, R_jac, D * D * sizeof(double));
+    memcpy(ah + 18, c_src, D * sizeof(double)); memcpy(ah + 21, c_dst, D * sizeof(double));
+    CALLCHK(hipMemcpyAsync(h->tp_affine, ah, sizeof h->tp_affine_host, hipMemcpyHostToDevice, s));
+    // chunk i computes on `s` in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_predict_all)
+    auto enqueue = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        gpt_handle::TransportStaging& t = h->tp_st[b];
+        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
+        TransportCall d;
+        d.M = m; d.scale = scale; d.R = h->tp_affine; d.R_jac = h->tp_affine + 9; d.c_src = h->tp_affine + 18; d.c_dst = h->tp_affine + 21;
+        for (int k = 0; k < TP_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
+        for (int k = 0; k < TP_INPUTS; ++k)
+            if (c.arr[k]) CALLCHK(hipMemcpyAsync(t.buf[k], c.arr[k] + (size_t)off * per[k], (size_t)m * per[k] * sizeof(double), hipMemcpyHostToDevice, s));
+        if (int rc = transport_dev(h, d)) return rc;
+        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
+        return GPT_OK;
+    };
+    auto copy_out = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        const gpt_handle::TransportStaging& t = h->tp_st[b];
+        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
+        for (int k = TP_INPUTS; k < TP_COUNT; ++k)
+            if (c.arr[k]) CALLCHK(hipMemcpyAsync(c.arr[k] + (size_t)off * per[k], t.buf[k], (size_t)m * per[k] * sizeof(double), hipMemcpyDeviceToHost, cs));
+        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
+        return GPT_OK;
+    };
+    if (int rc = enqueue(0)) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
+        if (int rc = copy_out(i)) return rc;
+    }
+    if (!single) CALLCHK(hipStreamSynchronize(cs));
     CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }

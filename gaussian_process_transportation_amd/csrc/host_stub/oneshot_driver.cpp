@@ -1,5 +1,5 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
-// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip) and gpt_inverse_map (gpt_api.hip) on the stand-in "device" memory of
+// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map and gpt_transport_policy (gpt_api.hip) on the stand-in "device" memory of
 // host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -11,6 +11,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <string>
@@ -379,6 +380,89 @@ void inverse_map_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- transport (gpt_api.hip): chunks of HOST_CHUNK through two staging sets, one buffer per array asked for ---------------------
+void transport_cases() {
+    const int64_t N = 5, HOST_CHUNK = 1 << 17;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle* h = nullptr;
+    begin("gpt_transport_policy setup");
+    CHECK(gpt_create(&h, 0) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    // bit k of `mask`: optional array k is passed
+    enum { VEL, ORI, POS_ROT, VAR, VEL_OUT, VEL_VAR, DET_VEL, ORI_OUT, DET_ORI, ORI_GAP, POST_MEAN, POST_J, POST_JVAR, POST_J_ORI, N_OPT };
+    const size_t width[N_OPT] = {3, 4, 3, 1, 3, 1, 1, 4, 1, 1, 3, 9, 3, 9};
+    struct Arrays {
+        D pos, pos_out;
+        std::vector<D> opt;
+        Arrays(int64_t M, const size_t* w) : pos(ramp(M * 3)), pos_out(M * 3, SENT) {
+            for (int k = 0; k < N_OPT; ++k) opt.push_back(k < 2 ? ramp(M * w[k]) : D(M * w[k], SENT));
+        }
+    };
+    auto call = [&](gpt_handle* hh, Arrays& a, int64_t M, int mask, const double* pos, double* pos_out) {
+        double* p[N_OPT];
+        for (int k = 0; k < N_OPT; ++k) p[k] = (mask >> k & 1) ? a.opt[k].p : nullptr;
+        return gpt_transport_policy(hh, pos, M, R.p, c_src.p, c_dst.p, 1.25, R.p, p[VEL], p[ORI], p[POS_ROT], pos_out, p[VAR], p[VEL_OUT],
+                                    p[VEL_VAR], p[DET_VEL], p[ORI_OUT], p[DET_ORI], p[ORI_GAP], p[POST_MEAN], p[POST_J], p[POST_JVAR],
+                                    p[POST_J_ORI]);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.pos_out.all(SENT));
+        for (int k = 2; k < N_OPT; ++k) CHECK(a.opt[k].all(SENT));
+    };
+    const int ALL = (1 << N_OPT) - 1;
+    {
+        Arrays a(1, width);
+        begin("gpt_transport_policy refuses a handle without a model"); done_held(call(h, a, 1, ALL, a.pos.p, a.pos_out.p), GPT_E_STATE);
+        CHECK(gpt_fit(h, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        begin("gpt_transport_policy refuses a NULL handle"); done_held(call(nullptr, a, 1, ALL, a.pos.p, a.pos_out.p), GPT_E_ARG);
+        begin("gpt_transport_policy refuses pos = NULL"); done_held(call(h, a, 1, ALL, nullptr, a.pos_out.p), GPT_E_ARG);
+        begin("gpt_transport_policy refuses pos_out = NULL"); done_held(call(h, a, 1, ALL, a.pos.p, nullptr), GPT_E_ARG);
+        begin("gpt_transport_policy refuses M = -1"); done_held(call(h, a, -1, ALL, a.pos.p, a.pos_out.p), GPT_E_ARG);
+        begin("gpt_transport_policy refuses vel_out without vel"); done_held(call(h, a, 1, ALL & ~(1 << VEL), a.pos.p, a.pos_out.p), GPT_E_ARG);
+        begin("gpt_transport_policy refuses ori_out without ori"); done_held(call(h, a, 1, ALL & ~(1 << ORI), a.pos.p, a.pos_out.p), GPT_E_ARG);
+        D nan_pos{0.5, std::nan(""), 0.5};
+        begin("gpt_transport_policy refuses NaN in pos"); done_held(call(h, a, 1, ALL, nan_pos.p, a.pos_out.p), GPT_E_ARG);
+        begin("gpt_transport_policy M = 0 does nothing"); done_held(call(h, a, 0, ALL, a.pos.p, a.pos_out.p), GPT_OK);
+        untouched(a);
+    }
+    // every optional array, none, and two complementary halves (an output never without its input)
+    const int half_a = 1 << VEL | 1 << POS_ROT | 1 << VEL_OUT | 1 << DET_VEL | 1 << DET_ORI | 1 << POST_MEAN | 1 << POST_JVAR;
+    const int half_b = 1 << ORI | 1 << VAR | 1 << ORI_OUT | 1 << ORI_GAP | 1 << POST_J | 1 << POST_J_ORI;
+    const int var_alone = 1 << VEL | 1 << VEL_VAR;                       // the Jacobian variance without the variance
+    for (int64_t M : {(int64_t)1, (int64_t)3, HOST_CHUNK + 1})           // growing; the last walks both staging sets
+        for (int mask : {0, ALL, half_a, half_b, var_alone}) {
+            if (M > 3 && mask != ALL) continue;
+            begin("gpt_transport_policy M=" + std::to_string(M) + " optional=" + std::to_string(mask));
+            Arrays a(M, width);
+            const int rc = call(h, a, M, mask, a.pos.p, a.pos_out.p);
+            CHECK(stub_live_objects >= held);                            // staging and scratch are kept and regrown, never dropped
+            held = stub_live_objects;
+            done_held(rc, GPT_OK);
+            CHECK(a.pos_out.all(0.0));
+            for (int k = 2; k < N_OPT; ++k) CHECK(a.opt[k].all(mask >> k & 1 ? 0.0 : SENT));
+        }
+    {
+        begin("gpt_transport_policy refuses orientations of a 2-D model");
+        D X2 = ramp(N * 2), Y2 = ramp(N * 2, 0.01, 0.01), ls2{0.5, 0.75};
+        CHECK(gpt_fit(h, X2.p, Y2.p, N, 2, 2, ls2.p, 2, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        Arrays a(1, width);
+        done_held(call(h, a, 1, 1 << ORI | 1 << DET_ORI, a.pos.p, a.pos_out.p), GPT_E_ARG);
+        untouched(a);
+    }
+    begin("gpt_transport_policy teardown");
+    gpt_destroy(h);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -396,6 +480,7 @@ int main() {
     svgp_cases("gpt_svgp_surface", gpt_svgp_surface_train, gpt_svgp_surface_elbo_grad, true);
     surface_predict_cases();
     inverse_map_cases();
+    transport_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

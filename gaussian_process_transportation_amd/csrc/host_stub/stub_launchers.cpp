@@ -4,6 +4,7 @@
 #include "../gpt_common.h"
 #include "../gpt_plan.h"
 #include "../gpt_fit_plan.h"
+#include "../gpt_transport.h"
 
 namespace gpt {
 
@@ -72,6 +73,25 @@ void launch_inverse_newton(hipStream_t, const KernelParams& p, const double* Xs,
     const size_t M = (size_t)a.M, D = (size_t)p.D;
     touch_r(Xs, (size_t)p.NP * 4 * 8); touch_r(A4, (size_t)p.NP * 4 * 8); touch_r(a.Y, M * D * 8); touch_r(a.Z0, M * D * 8);
     touch_w(a.Z, M * D * 8); touch_w(a.residual, M * 8); touch_w(a.det, M * 8); touch_w(a.passes, M * 4); touch_w(a.status, M * 4);
+}
+void launch_transport_affine(hipStream_t, int D_, const TransportArgs& a) {
+    if (a.M <= 0) return;
+    const size_t M = (size_t)a.M, D = (size_t)D_;
+    touch_r(a.pos, M * D * 8); touch_r(a.R, D * D * 8); touch_r(a.c_src, D * 8); touch_r(a.c_dst, D * 8); touch_w(a.pos_rot, M * D * 8);
+}
+// k_push_forward: an array that is null is neither read nor written; J, Jvar and J_ori are read for the outputs that consume them
+void launch_transport_push(hipStream_t, int D_, const TransportArgs& a) {
+    if (a.M <= 0) return;
+    const size_t M = (size_t)a.M, D = (size_t)D_;
+    touch_r(a.R_jac, D * D * 8); touch_r(a.pos_rot, M * D * 8); touch_r(a.mean, M * D * 8); touch_w(a.pos_out, M * D * 8);
+    if (a.det_vel || a.vel_out) touch_r(a.J, M * D * D * 8);
+    if (a.vel_out || a.vel_var) touch_r(a.vel, M * D * 8);
+    if (a.vel_var) touch_r(a.Jvar, M * D * 8);
+    touch_w(a.vel_out, M * D * 8); touch_w(a.vel_var, M * 8); touch_w(a.det_vel, M * 8);
+    if (a.ori_out || a.ori_gap || a.det_ori) touch_r(a.J_ori, M * D * D * 8);
+    if (a.ori_out) touch_r(a.ori, M * 32);
+    if (D == 3) { touch_w(a.ori_out, M * 32); touch_w(a.ori_gap, M * 8); }
+    touch_w(a.det_ori, M * 8);
 }
 void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, const void* Xs, const void* Wf, const void* Xq, int64_t M,
                 int ncomp, void* var, void* Jvar, void* dvar, const double* hdr) {

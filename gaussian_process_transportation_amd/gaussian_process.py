@@ -274,6 +274,53 @@ class GaussianProcess:
         z, info = self._handle.inverse_map(y, x0, rtol=rtol, max_passes=max_passes)
         return (z, info) if return_info else z
 
+    # ------------------------------------------------------------------ the whole transport in one device call
+    def transport_policy(self, x, rotation, scale, source_centroid, target_centroid, jacobian=None, vel=None, ori=None,
+                         return_posterior=False):
+        """Phi(x) = gamma(x) + predict(gamma(x)), gamma(x) = scale * rotation (x - source_centroid) + target_centroid, with the
+        velocities `vel` (M,D) and orientations `ori` (M,4; w,x,y,z) pushed through its Jacobian — the affine part, the
+        posterior and the algebra of PolicyTransportation.transport / transport_velocity / transport_orientation in one
+        call on the device (_lib.Handle.transport_policy).  `jacobian`: the Jacobian of gamma (default `rotation`, unscaled: the
+        reference's quirk).  Returns a dict: pos (M,D), pos_rot = gamma(x), std (as predict returns it), and with vel: vel,
+        vel_var (M,D) (as transport_velocity returns them), det_vel (M,); with ori: ori (M,4), ori_gap (M,) (0 where the closest
+        rotation is not unique) — both None unless D = 3 — and det_ori (M,) = det of the Jacobian at the UN-rotated x (the
+        reference's choice).
+        return_posterior: also post_mean, post_J, post_Jvar at gamma(x) and post_J_ori at x.  Needs n_outputs == n_features <= 3,
+        float64, and for a Matern model matern_derivatives=True.  With devices=[...] it runs on the device that holds the fit."""
+        self._require_fit()
+        if self.n_outputs != self.n_features or self.n_features > 3:
+            raise NotImplementedError(f"transport_policy(): the transport needs a map of a space onto itself with at most 3 "
+                                      f"dimensions (this model: {self.n_features} features, {self.n_outputs} outputs)")
+        if self._dtype != _lib.GPT_F64:
+            raise NotImplementedError("transport_policy(): float64 models only (this one was built with dtype='float32')")
+        self._require_derivatives("transport_policy")
+        D = self.n_features
+        want_ori = ori is not None
+        if want_ori and D != 3:                  # no quaternion of a 1-D or 2-D Jacobian: its determinant alone ("ori": None)
+            ori = None
+        names = ["pos_rot", "pos_out", "var"]
+        if vel is not None:
+            names += ["vel_out", "vel_var", "det_vel"]
+        if want_ori:
+            names += ["det_ori"]
+        if ori is not None:
+            names += ["ori_out", "ori_gap"]
+        if return_posterior:
+            names += ["post_mean", "post_J", "post_Jvar", "post_J_ori"]
+        out = self._handle.transport_policy(x, rotation, source_centroid, target_centroid, scale=scale, R_jac=jacobian, vel=vel, ori=ori,
+                                            outputs=names)
+        std = np.sqrt(out["var"])
+        if self.n_outputs > 1:
+            std = np.repeat(std[:, None], self.n_outputs, axis=1)
+        res = {"pos": out["pos_out"], "pos_rot": out["pos_rot"], "std": std - np.sqrt(self._noise)}
+        if vel is not None:
+            res.update(vel=out["vel_out"], vel_var=np.repeat(out["vel_var"][:, None], self.n_outputs, axis=1), det_vel=out["det_vel"])
+        if want_ori:
+            res.update(ori=out.get("ori_out"), ori_gap=out.get("ori_gap"), det_ori=out["det_ori"])
+        if return_posterior:
+            res.update({k: out[k] for k in ("post_mean", "post_J", "post_Jvar", "post_J_ori")})
+        return res
+
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):
         """Everything predict(x, return_std=True) and derivative(x, return_var=True) return, computed in ONE pass over

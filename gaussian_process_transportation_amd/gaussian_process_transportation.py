@@ -24,10 +24,13 @@ def _reference_default_kernel():
 
 class GaussianProcessTransportation:
     def __init__(self, kernel_transport=None, optimizer="fmin_l_bfgs_b", device=0, verbose=True, devices=None,
-                 matern_derivatives=False):
+                 matern_derivatives=False, fused=False):
         """`devices=[0, 1, ...]`: apply_transportation() shards the demonstration's rows over these GPUs (the fit stays on
         devices[0]); default: the one `device`.  `matern_derivatives=True`: a Matern(nu=1.5 / 2.5) kernel_transport
-        transports velocities and orientations with the analytic derivatives of its posterior (GaussianProcess)."""
+        transports velocities and orientations with the analytic derivatives of its posterior (GaussianProcess).
+        `fused=True`: apply_transportation() is one call (PolicyTransportation.transport_all: the affine part, the posterior
+        and the velocity / orientation algebra on the device, on the GPU that holds the fit) and sets the same attributes."""
+        self.fused = bool(fused)
         kernel = _reference_default_kernel() if kernel_transport is None else kernel_transport
         regressor = GaussianProcess(kernel=kernel, optimizer=optimizer, device=device, verbose=verbose, devices=devices,
                                     matern_derivatives=matern_derivatives)
@@ -45,9 +48,20 @@ class GaussianProcessTransportation:
         self.method.fit(source, target, do_scale=do_scale, do_rotation=do_rotation)
 
     def apply_transportation(self):
-        """Moves the demonstration; velocities and orientations follow when they were provided (:19-27)."""
+        """Moves the demonstration; velocities and orientations follow when they were provided (:19-27).  fused=True treats
+        training_delta / training_ori set to None as not provided; the unfused path, as the reference, skips only an
+        attribute that was never set and hands a None on to numpy, which fails."""
         before = self._input("training_traj")
         self.training_traj_old = before
+        if self.fused:
+            velocities, orientations = getattr(self, "training_delta", None), getattr(self, "training_ori", None)
+            traj, std, vel, var_vel, ori = self.method.transport_all(before, velocities, orientations)
+            self.training_traj, self.std = traj, std
+            if velocities is not None:
+                self.training_delta, self.var_vel_transported = vel, var_vel
+            if orientations is not None:
+                self.training_ori = ori
+            return
         velocities = getattr(self, "training_delta", _MISSING)
         if velocities is not _MISSING:
             self.method.prefetch(before)              # std and Jacobian variance at the same positions: one pass

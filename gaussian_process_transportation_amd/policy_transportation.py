@@ -97,6 +97,35 @@ class PolicyTransportation:
             return None
         return quaternion_multiply(quaternion_from_nonorthogonal(J_phi), np.asarray(ori, dtype=np.float64))
 
+    def transport_all(self, pos, vel=None, ori=None, return_info=False):
+        """transport(pos), transport_velocity(pos, vel) and transport_orientation(pos, ori) in ONE call of the delta_map's
+        `transport_policy` (GaussianProcess: the affine part, the posterior and this file's algebra on the device).  Returns
+        (positions, std, velocities, velocity variance, orientations), None for what was not given — and for orientations
+        when the space is not 3-D, after the reference's two lines.  With return_info also the delta_map's dict (det_vel,
+        det_ori, ori_gap, pos_rot per point).  Velocities use the reference's unscaled Jacobian of the affine part
+        (AffineTransform.derivative); orientations its Jacobian at the UN-rotated positions (transport_orientation)."""
+        fused = getattr(self.delta_map, "transport_policy", None)
+        if fused is None:
+            raise NotImplementedError(f"transport_all(): the delta_map ({type(self.delta_map).__name__}) has no "
+                                      "transport_policy(x, rotation, scale, source_centroid, target_centroid, ...); "
+                                      "GaussianProcess provides one")
+        aff = self.affine_transform
+        out = fused(pos, aff.rotation_matrix, aff.scale, aff.S_centroid, aff.T_centroid, jacobian=aff.rotation_matrix, vel=vel, ori=ori)
+        if vel is not None and self.verbose:
+            print("Is the map locally diffeomorphic?", np.all(np.abs(out["det_vel"]) > 0))
+        ori_out = None
+        if ori is not None:
+            if self.verbose:
+                print("Is the map locally diffeomorphic?", np.all(out["det_ori"] > 0))
+            D = np.shape(aff.rotation_matrix)[0]
+            if D != 3:
+                print("The Jacobain of the map as shape ", (D, D), " but it should be (3x3)")
+                print("Robot orientation is not transported")
+            else:
+                ori_out = out["ori"]
+        res = (out["pos"], out["std"], out.get("vel"), out.get("vel_var"), ori_out)
+        return res + (out,) if return_info else res
+
     def sample_transportation(self, pos):
         pos_rotated = self.affine_transform.predict(pos)
         return pos_rotated + self.delta_map.samples(pos_rotated)

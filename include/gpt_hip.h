@@ -302,6 +302,45 @@ int gpt_inverse_map_dev(gpt_handle* h, const double* Y_dev, const double* Z0_dev
 int gpt_inverse_map(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
                     double* residual, double* det, int* passes, int* status);
 
+/* (new) Transport of a demonstration in one device call: what PolicyTransportation.transport / transport_velocity /
+ * transport_orientation (transportation/policy_transportation.py:30-75) compute on the host around three posterior calls — the
+ * affine part, the posterior (the launches of gpt_predict_all_dev, unchanged), and the push-forward of positions, velocities and
+ * orientations.  All arrays fp64.  Inputs: pos (M,D); the affine part gamma(x) = scale R (x - c_src) + c_dst with R (D,D)
+ * row-major, c_src (D), c_dst (D); R_jac (D,D), the Jacobian of gamma as the caller defines it (the reference passes the
+ * UNSCALED rotation, affine_trasformation.py:55-57); vel (M,D) or NULL; ori (M,4) as w,x,y,z or NULL.  Outputs, each of which may
+ * be NULL except pos_out:
+ *   pos_rot (M,D)  = gamma(pos)
+ *   pos_out (M,D)  = gamma(pos) + mean(gamma(pos))
+ *   var     (M)    raw, as gpt_predict's (the caller applies sqrt, the `- sqrt(noise_level)` quirk and the tiling)
+ *   vel_out (M,D)  = (I + J(gamma pos)) R_jac vel
+ *   vel_var (M)    = sum_d Jvar_d(gamma pos) (R_jac vel)_d^2, the same for every output (the caller tiles it)
+ *   det_vel (M)    = det((I + J(gamma pos)) R_jac)
+ *   ori_out (M,4)  = q(J') (x) ori, J' = (I + J(pos)) R_jac at the UN-rotated positions as the reference's transport_orientation
+ *                    (:62); q: Bar-Itzhack's quaternion of the rotation closest to J', the dominant eigenvector of the
+ *                    symmetric 4 x 4 matrix K(J') (six sweeps of cyclic Jacobi, column of the largest diagonal entry, lowest
+ *                    index on a tie, normalised), sign fixed to w >= 0 before the product
+ *   det_ori (M)    = det J'
+ *   ori_gap (M)    = (lambda_4 - lambda_3) / |K|_F; where it is 0 the closest rotation is not unique and ori_out is one of several
+ *   post_mean (M,D), post_J (M,D,D), post_Jvar (M,D) at gamma(pos) and post_J_ori (M,D,D) at pos: the posterior the epilogue
+ *                    consumed (the reference keeps them as attributes)
+ * GPT_E_STATE: no model.  GPT_E_ARG (the message names the limit): D != O or D > 3; ori, ori_out or ori_gap with D != 3; a GPT_F32
+ * or multi-task (gpt_fit_svgp) model; Matern 1/2, or Matern 3/2 / 5/2 without gpt_set_matern_derivatives; M < 0 or M >= 2^31;
+ * vel_out or vel_var without vel, ori_out without ori; a NULL among pos, pos_out, R, c_src, c_dst, R_jac.  M = 0 does nothing.
+ * Device memory (the affine part too), asynchronous on the handle's stream; what the epilogue reads and the caller did not ask
+ * for lives in scratch of the handle (grow-only).  The model and the results of later gpt_predict_all calls are left as they were. */
+int gpt_transport_policy_dev(gpt_handle* h, const double* pos_dev, int64_t M, const double* R_dev, const double* c_src_dev,
+                             const double* c_dst_dev, double scale, const double* R_jac_dev, const double* vel_dev,
+                             const double* ori_dev, double* pos_rot_dev, double* pos_out_dev, double* var_dev, double* vel_out_dev,
+                             double* vel_var_dev, double* det_vel_dev, double* ori_out_dev, double* det_ori_dev, double* ori_gap_dev,
+                             double* post_mean_dev, double* post_J_dev, double* post_Jvar_dev, double* post_J_ori_dev);
+/* (new) The same with every pointer in host memory; also GPT_E_ARG for NaN / infinity in pos, vel, ori or the affine part.  The
+ * queries are streamed through the device in chunks of 131072 as gpt_predict_all's, the outputs of one chunk leaving on the copy
+ * stream while the next computes; only the arrays asked for cross the bus.  Returns when every output is in place. */
+int gpt_transport_policy(gpt_handle* h, const double* pos, int64_t M, const double* R, const double* c_src, const double* c_dst,
+                         double scale, const double* R_jac, const double* vel, const double* ori, double* pos_rot, double* pos_out,
+                         double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
+                         double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);
