@@ -19,6 +19,9 @@ INV_STATUS_NAMES = ("CONVERGED", "MAX_PASSES", "SINGULAR", "STALLED")
 # outputs of gpt_transport_policy, in the order of its arguments
 TRANSPORT_OUTPUTS = ("pos_rot", "pos_out", "var", "vel_out", "vel_var", "det_vel", "ori_out", "det_ori", "ori_gap",
                      "post_mean", "post_J", "post_Jvar", "post_J_ori")
+# outputs of gpt_pullback_policy, in the order of its arguments (passes and status are int32, the rest float64)
+PULLBACK_OUTPUTS = ("x", "vel", "f", "det", "residual", "passes", "status", "var_dyn", "map_var", "vel_var_map", "vel_var_dyn",
+                    "post_z", "post_A", "post_Jvar")
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -50,6 +53,10 @@ SIGNATURES = {
     "gpt_inverse_map": (C.c_int, [_vp, _dp, _dp, _i64, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gpt_transport_policy_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, C.c_double] + [_vp] * 16),
     "gpt_transport_policy": (C.c_int, [_vp, _dp, _i64, _dp, _dp, _dp, C.c_double] + [_dp] * 16),
+    "gpt_pullback_policy_dev": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_double, _vp, C.c_double, C.c_int, C.c_double]
+                                + [_vp] * 14),
+    "gpt_pullback_policy": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp, C.c_double, _dp, C.c_double, C.c_int, C.c_double]
+                            + [_dp] * 5 + [C.POINTER(C.c_int)] * 2 + [_dp] * 7),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -752,6 +759,58 @@ class Handle:
                                                 _vp(c_dst_ptr or None), float(scale), _vp(R_jac_ptr or None), _vp(vel_ptr or None),
                                                 _vp(ori_ptr or None), *(_vp(ptrs.get(k + "_ptr") or None) for k in TRANSPORT_OUTPUTS)),
               "gpt_transport_policy_dev")
+
+    # ---- the transported policy at target-space points: inverse, dynamics and push-forward in one call
+    def pullback_policy(self, dyn, y, R, c_src, c_dst, scale=1.0, R_jac=None, x0=None, rtol=1e-10, max_passes=64, std_offset=0.0,
+                        outputs=PULLBACK_OUTPUTS):
+        """gpt_pullback_policy on host arrays, this handle the map: for each row of y (M,D) the preimage x under
+        Phi = gamma + psi o gamma (gamma(x) = scale R (x - c_src) + c_dst, psi this handle's mean; damped Newton as inverse_map,
+        started at gamma(x0) or y), the mean f of the handle `dyn` at x and vel = (I + J_psi) R_jac f.  R_jac: the Jacobian of
+        gamma as the caller defines it (default R).  `outputs`: names out of PULLBACK_OUTPUTS; vel and status always come.
+        Returns a dict."""
+        N, D, O, _ = self.info()
+        y = as_f64(y, 2, "y")
+        if y.shape[1] != D:
+            raise ValueError(f"y has {y.shape[1]} columns, model was fitted with {D} features")
+        M = y.shape[0]
+        if x0 is not None:
+            x0 = as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
+        R = as_f64(R, 2, "R")
+        R_jac = R if R_jac is None else as_f64(R_jac, 2, "R_jac")
+        c_src, c_dst = as_f64(c_src, 1, "c_src"), as_f64(c_dst, 1, "c_dst")
+        if R.shape != (D, D) or R_jac.shape != (D, D) or c_src.shape != (D,) or c_dst.shape != (D,):
+            raise ValueError(f"the affine part of a {D}-dimensional model is R ({D},{D}), R_jac ({D},{D}), c_src ({D},), c_dst ({D},)")
+        unknown = set(outputs) - set(PULLBACK_OUTPUTS)
+        if unknown:
+            raise ValueError(f"pullback_policy: unknown outputs {sorted(unknown)}")
+        shapes = {"x": (M, D), "vel": (M, D), "f": (M, D), "det": (M,), "residual": (M,), "passes": (M,), "status": (M,),
+                  "var_dyn": (M,), "map_var": (M,), "vel_var_map": (M,), "vel_var_dyn": (M, D), "post_z": (M, D), "post_A": (M, D, D),
+                  "post_Jvar": (M, D)}
+        want = [k for k in PULLBACK_OUTPUTS if k in ("vel", "status") or k in outputs]
+        out = {k: np.empty(shapes[k], dtype=np.int32 if k in ("passes", "status") else np.float64) for k in want}
+        ip = C.POINTER(C.c_int)
+        ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(ip)) if k in ("passes", "status") else dptr(out.get(k))
+        check(self.lib.gpt_pullback_policy(self._h, dyn._h, dptr(y), dptr(x0), M, dptr(R), dptr(c_src), dptr(c_dst), float(scale),
+                                           dptr(R_jac), float(rtol), int(max_passes), float(std_offset),
+                                           *(ptr(k) for k in PULLBACK_OUTPUTS)),
+              "gpt_pullback_policy")
+        return out
+
+    def pullback_policy_dev(self, dyn, y_ptr, M, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr, vel_ptr, status_ptr, x0_ptr=0, rtol=1e-10,
+                            max_passes=64, std_offset=0.0, **out_ptrs):
+        """The same on device pointers (float64; passes / status int32; the affine part included), asynchronous on this handle's
+        stream (gpt_pullback_policy_dev).  out_ptrs: <name>_ptr for the further names of PULLBACK_OUTPUTS."""
+        ptrs = dict(out_ptrs, vel_ptr=vel_ptr, status_ptr=status_ptr)
+        unknown = set(ptrs) - {k + "_ptr" for k in PULLBACK_OUTPUTS}
+        if unknown:
+            raise TypeError(f"pullback_policy_dev: unknown arguments {sorted(unknown)}")
+        check(self.lib.gpt_pullback_policy_dev(self._h, dyn._h, _vp(y_ptr or None), _vp(x0_ptr or None), int(M), _vp(R_ptr or None),
+                                               _vp(c_src_ptr or None), _vp(c_dst_ptr or None), float(scale), _vp(R_jac_ptr or None),
+                                               float(rtol), int(max_passes), float(std_offset),
+                                               *(_vp(ptrs.get(k + "_ptr") or None) for k in PULLBACK_OUTPUTS)),
+              "gpt_pullback_policy_dev")
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

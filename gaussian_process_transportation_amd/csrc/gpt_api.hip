@@ -5,6 +5,7 @@
 #include "gpt_plan.h"
 #include "gpt_fit_plan.h"
 #include "gpt_transport.h"
+#include "gpt_pullback.h"
 #include "../../include/gpt_hip.h"
 
 #include <algorithm>
@@ -57,6 +58,11 @@ enum { ST_Q = 0, ST_MEAN, ST_VAR, ST_J, ST_JVAR, ST_DVAR, ST_COUNT };
 enum { TP_POS = 0, TP_VEL, TP_ORI, TP_POS_ROT, TP_POS_OUT, TP_VAR, TP_VEL_OUT, TP_VEL_VAR, TP_DET_VEL, TP_ORI_OUT, TP_DET_ORI, TP_ORI_GAP,
        TP_MEAN, TP_J, TP_JVAR, TP_J_ORI, TP_COUNT };
 constexpr int TP_INPUTS = 3;             // TP_POS .. TP_ORI travel to the device, the rest from it
+// arrays of gpt_pullback_policy, in the order of its arguments (passes and status hold ints, the rest doubles)
+enum { PB_Y = 0, PB_X0, PB_X, PB_VEL, PB_F, PB_DET, PB_RES, PB_PASSES, PB_STATUS, PB_VAR_DYN, PB_MAP_VAR, PB_VVAR_MAP, PB_VVAR_DYN,
+       PB_Z, PB_A, PB_JVAR, PB_COUNT };
+constexpr int PB_INPUTS = 2;             // PB_Y, PB_X0 travel to the device, the rest from it
+constexpr int PB_SCRATCH = 6;            // x, z, f, A, var_dyn, Jvar: what a later stage reads and the caller did not ask for
 constexpr int TP_AFFINE_DOUBLES = 24;    // device image of the host call's affine part: R (9) | R_jac (9) | c_src (3) | c_dst (3)
 
 }  // namespace
@@ -182,8 +188,13 @@ struct gpt_handle {
     // staging sets of the host call and its affine part; each grow-only, each its own owner
     DevBuf<double> tp_scratch[5];
     struct TransportStaging { DevBuf<double> buf[TP_COUNT]; } tp_st[2];
-    DevBuf<double> tp_affine;
+    DevBuf<double> tp_affine;          // (gpt_pullback_policy's affine part too: the same image)
     double tp_affine_host[TP_AFFINE_DOUBLES] = {};
+    // gpt_pullback_policy, held by the MAP handle: the scratch between its stages, the two staging sets of the host call and the
+    // events that hand over between this handle's stream and the dynamics handle's (created on first use)
+    DevBuf<double> pb_scratch[PB_SCRATCH];
+    struct PullbackStaging { DevBuf<unsigned char> buf[PB_COUNT]; } pb_st[2];
+    Event pb_ev[3];
     Event pev[4];
 
     ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
@@ -977,6 +988,207 @@ int gpt_transport_policy(gpt_handle* h, const double* pos, int64_t M, const doub
         if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
         for (int k = TP_INPUTS; k < TP_COUNT; ++k)
             if (c.arr[k]) CALLCHK(hipMemcpyAsync(c.arr[k] + (size_t)off * per[k], t.buf[k], (size_t)m * per[k] * sizeof(double), hipMemcpyDeviceToHost, cs));
+        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
+        return GPT_OK;
+    };
+    if (int rc = enqueue(0)) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
+        if (int rc = copy_out(i)) return rc;
+    }
+    if (!single) CALLCHK(hipStreamSynchronize(cs));
+    CALLCHK(hipStreamSynchronize(s));
+    return GPT_OK;
+}
+
+// ---- the transported policy at target-space points: Newton, affine inverse, dynamics mean and push-forward in one launch on the
+// map handle's stream; the two variance launches (unchanged), each on its own handle's stream; a one-thread-per-query epilogue
+namespace {
+
+// the arguments of both pullback entry points (host or device pointers alike), indexed by PB_*
+struct PullbackCall {
+    int64_t M = 0;
+    double scale = 1.0, rtol = 0.0, std_offset = 0.0;
+    int max_passes = 0;
+    const double *R = nullptr, *c_src = nullptr, *c_dst = nullptr, *R_jac = nullptr;
+    void* arr[PB_COUNT] = {};            // (the inputs PB_Y, PB_X0 are only read)
+};
+
+// what either model must be, in the words of inverse_check
+int pullback_model_check(const gpt_handle* h, const std::string& w, const char* role, bool is_map) {
+    const std::string r(role);
+    if (!h) return fail(GPT_E_ARG, w + ": NULL handle (" + r + ")");
+    if (!h->committed) return fail(GPT_E_STATE, w + ": the " + r + " model is not fitted");
+    const KernelParams& p = h->p;
+    if (p.D != p.O || p.D > 3)
+        return fail(GPT_E_ARG, w + ": the " + r + " model must map a space onto itself, D == O, with D <= 3 (this model: D = " +
+                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
+    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (the " + r + " model was fitted with GPT_F32)");
+    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (the " + r + " model is a multi-task gpt_fit_svgp model)");
+    if (!is_map) return GPT_OK;          // the dynamics are only evaluated: any of the four kernels
+    if (p.ktype == GPT_KERNEL_MATERN12)
+        return fail(GPT_E_ARG, w + ": a Matern 1/2 (nu = 0.5) map is not differentiable at the training points: Newton has no Jacobian "
+                                   "and the velocities nothing to be pushed through; use RBF, Matern 3/2 or Matern 5/2");
+    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
+        return fail(GPT_E_ARG, w + ": the pull-back through a Matern map uses the analytic derivatives of its posterior; "
+                                   "gpt_set_matern_derivatives(h_map, 1) enables them");
+    return GPT_OK;
+}
+
+// what both entry points refuse, in the order of the header's list
+int pullback_check(gpt_handle* hm, gpt_handle* hd, const char* who, const PullbackCall& c) {
+    const std::string w(who);
+    if (int rc = pullback_model_check(hm, w, "map", true)) return rc;
+    if (int rc = pullback_model_check(hd, w, "dynamics", false)) return rc;
+    if (hm == hd) return fail(GPT_E_ARG, w + ": h_map and h_dyn are the same handle; the map and the dynamics are two models");
+    if (hm->device != hd->device)
+        return fail(GPT_E_ARG, w + ": the two models live on different devices (map: " + std::to_string(hm->device) + ", dynamics: " +
+                                   std::to_string(hd->device) + "); gpt_factor_copy brings one to the other's");
+    if (hm->p.D != hd->p.D)
+        return fail(GPT_E_ARG, w + ": the map and the dynamics must share one space (map: D = " + std::to_string(hm->p.D) +
+                                   ", dynamics: D = " + std::to_string(hd->p.D) + ")");
+    if (!(c.rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
+    if (c.max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
+    if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
+    if (c.M > 0 && (!c.arr[PB_Y] || !c.arr[PB_VEL] || !c.arr[PB_STATUS] || !c.R || !c.c_src || !c.c_dst || !c.R_jac))
+        return fail(GPT_E_ARG, w + ": y, vel, status, R, c_src, c_dst and R_jac must not be NULL");
+    return GPT_OK;
+}
+
+int pullback_dev(gpt_handle* hm, gpt_handle* hd, const PullbackCall& c) {
+    if (int rc = set_device(hm)) return rc;
+    for (Event& e : hm->pb_ev)
+        if (!e) CALLCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+    hipStream_t s = hm->stream, sd = hd->stream;
+    const int64_t M = c.M;
+    const size_t D = hm->p.D;
+    void* const* u = c.arr;
+    // which intermediate quantities the outputs asked for consume
+    const bool need_var_dyn = u[PB_VAR_DYN] || u[PB_VVAR_DYN];
+    const bool need_jvar = u[PB_JVAR] || u[PB_VVAR_MAP];
+    const bool need_map = u[PB_MAP_VAR] || need_jvar;               // map_var and Jvar together: one pass of the 4-column launch
+    const bool epilogue = u[PB_VVAR_MAP] || u[PB_VVAR_DYN];
+    // each lives in the caller's array when there is one, else in the map handle's scratch
+    const struct { int which; bool need; size_t per; } mid[PB_SCRATCH] = {
+        {PB_X, need_var_dyn, D}, {PB_Z, need_map, D}, {PB_F, epilogue, D}, {PB_A, u[PB_VVAR_DYN] != nullptr, D * D},
+        {PB_VAR_DYN, need_var_dyn, 1}, {PB_JVAR, need_jvar, D}};
+    double* at[PB_SCRATCH];
+    for (int k = 0; k < PB_SCRATCH; ++k) {
+        at[k] = static_cast<double*>(u[mid[k].which]);
+        if (mid[k].need && !at[k]) {
+            CALLCHK(reserve(hm->pb_scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
+            at[k] = hm->pb_scratch[k];
+        }
+    }
+    PullbackArgs a{};
+    a.M = M; a.scale = c.scale; a.R = c.R; a.c_src = c.c_src; a.c_dst = c.c_dst; a.R_jac = c.R_jac;
+    a.Y = static_cast<const double*>(u[PB_Y]); a.X0 = static_cast<const double*>(u[PB_X0]);
+    a.rtol = c.rtol; a.max_passes = c.max_passes; a.std_offset = c.std_offset;
+    a.x = at[0]; a.z = at[1]; a.f = at[2]; a.A = at[3];
+    a.vel = static_cast<double*>(u[PB_VEL]); a.det = static_cast<double*>(u[PB_DET]); a.residual = static_cast<double*>(u[PB_RES]);
+    a.passes = static_cast<int*>(u[PB_PASSES]); a.status = static_cast<int*>(u[PB_STATUS]);
+    a.var_dyn = at[4]; a.Jvar = at[5];
+    a.vel_var_map = static_cast<double*>(u[PB_VVAR_MAP]); a.vel_var_dyn = static_cast<double*>(u[PB_VVAR_DYN]);
+    // what the dynamics handle's stream has enqueued so far (its fit, a gpt_factor_commit) comes first
+    CALLCHK(hipEventRecord(hm->pb_ev[0], sd));
+    CALLCHK(hipStreamWaitEvent(s, hm->pb_ev[0], 0));
+    launch_pullback_velocity(s, hm->p, static_cast<const double*>(hm->dXs()), static_cast<const double*>(hm->dA4()), hd->p,
+                             static_cast<const double*>(hd->dXs()), static_cast<const double*>(hd->dA4()), a);
+    // the dynamics handle's stream goes on once x is there and its model has been read
+    CALLCHK(hipEventRecord(hm->pb_ev[1], s));
+    CALLCHK(hipStreamWaitEvent(sd, hm->pb_ev[1], 0));
+    if (need_var_dyn) {                      // on h_dyn's own stream: the variance workspace belongs to the handle
+        if (int rc = gpt_predict_all_dev(hd, a.x, M, nullptr, at[4], nullptr, nullptr, nullptr)) return rc;
+        CALLCHK(hipEventRecord(hm->pb_ev[2], sd));
+    }
+    if (need_map) { if (int rc = gpt_predict_all_dev(hm, a.z, M, nullptr, u[PB_MAP_VAR], nullptr, need_jvar ? at[5] : nullptr, nullptr)) return rc; }
+    if (need_var_dyn) CALLCHK(hipStreamWaitEvent(s, hm->pb_ev[2], 0));
+    launch_pullback_variance(s, (int)D, a);
+    CALLCHK(hipGetLastError());
+    return GPT_OK;
+}
+
+}  // namespace
+
+#define PULLBACK_CALL(c)                                                                                                            \
+    PullbackCall c;                                                                                                                 \
+    c.M = M; c.scale = scale; c.rtol = rtol; c.max_passes = max_passes; c.std_offset = std_offset;                                  \
+    c.R = R; c.c_src = c_src; c.c_dst = c_dst; c.R_jac = R_jac;                                                                     \
+    {                                                                                                                               \
+        void* const all[PB_COUNT] = {const_cast<double*>(y), const_cast<double*>(x0), x, vel, f, det, residual, passes, status, var_dyn, \
+                                     map_var, vel_var_map, vel_var_dyn, post_z, post_A, post_Jvar};                                 \
+        for (int k = 0; k < PB_COUNT; ++k) c.arr[k] = all[k];                                                                       \
+    }
+
+int gpt_pullback_policy_dev(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M, const double* R,
+                            const double* c_src, const double* c_dst, double scale, const double* R_jac, double rtol, int max_passes,
+                            double std_offset, double* x, double* vel, double* f, double* det, double* residual, int* passes, int* status,
+                            double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
+                            double* post_Jvar) {
+    PULLBACK_CALL(c);
+    if (int rc = pullback_check(h_map, h_dyn, "gpt_pullback_policy_dev", c)) return rc;
+    if (M == 0) return GPT_OK;
+    return pullback_dev(h_map, h_dyn, c);
+}
+
+int gpt_pullback_policy(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M, const double* R,
+                        const double* c_src, const double* c_dst, double scale, const double* R_jac, double rtol, int max_passes,
+                        double std_offset, double* x, double* vel, double* f, double* det, double* residual, int* passes, int* status,
+                        double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
+                        double* post_Jvar) {
+    PULLBACK_CALL(c);
+    if (int rc = pullback_check(h_map, h_dyn, "gpt_pullback_policy", c)) return rc;
+    if (M == 0) return GPT_OK;
+    gpt_handle* const h = h_map;
+    const size_t D = h->p.D;
+    if (!all_finite(y, (size_t)M * D) || (x0 && !all_finite(x0, (size_t)M * D)) || !all_finite(R, D * D) || !all_finite(R_jac, D * D) ||
+        !all_finite(c_src, D) || !all_finite(c_dst, D) || !std::isfinite(scale) || !std::isfinite(rtol) || !std::isfinite(std_offset))
+        return fail(GPT_E_ARG, "gpt_pullback_policy: y / x0 / the affine part / rtol / std_offset contain NaN or infinity");
+    if (int rc = set_device(h)) return rc;
+    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
+    const int64_t nchunks = (M + cap - 1) / cap;
+    const size_t W = sizeof(double), I = sizeof(int);
+    const size_t per[PB_COUNT] = {D * W, D * W, D * W, D * W, D * W, W, W, I, I, W, W, W, D * W, D * W, D * D * W, D * W};   // bytes per query, by PB_*
+    const bool single = nchunks == 1;
+    if (!single) { if (int rc = ensure_copy_stream(h)) return rc; }
+    hipStream_t s = h->stream, cs = single ? h->stream : h->copy_stream;
+    // only what the caller asked for is staged and crosses the bus; the rest of what a later stage reads stays in the handle's scratch
+    for (int b = 0; b < (single ? 1 : 2); ++b)
+        for (int k = 0; k < PB_COUNT; ++k)
+            if (c.arr[k]) CALLCHK(reserve(h->pb_st[b].buf[k], (size_t)cap * per[k], s, h->copy_stream));
+    CALLCHK(reserve(h->tp_affine, sizeof h->tp_affine_host, s));
+    double* ah = h->tp_affine_host;            // a member: the source of an asynchronous copy
+    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
+    std::fill(ah, ah + TP_AFFINE_DOUBLES, 0.0);
+    memcpy(ah, R, D * D * sizeof(double)); memcpy(ah + 9, R_jac, D * D * sizeof(double));
+    memcpy(ah + 18, c_src, D * sizeof(double)); memcpy(ah + 21, c_dst, D * sizeof(double));
+    CALLCHK(hipMemcpyAsync(h->tp_affine, ah, sizeof h->tp_affine_host, hipMemcpyHostToDevice, s));
+    // chunk i computes in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_transport_policy)
+    auto enqueue = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        gpt_handle::PullbackStaging& t = h->pb_st[b];
+        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
+        PullbackCall d = c;
+        d.M = m; d.R = h->tp_affine; d.R_jac = h->tp_affine + 9; d.c_src = h->tp_affine + 18; d.c_dst = h->tp_affine + 21;
+        for (int k = 0; k < PB_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
+        for (int k = 0; k < PB_INPUTS; ++k)
+            if (c.arr[k])
+                CALLCHK(hipMemcpyAsync(t.buf[k], static_cast<const unsigned char*>(c.arr[k]) + (size_t)off * per[k], (size_t)m * per[k],
+                                       hipMemcpyHostToDevice, s));
+        if (int rc = pullback_dev(h, h_dyn, d)) return rc;
+        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
+        return GPT_OK;
+    };
+    auto copy_out = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        const gpt_handle::PullbackStaging& t = h->pb_st[b];
+        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
+        for (int k = PB_INPUTS; k < PB_COUNT; ++k)
+            if (c.arr[k])
+                CALLCHK(hipMemcpyAsync(static_cast<unsigned char*>(c.arr[k]) + (size_t)off * per[k], t.buf[k], (size_t)m * per[k],
+                                       hipMemcpyDeviceToHost, cs));
         if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
         return GPT_OK;
     };

@@ -14,90 +14,9 @@
 #include "gpt_common.h"
 #include "gpt_exp.h"
 #include "gpt_dispatch.h"
+#include "gpt_newton.h"
 
 namespace gpt {
-
-template <int D> __device__ __forceinline__ double inv_det(const double (&A)[D][D]) {
-    if constexpr (D == 1) return A[0][0];
-    else if constexpr (D == 2) return A[0][0] * A[1][1] - A[0][1] * A[1][0];
-    else return A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-}
-
-// s = adj(A) r / det
-template <int D> __device__ __forceinline__ void inv_solve(const double (&A)[D][D], const double det, const double (&r)[D], double (&s)[D]) {
-    const double id = 1.0 / det;
-    if constexpr (D == 1) s[0] = r[0] * id;
-    else if constexpr (D == 2) {
-        s[0] = (A[1][1] * r[0] - A[0][1] * r[1]) * id;
-        s[1] = (A[0][0] * r[1] - A[1][0] * r[0]) * id;
-    } else {
-        s[0] = ((A[1][1] * A[2][2] - A[1][2] * A[2][1]) * r[0] + (A[0][2] * A[2][1] - A[0][1] * A[2][2]) * r[1] +
-                (A[0][1] * A[1][2] - A[0][2] * A[1][1]) * r[2]) * id;
-        s[1] = ((A[1][2] * A[2][0] - A[1][0] * A[2][2]) * r[0] + (A[0][0] * A[2][2] - A[0][2] * A[2][0]) * r[1] +
-                (A[0][2] * A[1][0] - A[0][0] * A[1][2]) * r[2]) * id;
-        s[2] = ((A[1][0] * A[2][1] - A[1][1] * A[2][0]) * r[0] + (A[0][1] * A[2][0] - A[0][0] * A[2][1]) * r[1] +
-                (A[0][0] * A[1][1] - A[0][1] * A[1][0]) * r[2]) * id;
-    }
-}
-
-template <int D> __device__ __forceinline__ double inv_norm(const double (&v)[D]) {
-    double s = v[0] * v[0];
-#pragma unroll
-    for (int d = 1; d < D; ++d) s = fma(v[d], v[d], s);
-    return sqrt(s);
-}
-
-// One pass: r = z + mu(z) - y and A = I + J(z), the same in every lane.  qsc[d] = 1 / (sqrt(2) l_d), jsc[d] = sqrt(2) / l_d.
-template <int KT, int D>
-__device__ __forceinline__ void inv_pass(const int N, const double lnc, const double* __restrict__ Xs, const double* __restrict__ A4,
-                                         const double* __restrict__ Tt, const int lane, const double (&qsc)[D], const double (&jsc)[D],
-                                         const double (&z)[D], const double (&y)[D], double (&r)[D], double (&A)[D][D]) {
-    constexpr double RS2 = 0.70710678118654752440;
-    double q[D], acc[D][1 + D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) q[d] = z[d] * qsc[d];
-#pragma unroll
-    for (int o = 0; o < D; ++o)
-#pragma unroll
-        for (int e = 0; e < 1 + D; ++e) acc[o][e] = 0.0;
-#pragma unroll 2
-    for (int n = lane; n < N; n += 64) {
-        const d4 xs = *reinterpret_cast<const d4*>(Xs + (size_t)n * 4);
-        const d4 al = *reinterpret_cast<const d4*>(A4 + (size_t)n * 4);
-        double df[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) df[d] = xs[d] * RS2 - q[d];
-        double hh = df[0] * df[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) hh = fma(df[d], df[d], hh);
-        double kv, gv;
-        if constexpr (KT == KT_MATERN32 || KT == KT_MATERN52) kv = kernel_tab_kg<KT>(hh, lnc, Tt, gv);     // c k and c g from one exp
-        else { kv = kernel_tab<KT>(hh, lnc, Tt); gv = kv; }
-#pragma unroll
-        for (int o = 0; o < D; ++o) {
-            acc[o][0] += kv * al[o];
-            const double tg = gv * al[o];
-#pragma unroll
-            for (int d = 0; d < D; ++d) acc[o][1 + d] += tg * df[d];
-        }
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o)
-#pragma unroll
-        for (int e = 0; e < 1 + D; ++e) {
-            double v = acc[o][e];
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);     // a + b on one side, b + a on the other: the same bits in every lane
-            acc[o][e] = v;
-        }
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-        r[o] = z[o] + acc[o][0] - y[o];
-#pragma unroll
-        for (int d = 0; d < D; ++d) A[o][d] = (o == d ? 1.0 : 0.0) + acc[o][1 + d] * jsc[d];
-    }
-}
 
 template <int KT, int D>
 __global__ __launch_bounds__(256) void k_inverse_newton(KernelParams p, const double* __restrict__ Xs, const double* __restrict__ A4,

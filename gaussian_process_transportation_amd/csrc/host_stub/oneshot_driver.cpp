@@ -1,6 +1,6 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
-// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map and gpt_transport_policy (gpt_api.hip) on the stand-in "device" memory of
-// host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
+// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map, gpt_transport_policy and gpt_pullback_policy (gpt_api.hip)
+// on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
 // holds zeros from end to end, and one that was not, or that belongs to a failed member or a failed call, still holds the
@@ -463,6 +463,98 @@ void transport_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- pull-back (gpt_api.hip): two handles, chunks of HOST_CHUNK through the map handle's two staging sets, int and double arrays ---
+void pullback_cases() {
+    const int64_t N = 5, Nd = 7, HOST_CHUNK = 1 << 17;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h = nullptr, *hd = nullptr;
+    begin("gpt_pullback_policy setup");
+    CHECK(gpt_create(&h, 0) == GPT_OK && gpt_create(&hd, 0) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    // bit k of `mask`: optional array k is passed (X0 is the one optional input)
+    enum { X0, XO, F, DET, RES, PASSES, VAR_DYN, MAP_VAR, VVAR_MAP, VVAR_DYN, POST_Z, POST_A, POST_JVAR, N_OPT };
+    const size_t width[N_OPT] = {3, 3, 3, 1, 1, 0, 1, 1, 1, 3, 3, 9, 3};
+    struct Arrays {
+        D y, vel;
+        Arr<int> status, passes;
+        std::vector<D> opt;
+        Arrays(int64_t M, const size_t* w) : y(ramp(M * 3)), vel(M * 3, SENT), status(M, ISENT), passes(M, ISENT) {
+            for (int k = 0; k < N_OPT; ++k) opt.push_back(k == X0 ? ramp(M * w[k]) : D(M * w[k], SENT));
+        }
+    };
+    auto call = [&](gpt_handle* hm, gpt_handle* hdyn, Arrays& a, int64_t M, int mask, const double* y, double* vel, int* status,
+                    double rtol = 1e-10, int max_passes = 50) {
+        double* p[N_OPT];
+        for (int k = 0; k < N_OPT; ++k) p[k] = (mask >> k & 1) ? a.opt[k].p : nullptr;
+        return gpt_pullback_policy(hm, hdyn, y, p[X0], M, R.p, c_src.p, c_dst.p, 1.25, R.p, rtol, max_passes, 0.1, p[XO], vel, p[F], p[DET],
+                                   p[RES], (mask >> PASSES & 1) ? a.passes.p : nullptr, status, p[VAR_DYN], p[MAP_VAR], p[VVAR_MAP],
+                                   p[VVAR_DYN], p[POST_Z], p[POST_A], p[POST_JVAR]);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.vel.all(SENT) && a.status.all(ISENT) && a.passes.all(ISENT));
+        for (int k = 1; k < N_OPT; ++k) CHECK(a.opt[k].all(SENT));
+    };
+    const int ALL = (1 << N_OPT) - 1;
+    {
+        Arrays a(1, width);
+        begin("gpt_pullback_policy refuses a map handle without a model"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_STATE);
+        CHECK(gpt_fit(h, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        begin("gpt_pullback_policy refuses a dynamics handle without a model"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_STATE);
+        CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        begin("gpt_pullback_policy refuses a NULL map handle"); done_held(call(nullptr, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses a NULL dynamics handle"); done_held(call(h, nullptr, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses one handle twice"); done_held(call(h, h, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses y = NULL"); done_held(call(h, hd, a, 1, ALL, nullptr, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses vel = NULL"); done_held(call(h, hd, a, 1, ALL, a.y.p, nullptr, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses status = NULL"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, nullptr), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses M = -1"); done_held(call(h, hd, a, -1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses rtol = 0"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p, 0.0), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses rtol = NaN"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p, std::nan("")), GPT_E_ARG);
+        begin("gpt_pullback_policy refuses max_passes = 0"); done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p, 1e-10, 0), GPT_E_ARG);
+        D nan_y{0.5, std::nan(""), 0.5};
+        begin("gpt_pullback_policy refuses NaN in y"); done_held(call(h, hd, a, 1, ALL, nan_y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_policy M = 0 does nothing"); done_held(call(h, hd, a, 0, ALL, a.y.p, a.vel.p, a.status.p), GPT_OK);
+        untouched(a);
+    }
+    // every optional array on and off: none, all, each one alone, all but each one; then the staging arithmetic around HOST_CHUNK
+    std::vector<int> masks{0, ALL};
+    for (int k = 0; k < N_OPT; ++k) { masks.push_back(1 << k); masks.push_back(ALL & ~(1 << k)); }
+    for (int64_t M : {(int64_t)1, (int64_t)3, HOST_CHUNK - 1, HOST_CHUNK, HOST_CHUNK + 1, 2 * HOST_CHUNK + 3})   // growing; the last three walk both staging sets
+        for (int mask : masks) {
+            if (M > 3 && mask != ALL && mask != 0) continue;
+            begin("gpt_pullback_policy M=" + std::to_string(M) + " optional=" + std::to_string(mask));
+            Arrays a(M, width);
+            const int rc = call(h, hd, a, M, mask, a.y.p, a.vel.p, a.status.p);
+            CHECK(stub_live_objects >= held);                            // staging, scratch and events are kept and regrown, never dropped
+            held = stub_live_objects;
+            done_held(rc, GPT_OK);
+            CHECK(a.vel.all(0.0) && a.status.all(0) && a.passes.all(mask >> PASSES & 1 ? 0 : ISENT));
+            for (int k = 1; k < N_OPT; ++k) CHECK(a.opt[k].all(mask >> k & 1 ? 0.0 : SENT));
+        }
+    {
+        begin("gpt_pullback_policy refuses models of different dimension");
+        D X2 = ramp(Nd * 2), Y2 = ramp(Nd * 2, 0.01, 0.01), ls2{0.5, 0.75};
+        CHECK(gpt_fit(hd, X2.p, Y2.p, Nd, 2, 2, ls2.p, 2, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        Arrays a(1, width);
+        done_held(call(h, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        untouched(a);
+    }
+    begin("gpt_pullback_policy teardown");
+    gpt_destroy(h);
+    gpt_destroy(hd);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -481,6 +573,7 @@ int main() {
     surface_predict_cases();
     inverse_map_cases();
     transport_cases();
+    pullback_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

@@ -5,6 +5,7 @@
 #include "../gpt_plan.h"
 #include "../gpt_fit_plan.h"
 #include "../gpt_transport.h"
+#include "../gpt_pullback.h"
 
 namespace gpt {
 
@@ -92,6 +93,26 @@ void launch_transport_push(hipStream_t, int D_, const TransportArgs& a) {
     if (a.ori_out) touch_r(a.ori, M * 32);
     if (D == 3) { touch_w(a.ori_out, M * 32); touch_w(a.ori_gap, M * 8); }
     touch_w(a.det_ori, M * 8);
+}
+// k_pullback_velocity: both models' sources and alpha rows, the affine part, y and x0; an output that is null is not written
+void launch_pullback_velocity(hipStream_t, const KernelParams& pm, const double* Xs_map, const double* A4_map, const KernelParams& pd,
+                              const double* Xs_dyn, const double* A4_dyn, const PullbackArgs& a) {
+    if (a.M <= 0) return;
+    const size_t M = (size_t)a.M, D = (size_t)pm.D;
+    touch_r(Xs_map, (size_t)pm.NP * 4 * 8); touch_r(A4_map, (size_t)pm.NP * 4 * 8);
+    touch_r(Xs_dyn, (size_t)pd.NP * 4 * 8); touch_r(A4_dyn, (size_t)pd.NP * 4 * 8);
+    touch_r(a.R, D * D * 8); touch_r(a.R_jac, D * D * 8); touch_r(a.c_src, D * 8); touch_r(a.c_dst, D * 8);
+    touch_r(a.Y, M * D * 8); touch_r(a.X0, M * D * 8);
+    touch_w(a.x, M * D * 8); touch_w(a.z, M * D * 8); touch_w(a.f, M * D * 8); touch_w(a.vel, M * D * 8); touch_w(a.A, M * D * D * 8);
+    touch_w(a.det, M * 8); touch_w(a.residual, M * 8); touch_w(a.passes, M * 4); touch_w(a.status, M * 4);
+}
+// k_pullback_variance: f always; Jvar for vel_var_map; A and var_dyn for vel_var_dyn
+void launch_pullback_variance(hipStream_t, int D_, const PullbackArgs& a) {
+    if (a.M <= 0 || !(a.vel_var_map || a.vel_var_dyn)) return;
+    const size_t M = (size_t)a.M, D = (size_t)D_;
+    touch_r(a.R_jac, D * D * 8); touch_r(a.f, M * D * 8);
+    if (a.vel_var_map) { touch_r(a.Jvar, M * D * 8); touch_w(a.vel_var_map, M * 8); }
+    if (a.vel_var_dyn) { touch_r(a.A, M * D * D * 8); touch_r(a.var_dyn, M * 8); touch_w(a.vel_var_dyn, M * D * 8); }
 }
 void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, const void* Xs, const void* Wf, const void* Xq, int64_t M,
                 int ncomp, void* var, void* Jvar, void* dvar, const double* hdr) {

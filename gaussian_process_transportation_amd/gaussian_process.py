@@ -321,6 +321,81 @@ class GaussianProcess:
             res.update({k: out[k] for k in ("post_mean", "post_J", "post_Jvar", "post_J_ori")})
         return res
 
+    # ------------------------------------------------------------------ the transported policy at target-space points
+    def _require_self_map(self, what, role):
+        if self.n_outputs != self.n_features or self.n_features > 3:
+            raise NotImplementedError(f"{what}(): the {role} must be a model of a space onto itself with at most 3 dimensions "
+                                      f"(this model: {self.n_features} features, {self.n_outputs} outputs)")
+        if self._dtype != _lib.GPT_F64:
+            raise NotImplementedError(f"{what}(): float64 models only (the {role} was built with dtype='float32')")
+
+    def pullback_policy(self, dynamics, y, rotation, scale, source_centroid, target_centroid, jacobian=None, x0=None, rtol=1e-10,
+                        max_passes=64, variances=False, return_posterior=False):
+        """The transported policy at the target-space points y (M,D): with this model psi the displacement of the transport
+        Phi(x) = gamma(x) + predict(gamma(x)), gamma(x) = scale * rotation (x - source_centroid) + target_centroid, and `dynamics`
+        a second fitted GaussianProcess f of the source scene (any kernel, Matern(nu=0.5) included: it is only evaluated),
+            x = Phi^-1(y),   vel = J_Phi(x) dynamics.predict(x)
+        — the inverse (damped Newton as invert_displacement, started at gamma(x0) when x0 (M,D), a guess of the preimages, is
+        given), the dynamics mean and the push-forward in one launch on the device (_lib.Handle.pullback_policy), instead of
+        the reference's second GP fitted on the moved demonstration (example/2D/surface_generalization.py:81-88).  `jacobian`:
+        the Jacobian of gamma (default `rotation`, unscaled: the reference's quirk).  Returns a dict: x (M,D), vel (M,D), f (M,D)
+        = dynamics.predict(x), status, passes, residual, det (M,) as invert_displacement's info — a point that did not converge
+        has every value at the z it reached and says so in status.  variances=True adds std_dyn (M,D) = the std
+        dynamics.predict(x, return_std=True) returns, map_std (M,D) = this model's at gamma(x), vel_var_dyn (M,D) = std_dyn^2
+        times the row sums of J_Phi^2, and vel_var_map (M,D) = the variance transport_velocity returns for (x, f);
+        variances="vel" leaves map_std out (the variance of vel does not need it, and without it the map's variance launch has
+        three columns per point instead of four).
+        return_posterior: also post_z (M,D) = gamma(x), post_A (M,D,D) = I + derivative(post_z) and, with variances, post_Jvar
+        (M,D).  Both models need n_outputs == n_features <= 3 (the same), float64; this one, if Matern, matern_derivatives=True.
+        With devices=[...] the call runs on the device that holds the fit; the dynamics must hold its fit on the same device."""
+        self._require_fit()
+        self._require_self_map("pullback_policy", "map")
+        self._require_derivatives("pullback_policy")
+        if not isinstance(dynamics, GaussianProcess):
+            raise NotImplementedError(f"pullback_policy(): the dynamics ({type(dynamics).__name__}) must be a fitted GaussianProcess")
+        if dynamics is self:
+            raise ValueError("pullback_policy(): the map and the dynamics are the same object; they are two models")
+        dynamics._require_fit()
+        dynamics._require_self_map("pullback_policy", "dynamics")
+        if dynamics.n_features != self.n_features:
+            raise ValueError(f"pullback_policy(): the map has {self.n_features} features, the dynamics {dynamics.n_features}")
+        if dynamics.device != self.device:
+            raise ValueError(f"pullback_policy(): the map holds its fit on device {self.device}, the dynamics on {dynamics.device}")
+        if not float(rtol) > 0.0:
+            raise ValueError("pullback_policy(): rtol must be > 0")
+        if int(max_passes) < 1:
+            raise ValueError("pullback_policy(): max_passes must be >= 1")
+        y = _lib.as_f64(y, 2, "y")
+        if y.shape[1] != self.n_features:
+            raise ValueError(f"y has {y.shape[1]} columns, the model {self.n_features} features")
+        if x0 is not None:
+            x0 = _lib.as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
+        if y.shape[0] >= 2 ** 31:
+            raise ValueError("pullback_policy(): fewer than 2^31 points per call")
+        names = ["x", "vel", "f", "det", "residual", "passes", "status"]
+        if variances not in (False, True, "vel"):
+            raise ValueError("pullback_policy(): variances is False, True or 'vel'")
+        if variances:
+            names += ["var_dyn", "vel_var_map", "vel_var_dyn"] + (["map_var"] if variances is True else [])
+        if return_posterior:
+            names += ["post_z", "post_A"] + (["post_Jvar"] if variances else [])
+        dyn_handle = getattr(dynamics._handle, "primary", dynamics._handle)
+        out = self._handle.pullback_policy(dyn_handle, y, rotation, source_centroid, target_centroid, scale=scale, R_jac=jacobian, x0=x0,
+                                           rtol=rtol, max_passes=max_passes, std_offset=np.sqrt(dynamics._noise), outputs=names)
+        res = {k: out[k] for k in ("x", "vel", "f", "status", "passes", "residual", "det")}
+        if variances:
+            D = self.n_outputs
+            tile = lambda v: np.repeat(v[:, None], D, axis=1) if D > 1 else v
+            res.update(std_dyn=tile(np.sqrt(out["var_dyn"])) - np.sqrt(dynamics._noise),
+                       vel_var_dyn=out["vel_var_dyn"], vel_var_map=np.repeat(out["vel_var_map"][:, None], D, axis=1))
+            if variances is True:
+                res.update(map_std=tile(np.sqrt(out["map_var"])) - np.sqrt(self._noise))
+        if return_posterior:
+            res.update({k: out[k] for k in names if k.startswith("post_")})
+        return res
+
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):
         """Everything predict(x, return_std=True) and derivative(x, return_var=True) return, computed in ONE pass over

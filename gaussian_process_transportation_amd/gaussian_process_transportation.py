@@ -77,6 +77,13 @@ class GaussianProcessTransportation:
         x0: a guess of them, return_info: also status / passes / residual / det per point, solver: rtol, max_passes."""
         return self.method.inverse_transport(points, x0=x0, return_info=return_info, **solver)
 
+    def transported_policy(self, dynamics, points, x0=None, return_std=False, return_info=False, **solver):
+        """The transported policy at `points` of the target scene (an addition: PolicyTransportation.transported_policy):
+        the velocities a `dynamics` GaussianProcess fitted on the source demonstration commands there, pulled back through
+        fit_transportation()'s map; x0: a guess of the preimages, return_std: also their std, return_info: also x / status /
+        passes / residual / det / f per point, solver: rtol, max_passes."""
+        return self.method.transported_policy(dynamics, points, x0=x0, return_std=return_std, return_info=return_info, **solver)
+
     def sample_transportation(self):
         """Posterior draws of the moved demonstration, at the positions of the last apply_transportation() (:29-30)."""
         return self.method.sample_transportation(self._input("training_traj_old"))

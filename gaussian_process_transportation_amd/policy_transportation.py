@@ -1,7 +1,8 @@
 """PolicyTransportation — Phi(x) = gamma(x) + Psi(gamma(x)) with gamma an AffineTransform and Psi
 any `delta_map` exposing fit / predict / derivative / samples (duck-typed plugin slot of the
 reference, policy_transportation/transportation/policy_transportation.py:11-84); `inverse_transport` (an addition) needs a
-delta_map that also has `invert_displacement`."""
+delta_map that also has `invert_displacement`, `transport_all` one with `transport_policy`, `transported_policy` one with
+`pullback_policy`."""
 import numpy as np
 
 from .affine_transform import AffineTransform
@@ -125,6 +126,39 @@ class PolicyTransportation:
                 ori_out = out["ori"]
         res = (out["pos"], out["std"], out.get("vel"), out.get("vel_var"), ori_out)
         return res + (out,) if return_info else res
+
+    def transported_policy(self, dynamics, pos, x0=None, return_std=False, return_info=False, **solver):
+        """The transported policy at points `pos` (M,D) of the target scene that need not lie on the demonstration: the
+        velocity J_Phi(x) dynamics.predict(x) at x = inverse_transport(pos), `dynamics` a GaussianProcess fitted on the source
+        demonstration — in ONE call of the delta_map's `pullback_policy` (GaussianProcess: inverse, dynamics and push-forward
+        in one launch on the device), where the reference refits a GP on the moved demonstration
+        (example/2D/surface_generalization.py:81-88).  x0: a guess of the preimages; `solver` passes rtol / max_passes on.
+        Returns the velocities (M,D); with return_std also std (M,D) = sqrt(vel_var_dyn + vel_var_map), the sum of the
+        dynamics' own uncertainty pushed through J_Phi and of the map's (transport_velocity's variance), the two parts the
+        reference's heteroscedastic example adds up; with return_info also a dict: x, status, passes, residual, det, f and
+        (return_std) std_dyn, vel_var_dyn, vel_var_map, map_std per point.  Velocities use the reference's unscaled Jacobian
+        of the affine part (AffineTransform.derivative), as transport_velocity does."""
+        pull = getattr(self.delta_map, "pullback_policy", None)
+        if pull is None:
+            raise NotImplementedError(f"transported_policy(): the delta_map ({type(self.delta_map).__name__}) has no "
+                                      "pullback_policy(dynamics, y, rotation, scale, source_centroid, target_centroid, ...); "
+                                      "GaussianProcess provides one")
+        aff = self.affine_transform
+        out = pull(dynamics, np.asarray(pos, dtype=np.float64), aff.rotation_matrix, aff.scale, aff.S_centroid, aff.T_centroid,
+                   jacobian=aff.rotation_matrix, x0=x0, variances=(True if return_info else "vel") if return_std else False, **solver)
+        if self.verbose:
+            from ._lib import INV_CONVERGED, INV_STATUS_NAMES
+            status = np.asarray(out["status"])
+            counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(INV_STATUS_NAMES))
+            solved = status == INV_CONVERGED
+            print(f"Inverse of the map: {counts}; det(I + J_psi) <= 0 at {int(np.sum(np.asarray(out['det'])[solved] <= 0))} "
+                  f"of {int(np.sum(solved))} solutions (the map folds there: not a diffeomorphism)")
+        res = (out["vel"],)
+        if return_std:
+            res += (np.sqrt(out["vel_var_dyn"] + out["vel_var_map"]),)
+        if return_info:
+            res += ({k: v for k, v in out.items() if k != "vel"},)
+        return res if len(res) > 1 else res[0]
 
     def sample_transportation(self, pos):
         pos_rotated = self.affine_transform.predict(pos)

@@ -341,6 +341,55 @@ int gpt_transport_policy(gpt_handle* h, const double* pos, int64_t M, const doub
                          double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
                          double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori);
 
+/* (new) The transported POLICY at points of the target scene that are not on the demonstration (a robot's position, the grid of a
+ * stream plot): the source dynamics pulled back through the transport,
+ *     x = Phi^-1(y),   v(y) = J_Phi(x) f(x),   Phi = gamma + psi o gamma.
+ * The reference reaches this only by refitting a second GP on the moved demonstration (example/2D/surface_generalization.py:81-88)
+ * and a third for its uncertainty (example/2D/surface_generalization_heteroschedastic_uncertainty.py:150-175).  h_map: the fitted
+ * displacement model psi; h_dyn: a second fitted model, the dynamics f, with the same D; gamma(x) = scale R (x - c_src) + c_dst and
+ * R_jac as in gpt_transport_policy.  All arrays fp64 except passes and status (int).  Inputs: y (M,D); x0 (M,D) guesses of the
+ * preimages, or NULL; rtol, max_passes as gpt_inverse_map; std_offset.  Per point:
+ *   z            the damped Newton iteration of gpt_inverse_map on z + psi(z) = y, started at gamma(x0) (at y when x0 is NULL):
+ *                the same accept / reject rule, statuses, passes, residual and det = det(I + J_psi(z))
+ *   x     (M,D)  = (z - c_dst) R / scale + c_src
+ *   f     (M,D)  = mean of h_dyn at x
+ *   vel   (M,D)  = A R_jac f,  A = I + J_psi(z) of the last accepted pass
+ *   det, residual (M), passes, status (M, int; GPT_INV_*)
+ *   var_dyn (M)      raw posterior variance of h_dyn at x, as gpt_predict's
+ *   map_var (M)      raw posterior variance of h_map at z
+ *   vel_var_map (M)    = sum_d Jvar_d(z) (R_jac f)_d^2, what gpt_transport_policy calls vel_var
+ *   vel_var_dyn (M,D)  = s^2 sum_j (A R_jac)[i,j]^2,  s = sqrt(var_dyn) - std_offset: the std of the dynamics as the Python
+ *                      predict returns it (std_offset = sqrt(noise_level)) pushed through J_Phi
+ *   post_z (M,D), post_A (M,D,D), post_Jvar (M,D): z, A and the Jacobian variance of h_map at z, what the later stages consumed
+ * Every output may be NULL except vel and status.  A point whose iteration does not converge still gets every output, at the z
+ * it reached, and says so in its status.  x, f, vel, det, residual, passes, status, post_z and post_A come from ONE launch, one
+ * wave per query (k_pullback_velocity); a query's values there do not depend on M or on the other queries, bit for bit.  The
+ * variances come from the unchanged variance launches of the two handles (map_var and the Jacobian variance together: one pass of
+ * the 4-column launch; the Jacobian variance alone: the 3-column one) and a one-thread-per-query epilogue.
+ * GPT_E_STATE: a handle without a model.  GPT_E_ARG (the message names the limit): a NULL handle; h_map == h_dyn; handles on
+ * different devices; different D; D != O or D > 3, a GPT_F32 or multi-task (gpt_fit_svgp) model, on either handle; a Matern 1/2
+ * map, or a Matern 3/2 / 5/2 map without gpt_set_matern_derivatives (the dynamics may be any of the four kernels: it is only
+ * evaluated); rtol <= 0 or NaN; max_passes < 1; M < 0 or M >= 2^31; a NULL among y, vel, status, R, c_src, c_dst, R_jac.  M = 0
+ * does nothing.
+ * Device memory (the affine part too).  Asynchronous: enqueued on h_map's stream, which first waits for what h_dyn's stream holds
+ * so far; the variance of h_dyn runs on h_dyn's own stream (its workspace belongs to it) between two events, and h_dyn's stream
+ * goes on only after its model has been read.  No host synchronisation; correct for the handles' own streams and after
+ * gpt_set_stream on either.  Scratch and events belong to h_map (grow-only).  Both models are left as they were. */
+int gpt_pullback_policy_dev(gpt_handle* h_map, gpt_handle* h_dyn, const double* y_dev, const double* x0_dev, int64_t M,
+                            const double* R_dev, const double* c_src_dev, const double* c_dst_dev, double scale, const double* R_jac_dev,
+                            double rtol, int max_passes, double std_offset, double* x_dev, double* vel_dev, double* f_dev,
+                            double* det_dev, double* residual_dev, int* passes_dev, int* status_dev, double* var_dyn_dev,
+                            double* map_var_dev, double* vel_var_map_dev, double* vel_var_dyn_dev, double* post_z_dev,
+                            double* post_A_dev, double* post_Jvar_dev);
+/* (new) The same with every pointer in host memory; also GPT_E_ARG for NaN / infinity in y, x0, the affine part or std_offset.
+ * The queries are streamed through the device in chunks of 131072 as gpt_transport_policy's, through two staging sets of h_map;
+ * only the arrays asked for cross the bus.  Returns when every output is in place. */
+int gpt_pullback_policy(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M, const double* R,
+                        const double* c_src, const double* c_dst, double scale, const double* R_jac, double rtol, int max_passes,
+                        double std_offset, double* x, double* vel, double* f, double* det, double* residual, int* passes, int* status,
+                        double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
+                        double* post_Jvar);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);

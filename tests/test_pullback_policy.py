@@ -1,0 +1,678 @@
+"""The transported policy at target-space points: gpt_pullback_policy (csrc/gpt_pullback.hip: Newton, affine inverse, dynamics
+mean and push-forward in one launch; the two handles' variance launches; a one-thread-per-query epilogue),
+GaussianProcess.pullback_policy, PolicyTransportation.transported_policy.
+
+Bounds (no new constants).  Wave-strided sums — f, the entries of A — 64 eps S, S the same sum with absolute values on every
+term: the floor tests/test_inverse_map.py uses.  Sums of at most D + 1 products — x, vel, vel_var_* — 16 eps S, the convention of
+tests/test_transport_fused.py; vel with the first-order propagation of the floors of f and A through A R_jac f.  All of these in
+np.longdouble AT THE z AND x THE DEVICE RETURNED (tests/pullback_restatement.exact_at), for the model the device holds: the alpha
+it exports and the float64 scaled sources and query it forms its distances from (KernelModel(device_operands=True)).  z
+against a known preimage: twice inverse_map_restatement.error_bound; x the same carried through |R| / scale.  var_dyn, map_var,
+Jvar against predict_all at the returned x / z: VAR_SPLIT_RTOL of the prior variance.  The reference's numbers: GOLDEN_RTOL.
+Newton runs with rtol = 1e-10 everywhere, the anchors to the goldens included."""
+import numpy as np
+import pytest
+
+from tests import inverse_map_restatement as INV
+from tests import pullback_restatement as P
+from tests.conftest import load_golden, relmax
+
+EPS = np.finfo(np.float64).eps
+LD = np.longdouble
+RTOL = 1e-10
+VAR_SPLIT_RTOL = 1e-11         # tests/test_gpu_parity.py::_two_rank_worker: |var - var'| <= 1e-11 max(var) between launch sizes
+GOLDEN_RTOL = 1e-5             # tests/test_gpu_parity.py: RTOL of the unfused path against the same goldens
+HOST_CHUNK = 1 << 17           # csrc/gpt_api.hip
+SENT = -7.25e300
+ISENT = -77
+G0 = {None: 1.0, 1.5: 3.0, 2.5: 5.0 / 3.0}          # kernel_g0 of csrc/gpt_exp.h: prior variance of d/dx_d is c g0 / l_d^2
+
+
+def sk_kernel(c, ls, noise, nu=None):
+    from sklearn.gaussian_process.kernels import RBF, ConstantKernel, Matern, WhiteKernel
+    ls = np.atleast_1d(np.asarray(ls, dtype=float)).tolist()
+    base = RBF(length_scale=ls) if nu is None else Matern(length_scale=ls, nu=nu)
+    return ConstantKernel(float(c)) * base + WhiteKernel(float(noise))
+
+
+def _counts(status):
+    return np.bincount(status, minlength=4)
+
+
+# ------------------------------------------------------------------------------------------------------------ CPU
+@pytest.mark.parametrize("name", ["letterS_2d", "surface_3d"])
+def test_restatement_against_the_oracles_pieces(name):
+    """pullback(Phi(X)).x returns X and vel equals J_Phi(X) f(X) formed from GaussianProcessOracle's own predict / derivative."""
+    from oracle.gp_oracle import AffineTransformOracle, GaussianProcessOracle
+    g = load_golden(name)
+    aff_o = AffineTransformOracle().fit(g["source"], g["target"])
+    src = aff_o.predict(g["source"])
+    gp = GaussianProcessOracle(g["constant_value"], g["length_scale"], g["noise_level"]).fit(src, g["target"] - src)
+    X = g["demo"][::8]
+    dyn = GaussianProcessOracle(0.3, [1.5, 2.5, 2.0][:X.shape[1]], 0.01).fit(g["demo"], g["delta"])
+    aff = {"R": np.ascontiguousarray(aff_o.rotation_matrix), "scale": float(getattr(aff_o, "scale", 1.0)), "c_src": aff_o.S_centroid,
+           "c_dst": aff_o.T_centroid}
+    gam = aff_o.predict(X)
+    assert relmax(P.affine_forward(aff, X), gam) <= 1e-14
+    y = gam + gp.predict(gam)
+    map_model, dyn_model = P.oracle_model(gp), P.oracle_model(dyn)
+    out = P.pullback(map_model, dyn_model, aff, y, x0=X, rtol=RTOL)
+    assert np.all(out["status"] == INV.CONVERGED) and np.all(out["passes"] == 1)
+    bound, _ = INV.error_bound(map_model, out["z"], y, RTOL)
+    assert np.all(np.linalg.norm(out["x"] - X, axis=1) <= 2 * bound / aff["scale"] + 64 * EPS * np.linalg.norm(X, axis=1))
+    J_phi = (np.eye(X.shape[1])[None] + gp.derivative(gam)) @ aff["R"]
+    f = dyn.predict(X)
+    assert relmax(out["f"], f) <= 1e-12
+    assert relmax(out["vel"], np.einsum("mod,md->mo", J_phi, f)) <= 1e-11
+    # without the guess the iteration has to find its way back; where it converges it solves the same equation
+    free = P.pullback(map_model, dyn_model, aff, y, rtol=RTOL)
+    ok = free["status"] == INV.CONVERGED
+    assert np.mean(ok) >= 0.9
+    back = free["z"] + gp.predict(free["z"])
+    assert np.all(np.linalg.norm(back - y, axis=1)[ok] <= 2 * RTOL * (1 + np.linalg.norm(y, axis=1)[ok]))
+
+
+def test_kernel_model_matches_the_matern_helpers():
+    from tests.test_matern_derivatives import np_kernel
+    rng = np.random.default_rng(2)
+    X, a, z = rng.uniform(0, 1, (30, 2)), rng.standard_normal((30, 2)), rng.uniform(0, 1, (7, 2))
+    for nu in (1.5, 2.5):
+        m = P.KernelModel(X, a, 0.4, [0.3, 0.5], nu)
+        k, g, u = np_kernel(z, X, 0.4, np.array([0.3, 0.5]), nu)
+        assert relmax(m.mean(z)[0], k @ a) <= 1e-13
+        assert relmax(m.jac(z)[0], np.einsum("mnd,no->mod", g[:, :, None] * u, a)) <= 1e-13
+        held = P.KernelModel(X, a, 0.4, [0.3, 0.5], nu, device_operands=True)        # the same model up to an eps in X and l
+        assert relmax(held.mean(z)[0], m.mean(z)[0]) <= 1e-13 and relmax(held.jac(z)[0], m.jac(z)[0]) <= 1e-13
+    m = P.KernelModel(X, a, 0.4, [0.3, 0.5], 0.5)
+    r = np.sqrt(np.sum(((X[None] - z[:, None]) / np.array([0.3, 0.5])) ** 2, axis=-1))
+    assert relmax(m.mean(z)[0], 0.4 * np.exp(-r) @ a) <= 1e-13
+
+
+def test_python_refusals_need_no_device():
+    from gaussian_process_transportation_amd import GaussianProcess, GaussianProcessTransportation
+    from gaussian_process_transportation_amd.policy_transportation import PolicyTransportation
+    gp = GaussianProcess(kernel=sk_kernel(0.1, [0.3], 1e-3), optimizer=None, verbose=False)
+    dyn = GaussianProcess(kernel=sk_kernel(0.1, [0.3], 1e-3), optimizer=None, verbose=False)
+    with pytest.raises(RuntimeError, match="not fitted"):
+        gp.pullback_policy(dyn, np.zeros((2, 3)), np.eye(3), 1.0, np.zeros(3), np.zeros(3))
+
+    class NoPullback:
+        def fit(self, X, Y): pass
+    g = load_golden("letterS_2d")
+    bare = PolicyTransportation(NoPullback(), verbose=False)
+    bare.fit(g["source"], g["target"])
+    with pytest.raises(NotImplementedError, match="pullback_policy.*GaussianProcess"):
+        bare.transported_policy(dyn, g["traj"][:3])
+    tr = GaussianProcessTransportation(optimizer=None, verbose=False)
+    tr.method = bare
+    with pytest.raises(NotImplementedError, match="NoPullback"):
+        tr.transported_policy(dyn, g["traj"][:3])
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU
+def _fit_transport(g, do_scale=False, nu=None, **kw):
+    from gaussian_process_transportation_amd import GaussianProcessTransportation
+    tr = GaussianProcessTransportation(kernel_transport=sk_kernel(g["constant_value"], g["length_scale"], g["noise_level"], nu), optimizer=None,
+                                       verbose=False, **kw)
+    tr.source_distribution, tr.target_distribution = g["source"], g["target"]
+    tr.fit_transportation(do_scale=do_scale)
+    return tr
+
+
+def _affine_of(tr):
+    a = tr.method.affine_transform
+    return {"R": np.ascontiguousarray(a.rotation_matrix), "scale": float(a.scale), "c_src": a.S_centroid, "c_dst": a.T_centroid}
+
+
+def _model_of(gp, nu=None):
+    """KernelModel of a fitted GaussianProcess as the device holds it: its alpha and its scaled operands."""
+    return P.KernelModel(gp.X, gp.gp.alpha_, gp._c, gp._ls, nu, device_operands=True)
+
+
+def _fit_gp(X, Y, c, ls, noise, nu=None, **kw):
+    from gaussian_process_transportation_amd import GaussianProcess
+    return GaussianProcess(kernel=sk_kernel(c, ls, noise, nu), optimizer=None, verbose=False, **kw).fit(X, Y)
+
+
+def _call(gp_map, gp_dyn, y, aff, x0=None, outputs=None, rtol=RTOL, max_passes=64, std_offset=None):
+    from gaussian_process_transportation_amd import _lib
+    off = np.sqrt(gp_dyn._noise) if std_offset is None else std_offset
+    return gp_map._handle.pullback_policy(gp_dyn._handle, y, aff["R"], aff["c_src"], aff["c_dst"], scale=aff["scale"],
+                                          R_jac=aff.get("R_jac", aff["R"]), x0=x0, rtol=rtol, max_passes=max_passes, std_offset=off,
+                                          outputs=_lib.PULLBACK_OUTPUTS if outputs is None else outputs)
+
+
+def _share(what, k, err, tol):
+    share = np.divide(err, tol, out=np.zeros_like(err), where=tol > 0)
+    print(f"{what}: {k} largest share of its bound {float(np.max(share)) if share.size else 0.0:.3f}")
+
+
+def _check_elementwise(what, out, case, y, rtol=RTOL, variances=True):
+    """Every output against its exact value at the z and x the device returned."""
+    gp_map, gp_dyn, aff = case["gp_map"], case["gp_dyn"], case["aff"]
+    e = P.exact_at(case["map_model"], case["dyn_model"], aff, y, out["post_z"], out["x"])
+    for k, name in (("x", "x"), ("f", "f"), ("A", "post_A"), ("vel", "vel"), ("det", "det"), ("residual", "residual")):
+        exact, tol = e[k]
+        err = np.abs(out[name].astype(LD) - exact)
+        _share(what, name, err, tol)
+        assert np.all(err <= tol), (what, name)
+    tol_r = rtol * (1 + np.linalg.norm(y, axis=1))
+    conv = out["status"] == INV.CONVERGED
+    assert np.all(out["residual"][conv] <= tol_r[conv]) and np.all(out["passes"] >= 1)
+    assert np.all(np.isfinite(out["vel"])) and np.all(np.isfinite(out["x"]))
+    if not variances:
+        return
+    c_d, c_m = gp_dyn._c, gp_map._c
+    ref_d = gp_dyn._handle.predict_all(out["x"], var=True)["var"]
+    ref_m = gp_map._handle.predict_all(out["post_z"], var=True, Jvar=True)
+    prior_j = c_m * G0[case.get("nu_map")] / np.broadcast_to(gp_map._ls, (y.shape[1],)) ** 2
+    for name, got, ref, scale in (("var_dyn", out["var_dyn"], ref_d, c_d), ("map_var", out["map_var"], ref_m["var"], c_m),
+                                  ("post_Jvar", out["post_Jvar"], ref_m["Jvar"], prior_j[None])):
+        err = np.abs(got - ref)
+        _share(what, name, err, VAR_SPLIT_RTOL * scale * np.ones_like(err))
+        assert np.all(err <= VAR_SPLIT_RTOL * scale), (what, name)
+    off = np.sqrt(gp_dyn._noise)
+    v = P.variance_epilogue(aff, out["f"], out["post_A"], out["var_dyn"], out["post_Jvar"], off)
+    for name in ("vel_var_map", "vel_var_dyn"):
+        exact, tol = v[name]
+        err = np.abs(out[name].astype(LD) - exact)
+        _share(what, name, err, tol)
+        assert np.all(err <= tol), (what, name)
+
+
+@pytest.fixture(scope="module")
+def letter():
+    """The letter-S transport (do_scale=True: a scale != 1) with the four dynamics of tests/golden/matern_2d on its demonstration."""
+    g, gm = load_golden("letterS_2d"), load_golden("matern_2d")
+    tr = _fit_transport(g, do_scale=True)
+    gp = tr.method.delta_map
+    dyn = {nu: _fit_gp(gm["X"], gm["Y"], 0.3, [1.5, 2.5], 0.01, nu) for nu in (None, 0.5, 1.5, 2.5)}
+    xg, yg = np.meshgrid(np.linspace(g["traj2"][:, 0].min() - 5, g["traj2"][:, 0].max() + 5, 12),
+                         np.linspace(g["traj2"][:, 1].min() - 5, g["traj2"][:, 1].max() + 5, 12))
+    grid = np.ascontiguousarray(np.column_stack([xg.ravel(), yg.ravel()]))
+    return {"g": g, "tr": tr, "gp_map": gp, "aff": _affine_of(tr), "map_model": _model_of(gp), "dyn": dyn,
+            "dyn_model": {nu: _model_of(d, nu) for nu, d in dyn.items()}, "grid": grid}
+
+
+def _letter_case(letter, nu):
+    return dict(letter, gp_dyn=letter["dyn"][nu], dyn_model=letter["dyn_model"][nu])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("do_scale", [False, True])
+def test_anchor_letterS_goldens(letter, do_scale):
+    """y = the reference's transported trajectory, x0 = the demonstration: Newton must stay where it starts — the 21 points where
+    the map folds included — and (post_A R) delta is the reference's transported velocity."""
+    g = letter["g"]
+    tr = letter["tr"] if do_scale else _fit_transport(g, do_scale=False)
+    gp, aff = tr.method.delta_map, _affine_of(tr)
+    y = g["traj2"] if do_scale else g["traj"]
+    out = _call(gp, letter["dyn"][2.5], y, aff, x0=g["demo"], rtol=RTOL)
+    print(f"letterS do_scale={do_scale}: status {_counts(out['status'])}, passes {out['passes'].min()} .. {out['passes'].max()}, "
+          f"residual <= {out['residual'].max():.2e} (rtol (1 + |y|) >= {RTOL * (1 + np.linalg.norm(y, axis=1).min()):.2e}), "
+          f"det <= 0 at {int(np.sum(out['det'] <= 0))}")
+    assert np.all(out["status"] == INV.CONVERGED) and np.all(out["passes"] == 1)
+    n_fold = int(np.sum(out["det"] <= 0))                           # the map folds; started at the demonstration Newton stays there
+    assert n_fold > 0 if do_scale else n_fold == 21                 # (21: tests/test_inverse_map.py::test_letterS_baseline_restatement)
+    bound, _ = INV.error_bound(_model_of(gp), out["post_z"], y, RTOL)
+    err = np.linalg.norm(out["x"] - g["demo"], axis=1)
+    assert np.all(err <= 2 * bound / aff["scale"])
+    vel = np.einsum("mod,md->mo", out["post_A"] @ aff["R"], g["delta"])
+    from tests.conftest import assert_parity
+    assert_parity(vel, g["vel2"] if do_scale else g["vel"], GOLDEN_RTOL, "vel")
+
+
+@pytest.fixture(scope="module")
+def surface():
+    g = load_golden("surface_3d")
+    tr = _fit_transport(g)
+    gp = tr.method.delta_map
+    dyn = _fit_gp(g["demo"], g["delta"], 0.05, [0.5, 0.6, 0.7], 1e-4, 1.5)
+    return {"g": g, "tr": tr, "gp_map": gp, "aff": _affine_of(tr), "map_model": _model_of(gp), "gp_dyn": dyn, "dyn_model": _model_of(dyn, 1.5)}
+
+
+@pytest.mark.gpu
+def test_anchor_surface_3d(surface):
+    g = surface["g"]
+    out = _call(surface["gp_map"], surface["gp_dyn"], g["traj"], surface["aff"], x0=g["demo"], rtol=RTOL,
+                outputs=("x", "passes", "residual", "post_z"))
+    print(f"surface_3d: residual at the demonstration <= {out['residual'].max():.2e} "
+          f"(1e-10 (1 + |y|) >= {RTOL * (1 + np.linalg.norm(g['traj'], axis=1).min()):.2e})")
+    assert np.all(out["status"] == INV.CONVERGED) and np.all(out["passes"] == 1)
+    bound, _ = INV.error_bound(surface["map_model"], out["post_z"], g["traj"], RTOL)
+    assert np.all(np.linalg.norm(out["x"] - g["demo"], axis=1) <= 2 * bound / surface["aff"]["scale"])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nu", [None, 0.5, 1.5, 2.5])
+def test_elementwise_letterS(letter, nu):
+    case = _letter_case(letter, nu)
+    y = np.ascontiguousarray(np.concatenate([letter["g"]["traj2"][::9], letter["grid"][::5]]))
+    out = _call(case["gp_map"], case["gp_dyn"], y, case["aff"])
+    print(f"letterS, dynamics nu={nu}: status {_counts(out['status'])}")
+    _check_elementwise(f"letterS nu={nu}", out, case, y)
+
+
+@pytest.mark.gpu
+def test_elementwise_surface_3d(surface):
+    y = np.ascontiguousarray(surface["g"]["traj"][::7])
+    out = _call(surface["gp_map"], surface["gp_dyn"], y, surface["aff"])
+    print(f"surface_3d: status {_counts(out['status'])}, passes <= {out['passes'].max()}")
+    assert np.all(out["status"] == INV.CONVERGED)
+    _check_elementwise("surface_3d", out, surface, y)
+    bound, _ = INV.error_bound(surface["map_model"], out["post_z"], y, RTOL)
+    assert np.all(np.linalg.norm(out["x"] - surface["g"]["demo"][::7], axis=1) <= 2 * bound / surface["aff"]["scale"])
+
+
+def _rotation(D, rng):
+    Q, _ = np.linalg.qr(rng.standard_normal((D, D)))
+    if np.linalg.det(Q) < 0:
+        Q[:, -1] *= -1
+    return np.ascontiguousarray(Q)
+
+
+def _affine(D, seed=3):
+    """A rotation, a scale != 1, centroids and an R_jac that is neither R nor scale R (tests/test_transport_fused.py::_affine)."""
+    rng = np.random.default_rng(seed)
+    return {"R": _rotation(D, rng), "scale": 1.0 + 0.3 * rng.uniform(), "c_src": rng.uniform(0.3, 0.7, D), "c_dst": rng.uniform(0.3, 0.7, D),
+            "R_jac": np.ascontiguousarray(_rotation(D, rng) * np.array([1.2, 0.8, 1.1])[:D])}
+
+
+def _synthetic_case(D, n_map, n_dyn, nu_map=None, nu_dyn=None, seed=0):
+    """Small smooth displacement (so the map is invertible) and a dynamics field on [0, 1]^D, both fitted on the device."""
+    rng = np.random.default_rng(seed + 1000 * n_map + n_dyn)
+    Xm, Xd = rng.uniform(0, 1, (n_map, D)), rng.uniform(0, 1, (n_dyn, D))
+    ls_m, ls_d = np.array([0.3, 0.25, 0.35])[:D], np.array([0.2, 0.3, 0.25])[:D]
+    gp_map = _fit_gp(Xm, 0.05 * np.sin(4 * Xm + 0.3), 0.1, ls_m, 1e-4, nu_map, matern_derivatives=nu_map is not None)
+    gp_dyn = _fit_gp(Xd, np.cos(3 * Xd) - 0.5, 0.5, ls_d, 1e-3, nu_dyn)
+    return {"gp_map": gp_map, "gp_dyn": gp_dyn, "aff": _affine(D, seed), "map_model": _model_of(gp_map, nu_map),
+            "dyn_model": _model_of(gp_dyn, nu_dyn), "nu_map": nu_map, "rng": rng}
+
+
+def _round_trip_queries(case, M):
+    """x in the source scene and y = Phi(x) through the device's own forward pieces."""
+    D = case["gp_map"].n_features
+    x = case["aff"]["c_src"] + case["rng"].uniform(-0.3, 0.3, (M, D))
+    gam = P.affine_forward(case["aff"], x)
+    return x, np.ascontiguousarray(gam + case["gp_map"].predict(gam).reshape(M, D))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,nu_map,nu_dyn", [(3, 2.5, None), (3, 1.5, 0.5), (1, None, 1.5), (1, 2.5, 2.5), (2, None, 2.5)])
+def test_elementwise_synthetic(D, nu_map, nu_dyn):
+    case = _synthetic_case(D, 64, 100, nu_map, nu_dyn)
+    x, y = _round_trip_queries(case, 37)
+    for x0 in (None, x + 0.01):
+        out = _call(case["gp_map"], case["gp_dyn"], y, case["aff"], x0=x0)
+        what = f"synthetic D={D} map nu={nu_map} dynamics nu={nu_dyn} x0={'given' if x0 is not None else 'none'}"
+        print(what, "status", _counts(out["status"]), "passes <=", out["passes"].max())
+        assert np.all(out["status"] == INV.CONVERGED)
+        _check_elementwise(what, out, case, y)
+        bound, _ = INV.error_bound(case["map_model"], out["post_z"], y, RTOL)
+        # (y was formed in float64 from the device's own predict: its rounding, 8 eps (1 + |y|), is part of the equation solved)
+        slack = 8 * EPS * (1 + np.linalg.norm(y, axis=1)) / np.linalg.svd(out["post_A"], compute_uv=False)[:, -1]
+        assert np.all(np.linalg.norm(out["x"] - x, axis=1) <= (2 * bound + slack) / case["aff"]["scale"])
+
+
+@pytest.mark.gpu
+def test_against_the_existing_inverse(letter):
+    """Without x0 on the letter-S grid, where points fold and stall: the Newton phase is gpt_inverse_map's, bit for bit."""
+    case = _letter_case(letter, 1.5)
+    h = case["gp_map"]._handle
+    y = np.ascontiguousarray(np.concatenate([letter["grid"], letter["g"]["traj2"][::3]]))
+    for max_passes in (64, 1, 3):
+        z, info = h.inverse_map(y, rtol=RTOL, max_passes=max_passes)
+        out = _call(case["gp_map"], case["gp_dyn"], y, case["aff"], max_passes=max_passes)
+        print(f"letterS grid, max_passes={max_passes}: status {_counts(out['status'])}, passes <= {out['passes'].max()}")
+        assert np.array_equal(out["status"], info["status"]) and np.array_equal(out["passes"], info["passes"])
+        assert out["post_z"].tobytes() == z.tobytes()
+        assert out["residual"].tobytes() == info["residual"].tobytes() and out["det"].tobytes() == info["det"].tobytes()
+        if max_passes == 64:
+            assert len(set(out["status"])) >= 2                                     # (the launch holds queries that end differently)
+        else:
+            assert np.any(out["status"] == INV.MAX_PASSES) and np.all(out["passes"] <= max_passes)
+        _check_elementwise(f"letterS grid max_passes={max_passes}", out, case, y)   # at the z reached, converged or not
+
+
+@pytest.mark.gpu
+def test_wave_stride_tails_and_workgroup_tails():
+    """N_map, N_dyn in {1, 63, 64, 65, 129}: the tails of the 64-lane stride and the empty second trip; M in {0, 1, 3, 4, 5}: the
+    four-waves-per-workgroup tail."""
+    sizes = (1, 63, 64, 65, 129)
+    maps = {n: _synthetic_case(2, n, 1) for n in sizes}
+    dyns = {n: _synthetic_case(2, 1, n, seed=7) for n in sizes}
+    for nm in sizes:
+        for nd in sizes:
+            case = dict(maps[nm], gp_dyn=dyns[nd]["gp_dyn"], dyn_model=dyns[nd]["dyn_model"])
+            x, y = _round_trip_queries(case, 5)
+            full = _call(case["gp_map"], case["gp_dyn"], y, case["aff"])
+            assert np.all(full["status"] == INV.CONVERGED), (nm, nd)
+            _check_elementwise(f"N_map={nm} N_dyn={nd}", full, case, y, variances=(nm, nd) in ((1, 1), (65, 129), (129, 63)))
+            if (nm, nd) != (65, 63):
+                continue
+            for M in (0, 1, 3, 4):
+                part = _call(case["gp_map"], case["gp_dyn"], y[:M], case["aff"])
+                for k, v in part.items():
+                    assert v.shape[0] == M
+                    if k in ("x", "vel", "f", "det", "residual", "passes", "status", "post_z", "post_A"):
+                        assert v.tobytes() == full[k][:M].tobytes(), (M, k)
+
+
+def _raw(h, hd, M, y, x0, aff, outs, rtol=RTOL, max_passes=64, std_offset=0.1, entry="gpt_pullback_policy"):
+    """The C entry point itself on numpy arrays (`outs`: name -> array or None); returns (rc, message)."""
+    from gaussian_process_transportation_amd import _lib
+    p = _lib.dptr
+    ip = lambda a: None if a is None else a.ctypes.data_as(_lib.C.POINTER(_lib.C.c_int))
+    ptr = lambda k: ip(outs.get(k)) if k in ("passes", "status") else p(outs.get(k))
+    if entry.endswith("_dev"):
+        ptr = lambda k: None
+    rc = getattr(_lib.load(), entry)(None if h is None else h._h, None if hd is None else hd._h, p(y), p(x0), M, p(aff["R"]), p(aff["c_src"]),
+                               p(aff["c_dst"]), float(aff["scale"]), p(aff.get("R_jac", aff["R"])), float(rtol), int(max_passes),
+                               float(std_offset), *(ptr(k) for k in _lib.PULLBACK_OUTPUTS))
+    return rc, _lib.last_error()
+
+
+def _sentinels(M, D):
+    shapes = {"x": (M, D), "vel": (M, D), "f": (M, D), "det": (M,), "residual": (M,), "passes": (M,), "status": (M,), "var_dyn": (M,),
+              "map_var": (M,), "vel_var_map": (M,), "vel_var_dyn": (M, D), "post_z": (M, D), "post_A": (M, D, D), "post_Jvar": (M, D)}
+    return {k: (np.full(s, ISENT, dtype=np.int32) if k in ("passes", "status") else np.full(s, SENT)) for k, s in shapes.items()}
+
+
+def _untouched(v):
+    return np.all(v == (ISENT if v.dtype == np.int32 else SENT))
+
+
+@pytest.mark.gpu
+def test_chunk_tail_and_sentinels():
+    """M = HOST_CHUNK + 1 at N_map = 20, N_dyn = 65: the chunk tail and both staging sets, against two separate calls; arrays
+    longer than M stay sentinels past M * width; arrays that were not asked for are untouched."""
+    from gaussian_process_transportation_amd import _lib
+    case = _synthetic_case(2, 20, 65)
+    M = HOST_CHUNK + 1
+    base_x, base_y = _round_trip_queries(case, 257)
+    reps = -(-M // 257)
+    y = np.ascontiguousarray(np.tile(base_y, (reps, 1))[:M])
+    h, hd, aff = case["gp_map"]._handle, case["gp_dyn"]._handle, case["aff"]
+    outs = _sentinels(M + 3, 2)                                                   # three rows more than the call may write
+    rc, msg = _raw(h, hd, M, y, None, aff, outs, std_offset=np.sqrt(case["gp_dyn"]._noise))
+    assert rc == _lib.GPT_OK, msg
+    for k, v in outs.items():
+        assert _untouched(v[M:]), k
+    head = _call(case["gp_map"], case["gp_dyn"], y[:HOST_CHUNK], aff)
+    tail = _call(case["gp_map"], case["gp_dyn"], y[HOST_CHUNK:], aff)
+    prior_j = case["gp_map"]._c / case["gp_map"]._ls ** 2
+    for k, v in outs.items():
+        two = np.concatenate([head[k], tail[k]])
+        if k in ("var_dyn", "map_var", "post_Jvar"):                              # launches of different size
+            scale = {"var_dyn": case["gp_dyn"]._c, "map_var": case["gp_map"]._c, "post_Jvar": prior_j[None]}[k]
+            assert np.all(np.abs(v[:M] - two) <= VAR_SPLIT_RTOL * scale), k
+        elif k in ("vel_var_map", "vel_var_dyn"):                                 # the epilogue on this call's own variances
+            exact, tol = P.variance_epilogue(aff, outs["f"][:M], outs["post_A"][:M], outs["var_dyn"][:M], outs["post_Jvar"][:M],
+                                             np.sqrt(case["gp_dyn"]._noise))[k]
+            assert np.all(np.abs(v[:M].astype(LD) - exact) <= tol), k
+        else:
+            assert v[:M].tobytes() == two.tobytes(), k
+    assert np.all(outs["status"][:M] == INV.CONVERGED)
+    # the periodic input comes back periodic: nothing of one query leaks into another
+    assert outs["vel"][:257].tobytes() == outs["vel"][257:514].tobytes()
+    # only vel and status asked for: nothing else is written
+    few = _sentinels(5, 2)
+    rc, msg = _raw(h, hd, 5, y[:5], None, aff, {k: few[k] for k in ("vel", "status")})
+    assert rc == _lib.GPT_OK, msg
+    assert all(_untouched(v) for k, v in few.items() if k not in ("vel", "status"))
+    assert few["vel"].tobytes() == outs["vel"][:5].tobytes() and few["status"].tobytes() == outs["status"][:5].tobytes()
+
+
+@pytest.mark.gpu
+def test_independence_of_M(letter):
+    case = _letter_case(letter, 2.5)
+    base = np.ascontiguousarray(np.concatenate([letter["grid"], letter["g"]["traj2"]]))
+    y = np.ascontiguousarray(np.tile(base, (-(-4097 // len(base)), 1))[:4097])
+    big = _call(case["gp_map"], case["gp_dyn"], y, case["aff"])
+    prior_j = case["gp_map"]._c / case["gp_map"]._ls ** 2
+    for m in (0, 3, 77, 4096):                                                    # a fold, a stall, the last row among them
+        for lo, hi in ((m, m + 1), (max(0, m - 2), max(0, m - 2) + 5)):
+            if hi > len(y):
+                continue
+            part = _call(case["gp_map"], case["gp_dyn"], y[lo:hi], case["aff"])
+            for k in ("x", "f", "vel", "det", "status", "passes", "residual", "post_z", "post_A"):
+                assert part[k].tobytes() == big[k][lo:hi].tobytes(), (m, lo, k)
+            for k, scale in (("var_dyn", case["gp_dyn"]._c), ("map_var", case["gp_map"]._c), ("post_Jvar", prior_j[None])):
+                assert np.all(np.abs(part[k] - big[k][lo:hi]) <= VAR_SPLIT_RTOL * scale), (m, lo, k)
+
+
+def _device_call(h, hd, torch, dev, y, aff, names, x0=None, std_offset=0.1):
+    """gpt_pullback_policy_dev on torch tensors; returns {name: tensor} and the inputs (kept alive by the caller)."""
+    M, D = y.shape
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    shapes = _sentinels(M, D)
+    ins = {k: t(v) for k, v in (("y", y), ("x0", x0), ("R", aff["R"]), ("c_src", aff["c_src"]), ("c_dst", aff["c_dst"]),
+                                ("R_jac", aff.get("R_jac", aff["R"])))}
+    outs = {k: torch.from_numpy(shapes[k]).to(dev) for k in names}
+    ptr = lambda x: 0 if x is None else x.data_ptr()
+    h.pullback_policy_dev(hd, ptr(ins["y"]), M, ptr(ins["R"]), ptr(ins["c_src"]), ptr(ins["c_dst"]), aff["scale"], ptr(ins["R_jac"]),
+                          outs["vel"].data_ptr(), outs["status"].data_ptr(), x0_ptr=ptr(ins["x0"]), rtol=RTOL, std_offset=std_offset,
+                          **{k + "_ptr": v.data_ptr() for k, v in outs.items() if k not in ("vel", "status")})
+    return outs, ins
+
+
+@pytest.mark.gpu
+def test_streams_and_the_device_entry():
+    import torch
+    from gaussian_process_transportation_amd import _lib
+    case = _synthetic_case(3, 129, 200, None, 1.5)
+    x, y = _round_trip_queries(case, 301)
+    gp_map, gp_dyn, aff = case["gp_map"], case["gp_dyn"], case["aff"]
+    h, hd = gp_map._handle, gp_dyn._handle
+    off = np.sqrt(gp_dyn._noise)
+    host = _call(gp_map, gp_dyn, y, aff, x0=x)                                     # both handles on their own default streams
+    dev = torch.device("cuda", 0)
+    s_map, s_dyn = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    torch.cuda.synchronize()
+
+    def same(got, names):
+        for k in names:
+            a = got[k].cpu().numpy()
+            assert a.tobytes() == host[k].tobytes(), k                          # (the same launches at the same M, variances included)
+
+    every, keep1 = _device_call(h, hd, torch, dev, y, aff, _lib.PULLBACK_OUTPUTS, x0=x, std_offset=off)    # default streams
+    h.synchronize(); hd.synchronize()
+    same(every, _lib.PULLBACK_OUTPUTS)
+    h.set_stream(s_map.cuda_stream); hd.set_stream(s_dyn.cuda_stream)
+    try:
+        own, keep2 = _device_call(h, hd, torch, dev, y, aff, _lib.PULLBACK_OUTPUTS, x0=x, std_offset=off)   # each handle on its own torch stream
+        s_map.synchronize()
+        same(own, _lib.PULLBACK_OUTPUTS)
+        few, keep3 = _device_call(h, hd, torch, dev, y, aff, ("vel", "status", "vel_var_dyn"), x0=x, std_offset=off)   # optional outputs left out
+        s_map.synchronize()
+        same(few, ("vel", "status", "vel_var_dyn"))
+        bare, keep4 = _device_call(h, hd, torch, dev, y, aff, ("vel", "status"), std_offset=off)
+        s_map.synchronize()
+        assert np.all(bare["status"].cpu().numpy() == INV.CONVERGED)
+        # one stream for both handles
+        hd.set_stream(s_map.cuda_stream)
+        both, keep5 = _device_call(h, hd, torch, dev, y, aff, _lib.PULLBACK_OUTPUTS, x0=x, std_offset=off)
+        s_map.synchronize()
+        same(both, _lib.PULLBACK_OUTPUTS)
+    finally:
+        h.set_stream(0); hd.set_stream(0)
+    # straight after a refit of the dynamics, no synchronisation in between: the call sees the new model
+    Xd = gp_dyn.X
+    gp_dyn.fit(Xd, 2.0 * gp_dyn.Y)
+    again = _call(gp_map, gp_dyn, y, aff, x0=x)
+    assert again["post_z"].tobytes() == host["post_z"].tobytes() and again["x"].tobytes() == host["x"].tobytes()
+    model2 = _model_of(gp_dyn, 1.5)
+    f2, S2 = model2.mean(again["x"])
+    assert np.all(np.abs(again["f"] - f2) <= 64 * EPS * S2)
+    assert relmax(again["f"], 2.0 * host["f"]) <= 1e-9
+
+
+@pytest.mark.gpu
+def test_python_level(letter, capsys):
+    g, tr, dyn = letter["g"], letter["tr"], letter["dyn"][2.5]
+    pt = tr.method
+    y = np.ascontiguousarray(np.concatenate([g["traj2"][::5], letter["grid"][::7]]))
+    vel, std, info = pt.transported_policy(dyn, y, return_std=True, return_info=True, rtol=RTOL)
+    M, D = y.shape
+    assert vel.shape == (M, D) and std.shape == (M, D)
+    assert set(info) >= {"x", "status", "passes", "residual", "det", "f", "std_dyn", "vel_var_dyn", "vel_var_map", "map_std"}
+    for k in ("x", "f", "std_dyn", "vel_var_dyn", "vel_var_map", "map_std"):
+        assert info[k].shape == (M, D), k
+    assert np.array_equal(info["vel_var_map"][:, 0], info["vel_var_map"][:, 1])     # tiled, as transport_velocity's
+    # the composition through the existing public calls
+    x, inv = pt.inverse_transport(y, return_info=True, rtol=RTOL)
+    f, std_f = dyn.predict(x, return_std=True)
+    v, var_v = pt.transport_velocity(x, f)
+    assert np.array_equal(info["status"], inv["status"]) and np.array_equal(info["passes"], inv["passes"])
+    assert v.shape == vel.shape and var_v.shape == info["vel_var_map"].shape and std_f.shape == info["std_dyn"].shape
+    # each path against the restatement at ITS OWN points (one call: the z of the inverse and its x; composition: x and gamma(x)),
+    # plus the exact distance between the two restated values: the sum of the two paths' bounds
+    case = _letter_case(letter, 2.5)
+    aff = case["aff"]
+    z = pt.delta_map.invert_displacement(y, rtol=RTOL)
+    e1 = P.exact_at(case["map_model"], case["dyn_model"], aff, y, z, info["x"])
+    e2 = P.exact_at(case["map_model"], case["dyn_model"], aff, y, pt.affine_transform.predict(x), x)
+    between = lambda k: np.asarray(e1[k][1] + e2[k][1] + np.abs(e1[k][0] - e2[k][0]), dtype=np.float64)
+    assert np.all(np.abs(info["x"] - x) <= 2 * np.asarray(e1["x"][1], dtype=np.float64))
+    assert np.all(np.abs(info["f"] - f) <= between("f")) and np.all(np.abs(vel - v) <= between("vel"))
+    # variances: two launches agree to VAR_SPLIT_RTOL of the prior variance, each path has one, and the points 1e-14 apart move a
+    # variance three orders less than that: 4 VAR_SPLIT_RTOL of the prior variance; carried to first order through
+    # std^2 = std_f^2 rowsumsq(J_Phi) + var_v with the floors of f and A above (d std_f^2 = std_f / sqrt(var) d var <= d var)
+    res = pt.delta_map.pullback_policy(dyn, y, aff["R"], aff["scale"], aff["c_src"], aff["c_dst"], variances=True, return_posterior=True)
+    assert res["post_A"].shape == (M, D, D) and res["post_z"].shape == (M, D) and res["post_Jvar"].shape == (M, D)
+    assert res["vel"].tobytes() == vel.tobytes() and res["post_z"].tobytes() == z.tobytes()
+    off, R = np.sqrt(dyn._noise), aff["R"]
+    d_var = 4 * VAR_SPLIT_RTOL * dyn._c
+    assert np.all(np.abs((info["std_dyn"] + off) ** 2 - (std_f + off) ** 2) <= d_var)
+    prior_j = pt.delta_map._c / pt.delta_map._ls ** 2
+    gv, dg = f @ R.T, between("f") @ np.abs(R).T
+    d_var_v = 4 * VAR_SPLIT_RTOL * (gv ** 2 @ prior_j) + 2 * np.sum(res["post_Jvar"] * np.abs(gv) * dg, axis=1)
+    assert np.all(np.abs(info["vel_var_map"] - var_v) <= d_var_v[:, None] + 16 * EPS * np.abs(var_v))
+    B, dB = res["post_A"] @ R, between("A") @ np.abs(R)
+    rows, d_rows = np.sum(B ** 2, axis=2), 2 * np.sum(np.abs(B) * dB, axis=2)
+    want2 = std_f ** 2 * np.sum(((np.eye(D)[None] + pt.delta_map.derivative(pt.affine_transform.predict(x))) @ R) ** 2, axis=2) + var_v
+    tol2 = rows * d_var + std_f ** 2 * d_rows + d_var_v[:, None] + 16 * EPS * want2
+    print(f"python level: std^2 against the public calls, largest share of its bound {np.max(np.abs(std ** 2 - want2) / tol2):.3f}")
+    assert np.all(np.abs(std ** 2 - want2) <= tol2)
+    # return_std without the dict: the map's std is left out and its variance launch has three columns, not four — another launch
+    v3, std3 = pt.transported_policy(dyn, y, return_std=True, rtol=RTOL)
+    assert v3.tobytes() == vel.tobytes()
+    assert np.all(np.abs(std3 ** 2 - std ** 2) <= VAR_SPLIT_RTOL * (gv ** 2 @ prior_j)[:, None] + 16 * EPS * std ** 2)
+    with pytest.raises(ValueError, match="variances"):
+        pt.delta_map.pullback_policy(dyn, y, aff["R"], aff["scale"], aff["c_src"], aff["c_dst"], variances="all")
+    # plain call: the velocities alone; the user-facing class forwards
+    assert pt.transported_policy(dyn, y, rtol=RTOL).tobytes() == vel.tobytes()
+    assert tr.transported_policy(dyn, y, rtol=RTOL).tobytes() == vel.tobytes()
+    v0, i0 = tr.transported_policy(dyn, g["traj2"][:9], x0=g["demo"][:9], return_info=True, rtol=RTOL)
+    assert np.all(i0["passes"] == 1) and "std_dyn" not in i0
+    capsys.readouterr()
+    pt.verbose = True
+    try:
+        pt.transported_policy(dyn, y)
+    finally:
+        pt.verbose = False
+    said = capsys.readouterr().out
+    assert "CONVERGED" in said and "STALLED" in said and "det(I + J_psi) <= 0" in said
+
+@pytest.mark.gpu
+def test_refusals():
+    from gaussian_process_transportation_amd import _lib
+    case = _synthetic_case(3, 50, 40)
+    gp_map, gp_dyn, aff = case["gp_map"], case["gp_dyn"], case["aff"]
+    h, hd = gp_map._handle, gp_dyn._handle
+    x, y = _round_trip_queries(case, 4)
+    before = h.predict_all(y, mean=True, var=True, J=True, Jvar=True)
+    outs = _sentinels(4, 3)
+    rng = np.random.default_rng(0)
+    X3 = rng.uniform(0, 1, (50, 3))
+
+    def refused(match, hh=h, hhd=hd, M=4, y_=y, x0_=None, aff_=aff, drop=(), code=_lib.GPT_E_ARG, **kw):
+        for entry in ("gpt_pullback_policy",) + (("gpt_pullback_policy_dev",) if kw.pop("dev", False) else ()):
+            rc, msg = _raw(hh, hhd, M, y_, x0_, aff_, {k: v for k, v in outs.items() if k not in drop}, entry=entry, **kw)
+            assert rc == code and match in msg, (entry, rc, msg)
+        assert all(_untouched(v) for v in outs.values()), match
+
+    def py_refused(exc, match, gm=gp_map, gd=gp_dyn, y_=y, **kw):
+        with pytest.raises(exc, match=match):
+            gm.pullback_policy(gd, y_, aff["R"], aff["scale"], aff["c_src"], aff["c_dst"], **kw)
+
+    # handles: NULL, unfitted, the same twice
+    refused("NULL handle", hh=None, dev=True)
+    refused("NULL handle", hhd=None, dev=True)
+    empty = _lib.Handle(0)
+    refused("not fitted", hh=empty, code=_lib.GPT_E_STATE, dev=True)
+    refused("not fitted", hhd=empty, code=_lib.GPT_E_STATE, dev=True)
+    refused("same handle", hhd=h, dev=True)
+    py_refused(ValueError, "same object", gd=gp_map)
+    if _lib.load().gpt_device_count() >= 2:
+        other = _lib.Handle(1)
+        other.fit(X3, 0.05 * np.sin(X3), np.full(3, 0.3), 0.1, 1e-3, 1e-10)
+        refused("different devices", hhd=other, dev=True)
+        other.close()
+    # D differs; D != O; D > 3
+    two_d = _fit_gp(X3[:, :2], 0.05 * np.sin(X3[:, :2]), 0.1, [0.3], 1e-3)
+    refused("share one space", hhd=two_d._handle, dev=True)
+    py_refused(ValueError, "features", gd=two_d)
+    two_out = _fit_gp(X3, X3[:, :2], 0.1, [0.3], 1e-3)
+    refused("D == O", hh=two_out._handle)
+    refused("D == O", hhd=two_out._handle)
+    py_refused(NotImplementedError, "onto itself", gm=two_out)
+    py_refused(NotImplementedError, "onto itself", gd=two_out)
+    X4 = rng.uniform(0, 1, (50, 4))
+    wide = _fit_gp(X4, 0.05 * np.sin(X4), 0.1, [0.3], 1e-3)
+    refused("D <= 3", hh=wide._handle, y_=X4[:4])
+    refused("D <= 3", hhd=wide._handle)
+    py_refused(NotImplementedError, "at most 3", gm=wide, y_=X4[:4])
+    py_refused(NotImplementedError, "at most 3", gd=wide)
+    # fp32 and multi-task models, on either side
+    f32 = _fit_gp(X3, 0.05 * np.sin(X3), 0.1, [0.3], 1e-3, dtype="float32")
+    refused("fp64", hh=f32._handle)
+    refused("fp64", hhd=f32._handle)
+    py_refused(NotImplementedError, "float64", gm=f32)
+    py_refused(NotImplementedError, "float64", gd=f32)
+    empty.fit_svgp(X3, rng.standard_normal((3, 50)), 1e-2 * np.eye(50) * np.ones((3, 1, 1)), np.full(3, 0.3), np.ones(3))
+    refused("single-task", hh=empty)
+    refused("single-task", hhd=empty)
+    empty.close()
+    # a Matern map: 1/2 never, 3/2 and 5/2 only with the analytic derivatives enabled; Matern dynamics are fine
+    m12 = _fit_gp(X3, 0.05 * np.sin(X3), 0.1, 0.3, 1e-3, 0.5, matern_derivatives=True)
+    refused("Matern 1/2", hh=m12._handle)
+    py_refused(NotImplementedError, "nu=0.5", gm=m12)
+    ok = _call(gp_map, m12, y, aff, outputs=())
+    assert np.all(ok["status"] == INV.CONVERGED)
+    for nu in (1.5, 2.5):
+        m = _fit_gp(X3, 0.05 * np.sin(X3), 0.1, 0.3, 1e-3, nu)
+        refused("gpt_set_matern_derivatives", hh=m._handle)
+        py_refused(NotImplementedError, "matern_derivatives", gm=m)
+        assert np.all(_call(gp_map, m, y, aff, outputs=())["status"] == INV.CONVERGED)
+    # the solver's arguments, M, required arrays
+    for bad in (0.0, -1e-3, float("nan")):
+        refused("rtol", rtol=bad, dev=True)
+        py_refused(ValueError, "rtol", rtol=bad)
+    refused("max_passes", max_passes=0, dev=True)
+    py_refused(ValueError, "max_passes", max_passes=0)
+    refused("2^31", M=-1, dev=True)
+    refused("2^31", M=2 ** 31, dev=True)
+    refused("must not be NULL", y_=None)
+    refused("must not be NULL", drop=("vel",))
+    refused("must not be NULL", drop=("status",))
+    refused("must not be NULL", aff_=dict(aff, R_jac=None, R=None))
+    # NaN or infinity in the host call's inputs
+    nan_at = lambda a, i: np.ascontiguousarray(np.where(np.arange(a.size).reshape(a.shape) == i, np.nan, a))
+    for bad in (dict(y_=nan_at(y, 5)), dict(x0_=np.where(np.arange(12).reshape(4, 3) == 0, np.inf, x)), dict(aff_=dict(aff, scale=float("inf"))),
+                dict(aff_=dict(aff, R=nan_at(aff["R"], 4))), dict(aff_=dict(aff, R_jac=nan_at(aff["R_jac"], 0))),
+                dict(aff_=dict(aff, c_src=np.full(3, np.nan))), dict(aff_=dict(aff, c_dst=np.full(3, np.nan))), dict(std_offset=float("nan"))):
+        refused("NaN or infinity", **{k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in bad.items()})
+    py_refused(ValueError, "NaN or infinity", y_=np.full((2, 3), np.nan))
+    py_refused(ValueError, "columns", y_=np.zeros((4, 2)))
+    py_refused(ValueError, "shape", x0=x[:2])
+    # M = 0 does nothing
+    rc, _ = _raw(h, hd, 0, y, None, aff, outs)
+    assert rc == _lib.GPT_OK and all(_untouched(v) for v in outs.values())
+    none = _call(gp_map, gp_dyn, np.zeros((0, 3)), aff)
+    assert none["vel"].shape == (0, 3) and none["status"].shape == (0,) and none["post_A"].shape == (0, 3, 3)
+    # both models and their scratch are as they were
+    after = h.predict_all(y, mean=True, var=True, J=True, Jvar=True)
+    for k in before:
+        if before[k] is not None:
+            assert before[k].tobytes() == after[k].tobytes(), k
