@@ -22,12 +22,26 @@ TRANSPORT_OUTPUTS = ("pos_rot", "pos_out", "var", "vel_out", "vel_var", "det_vel
 # outputs of gpt_pullback_policy, in the order of its arguments (passes and status are int32, the rest float64)
 PULLBACK_OUTPUTS = ("x", "vel", "f", "det", "residual", "passes", "status", "var_dyn", "map_var", "vel_var_map", "vel_var_dyn",
                     "post_z", "post_A", "post_Jvar")
+# outputs of gpt_pullback_chain, in the order of its arguments (status, stage_status and stage_passes are int32, the rest float64);
+# the stage_* arrays are stage-major: (K, M, ...)
+CHAIN_OUTPUTS = ("x", "vel", "f", "status", "var_dyn", "vel_var_map", "vel_var_dyn", "stage_x", "stage_z", "stage_A", "stage_Jvar",
+                 "stage_map_var", "stage_status", "stage_passes", "stage_residual", "stage_det")
+CHAIN_INT_OUTPUTS = ("status", "stage_status", "stage_passes")
+CHAIN_MAX = 4      # GPT_CHAIN_MAX: stages of one gpt_pullback_chain call
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
+_ip = C.POINTER(C.c_int)
+
+
+class ChainStage(C.Structure):
+    """gpt_chain_stage: one transport of a gpt_pullback_chain call (the pointers: host or device memory, as the entry's)."""
+    _fields_ = [("h", _vp), ("R", _vp), ("c_src", _vp), ("c_dst", _vp), ("R_jac", _vp), ("scale", C.c_double)]
+
+
 
 # name -> (restype, argtypes); mirrors include/gpt_hip.h one to one
 SIGNATURES = {
@@ -57,6 +71,9 @@ SIGNATURES = {
                                 + [_vp] * 14),
     "gpt_pullback_policy": (C.c_int, [_vp, _vp, _dp, _dp, _i64, _dp, _dp, _dp, C.c_double, _dp, C.c_double, C.c_int, C.c_double]
                             + [_dp] * 5 + [C.POINTER(C.c_int)] * 2 + [_dp] * 7),
+    "gpt_pullback_chain_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _i64, C.c_double, C.c_int, C.c_double] + [_vp] * 16),
+    "gpt_pullback_chain": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, C.c_double, C.c_int, C.c_double]
+                           + [_dp] * 3 + [_ip] + [_dp] * 8 + [_ip] * 2 + [_dp] * 2),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -811,6 +828,75 @@ class Handle:
                                                float(rtol), int(max_passes), float(std_offset),
                                                *(_vp(ptrs.get(k + "_ptr") or None) for k in PULLBACK_OUTPUTS)),
               "gpt_pullback_policy_dev")
+
+    # ---- the transported policy through a chain of transports: K inverses, dynamics and push-forward in one call
+    def pullback_chain(self, inner, dyn, y, x0=None, rtol=1e-10, max_passes=64, std_offset=0.0, outputs=CHAIN_OUTPUTS):
+        """gpt_pullback_chain on host arrays, this handle the LAST stage of the chain (it owns the call's scratch and stream).
+        `inner`: the K stages in application order, stage 0 first, each a tuple (handle, R, c_src, c_dst, scale, R_jac) with
+        R_jac None for R; the last tuple's handle is this one.  For each row of y (M,D): the preimage x under Phi_{K-1} o ... o
+        Phi_0, the mean f of the handle `dyn` at x and vel = J_Phi(x) f; x0 (M,D): guesses of the source-space preimages.
+        `outputs`: names out of CHAIN_OUTPUTS; vel and status always come.  Returns a dict; the stage_* arrays are (K, M, ...)."""
+        stages = list(inner)
+        K = len(stages)
+        if not 1 <= K <= CHAIN_MAX:
+            raise ValueError(f"pullback_chain: 1 .. {CHAIN_MAX} stages, got {K}")
+        if stages[-1][0] is not self:
+            raise ValueError("pullback_chain: the last stage's handle must be the handle the call is made on")
+        N, D, O, _ = self.info()
+        y = as_f64(y, 2, "y")
+        if y.shape[1] != D:
+            raise ValueError(f"y has {y.shape[1]} columns, model was fitted with {D} features")
+        M = y.shape[0]
+        if x0 is not None:
+            x0 = as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
+        unknown = set(outputs) - set(CHAIN_OUTPUTS)
+        if unknown:
+            raise ValueError(f"pullback_chain: unknown outputs {sorted(unknown)}")
+        keep = []                                # the affine arrays live until the call returns
+        arr = (ChainStage * K)()
+        for k, (h, R, c_src, c_dst, scale, R_jac) in enumerate(stages):
+            R = as_f64(R, 2, "R")
+            R_jac = R if R_jac is None else as_f64(R_jac, 2, "R_jac")
+            c_src, c_dst = as_f64(c_src, 1, "c_src"), as_f64(c_dst, 1, "c_dst")
+            if R.shape != (D, D) or R_jac.shape != (D, D) or c_src.shape != (D,) or c_dst.shape != (D,):
+                raise ValueError(f"stage {k}: the affine part of a {D}-dimensional model is R ({D},{D}), R_jac ({D},{D}), c_src ({D},), "
+                                 f"c_dst ({D},)")
+            keep += [R, R_jac, c_src, c_dst]
+            arr[k] = ChainStage(h._h, R.ctypes.data, c_src.ctypes.data, c_dst.ctypes.data, R_jac.ctypes.data, float(scale))
+        shapes = {"x": (M, D), "vel": (M, D), "f": (M, D), "status": (M,), "var_dyn": (M,), "vel_var_map": (M, D), "vel_var_dyn": (M, D),
+                  "stage_x": (K, M, D), "stage_z": (K, M, D), "stage_A": (K, M, D, D), "stage_Jvar": (K, M, D), "stage_map_var": (K, M),
+                  "stage_status": (K, M), "stage_passes": (K, M), "stage_residual": (K, M), "stage_det": (K, M)}
+        want = [k for k in CHAIN_OUTPUTS if k in ("vel", "status") or k in outputs]
+        out = {k: np.empty(shapes[k], dtype=np.int32 if k in CHAIN_INT_OUTPUTS else np.float64) for k in want}
+        ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(_ip)) if k in CHAIN_INT_OUTPUTS else dptr(out.get(k))
+        check(self.lib.gpt_pullback_chain(arr, K, dyn._h, dptr(y), dptr(x0), M, float(rtol), int(max_passes), float(std_offset),
+                                          *(ptr(k) for k in CHAIN_OUTPUTS)),
+              "gpt_pullback_chain")
+        del keep
+        return out
+
+    def pullback_chain_dev(self, inner, dyn, y_ptr, M, vel_ptr, status_ptr, x0_ptr=0, rtol=1e-10, max_passes=64, std_offset=0.0, **out_ptrs):
+        """The same on device pointers (float64; status / stage_status / stage_passes int32), asynchronous on this handle's stream
+        (gpt_pullback_chain_dev).  `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers, the
+        last tuple's handle this one.  out_ptrs: <name>_ptr for the further names of CHAIN_OUTPUTS."""
+        stages = list(inner)
+        K = len(stages)
+        if not 1 <= K <= CHAIN_MAX:
+            raise ValueError(f"pullback_chain_dev: 1 .. {CHAIN_MAX} stages, got {K}")
+        if stages[-1][0] is not self:
+            raise ValueError("pullback_chain_dev: the last stage's handle must be the handle the call is made on")
+        ptrs = dict(out_ptrs, vel_ptr=vel_ptr, status_ptr=status_ptr)
+        unknown = set(ptrs) - {k + "_ptr" for k in CHAIN_OUTPUTS}
+        if unknown:
+            raise TypeError(f"pullback_chain_dev: unknown arguments {sorted(unknown)}")
+        arr = (ChainStage * K)()
+        for k, (h, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr) in enumerate(stages):
+            arr[k] = ChainStage(h._h, R_ptr or None, c_src_ptr or None, c_dst_ptr or None, R_jac_ptr or None, float(scale))
+        check(self.lib.gpt_pullback_chain_dev(arr, K, dyn._h, _vp(y_ptr or None), _vp(x0_ptr or None), int(M), float(rtol), int(max_passes),
+                                              float(std_offset), *(_vp(ptrs.get(k + "_ptr") or None) for k in CHAIN_OUTPUTS)),
+              "gpt_pullback_chain_dev")
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -6,6 +6,7 @@
 #include "gpt_fit_plan.h"
 #include "gpt_transport.h"
 #include "gpt_pullback.h"
+#include "gpt_chain.h"
 #include "../../include/gpt_hip.h"
 
 #include <algorithm>
@@ -195,6 +196,9 @@ struct gpt_handle {
     DevBuf<double> pb_scratch[PB_SCRATCH];
     struct PullbackStaging { DevBuf<unsigned char> buf[PB_COUNT]; } pb_st[2];
     Event pb_ev[3];
+    // gpt_pullback_chain, held by the handle of the chain's last stage (gpt_chain.h; created on first use)
+    std::unique_ptr<ChainResources> chain;
+    Event chain_ev[2 * CHAIN_MAX + 1];
     Event pev[4];
 
     ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
@@ -1201,6 +1205,44 @@ int gpt_pullback_policy(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, c
     CALLCHK(hipStreamSynchronize(s));
     return GPT_OK;
 }
+
+// ---- what gpt_pullback_chain (gpt_chain_host.hip) needs of a handle: gpt_chain.h
+extern "C++" {
+namespace gpt {
+
+int chain_handle_view(gpt_handle* h, const std::string& who, const std::string& role, bool is_map, ChainHandleView* v) {
+    if (int rc = pullback_model_check(h, who, role.c_str(), is_map)) return rc;
+    v->device = h->device; v->D = h->p.D; v->stream = h->stream;
+    v->m.N = h->p.N; v->m.ktype = h->p.ktype; v->m.lnc = h->p.lnc;
+    for (int d = 0; d < 3; ++d) v->m.inv_ls[d] = h->p.inv_ls[d];
+    v->m.Xs = static_cast<const double*>(h->dXs()); v->m.A4 = static_cast<const double*>(h->dA4());
+    return GPT_OK;
+}
+
+static int chain_events(gpt_handle* h) {
+    for (Event& e : h->chain_ev)
+        if (!e) CALLCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
+    ChainResources& r = *h->chain;
+    for (int k = 0; k < CHAIN_MAX; ++k) { r.ev_in[k] = h->chain_ev[2 * k]; r.ev_var[k] = h->chain_ev[2 * k + 1]; }
+    r.ev_mid = h->chain_ev[2 * CHAIN_MAX];
+    return GPT_OK;
+}
+
+ChainResources* chain_resources(gpt_handle* h) {
+    if (set_device(h)) return nullptr;
+    if (!h->chain) h->chain = std::make_unique<ChainResources>();
+    return chain_events(h) ? nullptr : h->chain.get();
+}
+
+int chain_copy_stream(gpt_handle* h, hipStream_t* copy_stream, hipEvent_t (&ev_done)[2], hipEvent_t (&ev_copied)[2]) {
+    if (int rc = ensure_copy_stream(h)) return rc;
+    *copy_stream = h->copy_stream;
+    for (int b = 0; b < 2; ++b) { ev_done[b] = h->ev_done[b]; ev_copied[b] = h->ev_copied[b]; }
+    return GPT_OK;
+}
+
+}  // namespace gpt
+}  // extern "C++"
 
 // alpha as (N,O) fp64 host array: from the fp64 workspace when this handle ran the fit, else converted from the blob
 static int fetch_alpha(gpt_handle* h, std::vector<double>& a4) {

@@ -1,0 +1,348 @@
+// The transported policy through a chain of transports for gfx950 (MI355X): the reference's obstacle example
+// (example/2D/surface_generalization_with_obstacle.py:142-200) moves a demonstration twice, from the old surface to the new one
+// and then round an obstacle, Phi = Phi_1 o Phi_0, and refits a GP on the result; here the source dynamics f is pulled back
+// through all K maps in one launch:  x = Phi^-1(y),  v(y) = J_Phi(x) f(x).
+//
+//  k_chain_velocity : one wave owns one query from start to end, four waves per workgroup, one launch, one barrier at entry for
+//               the exp table.  With a guess x0 of the source-space preimage, a mean-only forward pass (pb_mean) through stages
+//               0 .. K-2 gives every stage its start.  Then the stages are solved from the last to the first, each with the
+//               damped Newton iteration of k_pullback_velocity (pb_newton, gpt_pullback_wave.h) on z + psi_k(z) = y_k and the
+//               affine inverse x_k = gamma_k^-1(z_k), which is the y of the stage before; a stage that does not converge hands on
+//               the point it reached.  f = the dynamics mean at x_0 and vel = B_{K-1} ... B_1 (A_0 (R_jac,0 f)), B_k = A_k
+//               R_jac,k: the product of the outer stages is kept in registers as the sweep goes, the innermost stage is applied to
+//               f in the association of k_pullback_velocity, so that K = 1 is that kernel's arithmetic.  Each stage's kernel
+//               type and the dynamics' are wave-uniform run-time choices (scalar branches): the kernel is templated on D only.
+//               Per-stage values are stored by lane 0 as each stage finishes; nothing is indexed by the run-time stage number
+//               but the kernel arguments.  A query's sums run in a fixed order: its result does not depend on M or on the
+//               queries around it.
+//  k_chain_variance : one thread per query, plain fp64 FMA: the first-order propagation of each stage's Jacobian variance and
+//               of the dynamics variance through the stages after it.
+#include "gpt_chain.h"
+#include "gpt_dispatch.h"
+#include "gpt_newton.h"
+#include "gpt_pullback_wave.h"
+
+namespace gpt {
+
+// f = mean of the model at x; the kernel type is the same in every wave of the launch
+template <int D>
+__device__ __forceinline__ void ch_mean(const ChainModel& m, const double* __restrict__ Tt, const int lane, const double (&x)[D],
+                                        double (&f)[D]) {
+    double qsc[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) qsc[d] = m.inv_ls[d] * 0.70710678118654752440;
+    switch (m.ktype) {
+        case KT_MATERN12: pb_mean<KT_MATERN12, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        case KT_MATERN32: pb_mean<KT_MATERN32, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        case KT_MATERN52: pb_mean<KT_MATERN52, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        default: pb_mean<KT_RBF, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f);
+    }
+}
+
+// g = gamma(x) = scale R (x - c_src) + c_dst, the arithmetic of k_affine (gpt_transport.hip)
+template <int D>
+__device__ __forceinline__ void ch_affine(const ChainStage& S, const double (&x)[D], double (&g)[D]) {
+    double xc[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) xc[d] = x[d] - S.c_src[d];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double r = S.R[i * D] * xc[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) r = fma(S.R[i * D + d], xc[d], r);
+        g[i] = fma(S.scale, r, S.c_dst[i]);
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
+    __shared__ double Tt[256];
+    Tt[threadIdx.x] = g_exp2_table[threadIdx.x];
+    __syncthreads();                                  // the only barrier: from here on the four waves of a workgroup are on their own
+    const int lane = threadIdx.x & 63;
+    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (m >= a.M) return;
+    const int K = a.K;
+    double y[D], x[D], Q[D][D], A[D][D];
+    double start[CHAIN_MAX][D];                       // only ever indexed by unrolled constants: registers
+#pragma unroll
+    for (int k = 0; k < CHAIN_MAX; ++k)
+#pragma unroll
+        for (int d = 0; d < D; ++d) start[k][d] = 0.0;
+    if (a.X0) {                                       // g_0 = x0; stage k starts at gamma_k(g_k); g_{k+1} = gamma_k(g_k) + mean_k(gamma_k(g_k))
+        double g[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) g[d] = a.X0[m * D + d];
+        for (int k = 0; k < K; ++k) {
+            double z0[D];
+            ch_affine<D>(a.st[k], g, z0);
+#pragma unroll
+            for (int j = 0; j < CHAIN_MAX; ++j)
+                if (j == k) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) start[j][d] = z0[d];
+                }
+            if (k + 1 < K) {
+                double mu[D];
+                ch_mean<D>(a.st[k].m, Tt, lane, z0, mu);
+#pragma unroll
+                for (int d = 0; d < D; ++d) g[d] = z0[d] + mu[d];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        y[i] = a.Y[m * D + i];
+        x[i] = y[i];
+#pragma unroll
+        for (int d = 0; d < D; ++d) Q[i][d] = i == d ? 1.0 : 0.0;
+    }
+    int first = INV_CONVERGED;
+    for (int k = K - 1; k >= 0; --k) {
+        const ChainStage& S = a.st[k];
+        double R[D][D], qsc[D], jsc[D], z[D], rho;
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+#pragma unroll
+            for (int d = 0; d < D; ++d) R[i][d] = S.R[i * D + d];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            qsc[d] = S.m.inv_ls[d] * 0.70710678118654752440;
+            jsc[d] = S.m.inv_ls[d] * 1.41421356237309504880;
+            z[d] = y[d];
+        }
+        if (a.X0) {
+#pragma unroll
+            for (int j = 0; j < CHAIN_MAX; ++j)
+                if (j == k) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) z[d] = start[j][d];
+                }
+        }
+        int passes, status;
+        switch (S.m.ktype) {                          // (no Matern 1/2: the API refuses such a stage before a launch is reached)
+            case KT_MATERN32:
+                status = pb_newton<KT_MATERN32, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+                break;
+            case KT_MATERN52:
+                status = pb_newton<KT_MATERN52, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+                break;
+            default:
+                status = pb_newton<KT_RBF, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+        }
+        if (first == INV_CONVERGED) first = status;
+        // x = (z - c_dst) R / scale + c_src, the arithmetic of k_pullback_velocity
+        double zc[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) zc[d] = z[d] - S.c_dst[d];
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            double r = zc[0] * R[0][i];
+#pragma unroll
+            for (int d = 1; d < D; ++d) r = fma(zc[d], R[d][i], r);
+            x[i] = r / S.scale + S.c_src[i];
+        }
+        if (lane == 0) {
+            const int64_t row = (int64_t)k * a.M + m;
+#pragma unroll
+            for (int o = 0; o < D; ++o) {
+                if (a.stage_z) a.stage_z[row * D + o] = z[o];
+                if (a.stage_x) a.stage_x[row * D + o] = x[o];
+                if (a.stage_A) {
+#pragma unroll
+                    for (int d = 0; d < D; ++d) a.stage_A[(row * D + o) * D + d] = A[o][d];
+                }
+            }
+            if (a.stage_status) a.stage_status[row] = status;
+            if (a.stage_passes) a.stage_passes[row] = passes;
+            if (a.stage_residual) a.stage_residual[row] = rho;
+            if (a.stage_det) a.stage_det[row] = inv_det<D>(A);
+        }
+        if (k > 0) {                                  // Q <- Q (A_k R_jac,k); the innermost stage is applied to f below
+            double B[D][D], Qn[D][D];
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+                    double b = A[o][0] * S.R_jac[e];
+#pragma unroll
+                    for (int d = 1; d < D; ++d) b = fma(A[o][d], S.R_jac[d * D + e], b);
+                    B[o][e] = b;
+                }
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+                    double q = Q[o][0] * B[0][e];
+#pragma unroll
+                    for (int d = 1; d < D; ++d) q = fma(Q[o][d], B[d][e], q);
+                    Qn[o][e] = q;
+                }
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) Q[o][e] = Qn[o][e];
+#pragma unroll
+            for (int d = 0; d < D; ++d) y[d] = x[d];
+        }
+    }
+    double f[D], g[D], h[D];
+    ch_mean<D>(a.dyn, Tt, lane, x, f);
+    if (lane != 0) return;
+    // vel = Q (A_0 (R_jac,0 f)): A and x are stage 0's here
+    const double* Rj = a.st[0].R_jac;
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        double r = Rj[i * D] * f[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) r = fma(Rj[i * D + d], f[d], r);
+        g[i] = r;
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+        double r = A[o][0] * g[0];
+#pragma unroll
+        for (int d = 1; d < D; ++d) r = fma(A[o][d], g[d], r);
+        h[o] = r;
+    }
+#pragma unroll
+    for (int o = 0; o < D; ++o) {
+        double r = h[o];
+        if (K > 1) {                                  // (Q = I otherwise: nothing to multiply, and no 0 * inf of a point that ran away)
+            r = Q[o][0] * h[0];
+#pragma unroll
+            for (int d = 1; d < D; ++d) r = fma(Q[o][d], h[d], r);
+        }
+        a.vel[m * D + o] = r;
+        if (a.x) a.x[m * D + o] = x[o];
+        if (a.f) a.f[m * D + o] = f[o];
+    }
+    a.status[m] = first;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_chain_variance(ChainArgs a) {
+    const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= a.M) return;
+    const int K = a.K;
+    // forward: v_{-1} = f, g_k = R_jac,k v_{k-1}, sigma_k^2 = sum_d Jvar_k[d] g_k[d]^2, v_k = A_k g_k
+    double sig[CHAIN_MAX];                            // (unrolled: constants index it)
+    if (a.vel_var_map) {
+        double v[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) v[i] = a.f[m * D + i];
+#pragma unroll
+        for (int k = 0; k < CHAIN_MAX; ++k) {
+            sig[k] = 0.0;
+            if (k < K) {
+                const double* Rj = a.st[k].R_jac;
+                const int64_t row = (int64_t)k * a.M + m;
+                double g[D], s = 0.0;
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    double r = Rj[i * D] * v[0];
+#pragma unroll
+                    for (int d = 1; d < D; ++d) r = fma(Rj[i * D + d], v[d], r);
+                    g[i] = r;
+                    s = fma(a.stage_Jvar[row * D + i], r * r, s);
+                }
+                sig[k] = s;
+                if (k + 1 < K) {
+#pragma unroll
+                    for (int o = 0; o < D; ++o) {
+                        double r = a.stage_A[(row * D + o) * D] * g[0];
+#pragma unroll
+                        for (int d = 1; d < D; ++d) r = fma(a.stage_A[(row * D + o) * D + d], g[d], r);
+                        v[o] = r;
+                    }
+                }
+            }
+        }
+    }
+    // backward: Q = B_{K-1} ... B_{k+1} when stage k is reached, the whole product at the end
+    double Q[D][D], acc[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        acc[i] = 0.0;
+#pragma unroll
+        for (int d = 0; d < D; ++d) Q[i][d] = i == d ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = CHAIN_MAX - 1; k >= 0; --k) {
+        if (k < K) {
+            if (a.vel_var_map) {
+#pragma unroll
+                for (int i = 0; i < D; ++i) {
+                    double q2 = Q[i][0] * Q[i][0];
+#pragma unroll
+                    for (int d = 1; d < D; ++d) q2 = fma(Q[i][d], Q[i][d], q2);
+                    acc[i] = fma(sig[k], q2, acc[i]);
+                }
+            }
+            if (k == 0 && !a.vel_var_dyn) break;
+            const double* Rj = a.st[k].R_jac;
+            const int64_t row = (int64_t)k * a.M + m;
+            double B[D][D], Qn[D][D];
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+                    double b = a.stage_A[(row * D + o) * D] * Rj[e];           // (A_k R_jac,k)[o][e]
+#pragma unroll
+                    for (int d = 1; d < D; ++d) b = fma(a.stage_A[(row * D + o) * D + d], Rj[d * D + e], b);
+                    B[o][e] = b;
+                }
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+                    double q = Q[o][0] * B[0][e];
+#pragma unroll
+                    for (int d = 1; d < D; ++d) q = fma(Q[o][d], B[d][e], q);
+                    Qn[o][e] = q;
+                }
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+#pragma unroll
+                for (int e = 0; e < D; ++e) Q[o][e] = Qn[o][e];
+        }
+    }
+    if (a.vel_var_map) {
+#pragma unroll
+        for (int i = 0; i < D; ++i) a.vel_var_map[m * D + i] = acc[i];
+    }
+    if (a.vel_var_dyn) {
+        const double sd = sqrt(a.var_dyn[m]) - a.std_offset, s2 = sd * sd;
+#pragma unroll
+        for (int o = 0; o < D; ++o) {
+            double sum = 0.0;
+#pragma unroll
+            for (int e = 0; e < D; ++e) sum = fma(Q[o][e], Q[o][e], sum);
+            a.vel_var_dyn[m * D + o] = s2 * sum;
+        }
+    }
+}
+
+void launch_chain_velocity(hipStream_t s, int D, const ChainArgs& a) {
+    if (a.M <= 0) return;
+    const dim3 grid((unsigned)((a.M + 3) / 4));           // one wave per query, four per workgroup (M < 2^31: the grid fits)
+    auto go = [&](auto d) { hipLaunchKernelGGL((k_chain_velocity<decltype(d)::value>), grid, dim3(256), 0, s, a); };
+    switch (D) {
+        case 1: go(Int<1>{}); break;
+        case 2: go(Int<2>{}); break;
+        default: go(Int<3>{});
+    }
+}
+
+void launch_chain_variance(hipStream_t s, int D, const ChainArgs& a) {
+    if (a.M <= 0 || !(a.vel_var_map || a.vel_var_dyn)) return;
+    const dim3 grid((unsigned)((a.M + 255) / 256));
+    auto go = [&](auto d) { hipLaunchKernelGGL((k_chain_variance<decltype(d)::value>), grid, dim3(256), 0, s, a); };
+    switch (D) {
+        case 1: go(Int<1>{}); break;
+        case 2: go(Int<2>{}); break;
+        default: go(Int<3>{});
+    }
+}
+
+}  // namespace gpt

@@ -1,0 +1,273 @@
+// gpt_pullback_chain / gpt_pullback_chain_dev (include/gpt_hip.h): argument checks, the scratch between the launches, the
+// hand-over between the handles' streams, and the chunked staging of the host call.  Host code only (the kernels: gpt_chain.hip,
+// reached through the launchers of gpt_chain.h; the handles: through the three accessors gpt_api.hip defines), so it also
+// compiles under g++ against host_stub/ and runs under the sanitizers (make host-oneshot-asan).
+#include "gpt_chain.h"
+#include "gpt_call.h"
+
+#include <algorithm>
+#include <cstring>
+
+using namespace gpt;
+
+namespace {
+
+constexpr int64_t HOST_CHUNK = 1 << 17;  // queries per chunk of the host entry (two chunks in flight), as gpt_pullback_policy's
+
+// the arguments of both entry points (host or device pointers alike), arrays indexed by CH_*
+struct ChainCall {
+    int K = 0;
+    gpt_handle* h[CHAIN_MAX] = {};
+    gpt_handle* h_dyn = nullptr;
+    ChainHandleView v[CHAIN_MAX], v_dyn;
+    const double *R[CHAIN_MAX] = {}, *c_src[CHAIN_MAX] = {}, *c_dst[CHAIN_MAX] = {}, *R_jac[CHAIN_MAX] = {};
+    double scale[CHAIN_MAX] = {};
+    int64_t M = 0;
+    double rtol = 0.0, std_offset = 0.0;
+    int max_passes = 0;
+    void* arr[CH_COUNT] = {};            // (the inputs CH_Y, CH_X0 are only read)
+};
+
+// bytes per query (and per stage, from CH_FIRST_STAGE on), by CH_*
+size_t row_bytes(int which, size_t D) {
+    switch (which) {
+        case CH_STATUS: case CH_STAGE_STATUS: case CH_STAGE_PASSES: return sizeof(int);
+        case CH_VAR_DYN: case CH_STAGE_MAP_VAR: case CH_STAGE_RES: case CH_STAGE_DET: return sizeof(double);
+        case CH_STAGE_A: return D * D * sizeof(double);
+        default: return D * sizeof(double);
+    }
+}
+
+// what both entry points refuse, in the order of the header's list; fills the views
+int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
+    const std::string w(who);
+    if (c.K < 1 || c.K > CHAIN_MAX)
+        return fail(GPT_E_ARG, w + ": K must be 1 .. " + std::to_string(CHAIN_MAX) + " (GPT_CHAIN_MAX) stages, got " + std::to_string(c.K));
+    if (!stages) return fail(GPT_E_ARG, w + ": stages must not be NULL");
+    for (int k = 0; k < c.K; ++k) {
+        const std::string role = "stage " + std::to_string(k) + " map";
+        c.h[k] = stages[k].h; c.R[k] = stages[k].R; c.c_src[k] = stages[k].c_src; c.c_dst[k] = stages[k].c_dst; c.R_jac[k] = stages[k].R_jac;
+        c.scale[k] = stages[k].scale;
+        if (!c.h[k]) return fail(GPT_E_ARG, w + ": NULL handle (" + role + ")");
+        if (!c.R[k] || !c.c_src[k] || !c.c_dst[k] || !c.R_jac[k])
+            return fail(GPT_E_ARG, w + ": R, c_src, c_dst and R_jac must not be NULL (stage " + std::to_string(k) + ")");
+    }
+    if (!c.h_dyn) return fail(GPT_E_ARG, w + ": NULL handle (dynamics)");
+    for (int k = 0; k < c.K; ++k) {
+        for (int j = 0; j < k; ++j)
+            if (c.h[j] == c.h[k])
+                return fail(GPT_E_ARG, w + ": stages " + std::to_string(j) + " and " + std::to_string(k) + " are the same handle; every stage is a model of its own");
+        if (c.h[k] == c.h_dyn)
+            return fail(GPT_E_ARG, w + ": stage " + std::to_string(k) + " and h_dyn are the same handle; the maps and the dynamics are separate models");
+    }
+    for (int k = 0; k < c.K; ++k)
+        if (int rc = chain_handle_view(c.h[k], w, "stage " + std::to_string(k) + " map", true, &c.v[k])) return rc;
+    if (int rc = chain_handle_view(c.h_dyn, w, "dynamics", false, &c.v_dyn)) return rc;
+    const ChainHandleView& last = c.v[c.K - 1];
+    for (int k = 0; k < c.K; ++k) {
+        const ChainHandleView& v = k + 1 < c.K ? c.v[k] : c.v_dyn;
+        const std::string name = k + 1 < c.K ? "stage " + std::to_string(k) : std::string("the dynamics");
+        if (v.device != last.device)
+            return fail(GPT_E_ARG, w + ": the models live on different devices (stage " + std::to_string(c.K - 1) + ": " + std::to_string(last.device) +
+                                       ", " + name + ": " + std::to_string(v.device) + "); gpt_factor_copy brings one to the other's");
+        if (v.D != last.D)
+            return fail(GPT_E_ARG, w + ": every map and the dynamics must share one space (stage " + std::to_string(c.K - 1) + ": D = " +
+                                       std::to_string(last.D) + ", " + name + ": D = " + std::to_string(v.D) + ")");
+    }
+    if (!(c.rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
+    if (c.max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
+    if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
+    if (c.M > 0 && (!c.arr[CH_Y] || !c.arr[CH_VEL] || !c.arr[CH_STATUS])) return fail(GPT_E_ARG, w + ": y, vel and status must not be NULL");
+    return GPT_OK;
+}
+
+// every pointer of `c` in device memory; enqueues the whole call, waits for nothing
+int chain_dev(const ChainCall& c) {
+    const int K = c.K;
+    gpt_handle* const owner = c.h[K - 1];
+    ChainResources* const res = chain_resources(owner);
+    if (!res) return GPT_E_HIP;
+    hipStream_t s = c.v[K - 1].stream;
+    const int64_t M = c.M;
+    const size_t D = c.v[K - 1].D;
+    void* const* u = c.arr;
+    // which intermediate quantities the outputs asked for consume
+    const bool need_var_dyn = u[CH_VAR_DYN] || u[CH_VVAR_DYN];
+    const bool need_jvar = u[CH_STAGE_JVAR] || u[CH_VVAR_MAP];
+    const bool need_map = u[CH_STAGE_MAP_VAR] || need_jvar;         // map_var and Jvar together: one pass of the 4-column launch
+    const bool epilogue = u[CH_VVAR_MAP] || u[CH_VVAR_DYN];
+    const bool need_A = u[CH_VVAR_DYN] || (u[CH_VVAR_MAP] && K > 1);
+    // each lives in the caller's array when there is one, else in the owner's scratch
+    const struct { int which; bool need; size_t per; } mid[CH_SCRATCH] = {
+        {CH_X, need_var_dyn, D}, {CH_F, epilogue, D}, {CH_VAR_DYN, need_var_dyn, 1},
+        {CH_STAGE_Z, need_map, K * D}, {CH_STAGE_A, need_A, K * D * D}, {CH_STAGE_JVAR, need_jvar, K * D}};
+    double* at[CH_SCRATCH];
+    for (int k = 0; k < CH_SCRATCH; ++k) {
+        at[k] = static_cast<double*>(u[mid[k].which]);
+        if (mid[k].need && !at[k]) {
+            CALLCHK(reserve(res->scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
+            at[k] = res->scratch[k];
+        }
+    }
+    ChainArgs a{};
+    a.M = M; a.K = K;
+    for (int k = 0; k < K; ++k) {
+        a.st[k].m = c.v[k].m;
+        a.st[k].R = c.R[k]; a.st[k].c_src = c.c_src[k]; a.st[k].c_dst = c.c_dst[k]; a.st[k].R_jac = c.R_jac[k]; a.st[k].scale = c.scale[k];
+    }
+    a.dyn = c.v_dyn.m;
+    a.Y = static_cast<const double*>(u[CH_Y]); a.X0 = static_cast<const double*>(u[CH_X0]);
+    a.rtol = c.rtol; a.max_passes = c.max_passes; a.std_offset = c.std_offset;
+    a.x = at[0]; a.f = at[1]; a.vel = static_cast<double*>(u[CH_VEL]); a.status = static_cast<int*>(u[CH_STATUS]);
+    a.stage_x = static_cast<double*>(u[CH_STAGE_X]); a.stage_z = at[3]; a.stage_A = at[4];
+    a.stage_status = static_cast<int*>(u[CH_STAGE_STATUS]); a.stage_passes = static_cast<int*>(u[CH_STAGE_PASSES]);
+    a.stage_residual = static_cast<double*>(u[CH_STAGE_RES]); a.stage_det = static_cast<double*>(u[CH_STAGE_DET]);
+    a.var_dyn = at[2]; a.stage_Jvar = at[5];
+    a.vel_var_map = static_cast<double*>(u[CH_VVAR_MAP]); a.vel_var_dyn = static_cast<double*>(u[CH_VVAR_DYN]);
+    // the other handles, stages 0 .. K-2 and the dynamics: what their streams have enqueued so far (a fit, a gpt_factor_commit)
+    // comes first
+    hipStream_t other[CHAIN_MAX];
+    for (int j = 0; j < K; ++j) other[j] = j + 1 < K ? c.v[j].stream : c.v_dyn.stream;
+    for (int j = 0; j < K; ++j) {
+        CALLCHK(hipEventRecord(res->ev_in[j], other[j]));
+        CALLCHK(hipStreamWaitEvent(s, res->ev_in[j], 0));
+    }
+    launch_chain_velocity(s, (int)D, a);
+    // their streams go on once x and the z_k are there and their models have been read
+    CALLCHK(hipEventRecord(res->ev_mid, s));
+    for (int j = 0; j < K; ++j) CALLCHK(hipStreamWaitEvent(other[j], res->ev_mid, 0));
+    // each variance launch on its own handle's stream (the variance workspace belongs to the handle), one after the other: every
+    // one of them is sized to fill the device, and two of them side by side take longer than one after the other
+    hipEvent_t prev = nullptr;
+    if (need_var_dyn) {
+        if (int rc = gpt_predict_all_dev(c.h_dyn, a.x, M, nullptr, at[2], nullptr, nullptr, nullptr)) return rc;
+        CALLCHK(hipEventRecord(res->ev_var[K - 1], other[K - 1]));
+        prev = res->ev_var[K - 1];
+    }
+    if (need_map)
+        for (int k = 0; k < K; ++k) {
+            hipStream_t sk = k + 1 < K ? other[k] : s;
+            if (prev) CALLCHK(hipStreamWaitEvent(sk, prev, 0));
+            double* const mv = static_cast<double*>(u[CH_STAGE_MAP_VAR]);
+            if (int rc = gpt_predict_all_dev(c.h[k], a.stage_z + (size_t)k * M * D, M, nullptr, mv ? mv + (size_t)k * M : nullptr, nullptr,
+                                             need_jvar ? at[5] + (size_t)k * M * D : nullptr, nullptr))
+                return rc;
+            if (k + 1 < K) {
+                CALLCHK(hipEventRecord(res->ev_var[k], sk));
+                prev = res->ev_var[k];
+            }
+        }
+    else if (prev) CALLCHK(hipStreamWaitEvent(s, prev, 0));
+    launch_chain_variance(s, (int)D, a);
+    CALLCHK(hipGetLastError());
+    return GPT_OK;
+}
+
+}  // namespace
+
+#define CHAIN_CALL(c)                                                                                                               \
+    ChainCall c;                                                                                                                    \
+    c.K = K; c.h_dyn = h_dyn; c.M = M; c.rtol = rtol; c.max_passes = max_passes; c.std_offset = std_offset;                         \
+    {                                                                                                                               \
+        void* const all[CH_COUNT] = {const_cast<double*>(y), const_cast<double*>(x0), x, vel, f, status, var_dyn, vel_var_map,      \
+                                     vel_var_dyn, stage_x, stage_z, stage_A, stage_Jvar, stage_map_var, stage_status, stage_passes, \
+                                     stage_residual, stage_det};                                                                    \
+        for (int k = 0; k < CH_COUNT; ++k) c.arr[k] = all[k];                                                                       \
+    }
+
+extern "C" int gpt_pullback_chain_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M,
+                                      double rtol, int max_passes, double std_offset, double* x, double* vel, double* f, int* status,
+                                      double* var_dyn, double* vel_var_map, double* vel_var_dyn, double* stage_x, double* stage_z,
+                                      double* stage_A, double* stage_Jvar, double* stage_map_var, int* stage_status, int* stage_passes,
+                                      double* stage_residual, double* stage_det) {
+    CHAIN_CALL(c);
+    if (int rc = chain_check("gpt_pullback_chain_dev", stages, c)) return rc;
+    if (M == 0) return GPT_OK;
+    return chain_dev(c);
+}
+
+extern "C" int gpt_pullback_chain(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M,
+                                  double rtol, int max_passes, double std_offset, double* x, double* vel, double* f, int* status,
+                                  double* var_dyn, double* vel_var_map, double* vel_var_dyn, double* stage_x, double* stage_z,
+                                  double* stage_A, double* stage_Jvar, double* stage_map_var, int* stage_status, int* stage_passes,
+                                  double* stage_residual, double* stage_det) {
+    CHAIN_CALL(c);
+    const std::string w = "gpt_pullback_chain";
+    if (int rc = chain_check(w.c_str(), stages, c)) return rc;
+    if (M == 0) return GPT_OK;
+    const size_t D = c.v[K - 1].D;
+    bool finite = all_finite(y, (size_t)M * D) && (!x0 || all_finite(x0, (size_t)M * D)) && std::isfinite(rtol) && std::isfinite(std_offset);
+    for (int k = 0; k < K && finite; ++k)
+        finite = all_finite(c.R[k], D * D) && all_finite(c.R_jac[k], D * D) && all_finite(c.c_src[k], D) && all_finite(c.c_dst[k], D) &&
+                 std::isfinite(c.scale[k]);
+    if (!finite) return fail(GPT_E_ARG, w + ": y / x0 / the affine parts / rtol / std_offset contain NaN or infinity");
+    gpt_handle* const owner = c.h[K - 1];
+    ChainResources* const res = chain_resources(owner);
+    if (!res) return GPT_E_HIP;
+    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
+    const int64_t nchunks = (M + cap - 1) / cap;
+    const bool single = nchunks == 1;
+    hipStream_t s = c.v[K - 1].stream, cs = s;
+    hipEvent_t ev_done[2] = {}, ev_copied[2] = {};
+    if (!single) { if (int rc = chain_copy_stream(owner, &cs, ev_done, ev_copied)) return rc; }
+    // only what the caller asked for is staged and crosses the bus; the rest of what a later launch reads stays in the owner's scratch
+    size_t per[CH_COUNT];
+    for (int k = 0; k < CH_COUNT; ++k) per[k] = row_bytes(k, D);
+    for (int b = 0; b < (single ? 1 : 2); ++b)
+        for (int k = 0; k < CH_COUNT; ++k)
+            if (c.arr[k]) CALLCHK(reserve(res->st[b].buf[k], (size_t)cap * per[k] * (k >= CH_FIRST_STAGE ? K : 1), s, single ? nullptr : cs));
+    CALLCHK(reserve(res->affine, sizeof res->affine_host, s));
+    double* ah = res->affine_host;
+    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
+    std::fill(ah, ah + CHAIN_MAX * CH_AFFINE_DOUBLES, 0.0);
+    for (int k = 0; k < K; ++k) {
+        double* q = ah + k * CH_AFFINE_DOUBLES;
+        memcpy(q, c.R[k], D * D * sizeof(double)); memcpy(q + 9, c.R_jac[k], D * D * sizeof(double));
+        memcpy(q + 18, c.c_src[k], D * sizeof(double)); memcpy(q + 21, c.c_dst[k], D * sizeof(double));
+    }
+    CALLCHK(hipMemcpyAsync(res->affine, ah, sizeof res->affine_host, hipMemcpyHostToDevice, s));
+    // chunk i computes in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_pullback_policy)
+    auto enqueue = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        ChainResources::Staging& t = res->st[b];
+        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, ev_copied[b], 0));              // set b is free again
+        ChainCall d = c;
+        d.M = m;
+        for (int k = 0; k < K; ++k) {
+            const double* q = res->affine + k * CH_AFFINE_DOUBLES;
+            d.R[k] = q; d.R_jac[k] = q + 9; d.c_src[k] = q + 18; d.c_dst[k] = q + 21;
+        }
+        for (int k = 0; k < CH_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
+        for (int k = 0; k < CH_INPUTS; ++k)
+            if (c.arr[k])
+                CALLCHK(hipMemcpyAsync(t.buf[k], static_cast<const unsigned char*>(c.arr[k]) + (size_t)off * per[k], (size_t)m * per[k],
+                                       hipMemcpyHostToDevice, s));
+        if (int rc = chain_dev(d)) return rc;
+        if (!single) CALLCHK(hipEventRecord(ev_done[b], s));
+        return GPT_OK;
+    };
+    auto copy_out = [&](int64_t i) -> int {
+        const int b = (int)(i & 1);
+        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
+        const ChainResources::Staging& t = res->st[b];
+        if (!single) CALLCHK(hipStreamWaitEvent(cs, ev_done[b], 0));
+        for (int k = CH_INPUTS; k < CH_COUNT; ++k) {
+            if (!c.arr[k]) continue;
+            // a per-stage array: stage j's rows start at j * M rows on the host and at j * m rows in the chunk's image
+            for (int j = 0; j < (k >= CH_FIRST_STAGE ? K : 1); ++j)
+                CALLCHK(hipMemcpyAsync(static_cast<unsigned char*>(c.arr[k]) + ((size_t)j * M + off) * per[k], t.buf[k] + (size_t)j * m * per[k],
+                                       (size_t)m * per[k], hipMemcpyDeviceToHost, cs));
+        }
+        if (!single) CALLCHK(hipEventRecord(ev_copied[b], cs));
+        return GPT_OK;
+    };
+    if (int rc = enqueue(0)) return rc;
+    for (int64_t i = 0; i < nchunks; ++i) {
+        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
+        if (int rc = copy_out(i)) return rc;
+    }
+    if (!single) CALLCHK(hipStreamSynchronize(cs));
+    CALLCHK(hipStreamSynchronize(s));
+    return GPT_OK;
+}

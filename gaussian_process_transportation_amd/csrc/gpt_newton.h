@@ -1,5 +1,6 @@
 // Damped Newton on  z + mu(z) = y  inside one wave (device units only): the pass over the sources and the D x D solve, shared
-// by k_inverse_newton (gpt_inverse.hip) and k_pullback_velocity (gpt_pullback.hip), each with the iteration around them.  Every lane
+// by k_inverse_newton (gpt_inverse.hip) and, through gpt_pullback_wave.h, k_pullback_velocity (gpt_pullback.hip) and
+// k_chain_velocity (gpt_chain.hip), each with the iteration around them.  Every lane
 // of the wave runs the same arithmetic on the same bits; what differs between lanes is the stride of sources a lane sums
 // before the xor butterfly.  mu: the posterior mean of a committed fp64 model with D == O <= 3.
 #pragma once

@@ -1,5 +1,5 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
-// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map, gpt_transport_policy and gpt_pullback_policy (gpt_api.hip)
+// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map, gpt_transport_policy and gpt_pullback_policy (gpt_api.hip), gpt_pullback_chain (gpt_chain_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -555,6 +555,121 @@ void pullback_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- chain of pull-backs (gpt_chain_host.hip): K + 1 handles, stage-major (K, M, ...) arrays through the last stage's two staging sets
+void chain_cases() {
+    const int64_t N = 5, Nd = 7, HOST_CHUNK = 1 << 17;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h[GPT_CHAIN_MAX + 1] = {}, *hd = nullptr, *bare = nullptr;
+    begin("gpt_pullback_chain setup");
+    for (auto& q : h) CHECK(gpt_create(&q, 0) == GPT_OK);
+    CHECK(gpt_create(&hd, 0) == GPT_OK && gpt_create(&bare, 0) == GPT_OK);
+    for (auto& q : h) CHECK(gpt_fit(q, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    // bit k of `mask`: optional array k is passed (X0 is the one optional input); the int arrays have width 0 here and live apart
+    enum { X0, XO, F, VAR_DYN, VVAR_MAP, VVAR_DYN, ST_X, ST_Z, ST_A, ST_JVAR, ST_MAP_VAR, ST_STATUS, ST_PASSES, ST_RES, ST_DET, N_OPT };
+    const size_t width[N_OPT] = {3, 3, 3, 1, 3, 3, 3, 3, 9, 3, 1, 0, 0, 1, 1};
+    struct Arrays {
+        D y, vel;
+        Arr<int> status, st_status, st_passes;
+        std::vector<D> opt;
+        Arrays(int64_t M, int K, const size_t* w)
+            : y(ramp(M * 3)), vel(M * 3, SENT), status(M, ISENT), st_status((size_t)K * M, ISENT), st_passes((size_t)K * M, ISENT) {
+            for (int k = 0; k < N_OPT; ++k) opt.push_back(k == X0 ? ramp(M * w[k]) : D((k >= ST_X ? (size_t)K : 1) * M * w[k], SENT));
+        }
+    };
+    auto stages_of = [&](int K) {
+        std::vector<gpt_chain_stage> st(K);
+        for (int k = 0; k < K; ++k) st[k] = gpt_chain_stage{h[k], R.p, c_src.p, c_dst.p, R.p, 1.0 + 0.25 * k};
+        return st;
+    };
+    auto call = [&](const gpt_chain_stage* st, int K, gpt_handle* hdyn, Arrays& a, int64_t M, int mask, const double* y, double* vel, int* status,
+                    double rtol = 1e-10, int max_passes = 50) {
+        double* p[N_OPT];
+        for (int k = 0; k < N_OPT; ++k) p[k] = (mask >> k & 1) ? a.opt[k].p : nullptr;
+        return gpt_pullback_chain(st, K, hdyn, y, p[X0], M, rtol, max_passes, 0.1, p[XO], vel, p[F], status, p[VAR_DYN], p[VVAR_MAP], p[VVAR_DYN],
+                                  p[ST_X], p[ST_Z], p[ST_A], p[ST_JVAR], p[ST_MAP_VAR], (mask >> ST_STATUS & 1) ? a.st_status.p : nullptr,
+                                  (mask >> ST_PASSES & 1) ? a.st_passes.p : nullptr, p[ST_RES], p[ST_DET]);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.vel.all(SENT) && a.status.all(ISENT) && a.st_status.all(ISENT) && a.st_passes.all(ISENT));
+        for (int k = 1; k < N_OPT; ++k) CHECK(a.opt[k].all(SENT));
+    };
+    const int ALL = (1 << N_OPT) - 1;
+    {
+        Arrays a(1, 2, width);
+        auto st = stages_of(2);
+        begin("gpt_pullback_chain refuses K = 0"); done_held(call(st.data(), 0, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses K = 5"); done_held(call(st.data(), GPT_CHAIN_MAX + 1, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses stages = NULL"); done_held(call(nullptr, 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses a NULL dynamics handle"); done_held(call(st.data(), 2, nullptr, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses a dynamics handle without a model"); done_held(call(st.data(), 2, bare, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_STATE);
+        auto bad = st; bad[0].h = nullptr;
+        begin("gpt_pullback_chain refuses a NULL stage handle"); done_held(call(bad.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        bad = st; bad[0].h = bare;
+        begin("gpt_pullback_chain refuses a stage handle without a model"); done_held(call(bad.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_STATE);
+        bad = st; bad[1].c_dst = nullptr;
+        begin("gpt_pullback_chain refuses a NULL affine pointer"); done_held(call(bad.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        bad = st; bad[1].h = st[0].h;
+        begin("gpt_pullback_chain refuses one stage handle twice"); done_held(call(bad.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses a stage handle as the dynamics"); done_held(call(st.data(), 2, st[0].h, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses y = NULL"); done_held(call(st.data(), 2, hd, a, 1, ALL, nullptr, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses vel = NULL"); done_held(call(st.data(), 2, hd, a, 1, ALL, a.y.p, nullptr, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses status = NULL"); done_held(call(st.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, nullptr), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses M = -1"); done_held(call(st.data(), 2, hd, a, -1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses rtol = NaN"); done_held(call(st.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p, std::nan("")), GPT_E_ARG);
+        begin("gpt_pullback_chain refuses max_passes = 0"); done_held(call(st.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p, 1e-10, 0), GPT_E_ARG);
+        D nan_y{0.5, std::nan(""), 0.5};
+        begin("gpt_pullback_chain refuses NaN in y"); done_held(call(st.data(), 2, hd, a, 1, ALL, nan_y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        bad = st; bad[1].scale = std::nan("");
+        begin("gpt_pullback_chain refuses a NaN scale"); done_held(call(bad.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        begin("gpt_pullback_chain M = 0 does nothing"); done_held(call(st.data(), 2, hd, a, 0, ALL, a.y.p, a.vel.p, a.status.p), GPT_OK);
+        untouched(a);
+    }
+    // every optional array on and off: none, all, each one alone, all but each one, at K = 1, 2, 4 (the owner of scratch and staging
+    // changes with K); then the staging arithmetic of the stage-major arrays around HOST_CHUNK
+    std::vector<int> masks{0, ALL};
+    for (int k = 0; k < N_OPT; ++k) { masks.push_back(1 << k); masks.push_back(ALL & ~(1 << k)); }
+    for (int K : {1, 2, GPT_CHAIN_MAX}) {
+        auto st = stages_of(K);
+        for (int64_t M : {(int64_t)1, (int64_t)3, HOST_CHUNK + 1, 2 * HOST_CHUNK + 3})       // growing; the last two walk both staging sets
+            for (int mask : masks) {
+                if (M > 3 && (K != 2 || (mask != ALL && mask != 0))) continue;
+                begin("gpt_pullback_chain K=" + std::to_string(K) + " M=" + std::to_string(M) + " optional=" + std::to_string(mask));
+                Arrays a(M, K, width);
+                const int rc = call(st.data(), K, hd, a, M, mask, a.y.p, a.vel.p, a.status.p);
+                CHECK(stub_live_objects >= held);                        // staging, scratch and events are kept and regrown, never dropped
+                held = stub_live_objects;
+                done_held(rc, GPT_OK);
+                CHECK(a.vel.all(0.0) && a.status.all(0));
+                CHECK(a.st_status.all(mask >> ST_STATUS & 1 ? 0 : ISENT) && a.st_passes.all(mask >> ST_PASSES & 1 ? 0 : ISENT));
+                for (int k = 1; k < N_OPT; ++k) CHECK(a.opt[k].all(mask >> k & 1 ? 0.0 : SENT));
+            }
+    }
+    {
+        begin("gpt_pullback_chain refuses models of different dimension");
+        D X2 = ramp(Nd * 2), Y2 = ramp(Nd * 2, 0.01, 0.01), ls2{0.5, 0.75};
+        CHECK(gpt_fit(hd, X2.p, Y2.p, Nd, 2, 2, ls2.p, 2, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        Arrays a(1, 2, width);
+        auto st = stages_of(2);
+        done_held(call(st.data(), 2, hd, a, 1, ALL, a.y.p, a.vel.p, a.status.p), GPT_E_ARG);
+        untouched(a);
+    }
+    begin("gpt_pullback_chain teardown");
+    for (auto& q : h) gpt_destroy(q);
+    gpt_destroy(hd);
+    gpt_destroy(bare);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -574,6 +689,7 @@ int main() {
     inverse_map_cases();
     transport_cases();
     pullback_cases();
+    chain_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

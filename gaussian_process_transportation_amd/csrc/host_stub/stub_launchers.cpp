@@ -205,6 +205,18 @@ extern "C" int gpt_batch_predict(int, const double*, const double*, const int64_
     gpt::set_last_error("gpt_batch_predict: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_pullback_chain_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, double, int, double,
+                                      double*, double*, double*, int*, double*, double*, double*, double*, double*, double*, double*,
+                                      double*, int*, int*, double*, double*) {
+    gpt::set_last_error("gpt_pullback_chain_dev: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_pullback_chain(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, double, int, double,
+                                  double*, double*, double*, int*, double*, double*, double*, double*, double*, double*, double*, double*,
+                                  int*, int*, double*, double*) {
+    gpt::set_last_error("gpt_pullback_chain: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
                                int*) {
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
@@ -222,6 +234,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 #include "../gpt_select.h"
 #include "../gpt_svgp_train.h"
 #include "../gpt_svgp_surface.h"
+#include "../gpt_chain.h"
 #include <cstdio>
 
 namespace gpt {
@@ -299,6 +312,44 @@ void launch_sel_schedule(hipStream_t, const SelArgs& a, const double* X, const d
             a.selected[j + 1] = (int)i;
         }
         a.pivd[j + 1] = a.d[a.selected[j + 1]];
+    }
+}
+
+// ---- gpt_chain.hip ------------------------------------------------------------------------------------------------------------
+// k_chain_velocity: every stage's and the dynamics' sources and alpha rows, every affine part, y and x0; an output that is null is
+// not written; a per-stage array holds K * M rows
+void launch_chain_velocity(hipStream_t, int D_, const ChainArgs& a) {
+    if (a.M <= 0) return;
+    stub_check(a.K >= 1 && a.K <= CHAIN_MAX && a.vel && a.status);
+    const size_t M = (size_t)a.M, D = (size_t)D_, K = (size_t)a.K;
+    auto model = [](const ChainModel& m) {
+        const size_t NP = ((size_t)m.N + PAD_N - 1) / PAD_N * PAD_N;
+        touch_r(m.Xs, NP * 4 * 8); touch_r(m.A4, NP * 4 * 8);
+    };
+    for (size_t k = 0; k < K; ++k) {
+        const ChainStage& S = a.st[k];
+        model(S.m);
+        touch_r(S.R, D * D * 8); touch_r(S.R_jac, D * D * 8); touch_r(S.c_src, D * 8); touch_r(S.c_dst, D * 8);
+    }
+    model(a.dyn);
+    touch_r(a.Y, M * D * 8); touch_r(a.X0, M * D * 8);
+    touch_w(a.x, M * D * 8); touch_w(a.f, M * D * 8); touch_w(a.vel, M * D * 8); touch_w(a.status, M * 4);
+    touch_w(a.stage_x, K * M * D * 8); touch_w(a.stage_z, K * M * D * 8); touch_w(a.stage_A, K * M * D * D * 8);
+    touch_w(a.stage_status, K * M * 4); touch_w(a.stage_passes, K * M * 4); touch_w(a.stage_residual, K * M * 8); touch_w(a.stage_det, K * M * 8);
+}
+// k_chain_variance: f, Jvar_k and (K > 1) A_k for vel_var_map; A_k and var_dyn for vel_var_dyn
+void launch_chain_variance(hipStream_t, int D_, const ChainArgs& a) {
+    if (a.M <= 0 || !(a.vel_var_map || a.vel_var_dyn)) return;
+    const size_t M = (size_t)a.M, D = (size_t)D_, K = (size_t)a.K;
+    for (size_t k = 0; k < K; ++k) touch_r(a.st[k].R_jac, D * D * 8);
+    if (a.vel_var_map) {
+        stub_check(a.f && a.stage_Jvar && (K == 1 || a.stage_A));
+        touch_r(a.f, M * D * 8); touch_r(a.stage_Jvar, K * M * D * 8); touch_w(a.vel_var_map, M * D * 8);
+    }
+    if (a.vel_var_map && K > 1) touch_r(a.stage_A, K * M * D * D * 8);
+    if (a.vel_var_dyn) {
+        stub_check(a.stage_A && a.var_dyn);
+        touch_r(a.stage_A, K * M * D * D * 8); touch_r(a.var_dyn, M * 8); touch_w(a.vel_var_dyn, M * D * 8);
     }
 }
 

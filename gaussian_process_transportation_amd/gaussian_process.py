@@ -396,6 +396,71 @@ class GaussianProcess:
             res.update({k: out[k] for k in names if k.startswith("post_")})
         return res
 
+    def pullback_chain(self, inner, dynamics, y, affine, x0=None, rtol=1e-10, max_passes=64, variances=False, outputs=None):
+        """The transported policy at the target-space points y (M,D) through a CHAIN of transports Phi = Phi_{K-1} o ... o Phi_0,
+        this model the displacement psi_{K-1} of the LAST one and `inner` the GaussianProcess models psi_0 .. psi_{K-2} of the
+        ones applied before it (K <= 4):  x = Phi^-1(y),  vel = J_Phi(x) dynamics.predict(x), the K inverses, the dynamics mean and
+        the push-forward in one launch on the device (_lib.Handle.pullback_chain).  `affine`: K tuples (rotation, scale,
+        source_centroid, target_centroid, jacobian), stage 0 first, jacobian None for the rotation.  x0 (M,D): guesses of the
+        SOURCE-space preimages; they are pushed forward through the means to give every stage its start.  Returns a dict: x,
+        vel, f (M,D), status (M,) = the status of the first stage in solve order (the last stage first) that did not converge,
+        and per stage, stage-major (K,M,...): stage_x, stage_z, stage_A, stage_status, stage_passes, stage_residual, stage_det — a
+        stage that does not converge hands on the point it reached.  variances=True adds var_dyn (M,), vel_var_dyn (M,D),
+        vel_var_map (M,D) (each map's Jacobian variance pushed through the maps after it, summed), stage_Jvar (K,M,D) and
+        stage_map_var (K,M); variances="vel" leaves stage_map_var out.  `outputs`: instead of all that, just these names of
+        _lib.CHAIN_OUTPUTS (vel and status always come) — every array left out is one copy from the device less, which at a
+        handful of points is most of the call.  Every model needs n_outputs == n_features <= 3 (the
+        same), float64, a fit on one device; the maps, if Matern, matern_derivatives=True."""
+        maps = list(inner) + [self]
+        if not 1 <= len(maps) <= _lib.CHAIN_MAX:
+            raise ValueError(f"pullback_chain(): 1 .. {_lib.CHAIN_MAX} maps, got {len(maps)}")
+        affine = list(affine)
+        if len(affine) != len(maps):
+            raise ValueError(f"pullback_chain(): {len(maps)} maps, {len(affine)} affine parts")
+        if not isinstance(dynamics, GaussianProcess):
+            raise NotImplementedError(f"pullback_chain(): the dynamics ({type(dynamics).__name__}) must be a fitted GaussianProcess")
+        for k, g in enumerate(maps):
+            if not isinstance(g, GaussianProcess):
+                raise NotImplementedError(f"pullback_chain(): the map of stage {k} ({type(g).__name__}) must be a fitted GaussianProcess")
+            g._require_fit()
+            g._require_self_map("pullback_chain", f"map of stage {k}")
+            g._require_derivatives("pullback_chain")
+        dynamics._require_fit()
+        dynamics._require_self_map("pullback_chain", "dynamics")
+        models = maps + [dynamics]
+        if len({id(g) for g in models}) != len(models):
+            raise ValueError("pullback_chain(): one object twice among the maps and the dynamics; each is a model of its own")
+        for k, g in enumerate(models):
+            who = "the dynamics" if g is dynamics else f"the map of stage {k}"
+            if g.n_features != self.n_features:
+                raise ValueError(f"pullback_chain(): the last map has {self.n_features} features, {who} {g.n_features}")
+            if g.device != self.device:
+                raise ValueError(f"pullback_chain(): the last map holds its fit on device {self.device}, {who} on {g.device}")
+        if not float(rtol) > 0.0:
+            raise ValueError("pullback_chain(): rtol must be > 0")
+        if int(max_passes) < 1:
+            raise ValueError("pullback_chain(): max_passes must be >= 1")
+        y = _lib.as_f64(y, 2, "y")
+        if y.shape[1] != self.n_features:
+            raise ValueError(f"y has {y.shape[1]} columns, the model {self.n_features} features")
+        if x0 is not None:
+            x0 = _lib.as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
+        if y.shape[0] >= 2 ** 31:
+            raise ValueError("pullback_chain(): fewer than 2^31 points per call")
+        if variances not in (False, True, "vel"):
+            raise ValueError("pullback_chain(): variances is False, True or 'vel'")
+        names = ["x", "vel", "f", "status", "stage_x", "stage_z", "stage_A", "stage_status", "stage_passes", "stage_residual", "stage_det"]
+        if variances:
+            names += ["var_dyn", "vel_var_map", "vel_var_dyn", "stage_Jvar"] + (["stage_map_var"] if variances is True else [])
+        if outputs is not None:
+            names = list(outputs)
+        primary = lambda g: getattr(g._handle, "primary", g._handle)
+        stages = [(primary(g), rot, src, dst, scale, jac) for g, (rot, scale, src, dst, jac) in zip(maps, affine)]
+        return primary(self).pullback_chain(stages, primary(dynamics), y, x0=x0, rtol=rtol, max_passes=max_passes,
+                                            std_offset=np.sqrt(dynamics._noise), outputs=names)
+
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):
         """Everything predict(x, return_std=True) and derivative(x, return_var=True) return, computed in ONE pass over

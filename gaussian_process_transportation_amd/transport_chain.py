@@ -1,0 +1,105 @@
+"""TransportChain — several fitted transports applied one after the other, Phi = Phi_{K-1} o ... o Phi_0, as the reference's
+obstacle example does by hand (example/2D/surface_generalization_with_obstacle.py:142-200: a first transport from the old surface
+to the new one, a second, fitted in the new scene, round an obstacle).  The reference then refits a GP on the twice-moved
+demonstration to get a velocity field; here the source dynamics is pulled back through all the maps in ONE device call
+(GaussianProcess.pullback_chain): K inverses, the dynamics mean and the push-forward, with the variance of every map and of the
+dynamics carried through the maps after it."""
+import numpy as np
+
+from . import _lib
+
+
+class TransportChain:
+    def __init__(self, transports, verbose=True):
+        """`transports`: 1 .. 4 fitted GaussianProcessTransportation (or PolicyTransportation) objects in the order they are
+        applied, all of one dimension, each with a delta_map that has `pullback_policy` (GaussianProcess)."""
+        transports = list(transports)
+        if not 1 <= len(transports) <= _lib.CHAIN_MAX:
+            raise ValueError(f"TransportChain: 1 .. {_lib.CHAIN_MAX} transports, got {len(transports)}")
+        self.methods = [getattr(t, "method", t) for t in transports]          # the PolicyTransportation behind each
+        dims = []
+        for k, m in enumerate(self.methods):
+            if getattr(m, "affine_transform", None) is None or not hasattr(m.affine_transform, "rotation_matrix"):
+                raise RuntimeError(f"TransportChain: transport {k} is not fitted (fit_transportation() comes first)")
+            if getattr(m.delta_map, "pullback_policy", None) is None or getattr(m.delta_map, "pullback_chain", None) is None:
+                raise NotImplementedError(f"TransportChain: the delta_map of transport {k} ({type(m.delta_map).__name__}) has no "
+                                          "pullback_policy / pullback_chain; GaussianProcess provides them")
+            dims.append(int(np.shape(m.affine_transform.rotation_matrix)[0]))
+        if len(set(dims)) != 1:
+            raise ValueError(f"TransportChain: the transports must share one space, got dimensions {dims}")
+        self.n_features = dims[0]
+        self.verbose = verbose
+
+    def __len__(self):
+        return len(self.methods)
+
+    def transport(self, points, vel=None, ori=None):
+        """The forward composition: every stage's transport_all in turn, the positions, velocities and orientations of one
+        stage the inputs of the next (a host loop over the existing calls).  Returns (positions, velocities, orientations,
+        [std of stage 0, std of stage 1, ...]); None for what was not given."""
+        pos, stds = np.asarray(points, dtype=np.float64), []
+        for m in self.methods:
+            verbose, m.verbose = m.verbose, m.verbose and self.verbose
+            try:
+                pos, std, vel, _, ori = m.transport_all(pos, vel, ori)
+            finally:
+                m.verbose = verbose
+            stds.append(std)
+        return pos, vel, ori, stds
+
+    def _pull(self, dynamics, points, x0, variances, solver, outputs=None):
+        unknown = set(solver) - {"rtol", "max_passes"}
+        if unknown:
+            raise TypeError(f"TransportChain: unknown solver arguments {sorted(unknown)}")
+        affine = [(m.affine_transform.rotation_matrix, m.affine_transform.scale, m.affine_transform.S_centroid,
+                   m.affine_transform.T_centroid, m.affine_transform.rotation_matrix) for m in self.methods]
+        maps = [m.delta_map for m in self.methods]
+        if outputs is not None and self.verbose:
+            outputs = tuple(outputs) + ("stage_status", "stage_det")
+        out = maps[-1].pullback_chain(maps[:-1], dynamics, np.asarray(points, dtype=np.float64), affine, x0=x0, variances=variances,
+                                      outputs=outputs, **solver)
+        if self.verbose:
+            for k in range(len(maps) - 1, -1, -1):
+                status = out["stage_status"][k]
+                counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.INV_STATUS_NAMES))
+                solved = status == _lib.INV_CONVERGED
+                print(f"Inverse of map {k}: {counts}; det(I + J_psi) <= 0 at {int(np.sum(out['stage_det'][k][solved] <= 0))} "
+                      f"of {int(np.sum(solved))} solutions")
+        return out
+
+    def transported_policy(self, dynamics, points, x0=None, return_std=False, return_info=False, **solver):
+        """The transported policy at `points` (M,D) of the LAST scene: the velocity J_Phi(x) dynamics.predict(x) at
+        x = Phi^-1(points), `dynamics` a GaussianProcess fitted on the source demonstration.  x0: a guess of the source-space
+        preimages; `solver` passes rtol / max_passes on.  Returns the velocities (M,D); with return_std also std (M,D) =
+        sqrt(vel_var_dyn + vel_var_map); with return_info also a dict: x, f, status (the first stage in solve order that did
+        not converge) and the per-stage arrays stage_x, stage_z, stage_A, stage_status, stage_passes, stage_residual,
+        stage_det (K,M,...), with return_std also var_dyn, vel_var_dyn, vel_var_map, stage_Jvar, stage_map_var.  Velocities
+        use the reference's unscaled Jacobian of each affine part (AffineTransform.derivative)."""
+        # without the dict only what is returned leaves the device: at a handful of points the copies are most of the call
+        lean = None if return_info else ("vel_var_dyn", "vel_var_map") if return_std else ()
+        out = self._pull(dynamics, points, x0, (True if return_info else "vel") if return_std else False, solver, outputs=lean)
+        res = (out["vel"],)
+        if return_std:
+            res += (np.sqrt(out["vel_var_dyn"] + out["vel_var_map"]),)
+        if return_info:
+            res += ({k: v for k, v in out.items() if k != "vel"},)
+        return res if len(res) > 1 else res[0]
+
+    def _still_dynamics(self):
+        """A dynamics model for inverse_transport(), which asks the device call for x alone: zero velocities on two points,
+        fitted once on the device of the last map."""
+        if getattr(self, "_still", None) is None:
+            from sklearn.gaussian_process.kernels import RBF, ConstantKernel, WhiteKernel
+            from .gaussian_process import GaussianProcess
+            D = self.n_features
+            gp = GaussianProcess(kernel=ConstantKernel(1.0) * RBF(length_scale=[1.0] * D) + WhiteKernel(1e-6), optimizer=None,
+                                 device=self.methods[-1].delta_map.device, verbose=False)
+            self._still = gp.fit(np.vstack([np.zeros(D), np.ones(D)]), np.zeros((2, D)))
+        return self._still
+
+    def inverse_transport(self, points, x0=None, return_info=False, **solver):
+        """The x with transport(x) = points: `x` of the same device call as transported_policy (with a dynamics of zero
+        velocities, whose outputs are dropped).  With return_info also the status and the per-stage arrays."""
+        out = self._pull(self._still_dynamics(), points, x0, False, solver, outputs=None if return_info else ("x",))
+        info = {k: v for k, v in out.items() if k not in ("vel", "f", "x")}
+        return (out["x"], info) if return_info else out["x"]

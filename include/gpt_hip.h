@@ -390,6 +390,61 @@ int gpt_pullback_policy(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, c
                         double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
                         double* post_Jvar);
 
+/* (new) The transported policy through a CHAIN of transports, Phi = Phi_{K-1} o ... o Phi_0 (the reference's obstacle example moves
+ * a demonstration twice, example/2D/surface_generalization_with_obstacle.py:142-200, and refits a GP on the result):
+ *     x = Phi^-1(y),   v(y) = J_Phi(x) f(x),   Phi_k = gamma_k + psi_k o gamma_k.
+ * stages: a HOST array of K entries, 1 <= K <= GPT_CHAIN_MAX, in the order the transports are applied (stage 0 first); each names
+ * a handle with the fitted displacement model psi_k and gamma_k(x) = scale R (x - c_src) + c_dst with R_jac, as
+ * gpt_pullback_policy's.  h_dyn: the dynamics f.  All models share one D.  Inputs: y (M,D); x0 (M,D) guesses of the SOURCE-space
+ * preimages, or NULL; rtol, max_passes, std_offset as gpt_pullback_policy.  Per point:
+ *   starts       with x0: g_0 = x0, g_{k+1} = gamma_k(g_k) + mean_k(gamma_k(g_k)); stage k's iteration starts at gamma_k(g_k).
+ *                Without x0 every stage starts at its own y_k.
+ *   stages K-1 .. 0:  y_{K-1} = y; z_k: the damped Newton iteration of gpt_pullback_policy on z + psi_k(z) = y_k (the same accept /
+ *                reject rule, statuses, passes, residual, det); x_k = (z_k - c_dst) R / scale + c_src; y_{k-1} = x_k.  A stage that
+ *                does not converge hands on the point it reached and says so; the stages before it still run.
+ *   x     (M,D)  = x_0, the source-space preimage
+ *   f     (M,D)  = mean of h_dyn at x
+ *   vel   (M,D)  = B_{K-1} ... B_0 f,  B_k = A_k R_jac,k,  A_k = I + J_psi_k(z_k) of stage k's last accepted pass
+ *   status (M, int)   the GPT_INV_* of the first stage in solve order (K-1 first) that is not CONVERGED, else CONVERGED
+ *   var_dyn (M)       raw posterior variance of h_dyn at x
+ *   vel_var_map (M,D) = sum_k sigma_k^2 sum_j (B_{K-1} ... B_{k+1})[i,j]^2,  sigma_k^2 = sum_d Jvar_k,d(z_k) (R_jac,k v_{k-1})_d^2,
+ *                     v_{-1} = f, v_k = B_k v_{k-1}: each map's Jacobian variance pushed, to first order, through the maps after it
+ *   vel_var_dyn (M,D) = s^2 sum_j (B_{K-1} ... B_0)[i,j]^2,  s = sqrt(var_dyn) - std_offset
+ *   stage-major per-stage arrays, stage k's rows contiguous: stage_x (K,M,D), stage_z (K,M,D), stage_A (K,M,D,D), stage_Jvar
+ *   (K,M,D) the Jacobian variance of psi_k at z_k, stage_map_var (K,M) the raw posterior variance of psi_k at z_k, stage_status,
+ *   stage_passes (K,M, int), stage_residual, stage_det (K,M)
+ * Every output may be NULL except vel and status.  For K = 1, x, vel, f, status and the stage arrays are gpt_pullback_policy's x,
+ * vel, f, status, x, post_z, post_A, post_Jvar, map_var, status, passes, residual, det, and every column of vel_var_map its scalar.
+ * x, f, vel, status and the stage arrays but Jvar and map_var come from ONE launch, one wave per query (k_chain_velocity); a
+ * query's values there do not depend on M or on the other queries, bit for bit.  The variances come from the unchanged variance
+ * launches of the handles, only those whose outputs were asked for, and a one-thread-per-query epilogue.
+ * GPT_E_STATE: a handle without a model.  GPT_E_ARG (the message names the limit and the stage): K < 1 or K > GPT_CHAIN_MAX; stages
+ * NULL; a NULL handle or a NULL R, c_src, c_dst, R_jac in a stage; h_dyn NULL; one handle twice among the stages and h_dyn; handles
+ * on different devices or with different D; per handle what gpt_pullback_policy refuses of its map (every stage) and of its
+ * dynamics; rtol <= 0 or NaN; max_passes < 1; M < 0 or M >= 2^31; a NULL among y, vel, status.  M = 0 does nothing.
+ * Device memory (the affine parts too; the stages array itself is host memory and is not kept).  Asynchronous: enqueued on the
+ * stream of stages[K-1].h, which first waits for what the other handles' streams hold so far; each variance launch runs on its own
+ * handle's stream between two events, one after the other (each fills the device), and the other streams go on only after
+ * their models have been read.  No host synchronisation.  Scratch, staging and events belong to stages[K-1].h (grow-only).  Every model is left as it was. */
+#define GPT_CHAIN_MAX 4
+typedef struct {
+    gpt_handle* h;
+    const double *R, *c_src, *c_dst, *R_jac;
+    double scale;
+} gpt_chain_stage;
+int gpt_pullback_chain_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y_dev, const double* x0_dev, int64_t M,
+                           double rtol, int max_passes, double std_offset, double* x_dev, double* vel_dev, double* f_dev,
+                           int* status_dev, double* var_dyn_dev, double* vel_var_map_dev, double* vel_var_dyn_dev, double* stage_x_dev,
+                           double* stage_z_dev, double* stage_A_dev, double* stage_Jvar_dev, double* stage_map_var_dev,
+                           int* stage_status_dev, int* stage_passes_dev, double* stage_residual_dev, double* stage_det_dev);
+/* (new) The same with every data pointer in host memory; also GPT_E_ARG for NaN / infinity in y, x0, an affine part, rtol or
+ * std_offset.  The queries are streamed through the device in chunks of 131072 as gpt_pullback_policy's, through two staging sets
+ * of stages[K-1].h; only the arrays asked for cross the bus.  Returns when every output is in place. */
+int gpt_pullback_chain(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M,
+                       double rtol, int max_passes, double std_offset, double* x, double* vel, double* f, int* status, double* var_dyn,
+                       double* vel_var_map, double* vel_var_dyn, double* stage_x, double* stage_z, double* stage_A, double* stage_Jvar,
+                       double* stage_map_var, int* stage_status, int* stage_passes, double* stage_residual, double* stage_det);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);
