@@ -68,6 +68,14 @@ __device__ __forceinline__ void exp_tab4(const double (&tin)[4], const double* _
     for (int e = 0; e < 4; ++e) out[e] = ldexp(tj[e] * pz[e], ni[e] >> 8);
 }
 
+// The Matern kernels multiply the exponential by a polynomial in t = sqrt(nu') r.  A query so far out that h = r^2 / 2 overflows
+// has t = inf: the exponential is 0 (exp_tab's clamp, exp2 of -inf), the polynomial inf, their product NaN.  t is bounded
+// before both: exp(ln c - 1e4) is 0 for every c the fit accepts and the polynomial stays finite, in fp32 too, so such a query
+// gets k = g = 0, the prior.  Below the bound nothing changes, to the bit.
+constexpr double MATERN_T_MAX = 1e4;
+__device__ __forceinline__ double matern_bound(const double t) { return fmin(t, MATERN_T_MAX); }
+__device__ __forceinline__ float matern_bound(const float t) { return fminf(t, (float)MATERN_T_MAX); }
+
 // Stationary kernels of the path (sklearn/gaussian_process/kernels.py: RBF 1553-1565, Matern 1717-1745):
 //   KT 0: RBF  exp(-r^2/2)      KT 1: Matern 1/2  exp(-r)
 //   KT 2: Matern 3/2  (1 + sqrt3 r) exp(-sqrt3 r)      KT 3: Matern 5/2  (1 + sqrt5 r + 5/3 r^2) exp(-sqrt5 r)
@@ -89,8 +97,8 @@ __device__ __forceinline__ double kernel_tab(const double h, const double lnc, c
     if (KT == KT_RBF) return exp_tab(lnc - h, T);
     const double r = sqrt(h + h);
     if (KT == KT_MATERN12) return exp_tab(lnc - r, T);
-    if (KT == KT_MATERN32) { const double t = 1.7320508075688772 * r; return (1.0 + t) * exp_tab(lnc - t, T); }
-    const double t = 2.23606797749979 * r;
+    if (KT == KT_MATERN32) { const double t = matern_bound(1.7320508075688772 * r); return (1.0 + t) * exp_tab(lnc - t, T); }
+    const double t = matern_bound(2.23606797749979 * r);
     return (1.0 + t + t * t * (1.0 / 3.0)) * exp_tab(lnc - t, T);
 }
 
@@ -104,8 +112,8 @@ __device__ __forceinline__ void kernel_tab4(const double (&h)[4], const double l
         else {
             const double r = sqrt(h[e] + h[e]);
             if (KT == KT_MATERN12) { a[e] = lnc - r; pre[e] = 1.0; }
-            else if (KT == KT_MATERN32) { const double t = 1.7320508075688772 * r; a[e] = lnc - t; pre[e] = 1.0 + t; }
-            else { const double t = 2.23606797749979 * r; a[e] = lnc - t; pre[e] = 1.0 + t + t * t * (1.0 / 3.0); }
+            else if (KT == KT_MATERN32) { const double t = matern_bound(1.7320508075688772 * r); a[e] = lnc - t; pre[e] = 1.0 + t; }
+            else { const double t = matern_bound(2.23606797749979 * r); a[e] = lnc - t; pre[e] = 1.0 + t + t * t * (1.0 / 3.0); }
         }
     }
     exp_tab4(a, T, k);
@@ -121,8 +129,8 @@ __device__ __forceinline__ float kernel_tab(const float h, const float lnc, cons
     if (KT == KT_RBF) return __builtin_amdgcn_exp2f((lnc - h) * L2E);
     const float r = __builtin_sqrtf(h + h);
     if (KT == KT_MATERN12) return __builtin_amdgcn_exp2f((lnc - r) * L2E);
-    if (KT == KT_MATERN32) { const float t = 1.7320508075688772f * r; return (1.0f + t) * __builtin_amdgcn_exp2f((lnc - t) * L2E); }
-    const float t = 2.23606797749979f * r;
+    if (KT == KT_MATERN32) { const float t = matern_bound(1.7320508075688772f * r); return (1.0f + t) * __builtin_amdgcn_exp2f((lnc - t) * L2E); }
+    const float t = matern_bound(2.23606797749979f * r);
     return (1.0f + t + t * t * (1.0f / 3.0f)) * __builtin_amdgcn_exp2f((lnc - t) * L2E);
 }
 
@@ -149,7 +157,7 @@ __device__ __forceinline__ float ksqrt(const float x) { return __builtin_sqrtf(x
 template <int KT, typename R>
 __device__ __forceinline__ R matern_t(const R h) {
     static_assert(KT == KT_MATERN32 || KT == KT_MATERN52, "derivative columns: Matern 3/2 and 5/2");
-    return (KT == KT_MATERN32 ? (R)1.7320508075688772 : (R)2.23606797749979) * ksqrt(h + h);
+    return matern_bound((KT == KT_MATERN32 ? (R)1.7320508075688772 : (R)2.23606797749979) * ksqrt(h + h));
 }
 template <int KT, typename R>
 __device__ __forceinline__ R matern_pre_k(const R t) { return KT == KT_MATERN32 ? (R)1 + t : (R)1 + t + t * t * (R)(1.0 / 3.0); }

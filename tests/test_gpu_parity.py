@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests.conftest import assert_parity, load_golden, relmax
+from tests.posterior_restatement import KINDS as KERNEL_KINDS, assert_lml_gradient
 
 pytestmark = pytest.mark.gpu
 
@@ -497,6 +498,7 @@ def test_lml_value_and_gradient_vs_sklearn(name):
         lml, grad = h.lml_gradient(n_ls)
         assert lml == pytest.approx(float(v), rel=1e-9)
         assert_parity(grad, gr, 1e-6, "d lml / d theta")
+        assert_lml_gradient(g["X"], g["Y"], c, ls, noise, float(g["alpha"]), "rbf", lml, grad, f"{name} theta {th}")
         with pytest.raises(_lib.GptError):
             h.export()                      # the factor was consumed by the gradient; a new fit restores it
         h.fit(g["X"], g["Y"], ls, c, noise, float(g["alpha"]))
@@ -741,11 +743,15 @@ def test_matern_kernels_vs_reference(tag, nu, code):
         lml, grad = h.lml_gradient(2)
         assert lml == pytest.approx(float(v), rel=1e-9)
         assert_parity(grad, gr, 1e-6, "d lml / d theta (ARD)")
+        c, ls, noise = np.exp(th[0]), np.exp(th[1:3]), np.exp(th[3])
+        assert_lml_gradient(g["X"], g["Y"], c, ls, noise, 1e-10, KERNEL_KINDS[code], lml, grad, f"matern_2d {tag} ARD")
     th = g[f"m{tag}_iso_theta"]
     h.fit(g["X"][::4], g["Y"][::4], np.exp(th[1:2]), np.exp(th[0]), np.exp(th[2]), 1e-10, code)
     lml, grad = h.lml_gradient(1)
     assert lml == pytest.approx(float(g[f"m{tag}_iso_value"]), rel=1e-9)
     assert_parity(grad, g[f"m{tag}_iso_grad"], 1e-6, "d lml / d theta (isotropic)")
+    c, ls, noise = np.exp(th[0]), np.exp(th[1:2]), np.exp(th[2])
+    assert_lml_gradient(g["X"][::4], g["Y"][::4], c, ls, noise, 1e-10, KERNEL_KINDS[code], lml, grad, f"matern_2d {tag} iso")
     h.close()
 
 
@@ -1436,6 +1442,8 @@ def test_matern_kernels_in_five_dimensions_vs_reference(tag, nu, code):
             lml, grad = h.lml_gradient(n_ls)
             assert lml == pytest.approx(float(v), rel=1e-9)
             assert_parity(grad, gr, 1e-6, f"d lml / d theta ({kk})")
+            c, lsv, noise = np.exp(th[0]), np.exp(th[1:1 + n_ls]), np.exp(th[1 + n_ls])
+            assert_lml_gradient(g["X"], g["Y"], c, lsv, noise, 1e-10, KERNEL_KINDS[code], lml, grad, f"matern_5d {tag} {kk}")
         # Matern x fp32: fp64 factorisation, fp32 prediction kernels; against the fp64 model at fp32's resolution
         big = np.random.default_rng(3).uniform(-0.1, 1.1, (3000, 5))
         lsv = np.atleast_1d(np.asarray(ls, dtype=float))
