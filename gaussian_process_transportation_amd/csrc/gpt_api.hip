@@ -1,12 +1,9 @@
 // C ABI of libgpt_hip (see include/gpt_hip.h).  Host-side orchestration only: owns the device
 // buffers, prepares scaled/padded inputs, sequences the kernels of gpt_fit.hip / gpt_predict.hip
 // on one HIP stream and maps failures to error codes.
-#include "gpt_call.h"
+#include "gpt_stage.h"
 #include "gpt_plan.h"
 #include "gpt_fit_plan.h"
-#include "gpt_transport.h"
-#include "gpt_pullback.h"
-#include "gpt_chain.h"
 #include "../../include/gpt_hip.h"
 
 #include <algorithm>
@@ -30,7 +27,6 @@ constexpr int MAX_TASKS = 32;
 constexpr int HDR_LS = 8;                // hdr[8 + d], d < 3: length-scale of dimension d
 constexpr int HDR_LS_HI = 48;            // hdr[48 + d - 3], 3 <= d < MAX_DIMS: the further dimensions of the wide layouts (slots 48 .. 59)
 inline int hdr_ls_slot(int d) { return d < 3 ? HDR_LS + d : HDR_LS_HI + d - 3; }
-constexpr int64_t HOST_CHUNK = 1 << 17;  // queries per chunk of the host-pointer API (two chunks in flight)
 
 // Model blob: [header: 64 doubles][Xs: NP x 4 (D <= 3) or NP x 8][A4: npass x NP x 4][Wf: ntask tile sets + overrun],
 // the three arrays in the model's element type.  Offsets in bytes.
@@ -55,17 +51,6 @@ Layout make_layout(int64_t N, int D, int O, int ntask, int dtype) {
 }
 
 enum { ST_Q = 0, ST_MEAN, ST_VAR, ST_J, ST_JVAR, ST_DVAR, ST_COUNT };
-// arrays of gpt_transport_policy, in the order of its arguments: inputs, outputs, the posterior the epilogue consumed
-enum { TP_POS = 0, TP_VEL, TP_ORI, TP_POS_ROT, TP_POS_OUT, TP_VAR, TP_VEL_OUT, TP_VEL_VAR, TP_DET_VEL, TP_ORI_OUT, TP_DET_ORI, TP_ORI_GAP,
-       TP_MEAN, TP_J, TP_JVAR, TP_J_ORI, TP_COUNT };
-constexpr int TP_INPUTS = 3;             // TP_POS .. TP_ORI travel to the device, the rest from it
-// arrays of gpt_pullback_policy, in the order of its arguments (passes and status hold ints, the rest doubles)
-enum { PB_Y = 0, PB_X0, PB_X, PB_VEL, PB_F, PB_DET, PB_RES, PB_PASSES, PB_STATUS, PB_VAR_DYN, PB_MAP_VAR, PB_VVAR_MAP, PB_VVAR_DYN,
-       PB_Z, PB_A, PB_JVAR, PB_COUNT };
-constexpr int PB_INPUTS = 2;             // PB_Y, PB_X0 travel to the device, the rest from it
-constexpr int PB_SCRATCH = 6;            // x, z, f, A, var_dyn, Jvar: what a later stage reads and the caller did not ask for
-constexpr int TP_AFFINE_DOUBLES = 24;    // device image of the host call's affine part: R (9) | R_jac (9) | c_src (3) | c_dst (3)
-
 }  // namespace
 
 // ---- host side of the variance kernel: workgroup count, scratch buffers and the (cached) work plan of a launch shape
@@ -173,7 +158,7 @@ struct gpt_handle {
     int host_info = 0;
     // staging of the host-pointer API, grow-only per buffer
     // (two sets: while the results of one chunk travel to the host on `copy_stream`, the next chunk computes)
-    struct Staging { DevBuf<void> buf[ST_COUNT]; } st[2];
+    StagingSet st[2];
     Stream copy_stream;
     Event ev_done[2], ev_copied[2];   // chunk computed / chunk's outputs copied out, per staging set
     double fit_ms[6] = {0, 0, 0, 0, 0, 0};
@@ -184,21 +169,9 @@ struct gpt_handle {
     FitAux fit_aux;                // CU-masked streams + events of the factor + inverse plan (gpt_fit_plan.h)
     DevBuf<double> lml_partial;    // partial sums of the LML gradient (grow-only)
     DevBuf<unsigned char> cov_buf; // scratch of gpt_predict_cov (grow-only)
-    DevBuf<unsigned char> inv_buf; // device images of gpt_inverse_map's host arrays (grow-only)
-    // gpt_transport_policy: what the epilogue reads and the caller did not ask for (gamma(pos), mean, J, Jvar, J at pos), the two
-    // staging sets of the host call and its affine part; each grow-only, each its own owner
-    DevBuf<double> tp_scratch[5];
-    struct TransportStaging { DevBuf<double> buf[TP_COUNT]; } tp_st[2];
-    DevBuf<double> tp_affine;          // (gpt_pullback_policy's affine part too: the same image)
-    double tp_affine_host[TP_AFFINE_DOUBLES] = {};
-    // gpt_pullback_policy, held by the MAP handle: the scratch between its stages, the two staging sets of the host call and the
-    // events that hand over between this handle's stream and the dynamics handle's (created on first use)
-    DevBuf<double> pb_scratch[PB_SCRATCH];
-    struct PullbackStaging { DevBuf<unsigned char> buf[PB_COUNT]; } pb_st[2];
-    Event pb_ev[3];
-    // gpt_pullback_chain, held by the handle of the chain's last stage (gpt_chain.h; created on first use)
-    std::unique_ptr<ChainResources> chain;
-    Event chain_ev[2 * CHAIN_MAX + 1];
+    // gpt_inverse_map, gpt_transport_policy, gpt_pullback_policy (held by the MAP handle) and gpt_pullback_chain (held by the handle
+    // of the chain's last stage): what each call family keeps between calls (gpt_stage.h), created on first use
+    std::unique_ptr<CallResources> call[CALL_FAMILIES];
     Event pev[4];
 
     ~gpt_handle() { fit_aux_release(fit_aux); }     // every other member releases itself
@@ -265,12 +238,6 @@ int ensure_workspace(gpt_handle* h, int64_t NP, int npass) {
     CALLCHK(reserve(w.dinfo, sizeof(int), nullptr));
     if (int rc = ensure_scratch(h, NP)) return rc;
     w.np = NP; w.npass = npass;
-    return GPT_OK;
-}
-
-// one staging buffer of one set, grow-only; only what a call asks for is ever allocated
-int ensure_stage(gpt_handle* h, int set, int which, size_t bytes) {
-    CALLCHK(reserve(h->st[set].buf[which], bytes, h->stream, h->copy_stream));
     return GPT_OK;
 }
 
@@ -700,67 +667,23 @@ int gpt_predict_all_dev(gpt_handle* h, const void* Xq, int64_t M, void* mean, vo
     return GPT_OK;
 }
 
-int gpt_predict_all(gpt_handle* h, const void* Xq_, int64_t M, void* mean_, void* var_,
-                    void* J_, void* Jvar_, void* dvar_) {
+int gpt_predict_all(gpt_handle* h, const void* Xq, int64_t M, void* mean, void* var,
+                    void* J, void* Jvar, void* dvar) {
     if (!h) return fail(GPT_E_ARG, "gpt_predict_all: NULL handle");
     if (!h->committed) return fail(GPT_E_STATE, "predict: model is not fitted");
-    if (M < 0 || (M > 0 && !Xq_)) return fail(GPT_E_ARG, "predict: bad query buffer");
+    if (M < 0 || (M > 0 && !Xq)) return fail(GPT_E_ARG, "predict: bad query buffer");
     if (M == 0) return GPT_OK;
     if (int rc = set_device(h)) return rc;
     const size_t esz = h->lay.esz;
     const size_t D = h->p.D, O = h->p.O, NT = h->p.ntask;
-    const unsigned char* Xq = static_cast<const unsigned char*>(Xq_);
-    unsigned char *mean = static_cast<unsigned char*>(mean_), *var = static_cast<unsigned char*>(var_), *J = static_cast<unsigned char*>(J_),
-                  *Jvar = static_cast<unsigned char*>(Jvar_), *dvar = static_cast<unsigned char*>(dvar_);
-    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
-    const int64_t nchunks = (M + cap - 1) / cap;
-    // elements per query of each staged array
-    const size_t per[ST_COUNT] = {D, O, NT, O * D, NT * D, D};
-    void* const want[ST_COUNT] = {(void*)Xq, mean, var, J, Jvar, dvar};
-    for (int b = 0; b < (nchunks > 1 ? 2 : 1); ++b)
-        for (int i = 0; i < ST_COUNT; ++i)
-            if (want[i]) { if (int rc = ensure_stage(h, b, i, (size_t)cap * per[i] * esz)) return rc; }
-    // one chunk (the reference's own batch sizes): queries in, kernels, results out, all in the handle's stream — no second
-    // stream, no events; several chunks: the results of chunk i leave on the copy stream while chunk i + 1 computes
-    const bool single = nchunks == 1;
-    if (!single) { if (int rc = ensure_copy_stream(h)) return rc; }
-    hipStream_t s = h->stream, cs = single ? h->stream : h->copy_stream;
-    // chunk i computes on `s` in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes
-    auto enqueue = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        gpt_handle::Staging& t = h->st[b];
-        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
-        CALLCHK(hipMemcpyAsync(t.buf[ST_Q], Xq + (size_t)off * D * esz, (size_t)m * D * esz, hipMemcpyHostToDevice, s));
-        if (int rc = gpt_predict_all_dev(h, t.buf[ST_Q], m, mean ? t.buf[ST_MEAN].p : nullptr, var ? t.buf[ST_VAR].p : nullptr,
-                                         J ? t.buf[ST_J].p : nullptr, Jvar ? t.buf[ST_JVAR].p : nullptr, dvar ? t.buf[ST_DVAR].p : nullptr))
-            return rc;
-        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
-        return GPT_OK;
-    };
-    auto copy_out = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        const gpt_handle::Staging& t = h->st[b];
-        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
-        unsigned char* const dst[ST_COUNT] = {nullptr, mean, var, J, Jvar, nullptr};
-        for (int k = ST_MEAN; k <= ST_JVAR; ++k)
-            if (dst[k]) CALLCHK(hipMemcpyAsync(dst[k] + (size_t)off * per[k] * esz, t.buf[k], (size_t)m * per[k] * esz, hipMemcpyDeviceToHost, cs));
-        if (dvar)
-            for (size_t d = 0; d < D; ++d)   // device chunk is (D, m); host result is (D, M)
-                CALLCHK(hipMemcpyAsync(dvar + (d * (size_t)M + (size_t)off) * esz, static_cast<unsigned char*>(t.buf[ST_DVAR].p) + d * (size_t)m * esz,
-                                      (size_t)m * esz, hipMemcpyDeviceToHost, cs));
-        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
-        return GPT_OK;
-    };
-    if (int rc = enqueue(0)) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
-        if (int rc = copy_out(i)) return rc;
-    }
-    if (!single) CALLCHK(hipStreamSynchronize(cs));
-    CALLCHK(hipStreamSynchronize(s));
-    return GPT_OK;
+    ChunkStreams q;
+    if (int rc = handle_copy_stream(h, !one_chunk(M), &q)) return rc;
+    // elements per query of each staged array; the device's dvar is (D, m), the caller's (D, M)
+    const StagedArray table[ST_COUNT] = {{const_cast<void*>(Xq), D * esz, true, 1}, {mean, O * esz, false, 1}, {var, NT * esz, false, 1},
+                                         {J, O * D * esz, false, 1}, {Jvar, NT * D * esz, false, 1}, {dvar, esz, false, (int)D}};
+    return run_chunked(h->st, q, table, M, [&](void* const* dev, int64_t m) {
+        return gpt_predict_all_dev(h, dev[ST_Q], m, dev[ST_MEAN], dev[ST_VAR], dev[ST_J], dev[ST_JVAR], dev[ST_DVAR]);
+    });
 }
 
 int gpt_predict(gpt_handle* h, const void* Xq, int64_t M, void* mean, void* var) {
@@ -775,469 +698,33 @@ int gpt_dvariance(gpt_handle* h, const void* Xq, int64_t M, void* g) {
     return gpt_predict_all(h, Xq, M, nullptr, nullptr, nullptr, nullptr, g);
 }
 
-static_assert(GPT_INV_CONVERGED == INV_CONVERGED && GPT_INV_MAX_PASSES == INV_MAX_PASSES && GPT_INV_SINGULAR == INV_SINGULAR &&
-              GPT_INV_STALLED == INV_STALLED, "status codes of the header and of the kernel");
-
-// what both inverse entry points refuse, in the order of the header's list
-static int inverse_check(gpt_handle* h, const char* who, const double* Y, int64_t M, double rtol, int max_passes, const double* Z,
-                         const int* status) {
-    const std::string w(who);
-    if (!h) return fail(GPT_E_ARG, w + ": NULL handle");
-    if (!h->committed) return fail(GPT_E_STATE, w + ": model is not fitted");
-    const KernelParams& p = h->p;
-    if (p.D != p.O || p.D > 3)
-        return fail(GPT_E_ARG, w + ": the inverse needs a map of a space onto itself, D == O, with D <= 3 (this model: D = " +
-                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
-    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (this model was fitted with GPT_F32)");
-    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (this model is a multi-task gpt_fit_svgp model)");
-    if (p.ktype == GPT_KERNEL_MATERN12)
-        return fail(GPT_E_ARG, w + ": Matern 1/2 (nu = 0.5) is not differentiable at the training points: Newton has no Jacobian; "
-                                   "use RBF, Matern 3/2 or Matern 5/2");
-    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
-        return fail(GPT_E_ARG, w + ": the inverse of a Matern model uses the analytic derivatives of its posterior; "
-                                   "gpt_set_matern_derivatives(h, 1) enables them");
-    if (!(rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
-    if (max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
-    if (M < 0 || M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
-    if (M > 0 && (!Y || !Z || !status)) return fail(GPT_E_ARG, w + ": Y, Z and status must not be NULL");
-    return GPT_OK;
-}
-
-int gpt_inverse_map_dev(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
-                        double* residual, double* det, int* passes, int* status) {
-    if (int rc = inverse_check(h, "gpt_inverse_map_dev", Y, M, rtol, max_passes, Z, status)) return rc;
-    if (M == 0) return GPT_OK;
-    if (int rc = set_device(h)) return rc;
-    const InverseArgs a{Y, Z0, M, rtol, max_passes, Z, residual, det, passes, status};
-    launch_inverse_newton(h->stream, h->p, static_cast<const double*>(h->dXs()), static_cast<const double*>(h->dA4()), a);
-    CALLCHK(hipGetLastError());
-    return GPT_OK;
-}
-
-int gpt_inverse_map(gpt_handle* h, const double* Y, const double* Z0, int64_t M, double rtol, int max_passes, double* Z,
-                    double* residual, double* det, int* passes, int* status) {
-    if (int rc = inverse_check(h, "gpt_inverse_map", Y, M, rtol, max_passes, Z, status)) return rc;
-    if (M == 0) return GPT_OK;
-    const size_t D = h->p.D, nv = (size_t)M * D;
-    if (!all_finite(Y, nv) || (Z0 && !all_finite(Z0, nv))) return fail(GPT_E_ARG, "gpt_inverse_map: Y / Z0 contain NaN or infinity");
-    if (int rc = set_device(h)) return rc;
-    hipStream_t s = h->stream;
-    // one grow-only image: [Y | Z0 | Z | residual | det | passes | status]
-    const size_t bv = nv * sizeof(double), bs = (size_t)M * sizeof(double), bi = ((size_t)M * sizeof(int) + 15) / 16 * 16;
-    CALLCHK(reserve(h->inv_buf, 3 * bv + 2 * bs + 2 * bi, s));
-    unsigned char* const b = h->inv_buf;
-    double *dY = reinterpret_cast<double*>(b), *dZ0 = reinterpret_cast<double*>(b + bv), *dZ = reinterpret_cast<double*>(b + 2 * bv),
-           *dres = reinterpret_cast<double*>(b + 3 * bv), *ddet = reinterpret_cast<double*>(b + 3 * bv + bs);
-    int *dpass = reinterpret_cast<int*>(b + 3 * bv + 2 * bs), *dstat = reinterpret_cast<int*>(b + 3 * bv + 2 * bs + bi);
-    CALLCHK(hipMemcpyAsync(dY, Y, bv, hipMemcpyHostToDevice, s));
-    if (Z0) CALLCHK(hipMemcpyAsync(dZ0, Z0, bv, hipMemcpyHostToDevice, s));
-    if (int rc = gpt_inverse_map_dev(h, dY, Z0 ? dZ0 : nullptr, M, rtol, max_passes, dZ, residual ? dres : nullptr, det ? ddet : nullptr,
-                                     passes ? dpass : nullptr, dstat))
-        return rc;
-    CALLCHK(hipMemcpyAsync(Z, dZ, bv, hipMemcpyDeviceToHost, s));
-    if (residual) CALLCHK(hipMemcpyAsync(residual, dres, bs, hipMemcpyDeviceToHost, s));
-    if (det) CALLCHK(hipMemcpyAsync(det, ddet, bs, hipMemcpyDeviceToHost, s));
-    if (passes) CALLCHK(hipMemcpyAsync(passes, dpass, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
-    CALLCHK(hipMemcpyAsync(status, dstat, (size_t)M * sizeof(int), hipMemcpyDeviceToHost, s));
-    CALLCHK(hipStreamSynchronize(s));
-    return GPT_OK;
-}
-
-// ---- transport of positions, velocities and orientations: affine part, posterior, push-forward, all on the device
-namespace {
-
-// the arguments of both transport entry points (host or device pointers alike), indexed by TP_*
-struct TransportCall {
-    int64_t M = 0;
-    double scale = 1.0;
-    const double *R = nullptr, *c_src = nullptr, *c_dst = nullptr, *R_jac = nullptr;
-    double* arr[TP_COUNT] = {};          // (the inputs TP_POS .. TP_ORI are only read)
-};
-
-// what both entry points refuse, in the order of the header's list
-int transport_check(gpt_handle* h, const char* who, const TransportCall& c) {
-    const std::string w(who);
-    if (!h) return fail(GPT_E_ARG, w + ": NULL handle");
-    if (!h->committed) return fail(GPT_E_STATE, w + ": model is not fitted");
-    const KernelParams& p = h->p;
-    if (p.D != p.O || p.D > 3)
-        return fail(GPT_E_ARG, w + ": the transport needs a map of a space onto itself, D == O, with D <= 3 (this model: D = " +
-                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
-    if ((c.arr[TP_ORI] || c.arr[TP_ORI_OUT] || c.arr[TP_ORI_GAP]) && p.D != 3)
-        return fail(GPT_E_ARG, w + ": orientations (ori, ori_out, ori_gap) need D == 3: the rotation closest to a " + std::to_string(p.D) +
-                                   " x " + std::to_string(p.D) + " Jacobian is no quaternion");
-    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (this model was fitted with GPT_F32)");
-    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (this model is a multi-task gpt_fit_svgp model)");
-    if (p.ktype == GPT_KERNEL_MATERN12)
-        return fail(GPT_E_ARG, w + ": Matern 1/2 (nu = 0.5) is not differentiable at the training points: the map has no Jacobian to "
-                                   "push velocities and orientations through; use RBF, Matern 3/2 or Matern 5/2");
-    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
-        return fail(GPT_E_ARG, w + ": the transport through a Matern model uses the analytic derivatives of its posterior; "
-                                   "gpt_set_matern_derivatives(h, 1) enables them");
-    if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
-    if ((c.arr[TP_VEL_OUT] || c.arr[TP_VEL_VAR]) && !c.arr[TP_VEL])
-        return fail(GPT_E_ARG, w + ": vel_out and vel_var need vel (the velocities to push forward)");
-    if (c.arr[TP_ORI_OUT] && !c.arr[TP_ORI]) return fail(GPT_E_ARG, w + ": ori_out needs ori (the orientations to rotate)");
-    if (c.M > 0 && (!c.arr[TP_POS] || !c.arr[TP_POS_OUT] || !c.R || !c.c_src || !c.c_dst || !c.R_jac))
-        return fail(GPT_E_ARG, w + ": pos, pos_out, R, c_src, c_dst and R_jac must not be NULL");
-    return GPT_OK;
-}
-
-int transport_dev(gpt_handle* h, const TransportCall& c) {
-    if (int rc = set_device(h)) return rc;
-    hipStream_t s = h->stream;
-    const int64_t M = c.M;
-    const size_t D = h->p.D;
-    double* const* u = c.arr;
-    // which posterior quantities the outputs asked for consume
-    const bool need_J = u[TP_VEL_OUT] || u[TP_DET_VEL] || u[TP_J];
-    const bool need_Jvar = u[TP_VEL_VAR] || u[TP_JVAR];
-    const bool need_J_ori = u[TP_ORI_OUT] || u[TP_DET_ORI] || u[TP_ORI_GAP] || u[TP_J_ORI];
-    // each lives in the caller's array when there is one, else in the handle's scratch
-    const struct { int which; bool need; size_t per; } mid[5] = {
-        {TP_POS_ROT, true, D}, {TP_MEAN, true, D}, {TP_J, need_J, D * D}, {TP_JVAR, need_Jvar, D}, {TP_J_ORI, need_J_ori, D * D}};
-    double* at[5];
-    for (int k = 0; k < 5; ++k) {
-        at[k] = mid[k].need ? u[mid[k].which] : nullptr;
-        if (mid[k].need && !at[k]) {
-            CALLCHK(reserve(h->tp_scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
-            at[k] = h->tp_scratch[k];
-        }
-    }
-    TransportArgs a{};
-    a.M = M; a.scale = c.scale; a.R = c.R; a.c_src = c.c_src; a.c_dst = c.c_dst; a.R_jac = c.R_jac;
-    a.pos = u[TP_POS]; a.vel = u[TP_VEL]; a.ori = u[TP_ORI];
-    a.pos_rot = at[0]; a.mean = at[1]; a.J = at[2]; a.Jvar = at[3]; a.J_ori = at[4];
-    a.pos_out = u[TP_POS_OUT]; a.vel_out = u[TP_VEL_OUT]; a.vel_var = u[TP_VEL_VAR]; a.det_vel = u[TP_DET_VEL];
-    a.ori_out = u[TP_ORI_OUT]; a.det_ori = u[TP_DET_ORI]; a.ori_gap = u[TP_ORI_GAP];
-    launch_transport_affine(s, (int)D, a);
-    // the Jacobian at the un-rotated positions (the reference's transport_orientation), then the posterior at gamma(pos): the
-    // launches, query image and choice of variance path of gpt_predict_all_dev itself
-    if (need_J_ori) launch_mean_jac(s, h->p, h->dXs(), h->dA4(), a.pos, M, nullptr, at[4]);
-    if (int rc = gpt_predict_all_dev(h, a.pos_rot, M, at[1], u[TP_VAR], at[2], at[3], nullptr)) return rc;
-    launch_transport_push(s, (int)D, a);
-    CALLCHK(hipGetLastError());
-    return GPT_OK;
-}
-
-}  // namespace
-
-#define TRANSPORT_CALL(c)                                                                                                          \
-    TransportCall c;                                                                                                               \
-    c.M = M; c.scale = scale; c.R = R; c.c_src = c_src; c.c_dst = c_dst; c.R_jac = R_jac;                                          \
-    {                                                                                                                              \
-        double* const all[TP_COUNT] = {const_cast<double*>(pos), const_cast<double*>(vel), const_cast<double*>(ori), pos_rot, pos_out, var, \
-                                       vel_out, vel_var, det_vel, ori_out, det_ori, ori_gap, post_mean, post_J, post_Jvar, post_J_ori}; \
-        for (int k = 0; k < TP_COUNT; ++k) c.arr[k] = all[k];                                                                      \
-    }
-
-int gpt_transport_policy_dev(gpt_handle* h, const double* pos, int64_t M, const double* R, const double* c_src, const double* c_dst,
-                             double scale, const double* R_jac, const double* vel, const double* ori, double* pos_rot, double* pos_out,
-                             double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
-                             double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori) {
-    TRANSPORT_CALL(c);
-    if (int rc = transport_check(h, "gpt_transport_policy_dev", c)) return rc;
-    if (M == 0) return GPT_OK;
-    return transport_dev(h, c);
-}
-
-int gpt_transport_policy(gpt_handle* h, const double* pos, int64_t M, const double* R, const double* c_src, const double* c_dst,
-                         double scale, const double* R_jac, const double* vel, const double* ori, double* pos_rot, double* pos_out,
-                         double* var, double* vel_out, double* vel_var, double* det_vel, double* ori_out, double* det_ori,
-                         double* ori_gap, double* post_mean, double* post_J, double* post_Jvar, double* post_J_ori) {
-    TRANSPORT_CALL(c);
-    if (int rc = transport_check(h, "gpt_transport_policy", c)) return rc;
-    if (M == 0) return GPT_OK;
-    const size_t D = h->p.D;
-    if (!all_finite(pos, (size_t)M * D) || (vel && !all_finite(vel, (size_t)M * D)) || (ori && !all_finite(ori, (size_t)M * 4)) ||
-        !all_finite(R, D * D) || !all_finite(R_jac, D * D) || !all_finite(c_src, D) || !all_finite(c_dst, D) || !std::isfinite(scale))
-        return fail(GPT_E_ARG, "gpt_transport_policy: pos / vel / ori / the affine part contain NaN or infinity");
-    if (int rc = set_device(h)) return rc;
-    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
-    const int64_t nchunks = (M + cap - 1) / cap;
-    const size_t per[TP_COUNT] = {D, D, 4, D, D, 1, D, 1, 1, 4, 1, 1, D, D * D, D, D * D};       // doubles per query, by TP_*
-    const bool single = nchunks == 1;
-    if (!single) { if (int rc = ensure_copy_stream(h)) return rc; }
-    hipStream_t s = h->stream, cs = single ? h->stream : h->copy_stream;
-    // only what the caller asked for is staged and crosses the bus; the rest of what the epilogue reads stays in the handle's scratch
-    for (int b = 0; b < (single ? 1 : 2); ++b)
-        for (int k = 0; k < TP_COUNT; ++k)
-            if (c.arr[k]) CALLCHK(reserve(h->tp_st[b].buf[k], (size_t)cap * per[k] * sizeof(double), s, h->copy_stream));
-    CALLCHK(reserve(h->tp_affine, sizeof h->tp_affine_host, s));
-    double* ah = h->tp_affine_host;            // a member: the source of an asynchronous copy
-    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
-    std::fill(ah, ah + TP_AFFINE_DOUBLES, 0.0);
-    memcpy(ah, R, D * D * sizeof(double)); memcpy(ah + 9, R_jac, D * D * sizeof(double));
-    memcpy(ah + 18, c_src, D * sizeof(double)); memcpy(ah + 21, c_dst, D * sizeof(double));
-    CALLCHK(hipMemcpyAsync(h->tp_affine, ah, sizeof h->tp_affine_host, hipMemcpyHostToDevice, s));
-    // chunk i computes on `s` in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_predict_all)
-    auto enqueue = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        gpt_handle::TransportStaging& t = h->tp_st[b];
-        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
-        TransportCall d;
-        d.M = m; d.scale = scale; d.R = h->tp_affine; d.R_jac = h->tp_affine + 9; d.c_src = h->tp_affine + 18; d.c_dst = h->tp_affine + 21;
-        for (int k = 0; k < TP_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
-        for (int k = 0; k < TP_INPUTS; ++k)
-            if (c.arr[k]) CALLCHK(hipMemcpyAsync(t.buf[k], c.arr[k] + (size_t)off * per[k], (size_t)m * per[k] * sizeof(double), hipMemcpyHostToDevice, s));
-        if (int rc = transport_dev(h, d)) return rc;
-        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
-        return GPT_OK;
-    };
-    auto copy_out = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        const gpt_handle::TransportStaging& t = h->tp_st[b];
-        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
-        for (int k = TP_INPUTS; k < TP_COUNT; ++k)
-            if (c.arr[k]) CALLCHK(hipMemcpyAsync(c.arr[k] + (size_t)off * per[k], t.buf[k], (size_t)m * per[k] * sizeof(double), hipMemcpyDeviceToHost, cs));
-        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
-        return GPT_OK;
-    };
-    if (int rc = enqueue(0)) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
-        if (int rc = copy_out(i)) return rc;
-    }
-    if (!single) CALLCHK(hipStreamSynchronize(cs));
-    CALLCHK(hipStreamSynchronize(s));
-    return GPT_OK;
-}
-
-// ---- the transported policy at target-space points: Newton, affine inverse, dynamics mean and push-forward in one launch on the
-// map handle's stream; the two variance launches (unchanged), each on its own handle's stream; a one-thread-per-query epilogue
-namespace {
-
-// the arguments of both pullback entry points (host or device pointers alike), indexed by PB_*
-struct PullbackCall {
-    int64_t M = 0;
-    double scale = 1.0, rtol = 0.0, std_offset = 0.0;
-    int max_passes = 0;
-    const double *R = nullptr, *c_src = nullptr, *c_dst = nullptr, *R_jac = nullptr;
-    void* arr[PB_COUNT] = {};            // (the inputs PB_Y, PB_X0 are only read)
-};
-
-// what either model must be, in the words of inverse_check
-int pullback_model_check(const gpt_handle* h, const std::string& w, const char* role, bool is_map) {
-    const std::string r(role);
-    if (!h) return fail(GPT_E_ARG, w + ": NULL handle (" + r + ")");
-    if (!h->committed) return fail(GPT_E_STATE, w + ": the " + r + " model is not fitted");
-    const KernelParams& p = h->p;
-    if (p.D != p.O || p.D > 3)
-        return fail(GPT_E_ARG, w + ": the " + r + " model must map a space onto itself, D == O, with D <= 3 (this model: D = " +
-                                   std::to_string(p.D) + ", O = " + std::to_string(p.O) + ")");
-    if (p.dtype != DT_F64) return fail(GPT_E_ARG, w + ": fp64 models only (the " + r + " model was fitted with GPT_F32)");
-    if (p.ntask != 1) return fail(GPT_E_ARG, w + ": single-task models only (the " + r + " model is a multi-task gpt_fit_svgp model)");
-    if (!is_map) return GPT_OK;          // the dynamics are only evaluated: any of the four kernels
-    if (p.ktype == GPT_KERNEL_MATERN12)
-        return fail(GPT_E_ARG, w + ": a Matern 1/2 (nu = 0.5) map is not differentiable at the training points: Newton has no Jacobian "
-                                   "and the velocities nothing to be pushed through; use RBF, Matern 3/2 or Matern 5/2");
-    if (p.ktype != GPT_KERNEL_RBF && !h->matern_derivatives)
-        return fail(GPT_E_ARG, w + ": the pull-back through a Matern map uses the analytic derivatives of its posterior; "
-                                   "gpt_set_matern_derivatives(h_map, 1) enables them");
-    return GPT_OK;
-}
-
-// what both entry points refuse, in the order of the header's list
-int pullback_check(gpt_handle* hm, gpt_handle* hd, const char* who, const PullbackCall& c) {
-    const std::string w(who);
-    if (int rc = pullback_model_check(hm, w, "map", true)) return rc;
-    if (int rc = pullback_model_check(hd, w, "dynamics", false)) return rc;
-    if (hm == hd) return fail(GPT_E_ARG, w + ": h_map and h_dyn are the same handle; the map and the dynamics are two models");
-    if (hm->device != hd->device)
-        return fail(GPT_E_ARG, w + ": the two models live on different devices (map: " + std::to_string(hm->device) + ", dynamics: " +
-                                   std::to_string(hd->device) + "); gpt_factor_copy brings one to the other's");
-    if (hm->p.D != hd->p.D)
-        return fail(GPT_E_ARG, w + ": the map and the dynamics must share one space (map: D = " + std::to_string(hm->p.D) +
-                                   ", dynamics: D = " + std::to_string(hd->p.D) + ")");
-    if (!(c.rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
-    if (c.max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
-    if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
-    if (c.M > 0 && (!c.arr[PB_Y] || !c.arr[PB_VEL] || !c.arr[PB_STATUS] || !c.R || !c.c_src || !c.c_dst || !c.R_jac))
-        return fail(GPT_E_ARG, w + ": y, vel, status, R, c_src, c_dst and R_jac must not be NULL");
-    return GPT_OK;
-}
-
-int pullback_dev(gpt_handle* hm, gpt_handle* hd, const PullbackCall& c) {
-    if (int rc = set_device(hm)) return rc;
-    for (Event& e : hm->pb_ev)
-        if (!e) CALLCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-    hipStream_t s = hm->stream, sd = hd->stream;
-    const int64_t M = c.M;
-    const size_t D = hm->p.D;
-    void* const* u = c.arr;
-    // which intermediate quantities the outputs asked for consume
-    const bool need_var_dyn = u[PB_VAR_DYN] || u[PB_VVAR_DYN];
-    const bool need_jvar = u[PB_JVAR] || u[PB_VVAR_MAP];
-    const bool need_map = u[PB_MAP_VAR] || need_jvar;               // map_var and Jvar together: one pass of the 4-column launch
-    const bool epilogue = u[PB_VVAR_MAP] || u[PB_VVAR_DYN];
-    // each lives in the caller's array when there is one, else in the map handle's scratch
-    const struct { int which; bool need; size_t per; } mid[PB_SCRATCH] = {
-        {PB_X, need_var_dyn, D}, {PB_Z, need_map, D}, {PB_F, epilogue, D}, {PB_A, u[PB_VVAR_DYN] != nullptr, D * D},
-        {PB_VAR_DYN, need_var_dyn, 1}, {PB_JVAR, need_jvar, D}};
-    double* at[PB_SCRATCH];
-    for (int k = 0; k < PB_SCRATCH; ++k) {
-        at[k] = static_cast<double*>(u[mid[k].which]);
-        if (mid[k].need && !at[k]) {
-            CALLCHK(reserve(hm->pb_scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
-            at[k] = hm->pb_scratch[k];
-        }
-    }
-    PullbackArgs a{};
-    a.M = M; a.scale = c.scale; a.R = c.R; a.c_src = c.c_src; a.c_dst = c.c_dst; a.R_jac = c.R_jac;
-    a.Y = static_cast<const double*>(u[PB_Y]); a.X0 = static_cast<const double*>(u[PB_X0]);
-    a.rtol = c.rtol; a.max_passes = c.max_passes; a.std_offset = c.std_offset;
-    a.x = at[0]; a.z = at[1]; a.f = at[2]; a.A = at[3];
-    a.vel = static_cast<double*>(u[PB_VEL]); a.det = static_cast<double*>(u[PB_DET]); a.residual = static_cast<double*>(u[PB_RES]);
-    a.passes = static_cast<int*>(u[PB_PASSES]); a.status = static_cast<int*>(u[PB_STATUS]);
-    a.var_dyn = at[4]; a.Jvar = at[5];
-    a.vel_var_map = static_cast<double*>(u[PB_VVAR_MAP]); a.vel_var_dyn = static_cast<double*>(u[PB_VVAR_DYN]);
-    // what the dynamics handle's stream has enqueued so far (its fit, a gpt_factor_commit) comes first
-    CALLCHK(hipEventRecord(hm->pb_ev[0], sd));
-    CALLCHK(hipStreamWaitEvent(s, hm->pb_ev[0], 0));
-    launch_pullback_velocity(s, hm->p, static_cast<const double*>(hm->dXs()), static_cast<const double*>(hm->dA4()), hd->p,
-                             static_cast<const double*>(hd->dXs()), static_cast<const double*>(hd->dA4()), a);
-    // the dynamics handle's stream goes on once x is there and its model has been read
-    CALLCHK(hipEventRecord(hm->pb_ev[1], s));
-    CALLCHK(hipStreamWaitEvent(sd, hm->pb_ev[1], 0));
-    if (need_var_dyn) {                      // on h_dyn's own stream: the variance workspace belongs to the handle
-        if (int rc = gpt_predict_all_dev(hd, a.x, M, nullptr, at[4], nullptr, nullptr, nullptr)) return rc;
-        CALLCHK(hipEventRecord(hm->pb_ev[2], sd));
-    }
-    if (need_map) { if (int rc = gpt_predict_all_dev(hm, a.z, M, nullptr, u[PB_MAP_VAR], nullptr, need_jvar ? at[5] : nullptr, nullptr)) return rc; }
-    if (need_var_dyn) CALLCHK(hipStreamWaitEvent(s, hm->pb_ev[2], 0));
-    launch_pullback_variance(s, (int)D, a);
-    CALLCHK(hipGetLastError());
-    return GPT_OK;
-}
-
-}  // namespace
-
-#define PULLBACK_CALL(c)                                                                                                            \
-    PullbackCall c;                                                                                                                 \
-    c.M = M; c.scale = scale; c.rtol = rtol; c.max_passes = max_passes; c.std_offset = std_offset;                                  \
-    c.R = R; c.c_src = c_src; c.c_dst = c_dst; c.R_jac = R_jac;                                                                     \
-    {                                                                                                                               \
-        void* const all[PB_COUNT] = {const_cast<double*>(y), const_cast<double*>(x0), x, vel, f, det, residual, passes, status, var_dyn, \
-                                     map_var, vel_var_map, vel_var_dyn, post_z, post_A, post_Jvar};                                 \
-        for (int k = 0; k < PB_COUNT; ++k) c.arr[k] = all[k];                                                                       \
-    }
-
-int gpt_pullback_policy_dev(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M, const double* R,
-                            const double* c_src, const double* c_dst, double scale, const double* R_jac, double rtol, int max_passes,
-                            double std_offset, double* x, double* vel, double* f, double* det, double* residual, int* passes, int* status,
-                            double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
-                            double* post_Jvar) {
-    PULLBACK_CALL(c);
-    if (int rc = pullback_check(h_map, h_dyn, "gpt_pullback_policy_dev", c)) return rc;
-    if (M == 0) return GPT_OK;
-    return pullback_dev(h_map, h_dyn, c);
-}
-
-int gpt_pullback_policy(gpt_handle* h_map, gpt_handle* h_dyn, const double* y, const double* x0, int64_t M, const double* R,
-                        const double* c_src, const double* c_dst, double scale, const double* R_jac, double rtol, int max_passes,
-                        double std_offset, double* x, double* vel, double* f, double* det, double* residual, int* passes, int* status,
-                        double* var_dyn, double* map_var, double* vel_var_map, double* vel_var_dyn, double* post_z, double* post_A,
-                        double* post_Jvar) {
-    PULLBACK_CALL(c);
-    if (int rc = pullback_check(h_map, h_dyn, "gpt_pullback_policy", c)) return rc;
-    if (M == 0) return GPT_OK;
-    gpt_handle* const h = h_map;
-    const size_t D = h->p.D;
-    if (!all_finite(y, (size_t)M * D) || (x0 && !all_finite(x0, (size_t)M * D)) || !all_finite(R, D * D) || !all_finite(R_jac, D * D) ||
-        !all_finite(c_src, D) || !all_finite(c_dst, D) || !std::isfinite(scale) || !std::isfinite(rtol) || !std::isfinite(std_offset))
-        return fail(GPT_E_ARG, "gpt_pullback_policy: y / x0 / the affine part / rtol / std_offset contain NaN or infinity");
-    if (int rc = set_device(h)) return rc;
-    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
-    const int64_t nchunks = (M + cap - 1) / cap;
-    const size_t W = sizeof(double), I = sizeof(int);
-    const size_t per[PB_COUNT] = {D * W, D * W, D * W, D * W, D * W, W, W, I, I, W, W, W, D * W, D * W, D * D * W, D * W};   // bytes per query, by PB_*
-    const bool single = nchunks == 1;
-    if (!single) { if (int rc = ensure_copy_stream(h)) return rc; }
-    hipStream_t s = h->stream, cs = single ? h->stream : h->copy_stream;
-    // only what the caller asked for is staged and crosses the bus; the rest of what a later stage reads stays in the handle's scratch
-    for (int b = 0; b < (single ? 1 : 2); ++b)
-        for (int k = 0; k < PB_COUNT; ++k)
-            if (c.arr[k]) CALLCHK(reserve(h->pb_st[b].buf[k], (size_t)cap * per[k], s, h->copy_stream));
-    CALLCHK(reserve(h->tp_affine, sizeof h->tp_affine_host, s));
-    double* ah = h->tp_affine_host;            // a member: the source of an asynchronous copy
-    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
-    std::fill(ah, ah + TP_AFFINE_DOUBLES, 0.0);
-    memcpy(ah, R, D * D * sizeof(double)); memcpy(ah + 9, R_jac, D * D * sizeof(double));
-    memcpy(ah + 18, c_src, D * sizeof(double)); memcpy(ah + 21, c_dst, D * sizeof(double));
-    CALLCHK(hipMemcpyAsync(h->tp_affine, ah, sizeof h->tp_affine_host, hipMemcpyHostToDevice, s));
-    // chunk i computes in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_transport_policy)
-    auto enqueue = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        gpt_handle::PullbackStaging& t = h->pb_st[b];
-        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, h->ev_copied[b], 0));          // set b is free again
-        PullbackCall d = c;
-        d.M = m; d.R = h->tp_affine; d.R_jac = h->tp_affine + 9; d.c_src = h->tp_affine + 18; d.c_dst = h->tp_affine + 21;
-        for (int k = 0; k < PB_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
-        for (int k = 0; k < PB_INPUTS; ++k)
-            if (c.arr[k])
-                CALLCHK(hipMemcpyAsync(t.buf[k], static_cast<const unsigned char*>(c.arr[k]) + (size_t)off * per[k], (size_t)m * per[k],
-                                       hipMemcpyHostToDevice, s));
-        if (int rc = pullback_dev(h, h_dyn, d)) return rc;
-        if (!single) CALLCHK(hipEventRecord(h->ev_done[b], s));
-        return GPT_OK;
-    };
-    auto copy_out = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        const gpt_handle::PullbackStaging& t = h->pb_st[b];
-        if (!single) CALLCHK(hipStreamWaitEvent(cs, h->ev_done[b], 0));
-        for (int k = PB_INPUTS; k < PB_COUNT; ++k)
-            if (c.arr[k])
-                CALLCHK(hipMemcpyAsync(static_cast<unsigned char*>(c.arr[k]) + (size_t)off * per[k], t.buf[k], (size_t)m * per[k],
-                                       hipMemcpyDeviceToHost, cs));
-        if (!single) CALLCHK(hipEventRecord(h->ev_copied[b], cs));
-        return GPT_OK;
-    };
-    if (int rc = enqueue(0)) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
-        if (int rc = copy_out(i)) return rc;
-    }
-    if (!single) CALLCHK(hipStreamSynchronize(cs));
-    CALLCHK(hipStreamSynchronize(s));
-    return GPT_OK;
-}
-
-// ---- what gpt_pullback_chain (gpt_chain_host.hip) needs of a handle: gpt_chain.h
+// ---- what the host units that work on handles (gpt_transport_host.hip, gpt_chain_host.hip) need of one: gpt_stage.h
 extern "C++" {
 namespace gpt {
 
-int chain_handle_view(gpt_handle* h, const std::string& who, const std::string& role, bool is_map, ChainHandleView* v) {
-    if (int rc = pullback_model_check(h, who, role.c_str(), is_map)) return rc;
-    v->device = h->device; v->D = h->p.D; v->stream = h->stream;
-    v->m.N = h->p.N; v->m.ktype = h->p.ktype; v->m.lnc = h->p.lnc;
-    for (int d = 0; d < 3; ++d) v->m.inv_ls[d] = h->p.inv_ls[d];
-    v->m.Xs = static_cast<const double*>(h->dXs()); v->m.A4 = static_cast<const double*>(h->dA4());
+void model_view(gpt_handle* h, ModelView* v) {
+    v->committed = h->committed; v->matern_derivatives = h->matern_derivatives;
+    v->device = h->device; v->stream = h->stream; v->p = h->p;
+    if (h->committed) { v->Xs = static_cast<const double*>(h->dXs()); v->A4 = static_cast<const double*>(h->dA4()); }
+}
+
+static int create_events(CallResources& r, int events) {
+    for (int k = 0; k < events; ++k)
+        if (!r.ev[k]) CALLCHK(hipEventCreateWithFlags(&r.ev[k].h, hipEventDisableTiming));
     return GPT_OK;
 }
 
-static int chain_events(gpt_handle* h) {
-    for (Event& e : h->chain_ev)
-        if (!e) CALLCHK(hipEventCreateWithFlags(&e.h, hipEventDisableTiming));
-    ChainResources& r = *h->chain;
-    for (int k = 0; k < CHAIN_MAX; ++k) { r.ev_in[k] = h->chain_ev[2 * k]; r.ev_var[k] = h->chain_ev[2 * k + 1]; }
-    r.ev_mid = h->chain_ev[2 * CHAIN_MAX];
-    return GPT_OK;
-}
-
-ChainResources* chain_resources(gpt_handle* h) {
+CallResources* call_resources(gpt_handle* h, int family, int events) {
     if (set_device(h)) return nullptr;
-    if (!h->chain) h->chain = std::make_unique<ChainResources>();
-    return chain_events(h) ? nullptr : h->chain.get();
+    std::unique_ptr<CallResources>& r = h->call[family];
+    if (!r) r = std::make_unique<CallResources>();
+    return create_events(*r, events) ? nullptr : r.get();
 }
 
-int chain_copy_stream(gpt_handle* h, hipStream_t* copy_stream, hipEvent_t (&ev_done)[2], hipEvent_t (&ev_copied)[2]) {
-    if (int rc = ensure_copy_stream(h)) return rc;
-    *copy_stream = h->copy_stream;
-    for (int b = 0; b < 2; ++b) { ev_done[b] = h->ev_done[b]; ev_copied[b] = h->ev_copied[b]; }
+int handle_copy_stream(gpt_handle* h, bool create, ChunkStreams* q) {
+    if (create) { if (int rc = ensure_copy_stream(h)) return rc; }
+    q->s = h->stream; q->copy = h->copy_stream;
+    for (int b = 0; b < 2; ++b) { q->ev_done[b] = h->ev_done[b]; q->ev_copied[b] = h->ev_copied[b]; }
     return GPT_OK;
 }
 

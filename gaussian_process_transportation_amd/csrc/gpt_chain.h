@@ -8,10 +8,6 @@
 #pragma once
 #include "gpt_common.h"
 
-#include <string>
-
-struct gpt_handle;
-
 namespace gpt {
 
 constexpr int CHAIN_MAX = 4;             // = GPT_CHAIN_MAX of include/gpt_hip.h
@@ -66,36 +62,10 @@ void launch_chain_velocity(hipStream_t s, int D, const ChainArgs& a);
 // vel_var_map and vel_var_dyn, one thread per query
 void launch_chain_variance(hipStream_t s, int D, const ChainArgs& a);
 
-// ---- what gpt_chain_host.hip needs of a handle (gpt_api.hip owns the type)
 // arrays of gpt_pullback_chain, in the order of its arguments; ints: status, stage_status, stage_passes
 enum { CH_Y = 0, CH_X0, CH_X, CH_VEL, CH_F, CH_STATUS, CH_VAR_DYN, CH_VVAR_MAP, CH_VVAR_DYN, CH_STAGE_X, CH_STAGE_Z, CH_STAGE_A,
        CH_STAGE_JVAR, CH_STAGE_MAP_VAR, CH_STAGE_STATUS, CH_STAGE_PASSES, CH_STAGE_RES, CH_STAGE_DET, CH_COUNT };
 constexpr int CH_INPUTS = 2;             // CH_Y, CH_X0 travel to the device, the rest from it
 constexpr int CH_FIRST_STAGE = CH_STAGE_X;   // from here on (K,M,...) arrays
-constexpr int CH_SCRATCH = 6;            // x, f, var_dyn, stage_z, stage_A, stage_Jvar: what a later launch reads and the caller did not ask for
-constexpr int CH_AFFINE_DOUBLES = 24;    // per stage, the device image of the host call's affine part: R (9) | R_jac (9) | c_src (3) | c_dst (3)
-
-// Held by the handle of the LAST stage (created on first use): the scratch between the launches, the two staging sets and the
-// affine image of the host call, and the events that hand over between that handle's stream and the other handles'.  Grow-only.
-struct ChainResources {
-    DevBuf<double> scratch[CH_SCRATCH];
-    struct Staging { DevBuf<unsigned char> buf[CH_COUNT]; } st[2];
-    DevBuf<double> affine;
-    double affine_host[CHAIN_MAX * CH_AFFINE_DOUBLES] = {};     // a member: the source of an asynchronous copy
-    hipEvent_t ev_in[CHAIN_MAX] = {}, ev_mid = nullptr, ev_var[CHAIN_MAX] = {};     // (owned by the handle, next to this struct)
-};
-
-struct ChainHandleView {
-    int device = 0, D = 0;
-    hipStream_t stream = nullptr;
-    ChainModel m{};
-};
-
-// Checks one handle as gpt_pullback_policy checks its own (`role` goes into the message) and fills the view.  gpt_api.hip.
-int chain_handle_view(gpt_handle* h, const std::string& who, const std::string& role, bool is_map, ChainHandleView* v);
-// The handle's ChainResources with its events created; null after a HIP failure (the error text is set).  gpt_api.hip.
-ChainResources* chain_resources(gpt_handle* h);
-// The handle's copy stream and the per-staging-set events of its host calls (created on first use).  gpt_api.hip.
-int chain_copy_stream(gpt_handle* h, hipStream_t* copy_stream, hipEvent_t (&ev_done)[2], hipEvent_t (&ev_copied)[2]);
 
 }  // namespace gpt

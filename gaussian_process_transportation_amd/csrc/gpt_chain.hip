@@ -4,9 +4,9 @@
 // through all K maps in one launch:  x = Phi^-1(y),  v(y) = J_Phi(x) f(x).
 //
 //  k_chain_velocity : one wave owns one query from start to end, four waves per workgroup, one launch, one barrier at entry for
-//               the exp table.  With a guess x0 of the source-space preimage, a mean-only forward pass (pb_mean) through stages
+//               the exp table.  With a guess x0 of the source-space preimage, a mean-only forward pass (inv_mean) through stages
 //               0 .. K-2 gives every stage its start.  Then the stages are solved from the last to the first, each with the
-//               damped Newton iteration of k_pullback_velocity (pb_newton, gpt_pullback_wave.h) on z + psi_k(z) = y_k and the
+//               damped Newton iteration of k_pullback_velocity (inv_newton, gpt_newton.h) on z + psi_k(z) = y_k and the
 //               affine inverse x_k = gamma_k^-1(z_k), which is the y of the stage before; a stage that does not converge hands on
 //               the point it reached.  f = the dynamics mean at x_0 and vel = B_{K-1} ... B_1 (A_0 (R_jac,0 f)), B_k = A_k
 //               R_jac,k: the product of the outer stages is kept in registers as the sweep goes, the innermost stage is applied to
@@ -18,9 +18,7 @@
 //  k_chain_variance : one thread per query, plain fp64 FMA: the first-order propagation of each stage's Jacobian variance and
 //               of the dynamics variance through the stages after it.
 #include "gpt_chain.h"
-#include "gpt_dispatch.h"
 #include "gpt_newton.h"
-#include "gpt_pullback_wave.h"
 
 namespace gpt {
 
@@ -32,25 +30,10 @@ __device__ __forceinline__ void ch_mean(const ChainModel& m, const double* __res
 #pragma unroll
     for (int d = 0; d < D; ++d) qsc[d] = m.inv_ls[d] * 0.70710678118654752440;
     switch (m.ktype) {
-        case KT_MATERN12: pb_mean<KT_MATERN12, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        case KT_MATERN32: pb_mean<KT_MATERN32, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        case KT_MATERN52: pb_mean<KT_MATERN52, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        default: pb_mean<KT_RBF, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f);
-    }
-}
-
-// g = gamma(x) = scale R (x - c_src) + c_dst, the arithmetic of k_affine (gpt_transport.hip)
-template <int D>
-__device__ __forceinline__ void ch_affine(const ChainStage& S, const double (&x)[D], double (&g)[D]) {
-    double xc[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) xc[d] = x[d] - S.c_src[d];
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        double r = S.R[i * D] * xc[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(S.R[i * D + d], xc[d], r);
-        g[i] = fma(S.scale, r, S.c_dst[i]);
+        case KT_MATERN12: inv_mean<KT_MATERN12, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        case KT_MATERN32: inv_mean<KT_MATERN32, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        case KT_MATERN52: inv_mean<KT_MATERN52, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
+        default: inv_mean<KT_RBF, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f);
     }
 }
 
@@ -75,7 +58,7 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
         for (int d = 0; d < D; ++d) g[d] = a.X0[m * D + d];
         for (int k = 0; k < K; ++k) {
             double z0[D];
-            ch_affine<D>(a.st[k], g, z0);
+            sm_affine<D>(a.st[k], a.st[k].R, g, z0);     // the arithmetic of k_affine (gpt_transport.hip)
 #pragma unroll
             for (int j = 0; j < CHAIN_MAX; ++j)
                 if (j == k) {
@@ -122,13 +105,13 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
         int passes, status;
         switch (S.m.ktype) {                          // (no Matern 1/2: the API refuses such a stage before a launch is reached)
             case KT_MATERN32:
-                status = pb_newton<KT_MATERN32, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+                status = inv_newton<KT_MATERN32, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
                 break;
             case KT_MATERN52:
-                status = pb_newton<KT_MATERN52, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+                status = inv_newton<KT_MATERN52, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
                 break;
             default:
-                status = pb_newton<KT_RBF, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+                status = inv_newton<KT_RBF, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
         }
         if (first == INV_CONVERGED) first = status;
         // x = (z - c_dst) R / scale + c_src, the arithmetic of k_pullback_velocity
@@ -137,9 +120,7 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
         for (int d = 0; d < D; ++d) zc[d] = z[d] - S.c_dst[d];
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            double r = zc[0] * R[0][i];
-#pragma unroll
-            for (int d = 1; d < D; ++d) r = fma(zc[d], R[d][i], r);
+            const double r = sm_col_dot<D>(zc, R, i);
             x[i] = r / S.scale + S.c_src[i];
         }
         if (lane == 0) {
@@ -156,7 +137,7 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
             if (a.stage_status) a.stage_status[row] = status;
             if (a.stage_passes) a.stage_passes[row] = passes;
             if (a.stage_residual) a.stage_residual[row] = rho;
-            if (a.stage_det) a.stage_det[row] = inv_det<D>(A);
+            if (a.stage_det) a.stage_det[row] = sm_det<D>(A);
         }
         if (k > 0) {                                  // Q <- Q (A_k R_jac,k); the innermost stage is applied to f below
             double B[D][D], Qn[D][D];
@@ -172,12 +153,7 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
 #pragma unroll
             for (int o = 0; o < D; ++o)
 #pragma unroll
-                for (int e = 0; e < D; ++e) {
-                    double q = Q[o][0] * B[0][e];
-#pragma unroll
-                    for (int d = 1; d < D; ++d) q = fma(Q[o][d], B[d][e], q);
-                    Qn[o][e] = q;
-                }
+                for (int e = 0; e < D; ++e) Qn[o][e] = sm_mat_el<D>(Q, B, o, e);
 #pragma unroll
             for (int o = 0; o < D; ++o)
 #pragma unroll
@@ -192,12 +168,7 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
     // vel = Q (A_0 (R_jac,0 f)): A and x are stage 0's here
     const double* Rj = a.st[0].R_jac;
 #pragma unroll
-    for (int i = 0; i < D; ++i) {
-        double r = Rj[i * D] * f[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(Rj[i * D + d], f[d], r);
-        g[i] = r;
-    }
+    for (int i = 0; i < D; ++i) g[i] = sm_row_dot<D>(Rj, i, f);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
         double r = A[o][0] * g[0];
@@ -240,21 +211,13 @@ __global__ __launch_bounds__(256) void k_chain_variance(ChainArgs a) {
                 double g[D], s = 0.0;
 #pragma unroll
                 for (int i = 0; i < D; ++i) {
-                    double r = Rj[i * D] * v[0];
-#pragma unroll
-                    for (int d = 1; d < D; ++d) r = fma(Rj[i * D + d], v[d], r);
+                    const double r = sm_row_dot<D>(Rj, i, v);
                     g[i] = r;
                     s = fma(a.stage_Jvar[row * D + i], r * r, s);
                 }
                 sig[k] = s;
                 if (k + 1 < K) {
-#pragma unroll
-                    for (int o = 0; o < D; ++o) {
-                        double r = a.stage_A[(row * D + o) * D] * g[0];
-#pragma unroll
-                        for (int d = 1; d < D; ++d) r = fma(a.stage_A[(row * D + o) * D + d], g[d], r);
-                        v[o] = r;
-                    }
+                    sm_mat_vec<D>(a.stage_A + row * D * D, g, v);
                 }
             }
         }
@@ -295,12 +258,7 @@ __global__ __launch_bounds__(256) void k_chain_variance(ChainArgs a) {
 #pragma unroll
             for (int o = 0; o < D; ++o)
 #pragma unroll
-                for (int e = 0; e < D; ++e) {
-                    double q = Q[o][0] * B[0][e];
-#pragma unroll
-                    for (int d = 1; d < D; ++d) q = fma(Q[o][d], B[d][e], q);
-                    Qn[o][e] = q;
-                }
+                for (int e = 0; e < D; ++e) Qn[o][e] = sm_mat_el<D>(Q, B, o, e);
 #pragma unroll
             for (int o = 0; o < D; ++o)
 #pragma unroll
@@ -326,23 +284,13 @@ __global__ __launch_bounds__(256) void k_chain_variance(ChainArgs a) {
 void launch_chain_velocity(hipStream_t s, int D, const ChainArgs& a) {
     if (a.M <= 0) return;
     const dim3 grid((unsigned)((a.M + 3) / 4));           // one wave per query, four per workgroup (M < 2^31: the grid fits)
-    auto go = [&](auto d) { hipLaunchKernelGGL((k_chain_velocity<decltype(d)::value>), grid, dim3(256), 0, s, a); };
-    switch (D) {
-        case 1: go(Int<1>{}); break;
-        case 2: go(Int<2>{}); break;
-        default: go(Int<3>{});
-    }
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_chain_velocity<decltype(d)::value>), grid, dim3(256), 0, s, a); });
 }
 
 void launch_chain_variance(hipStream_t s, int D, const ChainArgs& a) {
     if (a.M <= 0 || !(a.vel_var_map || a.vel_var_dyn)) return;
     const dim3 grid((unsigned)((a.M + 255) / 256));
-    auto go = [&](auto d) { hipLaunchKernelGGL((k_chain_variance<decltype(d)::value>), grid, dim3(256), 0, s, a); };
-    switch (D) {
-        case 1: go(Int<1>{}); break;
-        case 2: go(Int<2>{}); break;
-        default: go(Int<3>{});
-    }
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_chain_variance<decltype(d)::value>), grid, dim3(256), 0, s, a); });
 }
 
 }  // namespace gpt

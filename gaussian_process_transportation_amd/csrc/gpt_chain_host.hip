@@ -1,26 +1,25 @@
 // gpt_pullback_chain / gpt_pullback_chain_dev (include/gpt_hip.h): argument checks, the scratch between the launches, the
 // hand-over between the handles' streams, and the chunked staging of the host call.  Host code only (the kernels: gpt_chain.hip,
-// reached through the launchers of gpt_chain.h; the handles: through the three accessors gpt_api.hip defines), so it also
-// compiles under g++ against host_stub/ and runs under the sanitizers (make host-oneshot-asan).
+// reached through the launchers of gpt_chain.h; the handles: through the accessors of gpt_stage.h), so it also compiles under
+// g++ against host_stub/ and runs under the sanitizers (make host-oneshot-asan).  The resources of the call (CALL_CHAIN) are held
+// by the handle of the LAST stage; its events: ev[j] the j-th other stream has caught up, ev[CHAIN_MAX + j] the variance launch on
+// it is done, ev[2 CHAIN_MAX] the velocity launch is done.
 #include "gpt_chain.h"
-#include "gpt_call.h"
-
-#include <algorithm>
-#include <cstring>
+#include "gpt_stage.h"
 
 using namespace gpt;
 
-namespace {
+static_assert(CHAIN_MAX == AFFINE_SLOTS, "the chain is the call with the most affine parts (gpt_stage.h)");
 
-constexpr int64_t HOST_CHUNK = 1 << 17;  // queries per chunk of the host entry (two chunks in flight), as gpt_pullback_policy's
+namespace {
 
 // the arguments of both entry points (host or device pointers alike), arrays indexed by CH_*
 struct ChainCall {
     int K = 0;
     gpt_handle* h[CHAIN_MAX] = {};
     gpt_handle* h_dyn = nullptr;
-    ChainHandleView v[CHAIN_MAX], v_dyn;
-    const double *R[CHAIN_MAX] = {}, *c_src[CHAIN_MAX] = {}, *c_dst[CHAIN_MAX] = {}, *R_jac[CHAIN_MAX] = {};
+    ModelView v[CHAIN_MAX], v_dyn;
+    AffinePart g[CHAIN_MAX] = {};
     double scale[CHAIN_MAX] = {};
     int64_t M = 0;
     double rtol = 0.0, std_offset = 0.0;
@@ -38,6 +37,15 @@ size_t row_bytes(int which, size_t D) {
     }
 }
 
+// what the wave-level passes read of a model
+ChainModel chain_model(const ModelView& v) {
+    ChainModel m{};
+    m.N = v.p.N; m.ktype = v.p.ktype; m.lnc = v.p.lnc;
+    for (int d = 0; d < 3; ++d) m.inv_ls[d] = v.p.inv_ls[d];
+    m.Xs = v.Xs; m.A4 = v.A4;
+    return m;
+}
+
 // what both entry points refuse, in the order of the header's list; fills the views
 int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
     const std::string w(who);
@@ -46,10 +54,10 @@ int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
     if (!stages) return fail(GPT_E_ARG, w + ": stages must not be NULL");
     for (int k = 0; k < c.K; ++k) {
         const std::string role = "stage " + std::to_string(k) + " map";
-        c.h[k] = stages[k].h; c.R[k] = stages[k].R; c.c_src[k] = stages[k].c_src; c.c_dst[k] = stages[k].c_dst; c.R_jac[k] = stages[k].R_jac;
+        c.h[k] = stages[k].h; c.g[k] = AffinePart{stages[k].R, stages[k].R_jac, stages[k].c_src, stages[k].c_dst};
         c.scale[k] = stages[k].scale;
         if (!c.h[k]) return fail(GPT_E_ARG, w + ": NULL handle (" + role + ")");
-        if (!c.R[k] || !c.c_src[k] || !c.c_dst[k] || !c.R_jac[k])
+        if (!c.g[k].R || !c.g[k].c_src || !c.g[k].c_dst || !c.g[k].R_jac)
             return fail(GPT_E_ARG, w + ": R, c_src, c_dst and R_jac must not be NULL (stage " + std::to_string(k) + ")");
     }
     if (!c.h_dyn) return fail(GPT_E_ARG, w + ": NULL handle (dynamics)");
@@ -60,19 +68,21 @@ int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
         if (c.h[k] == c.h_dyn)
             return fail(GPT_E_ARG, w + ": stage " + std::to_string(k) + " and h_dyn are the same handle; the maps and the dynamics are separate models");
     }
-    for (int k = 0; k < c.K; ++k)
-        if (int rc = chain_handle_view(c.h[k], w, "stage " + std::to_string(k) + " map", true, &c.v[k])) return rc;
-    if (int rc = chain_handle_view(c.h_dyn, w, "dynamics", false, &c.v_dyn)) return rc;
-    const ChainHandleView& last = c.v[c.K - 1];
     for (int k = 0; k < c.K; ++k) {
-        const ChainHandleView& v = k + 1 < c.K ? c.v[k] : c.v_dyn;
+        const std::string role = "stage " + std::to_string(k) + " map";
+        if (int rc = check_model(c.h[k], w, ModelCheck{role.c_str(), "", PULLBACK_MATERN12, PULLBACK_MATERN}, &c.v[k])) return rc;
+    }
+    if (int rc = check_model(c.h_dyn, w, ModelCheck{"dynamics", "", nullptr, nullptr}, &c.v_dyn)) return rc;
+    const ModelView& last = c.v[c.K - 1];
+    for (int k = 0; k < c.K; ++k) {
+        const ModelView& v = k + 1 < c.K ? c.v[k] : c.v_dyn;
         const std::string name = k + 1 < c.K ? "stage " + std::to_string(k) : std::string("the dynamics");
         if (v.device != last.device)
             return fail(GPT_E_ARG, w + ": the models live on different devices (stage " + std::to_string(c.K - 1) + ": " + std::to_string(last.device) +
                                        ", " + name + ": " + std::to_string(v.device) + "); gpt_factor_copy brings one to the other's");
-        if (v.D != last.D)
+        if (v.p.D != last.p.D)
             return fail(GPT_E_ARG, w + ": every map and the dynamics must share one space (stage " + std::to_string(c.K - 1) + ": D = " +
-                                       std::to_string(last.D) + ", " + name + ": D = " + std::to_string(v.D) + ")");
+                                       std::to_string(last.p.D) + ", " + name + ": D = " + std::to_string(v.p.D) + ")");
     }
     if (!(c.rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
     if (c.max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
@@ -85,11 +95,12 @@ int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
 int chain_dev(const ChainCall& c) {
     const int K = c.K;
     gpt_handle* const owner = c.h[K - 1];
-    ChainResources* const res = chain_resources(owner);
+    CallResources* const res = call_resources(owner, CALL_CHAIN, CALL_EVENTS);
     if (!res) return GPT_E_HIP;
+    const Event *ev_in = res->ev, *ev_var = res->ev + CHAIN_MAX, &ev_mid = res->ev[2 * CHAIN_MAX];
     hipStream_t s = c.v[K - 1].stream;
     const int64_t M = c.M;
-    const size_t D = c.v[K - 1].D;
+    const size_t D = c.v[K - 1].p.D;
     void* const* u = c.arr;
     // which intermediate quantities the outputs asked for consume
     const bool need_var_dyn = u[CH_VAR_DYN] || u[CH_VVAR_DYN];
@@ -97,25 +108,17 @@ int chain_dev(const ChainCall& c) {
     const bool need_map = u[CH_STAGE_MAP_VAR] || need_jvar;         // map_var and Jvar together: one pass of the 4-column launch
     const bool epilogue = u[CH_VVAR_MAP] || u[CH_VVAR_DYN];
     const bool need_A = u[CH_VVAR_DYN] || (u[CH_VVAR_MAP] && K > 1);
-    // each lives in the caller's array when there is one, else in the owner's scratch
-    const struct { int which; bool need; size_t per; } mid[CH_SCRATCH] = {
-        {CH_X, need_var_dyn, D}, {CH_F, epilogue, D}, {CH_VAR_DYN, need_var_dyn, 1},
-        {CH_STAGE_Z, need_map, K * D}, {CH_STAGE_A, need_A, K * D * D}, {CH_STAGE_JVAR, need_jvar, K * D}};
-    double* at[CH_SCRATCH];
-    for (int k = 0; k < CH_SCRATCH; ++k) {
-        at[k] = static_cast<double*>(u[mid[k].which]);
-        if (mid[k].need && !at[k]) {
-            CALLCHK(reserve(res->scratch[k], (size_t)M * mid[k].per * sizeof(double), s));
-            at[k] = res->scratch[k];
-        }
-    }
+    const MidArray mid[6] = {{CH_X, need_var_dyn, D}, {CH_F, epilogue, D}, {CH_VAR_DYN, need_var_dyn, 1},
+                             {CH_STAGE_Z, need_map, K * D}, {CH_STAGE_A, need_A, K * D * D}, {CH_STAGE_JVAR, need_jvar, K * D}};
+    double* at[6];
+    if (int rc = resolve_scratch(*res, u, mid, M, s, at)) return rc;
     ChainArgs a{};
     a.M = M; a.K = K;
     for (int k = 0; k < K; ++k) {
-        a.st[k].m = c.v[k].m;
-        a.st[k].R = c.R[k]; a.st[k].c_src = c.c_src[k]; a.st[k].c_dst = c.c_dst[k]; a.st[k].R_jac = c.R_jac[k]; a.st[k].scale = c.scale[k];
+        a.st[k].m = chain_model(c.v[k]);
+        a.st[k].R = c.g[k].R; a.st[k].c_src = c.g[k].c_src; a.st[k].c_dst = c.g[k].c_dst; a.st[k].R_jac = c.g[k].R_jac; a.st[k].scale = c.scale[k];
     }
-    a.dyn = c.v_dyn.m;
+    a.dyn = chain_model(c.v_dyn);
     a.Y = static_cast<const double*>(u[CH_Y]); a.X0 = static_cast<const double*>(u[CH_X0]);
     a.rtol = c.rtol; a.max_passes = c.max_passes; a.std_offset = c.std_offset;
     a.x = at[0]; a.f = at[1]; a.vel = static_cast<double*>(u[CH_VEL]); a.status = static_cast<int*>(u[CH_STATUS]);
@@ -129,20 +132,20 @@ int chain_dev(const ChainCall& c) {
     hipStream_t other[CHAIN_MAX];
     for (int j = 0; j < K; ++j) other[j] = j + 1 < K ? c.v[j].stream : c.v_dyn.stream;
     for (int j = 0; j < K; ++j) {
-        CALLCHK(hipEventRecord(res->ev_in[j], other[j]));
-        CALLCHK(hipStreamWaitEvent(s, res->ev_in[j], 0));
+        CALLCHK(hipEventRecord(ev_in[j], other[j]));
+        CALLCHK(hipStreamWaitEvent(s, ev_in[j], 0));
     }
     launch_chain_velocity(s, (int)D, a);
     // their streams go on once x and the z_k are there and their models have been read
-    CALLCHK(hipEventRecord(res->ev_mid, s));
-    for (int j = 0; j < K; ++j) CALLCHK(hipStreamWaitEvent(other[j], res->ev_mid, 0));
+    CALLCHK(hipEventRecord(ev_mid, s));
+    for (int j = 0; j < K; ++j) CALLCHK(hipStreamWaitEvent(other[j], ev_mid, 0));
     // each variance launch on its own handle's stream (the variance workspace belongs to the handle), one after the other: every
     // one of them is sized to fill the device, and two of them side by side take longer than one after the other
     hipEvent_t prev = nullptr;
     if (need_var_dyn) {
         if (int rc = gpt_predict_all_dev(c.h_dyn, a.x, M, nullptr, at[2], nullptr, nullptr, nullptr)) return rc;
-        CALLCHK(hipEventRecord(res->ev_var[K - 1], other[K - 1]));
-        prev = res->ev_var[K - 1];
+        CALLCHK(hipEventRecord(ev_var[K - 1], other[K - 1]));
+        prev = ev_var[K - 1];
     }
     if (need_map)
         for (int k = 0; k < K; ++k) {
@@ -153,8 +156,8 @@ int chain_dev(const ChainCall& c) {
                                              need_jvar ? at[5] + (size_t)k * M * D : nullptr, nullptr))
                 return rc;
             if (k + 1 < K) {
-                CALLCHK(hipEventRecord(res->ev_var[k], sk));
-                prev = res->ev_var[k];
+                CALLCHK(hipEventRecord(ev_var[k], sk));
+                prev = ev_var[k];
             }
         }
     else if (prev) CALLCHK(hipStreamWaitEvent(s, prev, 0));
@@ -195,79 +198,25 @@ extern "C" int gpt_pullback_chain(const gpt_chain_stage* stages, int K, gpt_hand
     const std::string w = "gpt_pullback_chain";
     if (int rc = chain_check(w.c_str(), stages, c)) return rc;
     if (M == 0) return GPT_OK;
-    const size_t D = c.v[K - 1].D;
+    const size_t D = c.v[K - 1].p.D;
     bool finite = all_finite(y, (size_t)M * D) && (!x0 || all_finite(x0, (size_t)M * D)) && std::isfinite(rtol) && std::isfinite(std_offset);
-    for (int k = 0; k < K && finite; ++k)
-        finite = all_finite(c.R[k], D * D) && all_finite(c.R_jac[k], D * D) && all_finite(c.c_src[k], D) && all_finite(c.c_dst[k], D) &&
-                 std::isfinite(c.scale[k]);
+    for (int k = 0; k < K && finite; ++k) finite = affine_finite(c.g[k], D) && std::isfinite(c.scale[k]);
     if (!finite) return fail(GPT_E_ARG, w + ": y / x0 / the affine parts / rtol / std_offset contain NaN or infinity");
     gpt_handle* const owner = c.h[K - 1];
-    ChainResources* const res = chain_resources(owner);
+    CallResources* const res = call_resources(owner, CALL_CHAIN, CALL_EVENTS);
     if (!res) return GPT_E_HIP;
-    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
-    const int64_t nchunks = (M + cap - 1) / cap;
-    const bool single = nchunks == 1;
-    hipStream_t s = c.v[K - 1].stream, cs = s;
-    hipEvent_t ev_done[2] = {}, ev_copied[2] = {};
-    if (!single) { if (int rc = chain_copy_stream(owner, &cs, ev_done, ev_copied)) return rc; }
-    // only what the caller asked for is staged and crosses the bus; the rest of what a later launch reads stays in the owner's scratch
-    size_t per[CH_COUNT];
-    for (int k = 0; k < CH_COUNT; ++k) per[k] = row_bytes(k, D);
-    for (int b = 0; b < (single ? 1 : 2); ++b)
-        for (int k = 0; k < CH_COUNT; ++k)
-            if (c.arr[k]) CALLCHK(reserve(res->st[b].buf[k], (size_t)cap * per[k] * (k >= CH_FIRST_STAGE ? K : 1), s, single ? nullptr : cs));
-    CALLCHK(reserve(res->affine, sizeof res->affine_host, s));
-    double* ah = res->affine_host;
-    CALLCHK(hipStreamSynchronize(s));          // (a copy out of it that an aborted call left in flight)
-    std::fill(ah, ah + CHAIN_MAX * CH_AFFINE_DOUBLES, 0.0);
-    for (int k = 0; k < K; ++k) {
-        double* q = ah + k * CH_AFFINE_DOUBLES;
-        memcpy(q, c.R[k], D * D * sizeof(double)); memcpy(q + 9, c.R_jac[k], D * D * sizeof(double));
-        memcpy(q + 18, c.c_src[k], D * sizeof(double)); memcpy(q + 21, c.c_dst[k], D * sizeof(double));
-    }
-    CALLCHK(hipMemcpyAsync(res->affine, ah, sizeof res->affine_host, hipMemcpyHostToDevice, s));
-    // chunk i computes in staging set i & 1; its outputs leave on `cs` while chunk i + 1 computes (as gpt_pullback_policy)
-    auto enqueue = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        ChainResources::Staging& t = res->st[b];
-        if (i >= 2) CALLCHK(hipStreamWaitEvent(s, ev_copied[b], 0));              // set b is free again
+    ChunkStreams q;
+    if (int rc = handle_copy_stream(owner, !one_chunk(M), &q)) return rc;
+    if (int rc = upload_affine(*res, CHAIN_MAX, c.g, K, D, q.s)) return rc;
+    // only what the caller asked for is staged and crosses the bus; the rest of what a later launch reads stays in the owner's
+    // scratch.  A per-stage array is K planes: stage j's rows start at j * M rows on the host and at j * m rows in a chunk's image
+    StagedArray table[CH_COUNT];
+    for (int k = 0; k < CH_COUNT; ++k) table[k] = StagedArray{c.arr[k], row_bytes(k, D), k < CH_INPUTS, k >= CH_FIRST_STAGE ? K : 1};
+    return run_chunked(res->st, q, table, M, [&](void* const* dev, int64_t m) {
         ChainCall d = c;
         d.M = m;
-        for (int k = 0; k < K; ++k) {
-            const double* q = res->affine + k * CH_AFFINE_DOUBLES;
-            d.R[k] = q; d.R_jac[k] = q + 9; d.c_src[k] = q + 18; d.c_dst[k] = q + 21;
-        }
-        for (int k = 0; k < CH_COUNT; ++k) d.arr[k] = c.arr[k] ? t.buf[k].p : nullptr;
-        for (int k = 0; k < CH_INPUTS; ++k)
-            if (c.arr[k])
-                CALLCHK(hipMemcpyAsync(t.buf[k], static_cast<const unsigned char*>(c.arr[k]) + (size_t)off * per[k], (size_t)m * per[k],
-                                       hipMemcpyHostToDevice, s));
-        if (int rc = chain_dev(d)) return rc;
-        if (!single) CALLCHK(hipEventRecord(ev_done[b], s));
-        return GPT_OK;
-    };
-    auto copy_out = [&](int64_t i) -> int {
-        const int b = (int)(i & 1);
-        const int64_t off = i * cap, m = (M - off) < cap ? (M - off) : cap;
-        const ChainResources::Staging& t = res->st[b];
-        if (!single) CALLCHK(hipStreamWaitEvent(cs, ev_done[b], 0));
-        for (int k = CH_INPUTS; k < CH_COUNT; ++k) {
-            if (!c.arr[k]) continue;
-            // a per-stage array: stage j's rows start at j * M rows on the host and at j * m rows in the chunk's image
-            for (int j = 0; j < (k >= CH_FIRST_STAGE ? K : 1); ++j)
-                CALLCHK(hipMemcpyAsync(static_cast<unsigned char*>(c.arr[k]) + ((size_t)j * M + off) * per[k], t.buf[k] + (size_t)j * m * per[k],
-                                       (size_t)m * per[k], hipMemcpyDeviceToHost, cs));
-        }
-        if (!single) CALLCHK(hipEventRecord(ev_copied[b], cs));
-        return GPT_OK;
-    };
-    if (int rc = enqueue(0)) return rc;
-    for (int64_t i = 0; i < nchunks; ++i) {
-        if (i + 1 < nchunks) { if (int rc = enqueue(i + 1)) return rc; }   // queued before chunk i's (host-blocking) copies
-        if (int rc = copy_out(i)) return rc;
-    }
-    if (!single) CALLCHK(hipStreamSynchronize(cs));
-    CALLCHK(hipStreamSynchronize(s));
-    return GPT_OK;
+        for (int k = 0; k < K; ++k) d.g[k] = affine_slot(res->affine, k);
+        std::copy(dev, dev + CH_COUNT, d.arr);
+        return chain_dev(d);
+    });
 }

@@ -14,9 +14,7 @@
 //               on the queries around it.
 //  k_pullback_variance : one thread per query, plain fp64 FMA: the two variances of vel from the variance launches' outputs.
 #include "gpt_pullback.h"
-#include "gpt_dispatch.h"
 #include "gpt_newton.h"
-#include "gpt_pullback_wave.h"
 
 namespace gpt {
 
@@ -42,21 +40,11 @@ __global__ __launch_bounds__(256) void k_pullback_velocity(KernelParams pm, cons
         y[d] = a.Y[m * D + d];
         z[d] = y[d];
     }
-    if (a.X0) {                                       // gamma(x0), the arithmetic of k_affine (gpt_transport.hip)
-        double x0[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) x0[d] = a.X0[m * D + d] - a.c_src[d];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            double r = R[i][0] * x0[0];
-#pragma unroll
-            for (int d = 1; d < D; ++d) r = fma(R[i][d], x0[d], r);
-            z[i] = fma(a.scale, r, a.c_dst[i]);
-        }
-    }
+    if (a.X0) sm_affine<D>(a, R, a.X0 + m * D, z);     // gamma(x0), the arithmetic of k_affine (gpt_transport.hip)
     int passes;
-    const int status = pb_newton<KT_MAP, D>(pm.N, pm.lnc, Xs_map, A4_map, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
-    // x = (z - c_dst) R / scale + c_src
+    const int status = inv_newton<KT_MAP, D>(pm.N, pm.lnc, Xs_map, A4_map, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
+    // x = (z - c_dst) R / scale + c_src.  Written out, where k_chain_velocity (gpt_chain.hip) calls sm_col_dot for the same sum:
+    // with the helper here the compiler commutes the final addition, and this kernel's instructions are to stay what they were
     double x[D], f[D], g[D], zc[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) zc[d] = z[d] - a.c_dst[d];
@@ -69,22 +57,13 @@ __global__ __launch_bounds__(256) void k_pullback_velocity(KernelParams pm, cons
     }
 #pragma unroll
     for (int d = 0; d < D; ++d) qsc[d] = pd.inv_ls[d] * 0.70710678118654752440;
-    pb_mean<KT_DYN, D>(pd.N, pd.lnc, Xs_dyn, A4_dyn, Tt, lane, qsc, x, f);
+    inv_mean<KT_DYN, D>(pd.N, pd.lnc, Xs_dyn, A4_dyn, Tt, lane, qsc, x, f);
     if (lane != 0) return;
     // vel = A (R_jac f)
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        double r = a.R_jac[i * D] * f[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(a.R_jac[i * D + d], f[d], r);
-        g[i] = r;
-    }
+    sm_mat_vec<D>(a.R_jac, f, g);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
-        double r = A[o][0] * g[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(A[o][d], g[d], r);
-        a.vel[m * D + o] = r;
+        a.vel[m * D + o] = sm_row_dot<D>(A, o, g);
         if (a.x) a.x[m * D + o] = x[o];
         if (a.z) a.z[m * D + o] = z[o];
         if (a.f) a.f[m * D + o] = f[o];
@@ -94,7 +73,7 @@ __global__ __launch_bounds__(256) void k_pullback_velocity(KernelParams pm, cons
         }
     }
     if (a.residual) a.residual[m] = rho;
-    if (a.det) a.det[m] = inv_det<D>(A);
+    if (a.det) a.det[m] = sm_det<D>(A);
     if (a.passes) a.passes[m] = passes;
     a.status[m] = status;
 }
@@ -114,9 +93,7 @@ __global__ __launch_bounds__(256) void k_pullback_variance(PullbackArgs a) {
         double v = 0.0;
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            double g = Rj[i][0] * f[0];
-#pragma unroll
-            for (int d = 1; d < D; ++d) g = fma(Rj[i][d], f[d], g);
+            const double g = sm_row_dot<D>(Rj, i, f);
             v = fma(a.Jvar[m * D + i], g * g, v);
         }
         a.vel_var_map[m] = v;
@@ -128,9 +105,7 @@ __global__ __launch_bounds__(256) void k_pullback_variance(PullbackArgs a) {
             double sum = 0.0;
 #pragma unroll
             for (int e = 0; e < D; ++e) {
-                double b = a.A[(m * D + o) * D] * Rj[0][e];               // (A R_jac)[o][e]
-#pragma unroll
-                for (int d = 1; d < D; ++d) b = fma(a.A[(m * D + o) * D + d], Rj[d][e], b);
+                const double b = sm_mat_el<D>(a.A + m * D * D, Rj, o, e);     // (A R_jac)[o][e]
                 sum = fma(b, b, sum);
             }
             a.vel_var_dyn[m * D + o] = s2 * sum;
@@ -147,15 +122,10 @@ void launch_pullback_velocity(hipStream_t s, const KernelParams& pm, const doubl
         if constexpr (KM != KT_MATERN12) {                 // (no derivative: the API refuses a Matern 1/2 map before a launch is reached)
             with_kernel_type(pd.ktype, [&](auto kd) {
                 constexpr int KD = decltype(kd)::value;
-                auto go = [&](auto d) {
+                with_small_dim(pm.D, [&](auto d) {
                     hipLaunchKernelGGL((k_pullback_velocity<KM, KD, decltype(d)::value>), grid, dim3(256), 0, s, pm, Xs_map, A4_map, pd, Xs_dyn,
                                        A4_dyn, a);
-                };
-                switch (pm.D) {
-                    case 1: go(Int<1>{}); break;
-                    case 2: go(Int<2>{}); break;
-                    default: go(Int<3>{});
-                }
+                });
             });
         }
     });
@@ -164,12 +134,7 @@ void launch_pullback_velocity(hipStream_t s, const KernelParams& pm, const doubl
 void launch_pullback_variance(hipStream_t s, int D, const PullbackArgs& a) {
     if (a.M <= 0 || !(a.vel_var_map || a.vel_var_dyn)) return;
     const dim3 grid((unsigned)((a.M + 255) / 256));
-    auto go = [&](auto d) { hipLaunchKernelGGL((k_pullback_variance<decltype(d)::value>), grid, dim3(256), 0, s, a); };
-    switch (D) {
-        case 1: go(Int<1>{}); break;
-        case 2: go(Int<2>{}); break;
-        default: go(Int<3>{});
-    }
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_pullback_variance<decltype(d)::value>), grid, dim3(256), 0, s, a); });
 }
 
 }  // namespace gpt

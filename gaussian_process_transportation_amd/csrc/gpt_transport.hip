@@ -11,7 +11,7 @@
 //               the column of the largest diagonal entry (lowest index on a tie), normalised, sign w >= 0.
 //               A query's result depends on its own row alone.
 #include "gpt_transport.h"
-#include "gpt_dispatch.h"
+#include "gpt_small.h"
 
 namespace gpt {
 
@@ -24,18 +24,9 @@ __global__ __launch_bounds__(256) void k_affine(TransportArgs a) {
     for (int d = 0; d < D; ++d) x[d] = a.pos[m * D + d] - a.c_src[d];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
-        double r = a.R[i * D] * x[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(a.R[i * D + d], x[d], r);
-        a.pos_rot[m * D + i] = fma(a.scale, r, a.c_dst[i]);
+        // (sm_affine's statement, kept here: through the helper the D = 3 instantiation merges its loads of R in another order)
+        a.pos_rot[m * D + i] = fma(a.scale, sm_row_dot<D>(a.R, i, x), a.c_dst[i]);
     }
-}
-
-template <int D> __device__ __forceinline__ double tp_det(const double (&A)[D][D]) {
-    if constexpr (D == 1) return A[0][0];
-    else if constexpr (D == 2) return A[0][0] * A[1][1] - A[0][1] * A[1][0];
-    else return A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
 }
 
 // B = (I + J[m]) Rj
@@ -46,15 +37,7 @@ __device__ __forceinline__ void tp_jacobian(const double* __restrict__ J, const 
     for (int o = 0; o < D; ++o)
 #pragma unroll
         for (int d = 0; d < D; ++d) A[o][d] = (o == d ? 1.0 : 0.0) + J[(m * D + o) * D + d];
-#pragma unroll
-    for (int o = 0; o < D; ++o)
-#pragma unroll
-        for (int e = 0; e < D; ++e) {
-            double b = A[o][0] * Rj[0][e];
-#pragma unroll
-            for (int d = 1; d < D; ++d) b = fma(A[o][d], Rj[d][e], b);
-            B[o][e] = b;
-        }
+    sm_mat_mat<D>(A, Rj, B);
 }
 
 // One Jacobi rotation in the (P,Q) plane of the symmetric K (both triangles kept), accumulated into V's columns.
@@ -148,16 +131,13 @@ __global__ __launch_bounds__(256) void k_push_forward(TransportArgs a) {
     if (a.det_vel) {
         double B[D][D];
         tp_jacobian<D>(a.J, m, Rj, B);
-        a.det_vel[m] = tp_det<D>(B);
+        a.det_vel[m] = sm_det<D>(B);
     }
     if (a.vel_out || a.vel_var) {
         double vr[D];                              // R_jac vel
 #pragma unroll
         for (int i = 0; i < D; ++i) {
-            double r = Rj[i][0] * a.vel[m * D];
-#pragma unroll
-            for (int d = 1; d < D; ++d) r = fma(Rj[i][d], a.vel[m * D + d], r);
-            vr[i] = r;
+            vr[i] = sm_row_dot<D>(Rj, i, a.vel + m * D);
         }
         if (a.vel_out) {
 #pragma unroll
@@ -180,7 +160,7 @@ __global__ __launch_bounds__(256) void k_push_forward(TransportArgs a) {
             double B[3][3], q[4], gap;
             tp_jacobian<3>(a.J_ori, m, Rj, B);
             tp_quaternion(B, q, gap);
-            if (a.det_ori) a.det_ori[m] = tp_det<3>(B);
+            if (a.det_ori) a.det_ori[m] = sm_det<3>(B);
             if (a.ori_gap) a.ori_gap[m] = gap;
             if (a.ori_out) {
                 const double bw = a.ori[m * 4], bx = a.ori[m * 4 + 1], by = a.ori[m * 4 + 2], bz = a.ori[m * 4 + 3];
@@ -195,29 +175,20 @@ __global__ __launch_bounds__(256) void k_push_forward(TransportArgs a) {
     if (a.det_ori) {
         double B[D][D];
         tp_jacobian<D>(a.J_ori, m, Rj, B);
-        a.det_ori[m] = tp_det<D>(B);
-    }
-}
-
-// f(Int<D>{}) for the D <= 3 of the transport
-template <class F> static void with_transport_dim(int D, F&& f) {
-    switch (D) {
-        case 1: f(Int<1>{}); break;
-        case 2: f(Int<2>{}); break;
-        default: f(Int<3>{});
+        a.det_ori[m] = sm_det<D>(B);
     }
 }
 
 void launch_transport_affine(hipStream_t s, int D, const TransportArgs& a) {
     if (a.M <= 0) return;
     const dim3 grid((unsigned)((a.M + 255) / 256));            // M < 2^31: the grid fits
-    with_transport_dim(D, [&](auto d) { hipLaunchKernelGGL((k_affine<decltype(d)::value>), grid, dim3(256), 0, s, a); });
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_affine<decltype(d)::value>), grid, dim3(256), 0, s, a); });
 }
 
 void launch_transport_push(hipStream_t s, int D, const TransportArgs& a) {
     if (a.M <= 0) return;
     const dim3 grid((unsigned)((a.M + 255) / 256));
-    with_transport_dim(D, [&](auto d) { hipLaunchKernelGGL((k_push_forward<decltype(d)::value>), grid, dim3(256), 0, s, a); });
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_push_forward<decltype(d)::value>), grid, dim3(256), 0, s, a); });
 }
 
 }  // namespace gpt

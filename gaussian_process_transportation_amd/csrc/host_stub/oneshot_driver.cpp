@@ -1,5 +1,6 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
-// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_inverse_map, gpt_transport_policy and gpt_pullback_policy (gpt_api.hip), gpt_pullback_chain (gpt_chain_host.hip)
+// gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
+// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -380,7 +381,45 @@ void inverse_map_cases() {
     done(GPT_OK, GPT_OK);
 }
 
-// ---- transport (gpt_api.hip): chunks of HOST_CHUNK through two staging sets, one buffer per array asked for ---------------------
+// ---- predict_all (gpt_api.hip): chunks of HOST_CHUNK through the handle's two staging sets in the model's element type T; dvar is
+// (D, M) plane-major, a chunk's image (D, m) ----------------------------------------------------------------------------------------
+template <class T> void predict_all_cases(int dtype, const char* tname) {
+    const int64_t N = 5, HOST_CHUNK = 1 << 17;
+    const T sent = (T)-7.25e30;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), ls{0.5, 0.75, 0.6};
+    const std::string who = std::string("gpt_predict_all ") + tname;
+    gpt_handle* h = nullptr;
+    begin(who + " setup");
+    CHECK(gpt_create(&h, 0) == GPT_OK && gpt_set_dtype(h, dtype) == GPT_OK);
+    CHECK(gpt_fit(h, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    long held = stub_live_objects;
+    enum { MEAN, VAR, J, JVAR, DVAR, N_OUT };                // bit k of `mask`: output k is asked for
+    const size_t width[N_OUT] = {3, 1, 9, 3, 3};
+    std::vector<int> masks;
+    const int ALL = (1 << N_OUT) - 1;
+    for (int k = 0; k < N_OUT; ++k) { masks.push_back(1 << k); masks.push_back(ALL & ~(1 << k)); }
+    for (int64_t M : {(int64_t)0, (int64_t)1, (int64_t)3, HOST_CHUNK - 1, HOST_CHUNK, HOST_CHUNK + 1, 2 * HOST_CHUNK + 3})   // growing; the last three walk both staging sets
+        for (int mask : masks) {
+            begin(who + " M=" + std::to_string(M) + " outputs=" + std::to_string(mask));
+            Arr<T> Xq((size_t)M * 3, (T)0.5);
+            std::vector<Arr<T>> out;
+            for (int k = 0; k < N_OUT; ++k) out.emplace_back((size_t)M * width[k], sent);
+            T* p[N_OUT];
+            for (int k = 0; k < N_OUT; ++k) p[k] = (mask >> k & 1) ? out[k].p : nullptr;
+            const int rc = gpt_predict_all(h, Xq.p, M, p[MEAN], p[VAR], p[J], p[JVAR], p[DVAR]);
+            CHECK(rc == GPT_OK);
+            CHECK(stub_live_objects >= held);                            // staging and the variance workspace are kept and regrown, never dropped
+            held = stub_live_objects;
+            for (int k = 0; k < N_OUT; ++k) CHECK(out[k].all(mask >> k & 1 ? (T)0 : sent));
+            printf("ok  %s\n", g_case.c_str());
+            ++g_cases;
+        }
+    begin(who + " teardown");
+    gpt_destroy(h);
+    done(GPT_OK, GPT_OK);
+}
+
+// ---- transport (gpt_transport_host.hip): chunks of HOST_CHUNK through two staging sets, one buffer per array asked for ----------
 void transport_cases() {
     const int64_t N = 5, HOST_CHUNK = 1 << 17;
     D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), ls{0.5, 0.75, 0.6};
@@ -463,7 +502,7 @@ void transport_cases() {
     done(GPT_OK, GPT_OK);
 }
 
-// ---- pull-back (gpt_api.hip): two handles, chunks of HOST_CHUNK through the map handle's two staging sets, int and double arrays ---
+// ---- pull-back (gpt_transport_host.hip): two handles, chunks of HOST_CHUNK through the map handle's two staging sets, int and double arrays ---
 void pullback_cases() {
     const int64_t N = 5, Nd = 7, HOST_CHUNK = 1 << 17;
     D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
@@ -686,6 +725,8 @@ int main() {
     svgp_cases("gpt_svgp", gpt_svgp_train, gpt_svgp_elbo_grad, false);
     svgp_cases("gpt_svgp_surface", gpt_svgp_surface_train, gpt_svgp_surface_elbo_grad, true);
     surface_predict_cases();
+    predict_all_cases<double>(GPT_F64, "fp64");
+    predict_all_cases<float>(GPT_F32, "fp32");
     inverse_map_cases();
     transport_cases();
     pullback_cases();

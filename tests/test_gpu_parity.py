@@ -1102,6 +1102,34 @@ def test_fp32_exact_gp_model():
         assert_parity(part["Jvar"], full["Jvar"][a:b], 1e-4, "Jvar across chunks (fp32)")
 
 
+def test_fp64_predict_all_with_dvar_across_the_chunk_boundary():
+    """The host-buffer path one query past the 131072-query chunk, fp64, every output asked for: dvar is (D, M) on the host
+    and (D, m) in a chunk's staging image, so each coordinate plane of each chunk has its own place in the result.  The same
+    rows as small calls of their own: mean and J come from per-query sums and must not move a bit; var, Jvar and dvar depend
+    on how the batch was tiled and agree to the 1e-10 of DESIGN section 2 ("the same queries inside a large batch").
+    N = 20: one 512-row tile per column block."""
+    from gaussian_process_transportation_amd import _lib
+    rng = np.random.default_rng(11)
+    X = rng.uniform(0, 1, (20, 3))
+    h = _lib.Handle(0)
+    try:
+        h.fit(X, np.sin(3 * X) + X[:, ::-1], np.array([0.3, 0.4, 0.5]), 0.8, 1e-3, 1e-10)
+        M = 131_072 + 1
+        big = rng.uniform(-0.1, 1.1, (M, 3))
+        want = dict(mean=True, var=True, J=True, Jvar=True, dvar=True)
+        full = h.predict_all(big, **want)
+        assert full["dvar"].shape == (3, M) and all(np.all(np.isfinite(v)) for v in full.values())
+        # the start; the 400 rows round the boundary and the last 500: at M = chunk + 1 both end at the one row past it
+        for a, b in ((0, 700), (M - 400, M), (M - 500, M)):
+            part = h.predict_all(big[a:b], **want)
+            assert np.array_equal(part["mean"], full["mean"][a:b]) and np.array_equal(part["J"], full["J"][a:b])
+            for k, ref in (("var", full["var"][a:b]), ("Jvar", full["Jvar"][a:b]), ("dvar", full["dvar"][:, a:b])):
+                print(f"rows [{a}, {b}) {k}: {relmax(part[k], ref):.3e}")
+                assert_parity(part[k], ref, 1e-10, f"{k} across chunks (fp64), rows [{a}, {b})")
+    finally:
+        h.close()
+
+
 def test_callable_optimizer_follows_sklearn_protocol():
     """sklearn accepts `optimizer=callable(obj_func, initial_theta, bounds) -> (theta_opt, func_min)` (_gpr.py:296-305,
     664-667).  A callable that runs scipy's L-BFGS-B itself must land where the built-in string option lands, and

@@ -22,7 +22,7 @@ LD = np.longdouble
 RTOL = 1e-10
 VAR_SPLIT_RTOL = 1e-11         # tests/test_gpu_parity.py::_two_rank_worker: |var - var'| <= 1e-11 max(var) between launch sizes
 GOLDEN_RTOL = 1e-5             # tests/test_gpu_parity.py: RTOL of the unfused path against the same goldens
-HOST_CHUNK = 1 << 17           # csrc/gpt_api.hip
+HOST_CHUNK = 1 << 17           # csrc/gpt_stage.h
 SENT = -7.25e300
 ISENT = -77
 G0 = {None: 1.0, 1.5: 3.0, 2.5: 5.0 / 3.0}          # kernel_g0 of csrc/gpt_exp.h: prior variance of d/dx_d is c g0 / l_d^2
