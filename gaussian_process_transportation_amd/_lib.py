@@ -114,6 +114,9 @@ SIGNATURES = {
                                 _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "gpt_batch_predict": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double,
                                     C.c_int, _dp, C.POINTER(_i64), _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "gpt_batch_optimize": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _i64,
+                                     _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -470,6 +473,51 @@ def batch_lml_objective_packed(X, Y, n_begin, length_scale, constant_value, nois
                                       ls.shape[1], dptr(c), dptr(noise), float(alpha), int(kernel_type), dptr(lml), dptr(grad),
                                       status.ctypes.data_as(C.POINTER(C.c_int))), "gpt_batch_lml_objective")
     return lml, grad, status
+
+
+GPT_OPT_PGTOL, GPT_OPT_FTOL, GPT_OPT_MAX_ITER, GPT_OPT_MAX_EVALS, GPT_OPT_LINESEARCH, GPT_OPT_NOT_PD_START = range(6)   # gpt_hip.h
+BATCH_MAX_R = 1 << 20
+
+
+def batch_opt_evals_per_launch():
+    """Objective evaluations a run may spend in one launch of the device search (GPT_BATCH_OPT_EVALS_PER_LAUNCH, default 64):
+    it bounds how long one launch can last."""
+    return int(os.environ.get("GPT_BATCH_OPT_EVALS_PER_LAUNCH", "64"))
+
+
+def batch_optimize_packed(X, Y, n_begin, n_ls, run_model, theta0, bounds, alpha, kernel_type=0, device=0, pgtol=1e-5, ftol=2.22e-9,
+                          max_iter=15000, max_evals=15000, evals_per_launch=None):
+    """gpt_batch_optimize on arrays in the ragged layout (batch_pack): R runs, run r minimising -LML of model run_model[r]
+    from theta0[r] (R, 2 + n_ls) = log [c, l.., noise] inside bounds (2 + n_ls, 2) (log space; lo == hi: fixed).  The defaults
+    are what sklearn passes to scipy's L-BFGS-B.  Returns (theta (R, 2 + n_ls), lml (R,), iterations (R,), evaluations (R,),
+    status (R,) GPT_OPT_*, launches)."""
+    who = "batch_optimize"
+    B, D = n_begin.size - 1, X.shape[1]
+    P = 2 + int(n_ls)
+    run_model = np.ascontiguousarray(run_model, dtype=np.int32)
+    theta0 = as_f64(theta0, 2, "theta0")
+    bounds = as_f64(bounds, 2, "bounds")
+    R = run_model.size
+    if not 1 <= R <= BATCH_MAX_R:
+        raise ValueError(f"{who}: a call holds 1 .. 2^20 runs, got {R}")
+    if theta0.shape != (R, P) or bounds.shape != (P, 2):
+        raise ValueError(f"{who}: theta0 must be (R, 2 + n_ls) = ({R}, {P}) and bounds (2 + n_ls, 2), got {theta0.shape} and {bounds.shape}")
+    if evals_per_launch is None:
+        evals_per_launch = batch_opt_evals_per_launch()
+    lib = load()
+    require_gpu()
+    theta = np.full((R, P), np.nan)
+    lml = np.full(R, np.nan)
+    iters, evals, status = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    ip = C.POINTER(C.c_int)
+    check(lib.gpt_batch_optimize(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(C.POINTER(_i64)), B, D, Y.shape[1], int(n_ls),
+                                 run_model.ctypes.data_as(ip), dptr(theta0), R, dptr(bounds), float(alpha), int(kernel_type), float(pgtol),
+                                 float(ftol), int(max_iter), int(max_evals), int(evals_per_launch), dptr(theta), dptr(lml),
+                                 iters.ctypes.data_as(ip), evals.ctypes.data_as(ip), status.ctypes.data_as(ip)), "gpt_batch_optimize")
+    # per round one launch for every size class that still has a live run; a run with E evaluations is live for ceil(E / epl) rounds
+    large = np.diff(n_begin)[run_model] > 32
+    launches = sum(int(-(-int(evals[large == cls].max()) // int(evals_per_launch))) for cls in (False, True) if (large == cls).any())
+    return theta, lml, iters, evals, status, launches
 
 
 def batch_lml_objective(Xs, Ys, length_scale, constant_value, noise_level, alpha, kernel_type=0, device=0):

@@ -7,7 +7,10 @@ The driver stays scipy's L-BFGS-B; what changes is who evaluates the objective. 
 on a thread of its own, and its objective callback hands (model, theta) to a coalescer and blocks.  Once every live run is
 waiting, the coalescer evaluates all pending requests with ONE gpt_batch_lml_objective call — one workgroup per request —
 and hands the results back.  A model's objective does not depend on the batch around it (bit for bit), so every run sees the
-values it would see alone and ends at the same optimum whatever the number of runs driven at once."""
+values it would see alone and ends at the same optimum whatever the number of runs driven at once.
+
+optimizer='device_bfgs' (opt-in) keeps the protocol — the same start points from the same RNG draws, the best run per model —
+and hands all runs to gpt_batch_optimize, which carries each through a projected BFGS iteration on the device."""
 from __future__ import annotations
 
 import os
@@ -36,13 +39,49 @@ def _stall_seconds():
     return float(os.environ.get("GPT_BATCH_OPT_STALL_S", "120"))
 
 
+DEVICE_SEARCH = "device_bfgs"                  # the opt-in search that runs on the device (gpt_batch_optimize)
+
+
 def check_optimizer(optimizer):
     """Refuses what cannot drive a batch (None, meaning no search, is the caller's business)."""
     if callable(optimizer):
         raise ValueError("a callable optimizer cannot drive a batch: its runs share threads and one batched objective, and "
                          "whether the callable is re-entrant is unknown.  Use optimizer='fmin_l_bfgs_b', or a loop of GaussianProcess")
-    if optimizer is not None and optimizer != "fmin_l_bfgs_b":
+    if optimizer is not None and optimizer not in ("fmin_l_bfgs_b", DEVICE_SEARCH):
         raise ValueError(f"Unknown optimizer {optimizer}.")            # sklearn/_gpr.py:668-669
+
+
+def _device_search(kernel, runs, free, n_ls, X_all, Y_all, n_begin, alpha, kernel_type, device, stats):
+    """Every run carried through a projected BFGS iteration on the device, one workgroup per run (gpt_batch_optimize):
+    [(theta (free components), f = -LML, warning or None)] in the order of `runs`, the shape of the scipy path's results."""
+    p = kernel.get_params()
+    fixed = np.log(np.concatenate([[float(p["k1__k1__constant_value"])], np.atleast_1d(np.asarray(p["k1__k2__length_scale"], dtype=np.float64)),
+                                   [float(p["k2__noise_level"])]]))
+    if not np.isfinite(kernel.bounds).all():
+        raise ValueError(f"optimizer='{DEVICE_SEARCH}' requires that all bounds are finite.")
+    if not np.isfinite(fixed[~free]).all():
+        raise ValueError(f"optimizer='{DEVICE_SEARCH}' searches in log space: a fixed hyper-parameter must be > 0")
+    bounds = np.column_stack([fixed, fixed])                       # (2 + n_ls, 2), log space; lo == hi: fixed
+    bounds[free] = kernel.bounds
+    theta0 = np.tile(fixed, (len(runs), 1))
+    theta0[:, free] = np.array([t for _, t in runs])
+    run_model = np.array([m for m, _ in runs], dtype=np.int32)
+    theta, lml, iters, evals, status, launches = _lib.batch_optimize_packed(X_all, Y_all, n_begin, n_ls, run_model, theta0, bounds, alpha,
+                                                                            kernel_type, device)
+    if stats is not None:
+        stats.update(runs=len(runs), launches=int(launches), evaluations=int(np.sum(evals)))
+    names = {_lib.GPT_OPT_MAX_ITER: "MAX_ITER", _lib.GPT_OPT_MAX_EVALS: "MAX_EVALS", _lib.GPT_OPT_LINESEARCH: "LINESEARCH"}
+    out = []
+    for r in range(len(runs)):
+        msg = None
+        if int(status[r]) in names:            # what the scipy path says of a non-zero status
+            msg = (f"{DEVICE_SEARCH} failed to converge (status={int(status[r])}): {names[int(status[r])]} after {int(iters[r])} "
+                   f"iterations and {int(evals[r])} evaluations")
+        if status[r] == _lib.GPT_OPT_NOT_PD_START:
+            out.append((np.array(runs[r][1]), np.inf, None))
+        else:
+            out.append((theta[r][free], -float(lml[r]), msg))
+    return out
 
 
 class _Coalescer:
@@ -114,7 +153,7 @@ def optimize_hyperparameters_batch(kernel, Xs, Ys, alpha=1e-10, optimizer="fmin_
                                    device=0, stats=None):
     """One (c, ls, noise, lml) per model, each maximising its log-marginal likelihood as sklearn would from `kernel`.
     Xs, Ys: validated sequences of (n_b, D) / (n_b, O) float64 arrays.  stats (a dict, optional) receives the number of
-    batched objective calls and of runs."""
+    batched objective calls and of runs; with optimizer='device_bfgs' the numbers of runs, launches and objective evaluations."""
     check_optimizer(optimizer)
     B = len(Xs)
     p = kernel.get_params()
@@ -139,6 +178,9 @@ def optimize_hyperparameters_batch(kernel, Xs, Ys, alpha=1e-10, optimizer="fmin_
 
     X_all, Y_all, n_begin = _lib.batch_pack(Xs, Ys, "optimize_hyperparameters_batch")
     rows = [np.arange(n_begin[m], n_begin[m + 1]) for m in range(B)]
+    if optimizer == DEVICE_SEARCH:
+        results = _device_search(kernel, runs, free, n_ls, X_all, Y_all, n_begin, alpha, kernel_type, device, stats)
+        return _best_per_model(kernel, results, B, n_restarts_optimizer)
     sizes = np.diff(n_begin)
 
     def evaluate(requests):
@@ -195,6 +237,11 @@ def optimize_hyperparameters_batch(kernel, Xs, Ys, alpha=1e-10, optimizer="fmin_
         stats.update(calls=co.calls, runs=len(runs))
     if errors:
         raise errors[0]
+    return _best_per_model(kernel, results, B, n_restarts_optimizer)
+
+
+def _best_per_model(kernel, results, B, n_restarts_optimizer):
+    """results: (theta, f, warning or None) per run, a model's runs together.  Warns, then keeps each model's best run."""
     for _, _, msg in results:
         if msg:
             warnings.warn(msg)                 # on the caller's thread: the warnings module's state is global

@@ -19,62 +19,17 @@
 // Every sum runs in an order fixed by (n, D, O) alone: a model's results do not depend on the batch around it, a query's not
 // on the other queries — bit for bit.  That is why the size class is chosen per model, not per batch.
 //
-// Device side only: the kernels and the two launchers of gpt_batch.h.  The entry points are in gpt_batch_host.hip.
+// Device side only: the kernels and the two launchers of gpt_batch.h.  The entry points are in gpt_batch_host.hip.  The size
+// classes (BatCfg), block_sum and kernel_libm_g are in gpt_batch_device.h, with bat_factor's body restated as a function for
+// bat_optimize (gpt_batch_opt.hip): a change to the body below belongs there too.
 #include "gpt_batch.h"
+#include "gpt_batch_device.h"
 #include "gpt_dispatch.h"
 #include "gpt_exp.h"
 #include "../../include/gpt_hip.h"
 
 namespace gpt {
 namespace {
-
-constexpr int BAT_RED = 4 + MAX_DIMS;    // values of the final reduction: y.alpha, sum log L_ii, d/dc, trace, d/dl_d
-
-// One size class: threads, their TX x TY arrangement over a triangle, row stride of the image, dynamic LDS.
-template <int NMAX> struct BatCfg {
-    static constexpr int NT = NMAX <= BAT_SMALL_N ? 64 : 256;
-    static constexpr int TX = NMAX <= BAT_SMALL_N ? 8 : 16;
-    static constexpr int TY = NT / TX;
-    static constexpr int LD = NMAX + 1;
-    static constexpr int PER_THREAD = NMAX * BAT_MAX_O / NT;          // (point, output) pairs a thread owns
-    static constexpr size_t factor_lds = ((size_t)NMAX * LD + (size_t)NMAX * BAT_MAX_O + NMAX) * sizeof(double);
-    static constexpr int W_PACKED = NMAX * (NMAX + 1) / 2;
-    static constexpr size_t predict_lds = ((size_t)W_PACKED + (size_t)NMAX * BAT_QT + (size_t)NMAX * MAX_DIMS + 256) * sizeof(double);
-};
-
-// c g(r) of dK/dlog l_d = c g(r) ((x_d - x'_d) / l_d)^2 (sklearn/gaussian_process/kernels.py:1568-1580, 1747-1778), beside
-// kernel_libm's c k(r): RBF g = k, Matern 1/2 k / r, 3/2 3 e^{-sqrt3 r}, 5/2 5/3 (1 + sqrt5 r) e^{-sqrt5 r}
-template <int KT>
-__device__ __forceinline__ double kernel_libm_g(const double c, const double r2, const double kv) {
-    if (KT == KT_RBF) return kv;
-    const double r = sqrt(r2);
-    if (KT == KT_MATERN12) return r > 0.0 ? kv / r : 0.0;
-    if (KT == KT_MATERN32) return 3.0 * c * exp(-1.7320508075688772 * r);
-    const double t = 2.23606797749979 * r;
-    return (5.0 / 3.0) * c * (1.0 + t) * exp(-t);
-}
-
-// Sums of NV values over the workgroup, in a fixed order (butterfly inside a wave, then the waves in turn); every thread
-// receives them.  Ends with a barrier: `red` may be reused at once.
-template <int NT, int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NT / 64]) {
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        double s = v[q];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (threadIdx.x % 64 == 0) red[q][threadIdx.x / 64] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NV; ++q) {
-        double s = red[q][0];
-#pragma unroll
-        for (int w = 1; w < NT / 64; ++w) s += red[q][w];
-        v[q] = s;
-    }
-    __syncthreads();
-}
 
 template <int NMAX, int KT, bool OBJ>
 __global__ __launch_bounds__(BatCfg<NMAX>::NT) void bat_factor(BatArgs a) {

@@ -1,0 +1,118 @@
+// Entry point of the device hyper-parameter search of a batch of small GPs — gpt_batch_optimize (include/gpt_hip.h): argument
+// checks, the device images of the call, the relaunch loop over the runs still live, the read-back.  Host code only (the kernel:
+// gpt_batch_opt.hip, reached through the launcher of gpt_batch_opt.h), so it also compiles under g++ against host_stub/ and runs
+// under the sanitizers (make host-oneshot-asan).
+#include "gpt_batch_opt.h"
+#include "gpt_call.h"
+
+#include <algorithm>
+
+using namespace gpt;
+
+extern "C" int gpt_batch_optimize(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O, int n_ls,
+                                  const int* run_model, const double* theta0, int64_t R, const double* bounds, double alpha_jitter,
+                                  int kernel_type, double pgtol, double ftol, int max_iter, int max_evals, int evals_per_launch,
+                                  double* theta, double* lml, int* iterations, int* evaluations, int* status) {
+    const std::string w = "gpt_batch_optimize";
+    if (!X || !Y || !n_begin || !run_model || !theta0 || !bounds || !theta || !lml || !iterations || !evaluations || !status)
+        return fail(GPT_E_ARG, w + ": NULL argument");
+    if (B < 1 || B > BAT_MAX_B) return fail(GPT_E_ARG, w + ": B (models) must be 1 .. 2^20, got " + std::to_string(B));
+    if (R < 1 || R > BAT_OPT_MAX_R) return fail(GPT_E_ARG, w + ": R (runs) must be 1 .. 2^20, got " + std::to_string(R));
+    if (D < 1 || D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
+    if (O < 1 || O > BAT_MAX_O) return fail(GPT_E_ARG, w + ": O (outputs) must be 1 .. 16, got " + std::to_string(O));
+    if (n_ls != 1 && n_ls != D) return fail(GPT_E_ARG, w + ": n_ls must be 1 or D");
+    if (kernel_type < GPT_KERNEL_RBF || kernel_type > GPT_KERNEL_MATERN52) return fail(GPT_E_ARG, w + ": unknown kernel_type");
+    if (!(alpha_jitter >= 0) || !std::isfinite(alpha_jitter)) return fail(GPT_E_ARG, w + ": alpha_jitter must be finite and >= 0");
+    if (!(pgtol > 0) || !(ftol > 0) || !std::isfinite(pgtol) || !std::isfinite(ftol))
+        return fail(GPT_E_ARG, w + ": pgtol and ftol must be finite and > 0");
+    if (max_iter < 1 || max_evals < 1 || evals_per_launch < 1)
+        return fail(GPT_E_ARG, w + ": max_iter, max_evals and evals_per_launch must be >= 1");
+    if (n_begin[0] != 0) return fail(GPT_E_ARG, w + ": n_begin[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = n_begin[b + 1] - n_begin[b];
+        if (n < 1 || n > BAT_MAX_N)
+            return fail(GPT_E_ARG, w + ": every model needs 1 <= n_b <= 128 points with increasing offsets; model " + std::to_string(b) +
+                                       " has n_begin " + std::to_string(n_begin[b]) + " .. " + std::to_string(n_begin[b + 1]));
+    }
+    const size_t rows = (size_t)n_begin[B], P = 2 + (size_t)n_ls, nx = rows * D, ny = rows * O;
+    if (!all_finite(X, nx) || !all_finite(Y, ny)) return fail(GPT_E_ARG, w + ": X or Y contains NaN or infinity");
+    if (!all_finite(bounds, 2 * P) || !all_finite(theta0, (size_t)R * P))
+        return fail(GPT_E_ARG, w + ": bounds or theta0 contains NaN or infinity");
+    for (size_t i = 0; i < P; ++i)
+        if (bounds[2 * i] > bounds[2 * i + 1])
+            return fail(GPT_E_ARG, w + ": bounds need lo <= hi (component " + std::to_string(i) + ")");
+    // the runs of this call, the small size class first; a run's class is its model's
+    std::vector<int> live, large;
+    live.reserve(R);
+    for (int64_t r = 0; r < R; ++r) {
+        const int b = run_model[r];
+        if (b < 0 || b >= B) return fail(GPT_E_ARG, w + ": run_model must be 0 .. B - 1 (run " + std::to_string(r) + ")");
+        (n_begin[b + 1] - n_begin[b] <= BAT_SMALL_N ? live : large).push_back((int)r);
+    }
+    int n_small = (int)live.size();
+    live.insert(live.end(), large.begin(), large.end());
+
+    if (int rc = use_device(w, device)) return rc;
+    CallBuffers buf;
+    CALLCHK(buf.open());
+    // doubles: X | Y | bounds | theta (the clipped starts, then the results) | lml | records
+    // ints:    n_begin (int64) | run_model | list | status | iterations | evaluations | counters
+    const size_t rec = bat_opt_record((int)P), nin = nx + ny + 2 * P + (size_t)R * P;
+    std::vector<double> hd;
+    hd.reserve(nin);
+    hd.insert(hd.end(), X, X + nx);
+    hd.insert(hd.end(), Y, Y + ny);
+    hd.insert(hd.end(), bounds, bounds + 2 * P);
+    for (int64_t r = 0; r < R; ++r)
+        for (size_t i = 0; i < P; ++i) hd.push_back(std::min(std::max(theta0[r * P + i], bounds[2 * i]), bounds[2 * i + 1]));
+    double* dd;
+    int64_t* dnb;
+    int* di;
+    CALLCHK(buf.alloc(&dd, nin + (size_t)R + (size_t)R * rec));
+    CALLCHK(buf.alloc(&dnb, (size_t)B + 1));
+    CALLCHK(buf.alloc(&di, (size_t)R * (5 + BAT_OPT_CNT)));
+    BatOptArgs a{};
+    a.X = dd; a.Y = dd + nx; a.bounds = dd + nx + ny; a.theta = dd + nx + ny + 2 * P; a.lml = dd + nin; a.rec = a.lml + R;
+    a.n_begin = dnb;
+    int* dlist = di + R;
+    a.run_model = di; a.list = dlist; a.status = di + 2 * R; a.iters = di + 3 * R; a.evals = di + 4 * R; a.cnt = di + 5 * R;
+    a.D = D; a.O = O; a.n_ls = n_ls; a.max_iter = max_iter; a.max_evals = max_evals; a.max_ls = BAT_OPT_MAX_LS;
+    a.evals_per_launch = evals_per_launch; a.jitter = alpha_jitter; a.pgtol = pgtol; a.ftol = ftol;
+    CALLCHK(hipMemcpyAsync(dd, hd.data(), nin * sizeof(double), hipMemcpyHostToDevice, buf.stream));
+    CALLCHK(hipMemcpyAsync(dnb, n_begin, ((size_t)B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, buf.stream));
+    CALLCHK(hipMemcpyAsync(di, run_model, (size_t)R * sizeof(int), hipMemcpyHostToDevice, buf.stream));
+    CALLCHK(hipMemsetAsync(a.status, 0xFF, (size_t)R * sizeof(int), buf.stream));                 // BAT_OPT_LIVE
+    CALLCHK(hipMemsetAsync(a.iters, 0, (size_t)R * (2 + BAT_OPT_CNT) * sizeof(int), buf.stream));   // iterations | evaluations | counters
+
+    // every launch spends at least one evaluation of every live run, and a run ends at max_evals at the latest
+    std::vector<int> st(R);
+    for (int64_t round = 0; !live.empty(); ++round) {
+        if (round > max_evals) return fail(GPT_E_HIP, w + ": runs still live after max_evals launches");
+        CALLCHK(hipMemcpyAsync(dlist, live.data(), live.size() * sizeof(int), hipMemcpyHostToDevice, buf.stream));
+        launch_bat_optimize(buf.stream, kernel_type, n_small, (int)live.size() - n_small, a);
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipMemcpyAsync(st.data(), a.status, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, buf.stream));
+        CALLCHK(hipStreamSynchronize(buf.stream));          // `live` is rewritten below
+        size_t kept = 0;
+        int kept_small = 0;
+        for (size_t k = 0; k < live.size(); ++k)
+            if (st[live[k]] == BAT_OPT_LIVE) {
+                if ((int)k < n_small) ++kept_small;
+                live[kept++] = live[k];
+            }
+        live.resize(kept);
+        n_small = kept_small;
+    }
+
+    std::vector<double> out((size_t)R * (P + 1));            // theta | lml are adjacent on the device
+    std::vector<int> outi((size_t)R * 2);                    // iterations | evaluations
+    CALLCHK(hipMemcpyAsync(out.data(), a.theta, out.size() * sizeof(double), hipMemcpyDeviceToHost, buf.stream));
+    CALLCHK(hipMemcpyAsync(outi.data(), a.iters, outi.size() * sizeof(int), hipMemcpyDeviceToHost, buf.stream));
+    CALLCHK(hipStreamSynchronize(buf.stream));
+    std::copy(out.begin(), out.begin() + (size_t)R * P, theta);
+    std::copy(out.begin() + (size_t)R * P, out.end(), lml);
+    std::copy(outi.begin(), outi.begin() + R, iterations);
+    std::copy(outi.begin() + R, outi.end(), evaluations);
+    std::copy(st.begin(), st.end(), status);
+    return GPT_OK;
+}

@@ -1,4 +1,4 @@
-// Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_select_host.hip,
+// Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
 // gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
@@ -21,6 +21,7 @@
 namespace gpt {
 extern int stub_fail_model;      // stub_launchers.cpp
 extern bool stub_fail_flag;
+extern int stub_opt_launches, stub_opt_launch_count;
 }
 
 namespace {
@@ -182,6 +183,74 @@ void batch_refusals() {
     done(gpt_batch_predict(0, X.p, Y.p, in.n_begin.p, 3, 3, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_MATERN52, Xq.p, q_begin.p, nullptr,
                            nullptr, mean.p, nullptr, nullptr, status.p), GPT_E_ARG);
     CHECK(lml.all(SENT) && grad.all(SENT) && alpha.all(SENT) && mean.all(SENT) && status.all(ISENT));
+}
+
+// ---- batch search -------------------------------------------------------------------------------------------------------------
+// R runs spread over the models (run r: model r % B), ending after 1 .. slices launches (stub_opt_launches): the relaunch loop
+// makes exactly `slices` rounds, one launch per size class that still has a live run, and compacts its list between them.  A
+// run that has ended holds zeros in its outputs and its number of launches in `evaluations`; the runs of the failed model end at
+// once as GPT_OPT_NOT_PD_START with their clipped start still in theta.
+void batch_opt_cases(const BatchShape& s, int64_t R, int slices, int failed) {
+    const int64_t B = s.B();
+    BatchInputs in(s);
+    const size_t rows = (size_t)in.n_begin.p[B], P = 2 + (size_t)s.n_ls;
+    D X = ramp(rows * s.Dm), Y = ramp(rows * s.O), theta0 = ramp(R * P, -3.0, 0.5), bounds(2 * P, 0.0);
+    for (size_t i = 0; i < P; ++i) { bounds.p[2 * i] = i == 0 ? 1.0 : -2.0; bounds.p[2 * i + 1] = i == 0 ? 1.0 : 2.0; }   // c fixed
+    Arr<int> run_model(R, 0);
+    for (int64_t r = 0; r < R; ++r) run_model.p[r] = (int)(r % B);
+    begin("gpt_batch_optimize " + s.name() + " R=" + std::to_string(R) + " slices=" + std::to_string(slices) +
+          (failed >= 0 ? " failed=" + std::to_string(failed) : ""));
+    gpt::stub_fail_model = failed;
+    gpt::stub_opt_launches = slices;
+    gpt::stub_opt_launch_count = 0;
+    D theta(R * P, SENT), lml(R, SENT);
+    Arr<int> iters(R, ISENT), evals(R, ISENT), status(R, ISENT);
+    done(gpt_batch_optimize(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, s.n_ls, run_model.p, theta0.p, R, bounds.p, 1e-10, GPT_KERNEL_MATERN52,
+                            1e-5, 2.22e-9, 15000, 15000, 7, theta.p, lml.p, iters.p, evals.p, status.p), GPT_OK);
+    int want_launches = 0;
+    for (int cls = 0; cls < 2; ++cls) {
+        int longest = 0;
+        for (int64_t r = 0; r < R; ++r)
+            if ((s.n[r % B] > 32) == (cls == 1)) longest = std::max(longest, r % B == failed ? 1 : 1 + (int)(r % slices));
+        want_launches += longest;
+    }
+    CHECK(gpt::stub_opt_launch_count == want_launches);
+    for (int64_t r = 0; r < R; ++r) {
+        const bool not_pd = r % B == failed;
+        CHECK(status.p[r] == (not_pd ? GPT_OPT_NOT_PD_START : GPT_OPT_PGTOL));
+        CHECK(evals.p[r] == (not_pd ? 1 : 1 + (int)(r % slices)) && iters.p[r] == 0 && lml.p[r] == 0.0);
+        for (size_t i = 0; i < P; ++i) {
+            const double clipped = std::min(std::max(theta0.p[r * P + i], bounds.p[2 * i]), bounds.p[2 * i + 1]);
+            CHECK(theta.p[r * P + i] == (not_pd ? clipped : 0.0));
+        }
+    }
+    gpt::stub_fail_model = -1;
+    gpt::stub_opt_launches = 1;
+}
+
+void batch_opt_refusals() {
+    BatchShape s{{1, 32, 33}, 3, 3, 3};
+    BatchInputs in(s);
+    D X = ramp(66 * 3), Y = ramp(66 * 3), theta0 = ramp(4 * 5, -1.0, 0.1), theta(4 * 5, SENT), lml(4, SENT);
+    D bounds{-2, 2, -2, 2, -2, 2, -2, 2, -2, 2};
+    Arr<int> run_model{0, 1, 2, 2}, iters(4, ISENT), evals(4, ISENT), status(4, ISENT);
+    auto call = [&](const int* rm, int64_t R, const double* bd, const double* t0, double pgtol, int max_evals, int per_launch) {
+        return gpt_batch_optimize(0, X.p, Y.p, in.n_begin.p, 3, 3, 3, 3, rm, t0, R, bd, 1e-10, GPT_KERNEL_RBF, pgtol, 2.22e-9, 15000, max_evals,
+                                  per_launch, theta.p, lml.p, iters.p, evals.p, status.p);
+    };
+    begin("gpt_batch_optimize refuses R = 0"); done(call(run_model.p, 0, bounds.p, theta0.p, 1e-5, 15000, 64), GPT_E_ARG);
+    begin("gpt_batch_optimize refuses run_model = NULL"); done(call(nullptr, 4, bounds.p, theta0.p, 1e-5, 15000, 64), GPT_E_ARG);
+    Arr<int> outside{0, 1, 3, 2};
+    begin("gpt_batch_optimize refuses run_model = B"); done(call(outside.p, 4, bounds.p, theta0.p, 1e-5, 15000, 64), GPT_E_ARG);
+    D crossed{-2, 2, 2, -2, -2, 2, -2, 2, -2, 2};
+    begin("gpt_batch_optimize refuses lo > hi"); done(call(run_model.p, 4, crossed.p, theta0.p, 1e-5, 15000, 64), GPT_E_ARG);
+    D nan0(theta0);
+    nan0.p[7] = std::nan("");
+    begin("gpt_batch_optimize refuses NaN in theta0"); done(call(run_model.p, 4, bounds.p, nan0.p, 1e-5, 15000, 64), GPT_E_ARG);
+    begin("gpt_batch_optimize refuses pgtol = 0"); done(call(run_model.p, 4, bounds.p, theta0.p, 0.0, 15000, 64), GPT_E_ARG);
+    begin("gpt_batch_optimize refuses max_evals = 0"); done(call(run_model.p, 4, bounds.p, theta0.p, 1e-5, 0, 64), GPT_E_ARG);
+    begin("gpt_batch_optimize refuses evals_per_launch = 0"); done(call(run_model.p, 4, bounds.p, theta0.p, 1e-5, 15000, 0), GPT_E_ARG);
+    CHECK(theta.all(SENT) && lml.all(SENT) && iters.all(ISENT) && evals.all(ISENT) && status.all(ISENT));
 }
 
 // ---- select -------------------------------------------------------------------------------------------------------------------
@@ -721,6 +790,12 @@ int main() {
     batch_cases({sizes3, 3, 3, 3}, {65, 64, 65}, 1);                       // the middle member is not positive definite
     batch_cases({sizes4, 15, 1, 16}, {65, 64, 0, 65}, 1);
     batch_refusals();
+    batch_opt_cases({{10}, 2, 2, 2}, 1, 1, -1);                            // R = 1
+    batch_opt_cases({sizes3, 1, 1, 1}, 5, 3, -1);                          // R odd: both size classes, several slices
+    batch_opt_cases({sizes4, 3, 3, 3}, 12, 4, -1);                         // R even
+    batch_opt_cases({sizes4, 15, 1, 16}, 7, 2, 1);                         // the runs of one model start where it is not PD
+    batch_opt_cases({sizes4, 15, 15, 16}, 9, 5, 0);                        // the largest record; the only large model fails
+    batch_opt_refusals();
     select_cases();
     svgp_cases("gpt_svgp", gpt_svgp_train, gpt_svgp_elbo_grad, false);
     svgp_cases("gpt_svgp_surface", gpt_svgp_surface_train, gpt_svgp_surface_elbo_grad, true);

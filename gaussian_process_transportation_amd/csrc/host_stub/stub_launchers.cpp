@@ -205,6 +205,11 @@ extern "C" int gpt_batch_predict(int, const double*, const double*, const int64_
     gpt::set_last_error("gpt_batch_predict: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_batch_optimize(int, const double*, const double*, const int64_t*, int64_t, int, int, int, const int*, const double*,
+                                  int64_t, const double*, double, int, double, double, int, int, int, double*, double*, int*, int*, int*) {
+    gpt::set_last_error("gpt_batch_optimize: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_pullback_chain_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, double, int, double,
                                       double*, double*, double*, int*, double*, double*, double*, double*, double*, double*, double*,
                                       double*, int*, int*, double*, double*) {
@@ -225,12 +230,13 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 
 #else
 // The program of `make host-oneshot-asan` (oneshot_driver.cpp) links the real entry points of the one-shot units (gpt_*_host.hip);
-// what follows stands in for their launchers (gpt_batch.h, gpt_select.h, gpt_svgp_train.h, gpt_svgp_surface.h).  As above, each
+// what follows stands in for their launchers (gpt_batch.h, gpt_batch_opt.h, gpt_select.h, gpt_svgp_train.h, gpt_svgp_surface.h).  As above, each
 // walks the memory its kernels would read and write, deriving every offset and size from its arguments the way the kernels do,
 // and writes the words the host reads back: status GPT_OK, failure flag and info untouched (no failure).  A layout the kernels
 // rely on and no memory access shows (a task's workspace running into the next one's, a model in the wrong size class) ends
 // the program through stub_check.
 #include "../gpt_batch.h"
+#include "../gpt_batch_opt.h"
 #include "../gpt_select.h"
 #include "../gpt_svgp_train.h"
 #include "../gpt_svgp_surface.h"
@@ -282,6 +288,37 @@ void launch_bat_predict(hipStream_t, int, bool der, int tiles_small, int tiles_l
         if (!der) continue;
         touch_w(a.J ? a.J + row * a.O * a.D : nullptr, nq * a.O * a.D * 8);
         touch_w(a.Jvar ? a.Jvar + row * a.D : nullptr, nq * a.D * 8); touch_w(a.dvar ? a.dvar + row * a.D : nullptr, nq * a.D * 8);
+    }
+}
+
+// ---- gpt_batch_opt.hip --------------------------------------------------------------------------------------------------------
+// Test only (oneshot_driver.cpp): run r ends in its (1 + r % stub_opt_launches)-th launch, so the relaunch loop of
+// gpt_batch_optimize runs stub_opt_launches rounds and compacts its list of live runs between them.  A run whose model is
+// stub_fail_model ends at once as GPT_OPT_NOT_PD_START.
+int stub_opt_launches = 1;
+int stub_opt_launch_count = 0;             // launches since the driver last reset it
+void launch_bat_optimize(hipStream_t, int, int n_small, int n_large, const BatOptArgs& a) {
+    const size_t P = 2 + (size_t)a.n_ls, rec = bat_opt_record((int)P);
+    stub_opt_launch_count += (n_small > 0) + (n_large > 0);                      // one launch per size class present
+    stub_check(n_small + n_large >= 1 && a.evals_per_launch >= 1 && a.max_ls == BAT_OPT_MAX_LS);
+    touch_r(a.bounds, 2 * P * 8);
+    for (int k = 0; k < n_small + n_large; ++k) {
+        const int r = a.list[k], b = a.run_model[r];
+        const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0;
+        stub_check(n >= 1 && n <= (k < n_small ? BAT_SMALL_N : BAT_MAX_N));      // the LDS image of the size class
+        stub_check(k == 0 || a.list[k - 1] < r || k == n_small);                  // a run once per launch: each class in rising order
+        stub_check(a.status[r] == BAT_OPT_LIVE);                                  // a run that has ended is not launched again
+        touch_r(a.X + n0 * a.D, n * a.D * 8); touch_r(a.Y + n0 * a.O, n * a.O * 8);
+        int* cn = a.cnt + (size_t)r * BAT_OPT_CNT;
+        if (cn[1] == 0) { stub_check(cn[0] == 0 && cn[2] == 0 && a.iters[r] == 0 && a.evals[r] == 0); touch_r(a.theta + r * P, P * 8); }
+        touch_w(a.rec + r * rec, rec * 8);
+        ++cn[1];
+        const bool not_pd = b == stub_fail_model;
+        if (!not_pd && cn[1] < 1 + r % stub_opt_launches) continue;
+        if (!not_pd) touch_w(a.theta + r * P, P * 8);                             // a start that is not PD stays in theta
+        touch_w(a.lml + r, 8); touch_w(a.iters + r, 4);
+        a.evals[r] = cn[1];
+        a.status[r] = not_pd ? GPT_OPT_NOT_PD_START : GPT_OPT_PGTOL;
     }
 }
 

@@ -90,6 +90,10 @@ class GaussianProcess:
         2.5) model return the analytic derivatives of its posterior (the reference multiplies the Matern k* by the RBF
         coefficient instead, which this path does not reproduce).  Default False: those calls raise NotImplementedError, as
         the reference's numbers or a refusal are the drop-in's rule.  No effect on RBF models; nu=0.5 is refused either way."""
+        if isinstance(optimizer, str) and optimizer == "device_bfgs":
+            raise ValueError("optimizer='device_bfgs' is the on-device search of a batch of small models (n <= 128 points each): use "
+                             "GaussianProcessBatch or GaussianProcessTransportationBatch.  GaussianProcess takes 'fmin_l_bfgs_b', a "
+                             "callable or None")
         self._kernel_in = kernel
         self.kernel = kernel
         self.alpha = alpha

@@ -18,7 +18,9 @@ from .gaussian_process import _PARAM_C, _PARAM_LS, _PARAM_NOISE, kernel_hyperpar
 class GaussianProcessBatch:
     def __init__(self, kernel, alpha=1e-10, optimizer="fmin_l_bfgs_b", n_restarts_optimizer=5, device=0, verbose=False):
         """Arguments as GaussianProcess's; `kernel` (ConstantKernel * RBF or Matern + WhiteKernel) is every model's starting
-        point.  A callable optimizer is refused (batch_hyperopt.py)."""
+        point.  A callable optimizer is refused (batch_hyperopt.py).  optimizer="device_bfgs" (opt-in) runs the search itself
+        on the device, one workgroup per (model, start point): same start points and restarts, a projected BFGS iteration in
+        place of scipy's L-BFGS-B; optimizer_stats_ then holds runs, launches and evaluations."""
         from .batch_hyperopt import check_optimizer
         check_optimizer(optimizer)
         self._kernel_in = kernel

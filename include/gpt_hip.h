@@ -244,6 +244,30 @@ int gpt_batch_predict(int device, const double* X, const double* Y, const int64_
                       double alpha_jitter, int kernel_type, const double* Xq, const int64_t* q_begin, double* mean, double* var,
                       double* J, double* Jvar, double* dvar, int* status);
 
+/* (new) gpt_batch_optimize — the hyper-parameter search of such a batch on the device: R runs, run r maximising the LML of model
+ * run_model[r] (0 .. B - 1) over theta = log [c, l.., noise] from theta0[r] (R, 2 + n_ls) inside `bounds` (2 + n_ls, 2: lo, hi
+ * in log space, finite; lo == hi fixes a component; a start outside its bounds is clipped).  One workgroup carries one run
+ * through a projected BFGS iteration with a backtracking line search (csrc/gpt_batch_opt.hip states it), evaluating the
+ * objective of gpt_batch_lml_objective in place; a launch spends at most evals_per_launch evaluations per run, then the host
+ * reads the R status words and launches again for the runs still live.  A run's five outputs do not depend on the other runs,
+ * on their order or on evals_per_launch, bit for bit.  The restarts of sklearn's protocol are runs of one model: the caller
+ * keeps the best.  pgtol, ftol, max_iter, max_evals: as scipy's L-BFGS-B (sklearn passes 1e-5, 2.22e-9, 15000, 15000).
+ * Outputs: theta (R, 2 + n_ls), lml (R), iterations (R), evaluations (R), status (R) GPT_OPT_*.  A run whose start is not PD
+ * has status GPT_OPT_NOT_PD_START, lml = -infinity and the clipped start in theta.  Limits (GPT_E_ARG, the message names the
+ * limit): those of gpt_batch_lml_objective, 1 <= R <= 2^20, run_model in [0, B), no NaN / infinity, lo <= hi, tolerances and
+ * caps > 0.  The return value is GPT_OK whenever the batch ran: a run that did not converge says so in its status.  Device
+ * memory: the inputs and 8 ((2 + n_ls)^2 + 7 (2 + n_ls) + 7) bytes per run. */
+#define GPT_OPT_PGTOL 0        /* projected gradient <= pgtol                                  */
+#define GPT_OPT_FTOL 1         /* relative decrease of an accepted step <= ftol                */
+#define GPT_OPT_MAX_ITER 2     /* iteration cap                                                */
+#define GPT_OPT_MAX_EVALS 3    /* evaluation cap                                               */
+#define GPT_OPT_LINESEARCH 4   /* no acceptable step after 30 halvings                         */
+#define GPT_OPT_NOT_PD_START 5 /* the (clipped) start point's matrix is not positive definite */
+int gpt_batch_optimize(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O, int n_ls,
+                       const int* run_model, const double* theta0, int64_t R, const double* bounds, double alpha_jitter,
+                       int kernel_type, double pgtol, double ftol, int max_iter, int max_evals, int evals_per_launch, double* theta,
+                       double* lml, int* iterations, int* evaluations, int* status);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */
