@@ -97,6 +97,7 @@ SIGNATURES = {
     "gpt_set_profiling": (C.c_int, [_vp, C.c_int]),
     "gpt_reserve": (C.c_int, [_vp, C.c_int64, C.c_int]),
     "gpt_predict_timings": (C.c_int, [_vp, _dp]),
+    "gpt_debug_var_path": (C.c_int, [_vp]),
     "gpt_svgp_train": (C.c_int, [C.c_int, _dp, _dp, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                  C.POINTER(_i64), _i64, C.POINTER(_i64), _i64, C.c_double, _dp]),
     "gpt_svgp_elbo_grad": (C.c_int, [C.c_int, _dp, _dp, _i64, _i64, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp,
@@ -963,6 +964,10 @@ class Handle:
         t = np.zeros(2)
         check(self.lib.gpt_predict_timings(self._h, dptr(t)), "gpt_predict_timings")
         return {"mean_jac_ms": float(t[0]), "var_ms": float(t[1])}
+
+    def var_path(self):
+        """Kernel of the last variance launch: 0 fp64, 1 residue (int8), -1 none yet."""
+        return int(self.lib.gpt_debug_var_path(self._h))
 
     def set_stream(self, stream_ptr):
         check(self.lib.gpt_set_stream(self._h, _vp(stream_ptr or None)), "gpt_set_stream")

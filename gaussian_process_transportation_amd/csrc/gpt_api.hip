@@ -3,6 +3,7 @@
 // on one HIP stream and maps failures to error codes.
 #include "gpt_stage.h"
 #include "gpt_plan.h"
+#include "gpt_plan_i8.h"
 #include "gpt_fit_plan.h"
 #include "../../include/gpt_hip.h"
 
@@ -166,6 +167,14 @@ struct gpt_handle {
     // per-kernel timing of the last predict (gpt_set_profiling)
     bool profiling = false, pred_mj = false, pred_var = false;
     VarWorkspace vws;              // scratch + cached plan of the variance kernel
+    // The residue (int8) variance path (gpt_plan_i8.h): the planes of W — a derived image beside Wf, not part of the blob —
+    // with their row scales, valid for the committed model only; and the path's scratch (grow-only).
+    struct VarI8 {
+        DevBuf<unsigned char> planes, rowmax, slab, bimg, park;
+        DevBuf<double> rowscale, qscale;
+        bool valid = false;
+        int last_path = -1;        // gpt_debug_var_path
+    } i8;
     FitAux fit_aux;                // CU-masked streams + events of the factor + inverse plan (gpt_fit_plan.h)
     DevBuf<double> lml_partial;    // partial sums of the LML gradient (grow-only)
     DevBuf<unsigned char> cov_buf; // scratch of gpt_predict_cov (grow-only)
@@ -192,6 +201,7 @@ int set_device(gpt_handle* h) {
 // No model, no factors: what the call that follows leaves behind is all the handle holds.
 void invalidate_model(gpt_handle* h) {
     h->committed = false;
+    h->i8.valid = false;           // the residue planes are an image of the model that goes
     h->have_L = h->have_W = false;
     h->objective_ready = false;
 }
@@ -248,6 +258,50 @@ int ensure_copy_stream(gpt_handle* h) {
         CALLCHK(hipEventCreateWithFlags(&h->ev_done[i].h, hipEventDisableTiming));
         CALLCHK(hipEventCreateWithFlags(&h->ev_copied[i].h, hipEventDisableTiming));
     }
+    return GPT_OK;
+}
+
+// ---- the residue (int8) variance path: who takes it, and its image of the model
+// GPT_VAR_INT8 = 0 / 1 forces the path off / on for every model and batch that can take it (read per call: tests compare both in
+// one process); unset: from I8_DEFAULT_NP padded sources and I8_DEFAULT_M queries upward (profiles/var_int8_ab.txt).
+// Measured (var_ms, fp64 kernel / residue kernel): N = 8192: M = 10^4 1.20, 16 384 1.42, 65 536 1.64, 500 000 1.53; N = 2500, M = 10^4
+// 0.71; N = 1024, M = 50 000 0.47 — nothing between N = 2500 and 8192 has been measured, so the smaller models stay on k_var.
+constexpr int I8_DEFAULT_NP = 8192;
+constexpr int64_t I8_DEFAULT_M = 10000;
+int var_i8_mode() {
+    const char* e = getenv("GPT_VAR_INT8");
+    return e ? (atoi(e) != 0 ? 1 : 0) : -1;
+}
+bool var_i8_can(const KernelParams& p) { return p.dtype == DT_F64 && p.ntask == 1 && p.D <= 3 && var_i8_shape_ok(p.NP); }
+// at fit time the batch size is not known: the model is prepared when a large enough batch would take the path
+bool var_i8_wanted(const KernelParams& p, int64_t M) {
+    if (!var_i8_can(p)) return false;
+    const int mode = var_i8_mode();
+    return mode >= 0 ? mode == 1 : (p.NP >= I8_DEFAULT_NP && (M < 0 || M >= I8_DEFAULT_M));
+}
+// the planes of the committed model's W, enqueued on the handle's stream behind whatever wrote Wf
+int ensure_i8_image(gpt_handle* h) {
+    if (h->i8.valid) return GPT_OK;
+    const int NP = h->p.NP;
+    hipStream_t s = h->stream;
+    CALLCHK(reserve(h->i8.planes, var_i8_plane_bytes(NP), s));
+    CALLCHK(reserve(h->i8.rowmax, (size_t)NP * 8, s));
+    CALLCHK(reserve(h->i8.rowscale, (size_t)NP * 8, s));
+    CALLCHK(reserve(h->i8.qscale, (size_t)NP * 8, s));
+    launch_var_i8_image(s, static_cast<const double*>(h->dWf()), NP, var_i8_bits(NP), h->i8.planes, h->i8.rowscale, h->i8.qscale, h->i8.rowmax);
+    CALLCHK(hipGetLastError());
+    h->i8.valid = true;
+    return GPT_OK;
+}
+
+// the plan of a launch with M queries and the path's scratch, grown to it
+int prepare_i8(gpt_handle* h, int64_t M, VarI8PlanDev* plan) {
+    const int P = var_workgroups();
+    *plan = build_var_i8_plan(M, h->p.NP / I8_ROWS, P);
+    hipStream_t s = h->stream;
+    CALLCHK(reserve(h->i8.slab, (size_t)plan->ncb * plan->nbi * I8_COLS * sizeof(double), s));
+    CALLCHK(reserve(h->i8.bimg, (size_t)P * var_i8_bimg_bytes(h->p.NP), s));
+    CALLCHK(reserve(h->i8.park, (size_t)P * var_i8_park_bytes(), s));
     return GPT_OK;
 }
 
@@ -492,6 +546,8 @@ static int fit_finish(gpt_handle* h, bool model) {
     h->committed = model;
     h->objective_ready = !model;
     h->have_L = h->have_W = true;
+    // behind the fit's last event: the planes are not part of the fit's timings and nothing of the fit waits for them
+    if (model && var_i8_wanted(h->p, -1)) return ensure_i8_image(h);
     return GPT_OK;
 }
 
@@ -616,6 +672,7 @@ int gpt_fit_svgp(gpt_handle* h, const double* Z, const double* y, const double* 
         return fail(GPT_E_NOT_PD, buf);
     }
     h->committed = true;           // dK / dW hold the LAST task's factors only: no export, covariance or LML for this model
+    if (var_i8_wanted(h->p, -1)) return ensure_i8_image(h);
     return GPT_OK;
 }
 
@@ -625,6 +682,11 @@ int gpt_reserve(gpt_handle* h, int64_t M, int jacobian_variance) {
     if (M < 0) return fail(GPT_E_ARG, "gpt_reserve: bad query count");
     if (int rc = set_device(h)) return rc;
     if (M == 0) return GPT_OK;
+    if (!jacobian_variance && var_i8_wanted(h->p, M)) {
+        VarI8PlanDev plan;
+        if (int rc = ensure_i8_image(h)) return rc;
+        return prepare_i8(h, M, &plan);
+    }
     CALLCHK(var_prepare(h->vws, h->stream, h->p, M, jacobian_variance ? var_fused_cols(h->p.D) : 1));
     return GPT_OK;
 }
@@ -658,10 +720,24 @@ int gpt_predict_all_dev(gpt_handle* h, const void* Xq, int64_t M, void* mean, vo
         const int fused = var_fused_cols(h->p.D);
         const int alone = h->p.D <= 3 ? 3 : (h->p.D == 4 ? VAR_NCOMP_DERIV4 : (h->p.D == 8 ? VAR_NCOMP_DERIV8 : fused));
         const int ncomp = dvar ? fused : (Jvar ? (var ? fused : alone) : 1);
+        if (ncomp == 1 && var_i8_wanted(h->p, M)) {
+            // k* alone of an fp64 single-task model: the product on the int8 matrix cores, by residues (gpt_plan_i8.h)
+            if (int rc = ensure_i8_image(h)) return rc;           // (a model prepared at its fit has it already)
+            h->i8.last_path = 1;
+            VarI8PlanDev plan;
+            if (int rc = prepare_i8(h, M, &plan)) return rc;
+            if (prof) CALLCHK(hipEventRecord(h->pev[2], s));
+            launch_var_i8(s, h->p, plan, var_i8_bits(h->p.NP), h->i8.planes, h->i8.rowscale, static_cast<const double*>(h->dXs()),
+                          static_cast<const double*>(Xq), M, reinterpret_cast<double*>(h->i8.slab.p), h->i8.bimg, h->i8.park,
+                          static_cast<double*>(var), h->dHdr());
+            if (prof) CALLCHK(hipEventRecord(h->pev[3], s));
+        } else {
+        h->i8.last_path = 0;
         CALLCHK(var_prepare(h->vws, s, h->p, M, ncomp));
         if (prof) CALLCHK(hipEventRecord(h->pev[2], s));
         launch_var(s, h->p, h->vws, h->dXs(), h->dWf(), Xq, M, ncomp, var, ncomp == 1 ? nullptr : Jvar, ncomp == 1 ? nullptr : dvar, h->dHdr());
         if (prof) CALLCHK(hipEventRecord(h->pev[3], s));
+        }
     }
     CALLCHK(hipGetLastError());
     return GPT_OK;
@@ -881,6 +957,8 @@ int gpt_factor_commit(gpt_handle* h) {
         return fail(GPT_E_STATE, "gpt_factor_commit: header geometry differs from gpt_factor_alloc");
     fill_params(h, hdr);
     h->committed = true;
+    h->i8.valid = false;           // the blob was written from outside
+    if (var_i8_wanted(h->p, -1)) return ensure_i8_image(h);
     return GPT_OK;
 }
 
@@ -913,6 +991,7 @@ int gpt_factor_copy(gpt_handle* dst, gpt_handle* src) {
     CALLCHK(hipStreamSynchronize(dst->stream));
     fill_params(dst, hdr);
     dst->committed = true;
+    if (var_i8_wanted(dst->p, -1)) return ensure_i8_image(dst);
     return GPT_OK;
 }
 
@@ -958,6 +1037,8 @@ int gpt_predict_timings(gpt_handle* h, double* ms_out) {
     }
     return GPT_OK;
 }
+
+int gpt_debug_var_path(gpt_handle* h) { return h ? h->i8.last_path : -1; }
 
 int gpt_fit_timings(gpt_handle* h, double* ms_out, int n) {
     if (!h || !ms_out) return fail(GPT_E_ARG, "gpt_fit_timings: NULL argument");

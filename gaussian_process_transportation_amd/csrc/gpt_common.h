@@ -200,6 +200,13 @@ void launch_var(hipStream_t s, const KernelParams& p, const VarWorkspace& ws, co
                 const void* Xq, int64_t M, int ncomp, void* var, void* Jvar, void* dvar, const double* hdr);
 int var_workgroups();
 
+// The residue (int8) variance path of fp64 single-task models with D <= 3, k* alone (gpt_predict_i8.hip; arithmetic, sizes and
+// work split: gpt_plan_i8.h).  The planes are a derived image of Wf, built once per model: rowmax NP x 8 bytes of scratch.
+struct VarI8PlanDev;
+void launch_var_i8_image(hipStream_t s, const double* Wf, int NP, int bits, void* planes, double* rowscale, double* qscale, void* rowmax);
+void launch_var_i8(hipStream_t s, const KernelParams& p, const VarI8PlanDev& plan, int bits, const void* planes, const double* rowscale,
+                   const double* Xs, const double* Xq, int64_t M, double* slab, void* bimg, void* park, double* var, const double* hdr);
+
 size_t wf_elems(int NP);          // elements of ONE task's tile set (+ prefetch overrun after the last task: wf_overrun_elems)
 size_t wf_overrun_elems();
 

@@ -1,0 +1,398 @@
+// The residue (int8) variance kernel k_var_i8 and the kernels around it: the image of W in residue planes, the finalizing sum.
+// Arithmetic and work split: gpt_plan_i8.h; derivation and measurements: DESIGN.md section 4.  k_var (gpt_kvar.h) is untouched.
+//
+// Shapes:
+//   * v_mfma_i32_16x16x64_i8: A fragment = 16 B per lane, lane l holds row l & 15, k = 16 (l >> 4) + byte; B fragment the same
+//     with the column in place of the row; C/D: column l & 15, rows 4 (l >> 4) + e.  Both operand images are written by this
+//     file in that order (the k order inside a step only has to be the same on both sides).
+//   * A planes: [modulus j][tile (ib, kb), kb <= ib][step s 0..8)[row group g 0..8)[row tile r 0..4)[lane] x 16 B — the tiles of
+//     an i-block are consecutive, so a sweep reads one contiguous stream per wave: 4 KiB per step.
+//   * a workgroup (512 threads, 8 waves, 2 per SIMD) owns a 128-column block: wave w accumulates the 64 x 128 product of its
+//     64-row group, 4 x 8 MFMA tiles = 128 int32 accumulators per lane.  The moduli are the OUTER loop of an i-block: one
+//     accumulator set, reduced modulo m_j when the sweep of modulus j ends and parked as one byte per element (4 elements per
+//     dword, in a per-workgroup global buffer that only the writing lane reads back); after the 14th the lane rebuilds its 128
+//     integers (Garner, fp32 — every intermediate is an integer below 2^24 — then Horner in fp64), scales, squares and sums.
+//   * B planes: generated once per column block (fp64 k*, the generating code of k_var, then 14 residues) into a per-workgroup
+//     image in fragment order, [modulus][step][column tile 0..8)[lane] x 16 B, and staged from there through a double-buffered
+//     LDS chunk of one 512-k tile (64 KiB), one barrier per tile; the next chunk is copied piecewise between the MFMA steps.
+//   * diagonal tile: row group g has nothing beyond step g; a wave runs an even number of steps there, (g + 2) & ~1 (the A ring
+//     below is two deep and indexed by step parity), row groups paired (0,7)(1,6)(2,5)(3,4) on the SIMDs as in k_var: 10 of 16 steps.
+#pragma once
+#include "gpt_common.h"
+#include "gpt_dispatch.h"
+#include "gpt_exp.h"
+#include "gpt_plan_i8.h"
+
+namespace gpt {
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+constexpr int I8_TILE_STEPS = I8_ROWS / I8_KSTEP;                        // 8 steps per 512-k tile
+constexpr size_t I8_A_STEP = (size_t)8 * 4 * 64;                         // v4i per step of the A planes (8 row groups x 4 row tiles x 64 lanes)
+constexpr size_t I8_B_STEP = (size_t)8 * 64;                             // v4i per step of a B plane (8 column tiles x 64 lanes)
+constexpr size_t I8_CHUNK = I8_TILE_STEPS * I8_B_STEP;                   // v4i per LDS chunk: 4096 = 64 KiB
+constexpr size_t I8_LDS_BYTES = 2 * I8_CHUNK * sizeof(v4i);              // 128 KiB
+constexpr size_t I8_PARK_WORDS = var_i8_park_bytes() / 4;                // dwords of a workgroup's parking buffer
+
+// ---- constants of the reconstruction, built at compile time ------------------------------------------------------------------
+struct I8Tab {
+    float m[I8_NMOD], rm[I8_NMOD];       // modulus, its reciprocal
+    float inv[I8_NMOD];                  // (m_0 .. m_{i-1})^-1 mod m_i, balanced
+    float w[I8_NMOD][I8_NMOD];           // w[l][i] = (m_0 .. m_{l-1}) mod m_i, balanced (l < i)
+};
+constexpr int i8_balanced(int x, int m) { x %= m; if (x < 0) x += m; return x > (m - 1) / 2 ? x - m : x; }
+constexpr I8Tab make_i8_tab() {
+    I8Tab t{};
+    for (int i = 0; i < I8_NMOD; ++i) {
+        const int m = I8_MODULI[i];
+        t.m[i] = (float)m; t.rm[i] = 1.0f / (float)m;
+        int prod = 1;
+        for (int l = 0; l < I8_NMOD; ++l) {
+            t.w[l][i] = l < i ? (float)i8_balanced(prod, m) : 0.0f;
+            if (l < i) prod = prod * I8_MODULI[l] % m;
+        }
+        int inv = 0;
+        for (int x = 1; x < m; ++x) if (prod * x % m == 1) inv = x;
+        t.inv[i] = (float)i8_balanced(inv, m);
+    }
+    return t;
+}
+static constexpr I8Tab I8_TAB = make_i8_tab();
+
+// run-time indexed copies for the loops over the moduli that stay rolled: modulus, reciprocal, largest and smallest balanced residue
+__constant__ double c_i8_mod[I8_NMOD] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199};
+__constant__ double c_i8_inv[I8_NMOD] = {1.0 / 256, 1.0 / 255, 1.0 / 253, 1.0 / 251, 1.0 / 247, 1.0 / 241, 1.0 / 239,
+                                         1.0 / 233, 1.0 / 229, 1.0 / 227, 1.0 / 223, 1.0 / 217, 1.0 / 211, 1.0 / 199};
+__constant__ double c_i8_hi[I8_NMOD] = {127, 127, 126, 125, 123, 120, 119, 116, 114, 113, 111, 108, 105, 99};
+__constant__ double c_i8_lo[I8_NMOD] = {-128, -127, -126, -125, -123, -120, -119, -116, -114, -113, -111, -108, -105, -99};
+
+// balanced residue of the integer-valued x (|x| < 2^52) modulo m: the quotient may be off by one, the remainder is exact (fma)
+static __device__ __forceinline__ int i8_residue(const double x, const double m, const double inv, const double hi, const double lo) {
+    const double q = rint(x * inv);
+    double r = fma(-q, m, x);
+    r = r > hi ? r - m : r;
+    r = r < lo ? r + m : r;
+    return (int)r;
+}
+static __device__ __forceinline__ int i8_pack4(const int r0, const int r1, const int r2, const int r3) {
+    return (int)((unsigned)(r0 & 255) | ((unsigned)(r1 & 255) << 8) | ((unsigned)(r2 & 255) << 16) | ((unsigned)r3 << 24));
+}
+// the 14 residue words of 16 integers (a lane's fragment of one step), plane j to dst[j * stride]
+static __device__ __forceinline__ void i8_store_planes(const double (&x)[16], v4i* __restrict__ dst, const size_t stride) {
+#pragma unroll 1
+    for (int j = 0; j < I8_NMOD; ++j) {
+        const double m = c_i8_mod[j], inv = c_i8_inv[j], hi = c_i8_hi[j], lo = c_i8_lo[j];
+        int r[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) r[b] = i8_residue(x[b], m, inv, hi, lo);
+        v4i o;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) o[v] = i8_pack4(r[4 * v], r[4 * v + 1], r[4 * v + 2], r[4 * v + 3]);
+        dst[(size_t)j * stride] = o;
+    }
+}
+
+// ---- the image of W: row exponents, then the planes --------------------------------------------------------------------------
+// Wf (fp64, gpt_fit.hip k_pack_w): tile (ib, kb) at ((ib (ib + 1) / 2 + kb) WT^2, [k4][g][q][lane][p] = W[64 g + 16 (2 q + p) + (lane & 15)][4 k4 + (lane >> 4)].
+// Pass 1, one workgroup (256 threads) per (tile, row group): thread th always sees the same row — its maximum over the tile's 128
+// k4-steps goes to rowmax[row] (bits of a non-negative double order as unsigned integers).
+__global__ __launch_bounds__(256) void k_i8_rowmax(const double* __restrict__ Wf, unsigned long long* __restrict__ rowmax) {
+    const int tile = blockIdx.x, g = blockIdx.y, th = threadIdx.x;
+    int ib = 0;
+    while ((ib + 1) * (ib + 2) / 2 <= tile) ++ib;
+    const double* src = Wf + (size_t)tile * WT_TILE_DOUBLES + (size_t)g * 256 + th;
+    double mx = 0.0;
+    for (int k4 = 0; k4 < WT_K4; ++k4) mx = fmax(mx, fabs(src[(size_t)k4 * WT_STEP_DOUBLES]));
+    const int q = th >> 7, lane = (th >> 1) & 63, pp = th & 1;
+    const int row = ib * WT + 64 * g + 16 * (2 * q + pp) + (lane & 15);
+    if (mx > 0.0) atomicMax(rowmax + row, (unsigned long long)__double_as_longlong(mx));
+}
+// rowscale[i] = 2^(e_i - p), qscale[i] = 2^(p - e_i), e_i the smallest integer with max_k |W_ik| <= 2^e_i
+__global__ __launch_bounds__(256) void k_i8_rowscale(const unsigned long long* __restrict__ rowmax, int NP, int p, double* __restrict__ rowscale,
+                                                     double* __restrict__ qscale) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= NP) return;
+    const double mx = __longlong_as_double((long long)rowmax[i]);
+    int e = 0;
+    if (mx > 0.0) {
+        int ex;
+        const double f = frexp(mx, &ex);
+        e = f == 0.5 ? ex - 1 : ex;
+    }
+    rowscale[i] = ldexp(1.0, e - p);
+    qscale[i] = ldexp(1.0, p - e);
+}
+// Pass 2, one workgroup per (tile, row group): thread handles the fragments (s, r, lane) of all 14 planes, 8 of them.
+__global__ __launch_bounds__(256) void k_i8_planes(const double* __restrict__ Wf, const double* __restrict__ qscale, int ntiles, v4i* __restrict__ planes) {
+    const int tile = blockIdx.x, g = blockIdx.y;
+    int ib = 0;
+    while ((ib + 1) * (ib + 2) / 2 <= tile) ++ib;
+    const double* src = Wf + (size_t)tile * WT_TILE_DOUBLES;
+    for (int u = threadIdx.x; u < I8_TILE_STEPS * 4 * 64; u += 256) {
+        const int lane = u & 63, r = (u >> 6) & 3, s = u >> 8;
+        const int lr = lane & 15, lk = lane >> 4;
+        const double sc = qscale[ib * WT + 64 * g + 16 * r + lr];
+        double x[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const int col = 64 * s + 16 * lk + b;                       // column of the tile
+            const int k4 = col >> 2, lkk = col & 3;
+            x[b] = rint(src[((((size_t)k4 * 8 + g) * 2 + (r >> 1)) * 64 + lkk * 16 + lr) * 2 + (r & 1)] * sc);
+        }
+        v4i* dst = planes + ((((size_t)tile * I8_TILE_STEPS + s) * 8 + g) * 4 + r) * 64 + lane;
+        i8_store_planes(x, dst, (size_t)ntiles * I8_TILE_STEPS * I8_A_STEP);
+    }
+}
+
+// ---- reconstruction ------------------------------------------------------------------------------------------------------------
+// r: the 14 balanced residues of an integer C, |C| < M / 2.  Mixed-radix digits d_i = ((r_i - sum_{l < i} d_l w[l][i]) inv_i) mod m_i,
+// balanced; C = d_0 + m_0 (d_1 + m_1 (d_2 + ...)).  The leading digits of a small C are zero, so the Horner sum keeps the relative
+// accuracy of fp64 (13 roundings at most).  Every fp32 value below is an integer of magnitude < 2^24, every fma exact; the
+// quotients are the nearest integers for the odd moduli (v / m stays 1 / (2 m) away from a tie, its rounding error below 2e-5),
+// and modulus 0 (256) has no digit to compute: d_0 = r_0.
+static __device__ __forceinline__ double i8_garner(const float (&r)[I8_NMOD]) {
+    float d[I8_NMOD];
+    d[0] = r[0];
+#pragma unroll
+    for (int i = 1; i < I8_NMOD; ++i) {
+        float s = 0.0f;
+#pragma unroll
+        for (int l = 0; l < i; ++l) s = fmaf(d[l], I8_TAB.w[l][i], s);
+        float u = r[i] - s;
+        u = fmaf(-rintf(u * I8_TAB.rm[i]), I8_TAB.m[i], u);
+        const float v = u * I8_TAB.inv[i];
+        d[i] = fmaf(-rintf(v * I8_TAB.rm[i]), I8_TAB.m[i], v);
+    }
+    double X = (double)d[I8_NMOD - 1];
+#pragma unroll
+    for (int i = I8_NMOD - 2; i >= 0; --i) X = fma(X, (double)I8_TAB.m[i], (double)d[i]);
+    return X;
+}
+
+struct VarI8Args {
+    const v4i* planes;            // A planes
+    const double* rowscale;       // 2^(e_i - p)
+    const double* Xs;             // scaled sources, rows of 4
+    const double* Xq;             // queries (M, D)
+    int64_t M;
+    double* slab;                 // [cb][ib][128]
+    v4i* bimg;                    // per-workgroup B planes
+    unsigned* park;               // per-workgroup parked residues
+    double bq;                    // 2^(p - f): kernel values -> integers
+    double colscale;              // 2^(f - p)
+    int ntiles;                   // nbi (nbi + 1) / 2
+};
+
+template <int KT>
+__global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev pl, VarI8Args a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char i8_lds_raw[];
+    v4i* const Bs = reinterpret_cast<v4i*>(i8_lds_raw);                 // [buffer 0..2)[step 0..8)[column tile 0..8)[lane]
+    __shared__ double red[8][I8_COLS];
+    __shared__ double Tt[256];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, lk = lane >> 4;
+    const int g = (w < 4) ? w : (11 - w);                               // row group of this wave: 0,1,2,3,7,6,5,4
+    const int nbi = pl.nbi, D = p.D;
+    const int nst = p.NP / I8_KSTEP;                                    // steps of a whole B plane
+    if (tid < 256) Tt[tid] = g_exp2_table[tid];
+    v4i* const bim = a.bimg + (size_t)blockIdx.x * ((size_t)I8_NMOD * nst * I8_B_STEP);
+    unsigned* const pk = a.park + (size_t)blockIdx.x * I8_PARK_WORDS + tid;
+    const size_t a_plane = (size_t)a.ntiles * I8_TILE_STEPS * I8_A_STEP;        // v4i per A plane
+    const v4i* const a_lane = a.planes + (size_t)g * 256 + lane;
+    constexpr double RS2 = 0.70710678118654752440;
+    const double lnc = p.lnc;
+    const int64_t n_rounds = pl.rnd_end - pl.rnd_begin;
+
+    for (int64_t it = 0;; ++it) {
+        int64_t cb; int ib_lo, ib_hi;
+        if (it < n_rounds) {
+            cb = (pl.rnd_begin + it) * pl.P + blockIdx.x; ib_lo = 0; ib_hi = nbi;
+        } else {
+            if (it > n_rounds || !pl.with_tail || pl.nparts <= 0) break;
+            const int64_t c = blockIdx.x / pl.nparts;
+            if (c >= pl.ncb - pl.nfull) break;
+            const int q = blockIdx.x % pl.nparts;
+            cb = pl.nfull + c; ib_lo = pl.bounds[q]; ib_hi = pl.bounds[q + 1];
+        }
+        // ---- the block's kernel columns: k* in fp64 as k_var's generating sweep computes it, B' = rint(k* 2^(p - f)), 14 residue planes.
+        // Wave w generates column tile w; a lane its column's 16 consecutive sources per step.  The image changes owner: its
+        // writers and readers are the waves of this workgroup (one CU), workgroup scope orders them (see k_var).
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+        {
+            const int64_t col = cb * I8_COLS + 16 * w + lc;
+            const int64_t mm = col < a.M ? col : a.M - 1;
+            const double* qp = a.Xq + mm * D;
+            double q[3];
+#pragma unroll
+            for (int d = 0; d < 3; ++d) q[d] = qp[d < D ? d : 0] * ((d < D) ? p.inv_ls[d] * 0.70710678118654752440 : 0.0);
+#pragma unroll 1
+            for (int s = 0; s < I8_TILE_STEPS * ib_hi; ++s) {
+                const double* xp = a.Xs + (size_t)(I8_KSTEP * s + 16 * lk) * 4;
+                double x[16];
+#pragma unroll
+                for (int b = 0; b < 16; ++b) {
+                    const d4 xs = *reinterpret_cast<const d4*>(xp + 4 * b);
+                    const double d0 = xs[0] * RS2 - q[0], d1 = xs[1] * RS2 - q[1], d2_ = xs[2] * RS2 - q[2];
+                    double hh = d0 * d0;
+                    hh = fma(d1, d1, hh);
+                    hh = fma(d2_, d2_, hh);
+                    x[b] = rint(kernel_tab<KT>(hh, lnc, Tt) * a.bq);
+                }
+                i8_store_planes(x, bim + ((size_t)s * 8 + w) * 64 + lane, (size_t)nst * I8_B_STEP);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+
+        for (int ib = ib_hi - 1; ib >= ib_lo; --ib) {
+            const int nmine = (g + 2) & ~1;                             // steps of the diagonal tile this wave runs (even)
+            const int lim = I8_TILE_STEPS * ib + nmine;                 // steps of a sweep this wave runs
+            const size_t tile0 = (size_t)ib * (ib + 1) / 2;
+            // A fragments of step S of modulus j's sweep; past the wave's last step: the next modulus' first steps
+            auto a_ptr = [&](int j, int S) -> const v4i* {
+                if (S >= lim) { S -= lim; ++j; }
+                if (j >= I8_NMOD) { j = I8_NMOD - 1; S = lim - 1; }     // (past the last sweep: a redundant load, in bounds)
+                return a_lane + (size_t)j * a_plane + (tile0 * I8_TILE_STEPS + S) * I8_A_STEP;
+            };
+            // first chunk: modulus 0, tile 0 -> buffer 0 (the last barrier has passed: both buffers are free)
+            {
+                const v4i* src = bim + tid;
+                v4i t8[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) t8[i] = src[512 * i];
+#pragma unroll
+                for (int i = 0; i < 8; ++i) Bs[tid + 512 * i] = t8[i];
+            }
+            v4i ar[2][4];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const v4i* ap = a_ptr(0, i);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ar[i][r] = ap[64 * r];
+            }
+            __syncthreads();
+            v4i acc[4][8];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < 8; ++t) acc[r][t] = v4i{0, 0, 0, 0};
+            int buf = 0;
+            // One tile of a sweep: 8 steps of 32 MFMAs.  FULL: every step runs and a chunk follows — straight-line code, no branch in
+            // it: hipcc places its waits by counting the loads in flight, and behind every join of two paths it waits for all of
+            // them, the A fragments requested two steps ahead included.  Not FULL (the diagonal tile): `nrun` steps, a chunk follows
+            // if `more_rt`.  (One straight-line copy per step count of the diagonal tile was built too: the four copies held
+            // 65 - 300 spill accesses each, accumulators moved around their join.)
+            // Order inside a step: a piece of the next chunk is requested first and written to LDS behind the MFMAs of the FOLLOWING
+            // step, the A fragments of step s + 2 are requested behind the MFMAs of step s, straight into the ring registers those
+            // have just read: no wait is for a load younger than a whole step.
+            auto tile = [&](auto full_tag, const int nrun, const bool more_rt, const int j, const int S0, const v4i* nsrc) __attribute__((always_inline)) {
+                constexpr bool FULL = decltype(full_tag)::value;
+                const bool more = FULL || more_rt;
+                const v4i* bcur = Bs + (size_t)buf * I8_CHUNK + lane;
+                v4i* bnext = Bs + (size_t)(buf ^ 1) * I8_CHUNK + tid;
+                v4i st[2];                                       // pieces of the next chunk on their way to LDS
+#pragma unroll
+                for (int s = 0; s < I8_TILE_STEPS; ++s) {
+                    const bool run = FULL || s < nrun;
+                    if (more) st[s & 1] = nsrc[512 * s];
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (run) {
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) {
+                            const v4i b = bcur[(s * 8 + t) * 64];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) acc[r][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[s & 1][r], b, acc[r][t], 0, 0, 0);
+                        }
+                        // B fragments are read two column tiles ahead of the MFMAs that take them
+                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+                        for (int t = 0; t < 6; ++t) {
+                            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        }
+                        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (more && s > 0) bnext[512 * (s - 1)] = st[(s - 1) & 1];
+                    if (run) {
+                        const v4i* ap = a_ptr(j, S0 + s + 2);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) ar[s & 1][r] = ap[64 * r];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (more) bnext[512 * (I8_TILE_STEPS - 1)] = st[(I8_TILE_STEPS - 1) & 1];
+                __syncthreads();
+                buf ^= 1;
+            };
+#pragma unroll 1
+            for (int j = 0; j < I8_NMOD; ++j) {
+#pragma unroll 1
+                for (int kb = 0; kb < ib; ++kb)         // full tiles; the next chunk is the next tile of this sweep
+                    tile(Bool<true>{}, I8_TILE_STEPS, true, j, kb * I8_TILE_STEPS, bim + ((size_t)j * nst + (kb + 1) * I8_TILE_STEPS) * I8_B_STEP + tid);
+                // diagonal tile; the next chunk is tile 0 of the next modulus
+                tile(Bool<false>{}, nmine, j + 1 < I8_NMOD, j, ib * I8_TILE_STEPS, bim + (size_t)(j + 1) * nst * I8_B_STEP + tid);
+                // the sweep of modulus j is complete: reduce, park (4 elements of a tile per dword), start over
+                {
+                    const double m = c_i8_mod[j], inv = c_i8_inv[j], hi = c_i8_hi[j], lo = c_i8_lo[j];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) {
+                            int rr[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) rr[e] = i8_residue((double)acc[r][t][e], m, inv, hi, lo);
+                            pk[(size_t)(j * 32 + r * 8 + t) * 512] = (unsigned)i8_pack4(rr[0], rr[1], rr[2], rr[3]);
+                            acc[r][t] = v4i{0, 0, 0, 0};
+                        }
+                }
+            }
+            // ---- all 14 residues of this i-block's 64 x 128 elements are parked: rebuild, scale, square, sum per column
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll 1
+            for (int t = 0; t < 8; ++t) {
+                double ssq = 0.0;
+#pragma unroll 1
+                for (int r = 0; r < 4; ++r) {
+                    unsigned wd[I8_NMOD];
+#pragma unroll
+                    for (int j = 0; j < I8_NMOD; ++j) wd[j] = pk[(size_t)(j * 32 + r * 8 + t) * 512];
+                    const d4 rs = *reinterpret_cast<const d4*>(a.rowscale + (size_t)ib * I8_ROWS + 64 * g + 16 * r + 4 * lk);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float res[I8_NMOD];
+#pragma unroll
+                        for (int j = 0; j < I8_NMOD; ++j) res[j] = (float)((int)(wd[j] << (24 - 8 * e)) >> 24);
+                        const double v = i8_garner(res) * rs[e] * a.colscale;
+                        ssq = fma(v, v, ssq);
+                    }
+                }
+                ssq += __shfl_xor(ssq, 16);
+                ssq += __shfl_xor(ssq, 32);
+                if (lk == 0) red[w][16 * t + lc] = ssq;
+            }
+            __syncthreads();
+            if (tid < I8_COLS) {
+                double v = 0.0;
+#pragma unroll
+                for (int ww = 0; ww < 8; ++ww) v += red[ww][tid];
+                a.slab[((size_t)cb * nbi + ib) * I8_COLS + tid] = v;
+            }
+        }
+    }
+}
+
+// var[m] = c + noise - sum over the i-blocks, in order, of the column's slots (k_var_finalize's formula)
+__global__ __launch_bounds__(I8_COLS) void k_var_i8_finalize(KernelParams p, int nbi, const double* __restrict__ slab, int64_t M,
+                                                             const double* __restrict__ hdr, double* __restrict__ var) {
+    const int64_t cb = blockIdx.x, m = cb * I8_COLS + threadIdx.x;
+    if (m >= M) return;
+    double s2 = 0.0;
+    for (int ib = 0; ib < nbi; ++ib) s2 += slab[((size_t)cb * nbi + ib) * I8_COLS + threadIdx.x];
+    const double v = hdr[16] + p.noise - s2;
+    var[m] = v < 0.0 ? 0.0 : v;
+}
+
+}  // namespace gpt

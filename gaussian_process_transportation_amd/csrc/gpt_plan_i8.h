@@ -1,0 +1,119 @@
+// Arithmetic constants and work decomposition of the residue (int8) variance kernel k_var_i8 (host-only C++, no HIP: the
+// plan is replayed on the CPU by tests/test_var_int8_cpu.py through a small program of its own).
+//
+// The product V = W K*^T of an fp64 single-task model is taken exactly on the int8 matrix cores: both operands are rounded to
+// p-bit integers (rows of W against their own power-of-two bound, kernel columns against the prior variance's), the integer
+// product is formed modulo 14 pairwise coprime moduli that fit int8 — one int8 GEMM per modulus, int32 sums — and rebuilt by
+// Garner's mixed-radix conversion.  DESIGN.md section 4 has the derivation; tests/var_int8_restatement.py restates it in numpy.
+//
+// Work split: a workgroup owns a 128-column block and walks the 512-row i-blocks, longest first, as k_var does.  Every
+// (column block, i-block) pair writes its 128 column sums to a slab slot of its own, [cb][ib], and the finalizing kernel adds a
+// column's nbi slots in i-block order: integer partial sums are exact and the fp64 sums have one fixed grouping, so ANY
+// assignment of the pairs to workgroups gives the same bits.
+//   * Rounds: while at least P column blocks are left, workgroup p takes block r P + p whole (all workgroups walk the W planes
+//     in step: an XCD shares one copy of that stream in L2).
+//   * Tail: the ncb_t < P blocks that are left get floor(P / ncb_t) workgroups each (at most nbi); the i-blocks of a block are
+//     dealt to its workgroups in contiguous ranges of about equal cost.  Rows are independent given the kernel columns, so a part
+//     generates the columns it needs again and nothing has to be combined.
+#pragma once
+#include <cstdint>
+#include <cmath>
+#include <vector>
+
+namespace gpt {
+
+constexpr int I8_NMOD = 14;
+constexpr int I8_MODULI[I8_NMOD] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199};
+constexpr int I8_COLS = 128;          // columns per column block (8 MFMA column tiles)
+constexpr int I8_ROWS = 512;          // rows of an i-block (= WT)
+constexpr int I8_KSTEP = 64;          // k per v_mfma_i32_16x16x64_i8
+constexpr int I8_MAX_NBI = 32;        // i-blocks of the largest model the path takes (NP <= 16384: p = 47)
+constexpr int I8_MIN_BITS = 44;       // below this many bits per operand a model stays on the fp64 kernel
+constexpr int I8_SWEEP_FIXED = 3;     // cost of an i-block beside its tiles, in tiles: reduction, reconstruction, first fill
+
+// log2 of the product of the moduli (110.16)
+inline double var_i8_log2_modulus() {
+    double s = 0;
+    for (int j = 0; j < I8_NMOD; ++j) s += std::log2((double)I8_MODULI[j]);
+    return s;
+}
+// bits per operand: NP 2^(2p) < M / 2, so that the integer product is recovered without wrap-around
+inline int var_i8_bits(int NP) {
+    int lg = 0;
+    while (((int64_t)1 << lg) < NP) ++lg;
+    return (int)std::floor((var_i8_log2_modulus() - 1.0 - lg) / 2.0);
+}
+// smallest e with x <= 2^e (x > 0); 0 for x == 0
+inline int var_i8_exponent(double x) {
+    if (!(x > 0)) return 0;
+    int ex;
+    const double f = std::frexp(x, &ex);
+    return f == 0.5 ? ex - 1 : ex;
+}
+// whether a model with this geometry can take the path at all (fp64, one task, D <= 3 is checked by the caller)
+inline bool var_i8_shape_ok(int NP) {
+    return NP >= I8_ROWS && NP % I8_ROWS == 0 && NP / I8_ROWS <= I8_MAX_NBI && var_i8_bits(NP) >= I8_MIN_BITS;
+}
+
+// Device images, in bytes: the residue planes of W (one byte per element of the block lower triangle and modulus); and per
+// workgroup the planes of a column block's kernel columns and the parked residues of an i-block (512 x 128 elements x 14 bytes).
+inline size_t var_i8_plane_bytes(int NP) { const size_t nb = NP / I8_ROWS; return (size_t)I8_NMOD * (nb * (nb + 1) / 2) * I8_ROWS * I8_ROWS; }
+inline size_t var_i8_bimg_bytes(int NP) { return (size_t)I8_NMOD * NP * I8_COLS; }
+constexpr size_t var_i8_park_bytes() { return (size_t)I8_NMOD * I8_ROWS * I8_COLS; }
+
+// Passed by value to the kernels.
+struct VarI8PlanDev {
+    int64_t ncb;          // column blocks
+    int64_t nfull;        // blocks handled whole in rounds (a multiple of P)
+    int P, nbi;
+    int nparts;           // workgroups per tail block (0: no tail)
+    int bounds[I8_MAX_NBI + 1];      // part q of a tail block takes the i-blocks [bounds[q], bounds[q + 1])
+    // the part of the plan one launch executes (launch_var_i8: rounds are dealt to several launches, the tail goes with the last)
+    int64_t rnd_begin = 0, rnd_end = 0;
+    int with_tail = 1;
+};
+
+inline int var_i8_iblock_cost(int ib) { return ib + 1 + I8_SWEEP_FIXED; }
+
+inline VarI8PlanDev build_var_i8_plan(int64_t ncols, int nbi, int P) {
+    VarI8PlanDev d{};
+    d.ncb = (ncols + I8_COLS - 1) / I8_COLS;
+    d.P = P; d.nbi = nbi;
+    d.nfull = d.ncb / P * P;
+    const int64_t ncb_t = d.ncb - d.nfull;
+    d.nparts = 0;
+    for (int q = 0; q <= I8_MAX_NBI; ++q) d.bounds[q] = nbi;
+    if (ncb_t == 0) return d;
+    int nparts = (int)(P / ncb_t);
+    if (nparts > nbi) nparts = nbi;
+    if (nparts < 1) nparts = 1;
+    d.nparts = nparts;
+    // contiguous ranges of about equal cost: boundary q sits where the running cost passes q / nparts of the total, and every
+    // part keeps at least one i-block
+    int64_t total = 0;
+    for (int ib = 0; ib < nbi; ++ib) total += var_i8_iblock_cost(ib);
+    d.bounds[0] = 0;
+    int ib = 0;
+    int64_t cum = 0;
+    for (int q = 1; q < nparts; ++q) {
+        const int64_t target = total * q / nparts;
+        const int lo = d.bounds[q - 1] + 1, hi = nbi - (nparts - q);      // leave one i-block for every later part
+        while (ib < hi && (ib < lo || cum + var_i8_iblock_cost(ib) / 2 < target)) cum += var_i8_iblock_cost(ib++);
+        d.bounds[q] = ib;
+    }
+    d.bounds[nparts] = nbi;
+    return d;
+}
+
+// What workgroup `wg` does in the tail: column block *cb, i-blocks [*ib_lo, *ib_hi); false: nothing.  (The kernel has the same
+// three lines; this copy is for the host-side replay.)
+inline bool var_i8_tail_item(const VarI8PlanDev& d, int wg, int64_t* cb, int* ib_lo, int* ib_hi) {
+    if (d.nparts <= 0) return false;
+    const int64_t c = wg / d.nparts;
+    if (c >= d.ncb - d.nfull) return false;
+    const int q = wg % d.nparts;
+    *cb = d.nfull + c; *ib_lo = d.bounds[q]; *ib_hi = d.bounds[q + 1];
+    return true;
+}
+
+}  // namespace gpt

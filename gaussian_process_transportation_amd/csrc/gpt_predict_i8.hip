@@ -1,0 +1,49 @@
+// Launchers of the residue (int8) variance path: the image of W in residue planes (once per model) and the k*-alone variance of
+// an fp64 single-task model, D <= 3.  Kernels: gpt_kvar_i8.h; arithmetic and plan: gpt_plan_i8.h; who takes the path: gpt_api.hip.
+#include "gpt_common.h"
+#include "gpt_kvar_i8.h"
+#include <cstdlib>
+
+namespace gpt {
+
+void launch_var_i8_image(hipStream_t s, const double* Wf, int NP, int bits, void* planes, double* rowscale, double* qscale, void* rowmax) {
+    const int nbi = NP / I8_ROWS, ntiles = nbi * (nbi + 1) / 2;
+    unsigned long long* rm = static_cast<unsigned long long*>(rowmax);
+    (void)hipMemsetAsync(rm, 0, (size_t)NP * sizeof(unsigned long long), s);
+    const dim3 grid(ntiles, 8);
+    hipLaunchKernelGGL(k_i8_rowmax, grid, dim3(256), 0, s, Wf, rm);
+    hipLaunchKernelGGL(k_i8_rowscale, dim3((NP + 255) / 256), dim3(256), 0, s, rm, NP, bits, rowscale, qscale);
+    hipLaunchKernelGGL(k_i8_planes, grid, dim3(256), 0, s, Wf, qscale, ntiles, static_cast<v4i*>(planes));
+}
+
+void launch_var_i8(hipStream_t s, const KernelParams& p, const VarI8PlanDev& plan, int bits, const void* planes, const double* rowscale,
+                   const double* Xs, const double* Xq, int64_t M, double* slab, void* bimg, void* park, double* var, const double* hdr) {
+    if (M <= 0) return;
+    VarI8Args a{};
+    a.planes = static_cast<const v4i*>(planes); a.rowscale = rowscale; a.Xs = Xs; a.Xq = Xq; a.M = M;
+    a.slab = slab; a.bimg = static_cast<v4i*>(bimg); a.park = static_cast<unsigned*>(park);
+    const int f = var_i8_exponent(p.c);                  // one column exponent, from the prior variance: k* <= c <= 2^f
+    a.bq = std::ldexp(1.0, bits - f);
+    a.colscale = std::ldexp(1.0, f - bits);
+    a.ntiles = plan.nbi * (plan.nbi + 1) / 2;
+    // rounds per launch: the setting of launch_var (in rounds of 136 tiles), for the same reason — workgroups that drift apart stop
+    // sharing the W stream in L2, and a kernel boundary brings them together
+    const int64_t rounds = plan.nfull / plan.P;
+    const char* e = getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
+    const int rpl_set = e ? (atoi(e) < 0 ? 0 : atoi(e)) : 16;
+    const int64_t rpl_scaled = ((int64_t)rpl_set * 136 + a.ntiles - 1) / a.ntiles;
+    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
+    if (const char* x = getenv("GPT_VAR_ROUNDS_EXACT")) { if (atoi(x) > 0) rpl = atoi(x); }
+    for (int64_t r0 = 0; r0 == 0 || r0 < rounds; r0 += rpl) {
+        VarI8PlanDev pl = plan;
+        pl.rnd_begin = r0;
+        pl.rnd_end = r0 + rpl < rounds ? r0 + rpl : rounds;
+        pl.with_tail = pl.rnd_end >= rounds ? 1 : 0;
+        with_kernel_type(p.ktype, [&](auto kt) {
+            launch_lds<k_var_i8<decltype(kt)::value>>(dim3((unsigned)plan.P), dim3(512), I8_LDS_BYTES, s, p, pl, a);
+        });
+    }
+    hipLaunchKernelGGL(k_var_i8_finalize, dim3((unsigned)plan.ncb), dim3(I8_COLS), 0, s, p, plan.nbi, slab, M, hdr, var);
+}
+
+}  // namespace gpt

@@ -3,6 +3,7 @@
 // checks the buffer sizing of the host orchestration (staging, model blob, slab / vslab / scratch of the variance plan).
 #include "../gpt_common.h"
 #include "../gpt_plan.h"
+#include "../gpt_plan_i8.h"
 #include "../gpt_fit_plan.h"
 #include "../gpt_transport.h"
 #include "../gpt_pullback.h"
@@ -144,6 +145,20 @@ void launch_var(hipStream_t, const KernelParams& p, const VarWorkspace& ws, cons
         }
     (void)var_cols_per_query(p.D, ncomp);
     touch_w(var, (size_t)M * p.ntask * e); touch_w(Jvar, (size_t)M * p.ntask * p.D * e); touch_w(dvar, (size_t)M * p.D * e);
+}
+
+void launch_var_i8_image(hipStream_t, const double* Wf, int NP, int, void* planes, double* rowscale, double* qscale, void* rowmax) {
+    touch_r(Wf, wf_elems(NP) * 8);
+    touch_w(planes, var_i8_plane_bytes(NP)); touch_w(rowscale, (size_t)NP * 8); touch_w(qscale, (size_t)NP * 8); touch_w(rowmax, (size_t)NP * 8);
+}
+void launch_var_i8(hipStream_t, const KernelParams& p, const VarI8PlanDev& plan, int, const void* planes, const double* rowscale,
+                   const double* Xs, const double* Xq, int64_t M, double* slab, void* bimg, void* park, double* var, const double* hdr) {
+    if (M <= 0) return;
+    touch_r(planes, var_i8_plane_bytes(p.NP)); touch_r(rowscale, (size_t)p.NP * 8); touch_r(Xs, (size_t)p.NP * 4 * 8);
+    touch_r(Xq, (size_t)M * p.D * 8); touch_r(hdr, 17 * 8);
+    touch_w(slab, (size_t)plan.ncb * plan.nbi * I8_COLS * 8);
+    touch_w(bimg, (size_t)plan.P * var_i8_bimg_bytes(p.NP)); touch_w(park, (size_t)plan.P * var_i8_park_bytes());
+    touch_w(var, (size_t)M * 8);
 }
 
 }  // namespace gpt

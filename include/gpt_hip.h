@@ -533,6 +533,10 @@ int gpt_fit_timings(gpt_handle* h, double* ms_out, int n);
  * ms_out[1] = variance (MFMA) kernel; 0 for a kernel that was not launched. */
 int gpt_set_profiling(gpt_handle* h, int enable);
 int gpt_predict_timings(gpt_handle* h, double* ms_out);
+/* Which kernel the last variance launch of this handle took: 0 the fp64 kernel, 1 the residue (int8) kernel, -1 no launch yet.
+ * The int8 path takes k*-alone launches of fp64 single-task models with D <= 3; GPT_VAR_INT8 = 0 / 1 in the environment forces
+ * it off / on (read per call). */
+int gpt_debug_var_path(gpt_handle* h);
 
 /* Test hook (host only, no GPU): the work decomposition of the variance kernel for a launch of n_columns kernel
  * columns over n_iblocks 512-row blocks x n_tasks tasks on n_workgroups workgroups (csrc/gpt_plan.h).

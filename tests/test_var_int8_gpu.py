@@ -1,0 +1,177 @@
+"""The residue (int8) variance kernel on the GPU, forced on with GPT_VAR_INT8=1: against the numpy restatement
+(tests/var_int8_restatement.py, 1e-12 absolute), against the oracle (RTOL), and bit-equal between any two ways of running
+the same queries.  Model: N = 1300 (padded to 1536: three i-blocks, rows off the tile edge); column blocks have 128 columns and
+the device has one workgroup per CU, so 33 000 queries are more than 256 blocks plus a remainder (whole rounds and a split tail)
+on a 256-CU device."""
+import numpy as np
+import pytest
+from scipy.linalg import solve_triangular
+
+from oracle import gp_oracle as orc
+from tests import var_int8_restatement as r8
+
+pytestmark = pytest.mark.gpu
+
+RTOL = 1e-5
+ATOL8 = 1e-12
+N, NP = 1300, 1536
+C0, LS, NOISE, JIT = 0.1, np.array([0.1, 0.1, 0.1]), 1e-4, 1e-10
+KINDS = ("rbf", "matern12", "matern32", "matern52")
+BATCHES = [1, 128, 129, 33000]
+
+
+def fit(X, Y, kind=0, ls=LS):
+    from gaussian_process_transportation_amd import _lib
+    h = _lib.Handle(0)
+    h.fit(X, Y, ls, C0, NOISE, JIT, kernel_type=kind)
+    return h
+
+
+def var_i8(h, Xq):
+    v = h.predict_all(Xq, var=True)["var"]
+    assert h.var_path() == 1, "the residue kernel did not take this launch"
+    return v
+
+
+@pytest.fixture(scope="module")
+def problem():
+    X, Y, Xq = orc.synthetic_problem(N, max(BATCHES))
+    return X, Y, Xq
+
+
+@pytest.fixture()
+def forced(monkeypatch):
+    monkeypatch.setenv("GPT_VAR_INT8", "1")
+    return monkeypatch
+
+
+@pytest.fixture(scope="module")
+def reference(problem):
+    """W of the GPU's own fit, the restatement's variance of every query (fast form; the residue pipeline itself on the first 256
+    and the last 256 queries) and the oracle's — computed once"""
+    X, Y, Xq = problem
+    h = fit(X, Y)
+    W = h.export_inverse_factor()
+    h.close()
+    Kst = orc.kernel_cross(Xq, X, C0, LS).T.copy()
+    fast = r8.variance_quantised(W, Kst, C0, NOISE, NP)
+    ends = np.r_[0:256, Xq.shape[0] - 256:Xq.shape[0]]
+    full = r8.variance(W, Kst[:, ends], C0, NOISE, NP)
+    L, a = orc.gpr_fit(X, Y, C0, LS, NOISE, JIT)
+    V = solve_triangular(L, Kst, lower=True, check_finite=False)
+    oracle = np.maximum(C0 + NOISE - np.sum(V * V, axis=0), 0.0)
+    return dict(W=W, fast=fast, ends=ends, full=full, oracle=oracle)
+
+
+@pytest.fixture()
+def handle(problem, forced):
+    X, Y, _ = problem
+    h = fit(X, Y)
+    yield h
+    h.close()
+
+
+@pytest.mark.parametrize("M", BATCHES)
+def test_against_restatement_and_oracle(handle, problem, reference, M):
+    Xq = problem[2][:M]
+    v = var_i8(handle, Xq)
+    e_fast = float(np.max(np.abs(v - reference["fast"][:M])))
+    e_or = float(np.max(np.abs(v - reference["oracle"][:M])) / np.max(np.abs(reference["oracle"][:M])))
+    print(f"M={M}: max |var - restatement| = {e_fast:.3e}, oracle rel = {e_or:.3e}")
+    assert e_fast <= ATOL8
+    assert e_or <= RTOL
+    n = min(M, 256)
+    assert np.max(np.abs(v[:n] - reference["full"][:n])) <= ATOL8
+    if M == max(BATCHES):
+        assert np.max(np.abs(v[-256:] - reference["full"][256:])) <= ATOL8
+
+
+def test_bit_equal_between_calls_halves_and_launch_splits(handle, problem, forced):
+    Xq = np.vstack([problem[2], problem[2][::-1]])       # 66 000 queries: two whole rounds on 256 CUs, so that the launches can be split
+    M = Xq.shape[0]
+    a = var_i8(handle, Xq)
+    assert np.array_equal(a, var_i8(handle, Xq))
+    assert np.array_equal(a[:33000], a[:32999:-1])       # the same query at another place of another block
+    half = M // 2 + 37                       # not a multiple of the block: every column changes its place in its block
+    assert np.array_equal(a[:half], var_i8(handle, Xq[:half]))
+    assert np.array_equal(a[half:], var_i8(handle, Xq[half:]))
+    for exact in ("1", "1000"):
+        forced.setenv("GPT_VAR_ROUNDS_EXACT", exact)
+        assert np.array_equal(a, var_i8(handle, Xq))
+    forced.delenv("GPT_VAR_ROUNDS_EXACT")
+    # and the path is a choice per call: off gives the fp64 kernel's result, within its own bound of this one
+    forced.setenv("GPT_VAR_INT8", "0")
+    b = handle.predict_all(Xq[:1000], var=True)["var"]
+    assert handle.var_path() == 0
+    assert np.max(np.abs(b - a[:1000])) <= 1e-11
+
+
+def test_refit_with_other_data_rebuilds_the_planes(handle, problem, forced):
+    X, Y, Xq = problem
+    Xq = Xq[:300]
+    var_i8(handle, Xq)
+    X2, Y2, _ = orc.synthetic_problem(N, 1, seed=7)
+    handle.fit(X2, Y2, LS, C0, NOISE, JIT)
+    reused = var_i8(handle, Xq)
+    fresh_h = fit(X2, Y2)
+    fresh = var_i8(fresh_h, Xq)
+    # a replica made from the blob alone builds its own planes
+    from gaussian_process_transportation_amd import _lib
+    rep = _lib.Handle(0)
+    rep.factor_copy_from(fresh_h)
+    copied = var_i8(rep, Xq)
+    fresh_h.close(); rep.close()
+    assert np.array_equal(reused, fresh)
+    assert np.array_equal(copied, fresh)
+
+
+def test_queries_far_outside_the_data_get_the_prior(handle, forced):
+    v = var_i8(handle, np.full((130, 3), 40.0))
+    assert np.max(np.abs(v - (C0 + NOISE))) <= 1e-15
+
+
+def test_query_on_a_source_point(handle, problem, reference, forced):
+    X = problem[0]
+    Xq = X[[0, 17, N - 1]]
+    v = var_i8(handle, Xq)
+    Kst = orc.kernel_cross(Xq, X, C0, LS).T.copy()
+    ref = r8.variance(reference["W"], Kst, C0, NOISE, NP)
+    assert np.max(np.abs(v - ref)) <= ATOL8
+    assert np.all(v < 2 * NOISE)             # at a source the posterior variance is of the size of the noise
+
+
+def test_matern52_model(problem, forced):
+    X, Y, Xq = problem
+    Xq = Xq[:200]
+    forced.setenv("GPT_VAR_INT8", "0")
+    h = fit(X, Y, kind=3)
+    W = h.export_inverse_factor()
+    v0 = h.predict_all(Xq, var=True)["var"]
+    forced.setenv("GPT_VAR_INT8", "1")
+    v = var_i8(h, Xq)                        # (the planes are built at the first call that wants them)
+    h.close()
+    Kst = orc.kernel_cross(Xq, X, C0, LS, kind="matern52").T.copy()
+    assert np.max(np.abs(v - r8.variance(W, Kst, C0, NOISE, NP))) <= ATOL8
+    assert np.max(np.abs(v - v0)) <= 1e-11
+
+
+def test_wide_models_fp32_models_and_derivative_launches_stay_on_k_var(forced):
+    from gaussian_process_transportation_amd import _lib
+    X, Y, Xq = orc.synthetic_problem(600, 50, D=5)
+    h = _lib.Handle(0)
+    h.fit(X, Y, np.full(5, 0.3), C0, NOISE, JIT)
+    h.predict_all(Xq, var=True)
+    assert h.var_path() == 0                 # D = 5: the path does not claim the wide layouts
+    h.close()
+    X, Y, Xq = orc.synthetic_problem(600, 50)
+    h = _lib.Handle(0)
+    h.fit(X, Y, LS, C0, NOISE, JIT)
+    h.predict_all(Xq, var=True, Jvar=True)
+    assert h.var_path() == 0                 # derivative columns
+    h.predict_all(Xq, var=True)
+    assert h.var_path() == 1
+    h.set_dtype(_lib.GPT_F32)
+    h.fit(X, Y, LS, C0, NOISE, JIT)
+    h.predict_all(Xq.astype(np.float32), var=True)
+    assert h.var_path() == 0                 # fp32 model
+    h.close()
