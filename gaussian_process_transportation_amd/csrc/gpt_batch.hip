@@ -4,7 +4,8 @@
 // model costs.  Here ONE workgroup owns one model from the Gram matrix to the gradient, and one launch serves every model of a
 // size class (n <= 32: 64 threads and 12.5 KB of LDS, so many models share a CU; n <= 128: 256 threads and the 129-column image).
 //
-// bat_factor keeps the n x n image A in LDS with an odd row stride (column walks hit distinct banks):
+// bat_factor is a prologue (the model's rows and hyper-parameters), bat_factor_body (gpt_batch_device.h) and the write of the
+// LML, the gradient and the status.  The body keeps the n x n image A in LDS with an odd row stride (column walks hit distinct banks):
 //     lower triangle: K, then its Cholesky factor L in place (right-looking, two barriers per column)
 //     upper triangle: W^T, W = L^-1, built row by row (row i of W needs row i of L and the finished rows above it; writing
 //                     it transposed leaves L readable, so a step has one barrier); 1 / L_ii in a vector of its own
@@ -20,8 +21,8 @@
 // on the other queries — bit for bit.  That is why the size class is chosen per model, not per batch.
 //
 // Device side only: the kernels and the two launchers of gpt_batch.h.  The entry points are in gpt_batch_host.hip.  The size
-// classes (BatCfg), block_sum and kernel_libm_g are in gpt_batch_device.h, with bat_factor's body restated as a function for
-// bat_optimize (gpt_batch_opt.hip): a change to the body below belongs there too.
+// classes (BatCfg), block_sum, kernel_libm_g and the one text of the factorisation, bat_factor_body, with bat_lml and bat_grad, are
+// in gpt_batch_device.h: bat_optimize (gpt_batch_opt.hip) runs the same function once per objective evaluation.
 #include "gpt_batch.h"
 #include "gpt_batch_device.h"
 #include "gpt_dispatch.h"
@@ -34,7 +35,7 @@ namespace {
 template <int NMAX, int KT, bool OBJ>
 __global__ __launch_bounds__(BatCfg<NMAX>::NT) void bat_factor(BatArgs a) {
     using Cfg = BatCfg<NMAX>;
-    constexpr int NT = Cfg::NT, TX = Cfg::TX, TY = Cfg::TY, LD = Cfg::LD;
+    constexpr int NT = Cfg::NT, LD = Cfg::LD;
     extern __shared__ __attribute__((aligned(16))) double bat_lds[];
     double* __restrict__ A = bat_lds;                    // NMAX x LD
     double* __restrict__ buf = A + NMAX * LD;            // n x O: y, then W y, then alpha
@@ -44,163 +45,20 @@ __global__ __launch_bounds__(BatCfg<NMAX>::NT) void bat_factor(BatArgs a) {
     const int b = a.list[blockIdx.x];
     const int64_t n0 = a.n_begin[b];
     const int n = (int)(a.n_begin[b + 1] - n0);
-    const int D = a.D, O = a.O, tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
+    const int D = a.D, tid = threadIdx.x;
     const double c = a.c[b], noise = a.noise[b];
-    const double* __restrict__ X = a.X + n0 * D;
-    const double* __restrict__ Y = a.Y + n0 * O;
     double il[MAX_DIMS];
 #pragma unroll
     for (int d = 0; d < MAX_DIMS; ++d) il[d] = d < D ? 1.0 / a.ls[(int64_t)b * a.n_ls + (a.n_ls == 1 ? 0 : d)] : 0.0;
 
-    // K: sklearn's kernel_(X) with the WhiteKernel on the diagonal, then + alpha (_gpr.py:346-347)
-    for (int i = ty; i < n; i += TY)
-        for (int j = tx; j <= i; j += TX) {
-            double kv = (c + noise) + a.jitter;
-            if (i != j) {
-                double r2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < MAX_DIMS; ++d)
-                    if (d < D) { const double u = (X[i * D + d] - X[j * D + d]) * il[d]; r2 = fma(u, u, r2); }
-                kv = kernel_libm(KT, c, r2);
-            }
-            A[i * LD + j] = kv;
-        }
-    __syncthreads();
-
-    // Cholesky, right-looking; the diagonal keeps the pivots until the end (nothing below reads it after its own column)
-    for (int j = 0; j < n; ++j) {
-        const double piv = A[j * LD + j];
-        if (!(piv > 0.0)) {                       // the same LDS value in every thread: all of them leave
-            if (tid == 0) a.status[b] = GPT_E_NOT_PD;
-            return;
-        }
-        const double r = sqrt(piv);
-        for (int i = j + 1 + tid; i < n; i += NT) A[i * LD + j] /= r;
-        __syncthreads();
-        for (int i = j + 1 + ty; i < n; i += TY) {
-            const double lij = A[i * LD + j];
-            for (int k = j + 1 + tx; k <= i; k += TX) A[i * LD + k] = fma(-lij, A[k * LD + j], A[i * LD + k]);
-        }
-        __syncthreads();
-    }
-    double sums[BAT_RED] = {};                     // [0] y.alpha  [1] sum log L_ii  [2] d/dc (off-diagonal)  [3] trace  [4 + d] d/dl_d
-    for (int i = tid; i < n; i += NT) {
-        const double l = sqrt(A[i * LD + i]);
-        A[i * LD + i] = l;
-        dinv[i] = 1.0 / l;
-        sums[1] += log(l);
-    }
-    __syncthreads();
-
-    // W = L^-1, row by row, W_ij kept at A[j][i]:  W_ij = -(sum_{k=j}^{i-1} L_ik W_kj) / L_ii
-    for (int i = 1; i < n; ++i) {
-        for (int j = tid; j < i; j += NT) {
-            double s = A[i * LD + j] * dinv[j];
-            for (int k = i - 1; k > j; --k) s = fma(A[i * LD + k], A[j * LD + k], s);
-            A[j * LD + i] = -s * dinv[i];
-        }
-        __syncthreads();
-    }
-
-    // alpha = W^T (W y): each thread owns up to PER_THREAD (point, output) pairs and carries them over the two barriers
-    const int nO = n * O;
-    for (int e = tid; e < nO; e += NT) buf[e] = Y[e];
-    __syncthreads();
-    double reg[Cfg::PER_THREAD];
-#pragma unroll
-    for (int u = 0; u < Cfg::PER_THREAD; ++u) {
-        const int e = tid + u * NT;
-        reg[u] = 0.0;
-        if (e < nO) {
-            const int i = e / O, o = e - i * O;
-            double s = 0.0;
-            for (int k = 0; k < i; ++k) s = fma(A[k * LD + i], buf[k * O + o], s);
-            reg[u] = fma(dinv[i], buf[e], s);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < Cfg::PER_THREAD; ++u) {
-        const int e = tid + u * NT;
-        if (e < nO) buf[e] = reg[u];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < Cfg::PER_THREAD; ++u) {
-        const int e = tid + u * NT;
-        if (e < nO) {
-            const int i = e / O, o = e - i * O;
-            double s = dinv[i] * buf[e];
-            for (int k = i + 1; k < n; ++k) s = fma(A[i * LD + k], buf[k * O + o], s);
-            reg[u] = s;
-            sums[0] = fma(Y[e], s, sums[0]);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < Cfg::PER_THREAD; ++u) {
-        const int e = tid + u * NT;
-        if (e < nO) {
-            buf[e] = reg[u];
-            if (!OBJ) a.alpha[n0 * O + e] = reg[u];
-        }
-    }
-    __syncthreads();
-
-    if (!OBJ) {
-        if (a.L) {
-            double* __restrict__ Lg = a.L + a.l_begin[b];
-            for (int i = ty; i < n; i += TY)
-                for (int j = tx; j < n; j += TX) Lg[i * n + j] = j <= i ? A[i * LD + j] : 0.0;
-        }
-        if (a.Wp) {
-            double* __restrict__ Wg = a.Wp + a.w_begin[b];
-            for (int i = ty; i < n; i += TY)
-                for (int j = tx; j <= i; j += TX) Wg[i * (i + 1) / 2 + j] = j < i ? A[j * LD + i] : dinv[i];
-        }
-    }
-
-    if (OBJ) {
-        // 1/2 tr((alpha alpha^T - O K^-1) dK/dtheta): the strict lower triangle counts twice, dK/dtheta from the coordinates
-        for (int i = ty; i < n; i += TY)
-            for (int j = tx; j <= i; j += TX) {
-                double kin = i == j ? dinv[i] * dinv[i] : dinv[i] * A[j * LD + i];
-                for (int k = i + 1; k < n; ++k) kin = fma(A[i * LD + k], A[j * LD + k], kin);
-                double aa = 0.0;
-                for (int o = 0; o < O; ++o) aa = fma(buf[i * O + o], buf[j * O + o], aa);
-                const double inner = aa - (double)O * kin;
-                if (i == j) { sums[3] += inner; continue; }
-                double r2 = 0.0;
-#pragma unroll
-                for (int d = 0; d < MAX_DIMS; ++d)
-                    if (d < D) { const double u = (X[i * D + d] - X[j * D + d]) * il[d]; r2 = fma(u, u, r2); }
-                const double kv = kernel_libm(KT, c, r2);
-                const double wg = inner * kernel_libm_g<KT>(c, r2, kv);
-                sums[2] = fma(inner, kv, sums[2]);
-                if (a.n_ls == 1) sums[4] = fma(wg, r2, sums[4]);
-                else {
-#pragma unroll
-                    for (int d = 0; d < MAX_DIMS; ++d)
-                        if (d < D) { const double u = (X[i * D + d] - X[j * D + d]) * il[d]; sums[4 + d] = fma(wg, u * u, sums[4 + d]); }
-                }
-            }
-        block_sum<NT, BAT_RED>(sums, red);
-    } else {
-        double two[2] = {sums[0], sums[1]};
-        block_sum<NT, 2>(two, red);
-        sums[0] = two[0]; sums[1] = two[1];
+    double sums[BAT_RED];                                // zeroed by the body
+    if (!bat_factor_body<NMAX, KT, OBJ>(a, b, n0, n, c, noise, il, A, buf, dinv, red, sums)) {
+        if (tid == 0) a.status[b] = GPT_E_NOT_PD;        // every thread is here: nothing else of the model is written
+        return;
     }
     if (tid == 0) {
-        const double lml = -0.5 * sums[0] - (double)O * sums[1] - (double)O * (0.5 * n) * 1.8378770664093453;   // log(2 pi)
-        if (a.lml) a.lml[b] = lml;
-        if (OBJ) {
-            double* __restrict__ g = a.grad + (int64_t)b * (2 + a.n_ls);
-            g[0] = sums[2] + 0.5 * c * sums[3];
-#pragma unroll
-            for (int d = 0; d < MAX_DIMS; ++d)
-                if (d < a.n_ls) g[1 + d] = sums[4 + d];
-            g[1 + a.n_ls] = 0.5 * noise * sums[3];
-        }
+        if (a.lml) a.lml[b] = bat_lml(sums, n, a.O);
+        if (OBJ) bat_grad(sums, c, noise, a.n_ls, a.grad + (int64_t)b * (2 + a.n_ls));
         a.status[b] = GPT_OK;
     }
 }

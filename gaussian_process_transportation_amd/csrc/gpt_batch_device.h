@@ -1,10 +1,10 @@
 // Device code of the batched small-GP unit outside its kernels (internal header, device halves only): the size classes, the
 // workgroup sum, and one model's factorisation from the Gram matrix to the reduced sums of the LML and its gradient as a function,
-// bat_factor_body, which bat_optimize (gpt_batch_opt.hip) runs once per objective evaluation of a run.  It restates the body of
-// bat_factor (gpt_batch.hip) statement for statement, with a return value in place of the kernel's exit at a bad pivot.
-// bat_factor keeps its own text: built on this function its instruction stream differs from the one its tests and measurements
-// were taken on (tools/device_isa_diff.py), built as it is it does not.  A change to either belongs in both.  The image and the
-// summation orders are described at the top of gpt_batch.hip.
+// bat_factor_body, with the LML and the gradient assembled from those sums (bat_lml, bat_grad).  It is the only text of that
+// computation: bat_factor (gpt_batch.hip) calls it once per model, bat_optimize (gpt_batch_opt.hip) once per objective evaluation
+// of a run, so the search optimises exactly what gpt_batch_lml_objective and gpt_batch_fit report.  The order of its statements,
+// barriers and sums is what the bit-for-bit independence of a model from its batch rests on.  The image and the summation orders
+// are described at the top of gpt_batch.hip.
 #pragma once
 #include "gpt_batch.h"
 #include "gpt_exp.h"
@@ -63,7 +63,9 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double (*red)[NT / 64
 // in buf, 1 / L_ii in dinv, and in every thread the reduced sums
 //     [0] y.alpha  [1] sum log L_ii  and, OBJ only,  [2] d/dc (off-diagonal)  [3] trace  [4 + d] d/dl_d.
 // !OBJ also writes a.alpha and whichever of a.L, a.Wp are not null.  Returns false at a pivot that is not positive: the pivot is
-// the same LDS value in every thread, so all of them return there together, after the same barriers.
+// the same LDS value in every thread, so all of them return there together, after the same barriers, with nothing written to
+// global memory.  `sums` comes in uninitialised and is zeroed here, after the Cholesky loop: zeroed by the caller its BAT_RED
+// values would stay live in registers through the Gram and Cholesky loops.
 template <int NMAX, int KT, bool OBJ>
 __device__ __forceinline__ bool bat_factor_body(const BatArgs& a, const int b, const int64_t n0, const int n, const double c, const double noise,
                                                 const double (&il)[MAX_DIMS], double* __restrict__ A, double* __restrict__ buf,
@@ -102,6 +104,8 @@ __device__ __forceinline__ bool bat_factor_body(const BatArgs& a, const int b, c
         }
         __syncthreads();
     }
+#pragma unroll
+    for (int q = 0; q < BAT_RED; ++q) sums[q] = 0.0;
     for (int i = tid; i < n; i += NT) {
         const double l = sqrt(A[i * LD + i]);
         A[i * LD + i] = l;
@@ -214,6 +218,15 @@ __device__ __forceinline__ bool bat_factor_body(const BatArgs& a, const int b, c
 // LML from the reduced sums of bat_factor_body
 __device__ __forceinline__ double bat_lml(const double (&sums)[BAT_RED], const int n, const int O) {
     return -0.5 * sums[0] - (double)O * sums[1] - (double)O * (0.5 * n) * 1.8378770664093453;   // log(2 pi)
+}
+
+// ... and its gradient by theta = log [c, l (n_ls of them), noise] into g[0 .. 2 + n_ls)
+__device__ __forceinline__ void bat_grad(const double (&sums)[BAT_RED], const double c, const double noise, const int n_ls, double* __restrict__ g) {
+    g[0] = sums[2] + 0.5 * c * sums[3];
+#pragma unroll
+    for (int d = 0; d < MAX_DIMS; ++d)
+        if (d < n_ls) g[1 + d] = sums[4 + d];
+    g[1 + n_ls] = 0.5 * noise * sums[3];
 }
 
 }  // namespace gpt

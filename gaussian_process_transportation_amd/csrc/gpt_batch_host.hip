@@ -8,6 +8,40 @@
 #include <algorithm>
 
 namespace gpt {
+
+int check_batch_geometry(const std::string& w, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O,
+                         int n_ls, double jitter, int ktype) {
+    if (B < 1 || B > BAT_MAX_B) return fail(GPT_E_ARG, w + ": B (models) must be 1 .. 2^20, got " + std::to_string(B));
+    if (D < 1 || D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
+    if (O < 1 || O > BAT_MAX_O) return fail(GPT_E_ARG, w + ": O (outputs) must be 1 .. 16, got " + std::to_string(O));
+    if (n_ls != 1 && n_ls != D) return fail(GPT_E_ARG, w + ": n_ls must be 1 or D");
+    if (ktype < GPT_KERNEL_RBF || ktype > GPT_KERNEL_MATERN52) return fail(GPT_E_ARG, w + ": unknown kernel_type");
+    if (!(jitter >= 0) || !std::isfinite(jitter)) return fail(GPT_E_ARG, w + ": alpha_jitter must be finite and >= 0");
+    if (n_begin[0] != 0) return fail(GPT_E_ARG, w + ": n_begin[0] must be 0");
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = n_begin[b + 1] - n_begin[b];
+        if (n < 1 || n > BAT_MAX_N)
+            return fail(GPT_E_ARG, w + ": every model needs 1 <= n_b <= 128 points with increasing offsets; model " + std::to_string(b) +
+                                       " has n_begin " + std::to_string(n_begin[b]) + " .. " + std::to_string(n_begin[b + 1]));
+    }
+    if (!all_finite(X, (size_t)n_begin[B] * D) || !all_finite(Y, (size_t)n_begin[B] * O))
+        return fail(GPT_E_ARG, w + ": X or Y contains NaN or infinity");
+    return GPT_OK;
+}
+
+int small_class_first(const int64_t* n_begin, const int* model, int64_t count, std::vector<int>& list) {
+    std::vector<int> large;
+    list.clear();
+    list.reserve(count);
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t b = model ? model[i] : i;
+        (n_begin[b + 1] - n_begin[b] <= BAT_SMALL_N ? list : large).push_back((int)i);
+    }
+    const int n_small = (int)list.size();
+    list.insert(list.end(), large.begin(), large.end());
+    return n_small;
+}
+
 namespace {
 
 // What the three entry points share: the validated batch and the prefix sums the kernels index by.
@@ -21,34 +55,19 @@ struct Batch {
 int check_batch(const std::string& w, Batch& bt, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O,
                 const double* ls, int n_ls, const double* c, const double* noise, double jitter, int ktype, const int* status) {
     if (!X || !Y || !n_begin || !ls || !c || !noise || !status) return fail(GPT_E_ARG, w + ": NULL argument");
-    if (B < 1 || B > BAT_MAX_B) return fail(GPT_E_ARG, w + ": B (models) must be 1 .. 2^20, got " + std::to_string(B));
-    if (D < 1 || D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
-    if (O < 1 || O > BAT_MAX_O) return fail(GPT_E_ARG, w + ": O (outputs) must be 1 .. 16, got " + std::to_string(O));
-    if (n_ls != 1 && n_ls != D) return fail(GPT_E_ARG, w + ": n_ls must be 1 or D");
-    if (ktype < GPT_KERNEL_RBF || ktype > GPT_KERNEL_MATERN52) return fail(GPT_E_ARG, w + ": unknown kernel_type");
-    if (!(jitter >= 0) || !std::isfinite(jitter)) return fail(GPT_E_ARG, w + ": alpha_jitter must be finite and >= 0");
-    if (n_begin[0] != 0) return fail(GPT_E_ARG, w + ": n_begin[0] must be 0");
+    if (int rc = check_batch_geometry(w, X, Y, n_begin, B, D, O, n_ls, jitter, ktype)) return rc;
     bt.B = B;
     bt.l_begin.assign(B + 1, 0);
     bt.w_begin.assign(B + 1, 0);
-    bt.list.resize(B);
-    std::vector<int> large;
     for (int64_t b = 0; b < B; ++b) {
         const int64_t n = n_begin[b + 1] - n_begin[b];
-        if (n < 1 || n > BAT_MAX_N)
-            return fail(GPT_E_ARG, w + ": every model needs 1 <= n_b <= 128 points with increasing offsets; model " + std::to_string(b) +
-                                       " has n_begin " + std::to_string(n_begin[b]) + " .. " + std::to_string(n_begin[b + 1]));
         bt.l_begin[b + 1] = bt.l_begin[b] + n * n;
         bt.w_begin[b + 1] = bt.w_begin[b] + n * (n + 1) / 2;
-        if (n <= BAT_SMALL_N) bt.list[bt.n_small++] = (int)b;
-        else large.push_back((int)b);
     }
-    std::copy(large.begin(), large.end(), bt.list.begin() + bt.n_small);
+    bt.n_small = small_class_first(n_begin, nullptr, B, bt.list);
     bt.rows = n_begin[B];
     bt.l_total = bt.l_begin[B];
     bt.w_total = bt.w_begin[B];
-    if (!all_finite(X, (size_t)bt.rows * D) || !all_finite(Y, (size_t)bt.rows * O))
-        return fail(GPT_E_ARG, w + ": X or Y contains NaN or infinity");
     for (int64_t e = 0; e < B * n_ls; ++e)
         if (!(ls[e] > 0) || !std::isfinite(ls[e])) return fail(GPT_E_ARG, w + ": length_scale must be finite and > 0 (model " + std::to_string(e / n_ls) + ")");
     for (int64_t b = 0; b < B; ++b)

@@ -9,9 +9,9 @@
 //             f(xn) <= f + 1e-4 g.(xn - x); otherwise t /= 2, at most max_ls times, then LINESEARCH
 //             accepted: s = xn - x, y = gn - g (0 on fixed components); BFGS update of H if s.y > 1e-10 |s| |y|;
 //             FTOL if f - fn <= ftol max(|f|, |fn|, 1)
-// (tests/batch_search_restatement.py states the same iteration in numpy.)  The objective and its gradient are what bat_factor
-// computes for gpt_batch_lml_objective (bat_factor_body, gpt_batch_device.h): the whole workgroup works on them, with the same
-// size classes, LDS image and summation orders, so a run's result does not depend on the batch around it.  Everything else is
+// (tests/batch_search_restatement.py states the same iteration in numpy.)  The objective and its gradient come from the function
+// bat_factor is built on for gpt_batch_lml_objective (bat_factor_body, bat_lml, bat_grad: gpt_batch_device.h): the whole workgroup
+// works on them, in the same size classes, so a run's result does not depend on the batch around it.  Everything else is
 // O(P^2) arithmetic, P = 2 + n_ls <= 17, done by thread 0 on the run's record in global memory (gpt_batch_opt.h); the trial point
 // reaches the other threads through LDS.
 //
@@ -47,13 +47,9 @@ __device__ __forceinline__ bool opt_advance(const BatOptArgs& a, const int r, co
     double fn = INF;
     if (ok) {
         fn = -bat_lml(sums, n, a.O);
-        gn[0] = -(sums[2] + 0.5 * c * sums[3]);
-#pragma unroll
-        for (int k = 0; k < MAX_DIMS; ++k)
-            if (k < a.n_ls) gn[1 + k] = -sums[4 + k];
-        gn[1 + a.n_ls] = -(0.5 * noise * sums[3]);
+        bat_grad(sums, c, noise, a.n_ls, gn);              // of the LML; f = -LML
         bool finite = isfinite(fn);
-        for (int i = 0; i < P; ++i) finite = finite && isfinite(gn[i]);
+        for (int i = 0; i < P; ++i) { gn[i] = -gn[i]; finite = finite && isfinite(gn[i]); }
         if (!finite) fn = INF;
     }
     const int evals = cn[1] + 1;
@@ -186,7 +182,7 @@ __global__ __launch_bounds__(BatCfg<NMAX>::NT) void bat_optimize(BatOptArgs a) {
         double il[MAX_DIMS];
 #pragma unroll
         for (int k = 0; k < MAX_DIMS; ++k) il[k] = k < D ? 1.0 / exp(th[1 + (a.n_ls == 1 ? 0 : k)]) : 0.0;
-        double sums[BAT_RED] = {};
+        double sums[BAT_RED];                            // zeroed by the body
         // th is not written before every thread has passed the body's first barrier, go not before the barrier below
         const bool ok = bat_factor_body<NMAX, KT, true>(fa, b, n0, n, c, noise, il, A, buf, dinv, red, sums);
         if (tid == 0) go = opt_advance(a, r, n, ok, sums, c, noise, th);

@@ -16,41 +16,23 @@ extern "C" int gpt_batch_optimize(int device, const double* X, const double* Y, 
     const std::string w = "gpt_batch_optimize";
     if (!X || !Y || !n_begin || !run_model || !theta0 || !bounds || !theta || !lml || !iterations || !evaluations || !status)
         return fail(GPT_E_ARG, w + ": NULL argument");
-    if (B < 1 || B > BAT_MAX_B) return fail(GPT_E_ARG, w + ": B (models) must be 1 .. 2^20, got " + std::to_string(B));
     if (R < 1 || R > BAT_OPT_MAX_R) return fail(GPT_E_ARG, w + ": R (runs) must be 1 .. 2^20, got " + std::to_string(R));
-    if (D < 1 || D > MAX_DIMS) return fail(GPT_E_ARG, w + ": D must be 1 .. 15, got " + std::to_string(D));
-    if (O < 1 || O > BAT_MAX_O) return fail(GPT_E_ARG, w + ": O (outputs) must be 1 .. 16, got " + std::to_string(O));
-    if (n_ls != 1 && n_ls != D) return fail(GPT_E_ARG, w + ": n_ls must be 1 or D");
-    if (kernel_type < GPT_KERNEL_RBF || kernel_type > GPT_KERNEL_MATERN52) return fail(GPT_E_ARG, w + ": unknown kernel_type");
-    if (!(alpha_jitter >= 0) || !std::isfinite(alpha_jitter)) return fail(GPT_E_ARG, w + ": alpha_jitter must be finite and >= 0");
     if (!(pgtol > 0) || !(ftol > 0) || !std::isfinite(pgtol) || !std::isfinite(ftol))
         return fail(GPT_E_ARG, w + ": pgtol and ftol must be finite and > 0");
     if (max_iter < 1 || max_evals < 1 || evals_per_launch < 1)
         return fail(GPT_E_ARG, w + ": max_iter, max_evals and evals_per_launch must be >= 1");
-    if (n_begin[0] != 0) return fail(GPT_E_ARG, w + ": n_begin[0] must be 0");
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t n = n_begin[b + 1] - n_begin[b];
-        if (n < 1 || n > BAT_MAX_N)
-            return fail(GPT_E_ARG, w + ": every model needs 1 <= n_b <= 128 points with increasing offsets; model " + std::to_string(b) +
-                                       " has n_begin " + std::to_string(n_begin[b]) + " .. " + std::to_string(n_begin[b + 1]));
-    }
+    if (int rc = check_batch_geometry(w, X, Y, n_begin, B, D, O, n_ls, alpha_jitter, kernel_type)) return rc;
     const size_t rows = (size_t)n_begin[B], P = 2 + (size_t)n_ls, nx = rows * D, ny = rows * O;
-    if (!all_finite(X, nx) || !all_finite(Y, ny)) return fail(GPT_E_ARG, w + ": X or Y contains NaN or infinity");
     if (!all_finite(bounds, 2 * P) || !all_finite(theta0, (size_t)R * P))
         return fail(GPT_E_ARG, w + ": bounds or theta0 contains NaN or infinity");
     for (size_t i = 0; i < P; ++i)
         if (bounds[2 * i] > bounds[2 * i + 1])
             return fail(GPT_E_ARG, w + ": bounds need lo <= hi (component " + std::to_string(i) + ")");
+    for (int64_t r = 0; r < R; ++r)
+        if (run_model[r] < 0 || run_model[r] >= B) return fail(GPT_E_ARG, w + ": run_model must be 0 .. B - 1 (run " + std::to_string(r) + ")");
     // the runs of this call, the small size class first; a run's class is its model's
-    std::vector<int> live, large;
-    live.reserve(R);
-    for (int64_t r = 0; r < R; ++r) {
-        const int b = run_model[r];
-        if (b < 0 || b >= B) return fail(GPT_E_ARG, w + ": run_model must be 0 .. B - 1 (run " + std::to_string(r) + ")");
-        (n_begin[b + 1] - n_begin[b] <= BAT_SMALL_N ? live : large).push_back((int)r);
-    }
-    int n_small = (int)live.size();
-    live.insert(live.end(), large.begin(), large.end());
+    std::vector<int> live;
+    int n_small = small_class_first(n_begin, run_model, R, live);
 
     if (int rc = use_device(w, device)) return rc;
     CallBuffers buf;

@@ -2,7 +2,8 @@
 
   python tools/batch_small_timing.py --resources        (CPU only: hipcc -save-temps, the factor kernel's resource summary)
   timeout 900 python tools/batch_small_timing.py --gpu  (on an MI355X: the measurements)
-  Each run replaces its own section of the file and keeps the other; --out FILE names another file than the profile.
+  Each run replaces its own section of the file and keeps the others (the hand-written "# old against new" among them);
+  --out FILE names another file than the profile.
 
 Objective: the median of 20 runs of one gpt_batch_lml_objective at B = 64, n = 20, D = 2, O = 2 against 64 sequential
 Handle.lml_objective calls on one handle; the batched call must take no longer than 8 of the sequential calls (one launch
@@ -31,22 +32,22 @@ OUT = os.path.join(ROOT, "profiles", "batch_small_models.txt")
 CSRC = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
 
 
-def resources():
+def resources(unit, kernel):
+    """The compiler's resource report of one kernel's instantiations in a unit of csrc (CPU only)."""
     lines = []
     with tempfile.TemporaryDirectory() as d:
         subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc",
-                        "-save-temps", "-c", os.path.join(CSRC, "gpt_batch.hip"), "-o", os.path.join(d, "gpt_batch.o")], check=True, cwd=d,
+                        "-save-temps", "-c", os.path.join(CSRC, unit + ".hip"), "-o", os.path.join(d, unit + ".o")], check=True, cwd=d,
                        stderr=subprocess.DEVNULL)
         asm = open([os.path.join(d, f) for f in os.listdir(d) if f.endswith(".s") and "amdgcn" in f][0]).read()
-    from gaussian_process_transportation_amd import _lib  # noqa: F401  (only to fail early if the tree is broken)
-    for m in re.finditer(r"\.amdhsa_kernel (\S*bat_factor\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S):
+    for m in re.finditer(r"\.amdhsa_kernel (\S*" + kernel + r"\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S):
         def field(k):
             r = re.search(r"\.amdhsa_" + k + r"\s+(\S+)", m.group(2))
             return r.group(1) if r else "?"
-        t = re.search(r"bat_factorILi(\d+)ELi(\d)ELb(\d)", m.group(1))
-        nmax, kt, obj = int(t.group(1)), int(t.group(2)), int(t.group(3))
-        dyn = (nmax * (nmax + 1) + nmax * 16 + nmax) * 8
-        lines.append(f"bat_factor<NMAX={nmax}, KT={kt}, OBJ={obj}>: VGPRs {field('next_free_vgpr')}, SGPRs {field('next_free_sgpr')}, "
+        nmax, kt, obj = re.search(kernel + r"ILi(\d+)ELi(\d)E(?:Lb(\d))?", m.group(1)).groups()
+        dyn = (int(nmax) * (int(nmax) + 1) + int(nmax) * 16 + int(nmax)) * 8
+        name = f"{kernel}<NMAX={nmax}, KT={kt}" + (f", OBJ={obj}>" if obj else ">")
+        lines.append(f"{name}: VGPRs {field('next_free_vgpr')}, SGPRs {field('next_free_sgpr')}, "
                      f"static LDS {field('group_segment_fixed_size')} B, dynamic LDS (computed) {dyn} B, scratch {field('private_segment_fixed_size')} B")
     return lines
 
@@ -105,26 +106,6 @@ def gpu():
 
 
 SEARCH_OUT = os.path.join(ROOT, "profiles", "batch_device_search.txt")
-
-
-def search_resources():
-    """The compiler's resource report of bat_optimize's instantiations (CPU only)."""
-    lines = []
-    with tempfile.TemporaryDirectory() as d:
-        subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-value", "-fno-gpu-rdc",
-                        "-save-temps", "-c", os.path.join(CSRC, "gpt_batch_opt.hip"), "-o", os.path.join(d, "gpt_batch_opt.o")], check=True,
-                       cwd=d, stderr=subprocess.DEVNULL)
-        asm = open([os.path.join(d, f) for f in os.listdir(d) if f.endswith(".s") and "amdgcn" in f][0]).read()
-    for m in re.finditer(r"\.amdhsa_kernel (\S*bat_optimize\S*)(.*?)\.end_amdhsa_kernel", asm, flags=re.S):
-        def field(k):
-            r = re.search(r"\.amdhsa_" + k + r"\s+(\S+)", m.group(2))
-            return r.group(1) if r else "?"
-        t = re.search(r"bat_optimizeILi(\d+)ELi(\d)E", m.group(1))
-        nmax, kt = int(t.group(1)), int(t.group(2))
-        dyn = (nmax * (nmax + 1) + nmax * 16 + nmax) * 8
-        lines.append(f"bat_optimize<NMAX={nmax}, KT={kt}>: VGPRs {field('next_free_vgpr')}, SGPRs {field('next_free_sgpr')}, "
-                     f"static LDS {field('group_segment_fixed_size')} B, dynamic LDS (computed) {dyn} B, scratch {field('private_segment_fixed_size')} B")
-    return sorted(lines)
 
 
 def search_once(n_pairs):
@@ -189,20 +170,23 @@ def search_main():
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else SEARCH_OUT
     HEADS = {"resources": "# resources of bat_optimize (hipcc --offload-arch=gfx950 -save-temps, as for bat_factor in batch_small_models.txt)",
              "measurements": "# measurements on an MI355X (tools/batch_small_timing.py --device-search --gpu)",
+             "old_new": OLD_NEW_HEAD,
              "notes": "# notes"}
     if "--once" in sys.argv:
         search_once(int(sys.argv[sys.argv.index("--once") + 1]))
     if "--resources" in sys.argv:
-        write_section(out, "resources", search_resources())
+        write_section(out, "resources", sorted(resources("gpt_batch_opt", "bat_optimize")))
     if "--gpu" in sys.argv:
         lines = search_gpu()
         write_section(out, "measurements", lines)
         print("\n".join(lines))
 
 
+OLD_NEW_HEAD = "# old against new (written by hand from an A/B of two builds; this tool keeps the section as it is)"
 HEADS = {"resources": "# resources of bat_factor (hipcc --offload-arch=gfx950 -save-temps: VGPRs, SGPRs, static LDS and scratch from the "
                       "compiler's kernel descriptor; the dynamic LDS is what the launch asks for, computed here as BatCfg::factor_lds does)",
-         "measurements": "# measurements on an MI355X (tools/batch_small_timing.py --gpu)"}
+         "measurements": "# measurements on an MI355X (tools/batch_small_timing.py --gpu)",
+         "old_new": OLD_NEW_HEAD}
 
 
 def write_section(path, name, lines):
@@ -228,7 +212,7 @@ def main():
         return search_main()
     out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else OUT
     if "--resources" in sys.argv:
-        write_section(out, "resources", resources())
+        write_section(out, "resources", resources("gpt_batch", "bat_factor"))
     if "--gpu" in sys.argv:
         lines, ratio = gpu()
         write_section(out, "measurements", lines)
