@@ -28,6 +28,9 @@ CHAIN_OUTPUTS = ("x", "vel", "f", "status", "var_dyn", "vel_var_map", "vel_var_d
                  "stage_map_var", "stage_status", "stage_passes", "stage_residual", "stage_det")
 CHAIN_INT_OUTPUTS = ("status", "stage_status", "stage_passes")
 CHAIN_MAX = 4      # GPT_CHAIN_MAX: stages of one gpt_pullback_chain call
+# outputs of gpt_rollout_policy, in the order of its arguments (steps_done and status are int32, the rest float64)
+ROLLOUT_OUTPUTS = ("path", "vel", "x", "steps_done", "status")
+ROLLOUT_INT_OUTPUTS = ("steps_done", "status")
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -74,6 +77,9 @@ SIGNATURES = {
     "gpt_pullback_chain_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _i64, C.c_double, C.c_int, C.c_double] + [_vp] * 16),
     "gpt_pullback_chain": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, C.c_double, C.c_int, C.c_double]
                            + [_dp] * 3 + [_ip] + [_dp] * 8 + [_ip] * 2 + [_dp] * 2),
+    "gpt_rollout_policy_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int] + [_vp] * 5),
+    "gpt_rollout_policy": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int]
+                           + [_dp] * 3 + [_ip] * 2),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -946,6 +952,75 @@ class Handle:
         check(self.lib.gpt_pullback_chain_dev(arr, K, dyn._h, _vp(y_ptr or None), _vp(x0_ptr or None), int(M), float(rtol), int(max_passes),
                                               float(std_offset), *(_vp(ptrs.get(k + "_ptr") or None) for k in CHAIN_OUTPUTS)),
               "gpt_pullback_chain_dev")
+
+    # ---- whole paths of the transported policy: the loop over the steps on the device
+    def rollout_policy(self, inner, dyn, y0, n_steps, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x")):
+        """gpt_rollout_policy on host arrays: n_steps explicit Euler steps y += dt * vel from every row of y0 (M,D), vel the mean
+        policy of pullback_chain at y with the x of the step before as its guess (x0 (M,D): guesses for the starts).  `inner`: the K
+        stages as pullback_chain's, 0 <= K <= CHAIN_MAX; this handle is the last stage's, or — K = 0, the model `dyn` rolls out
+        itself — dyn.  `outputs`: which of "vel" and "x" (M,n_steps,D) come back besides path (M,n_steps+1,D), steps_done and status
+        (M,).  A trajectory ends at the first step that does not converge or leaves the finite numbers; every row after its end is
+        NaN.  Returns a dict."""
+        stages = list(inner)
+        K = len(stages)
+        if K > CHAIN_MAX:
+            raise ValueError(f"rollout_policy: 0 .. {CHAIN_MAX} stages, got {K}")
+        if (stages[-1][0] if K else dyn) is not self:
+            raise ValueError("rollout_policy: the last stage's handle (without stages: dyn) must be the handle the call is made on")
+        N, D, O, _ = self.info()
+        y0 = as_f64(y0, 2, "y0")
+        if y0.shape[1] != D:
+            raise ValueError(f"y0 has {y0.shape[1]} columns, model was fitted with {D} features")
+        M, T = y0.shape[0], int(n_steps)
+        if x0 is not None:
+            x0 = as_f64(x0, 2, "x0")
+            if x0.shape != y0.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, y0 {y0.shape}")
+        unknown = set(outputs) - {"vel", "x"}
+        if unknown:
+            raise ValueError(f"rollout_policy: unknown outputs {sorted(unknown)}")
+        if T < 0:
+            raise ValueError("rollout_policy: n_steps must be >= 0")
+        if M * (T + 1) >= 2 ** 31:
+            raise ValueError("rollout_policy: M (n_steps + 1), the rows of path, must be below 2^31")
+        keep = []                                # the affine arrays live until the call returns
+        arr = (ChainStage * max(K, 1))()
+        for k, (h, R, c_src, c_dst, scale, R_jac) in enumerate(stages):
+            R = as_f64(R, 2, "R")
+            R_jac = R if R_jac is None else as_f64(R_jac, 2, "R_jac")
+            c_src, c_dst = as_f64(c_src, 1, "c_src"), as_f64(c_dst, 1, "c_dst")
+            if R.shape != (D, D) or R_jac.shape != (D, D) or c_src.shape != (D,) or c_dst.shape != (D,):
+                raise ValueError(f"stage {k}: the affine part of a {D}-dimensional model is R ({D},{D}), R_jac ({D},{D}), c_src ({D},), "
+                                 f"c_dst ({D},)")
+            keep += [R, R_jac, c_src, c_dst]
+            arr[k] = ChainStage(h._h, R.ctypes.data, c_src.ctypes.data, c_dst.ctypes.data, R_jac.ctypes.data, float(scale))
+        shapes = {"path": (M, T + 1, D), "vel": (M, T, D), "x": (M, T, D), "steps_done": (M,), "status": (M,)}
+        want = [k for k in ROLLOUT_OUTPUTS if k not in ("vel", "x") or k in outputs]
+        out = {k: np.empty(shapes[k], dtype=np.int32 if k in ROLLOUT_INT_OUTPUTS else np.float64) for k in want}
+        ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(_ip)) if k in ROLLOUT_INT_OUTPUTS else dptr(out.get(k))
+        check(self.lib.gpt_rollout_policy(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), M, T, float(dt), float(rtol), int(max_passes),
+                                          *(ptr(k) for k in ROLLOUT_OUTPUTS)),
+              "gpt_rollout_policy")
+        del keep
+        return out
+
+    def rollout_policy_dev(self, inner, dyn, y0_ptr, M, n_steps, path_ptr, steps_done_ptr, status_ptr, dt=1.0, x0_ptr=0, rtol=1e-10,
+                           max_passes=64, vel_ptr=0, x_ptr=0):
+        """The same on device pointers (float64; steps_done / status int32), asynchronous on this handle's stream
+        (gpt_rollout_policy_dev).  `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers."""
+        stages = list(inner)
+        K = len(stages)
+        if K > CHAIN_MAX:
+            raise ValueError(f"rollout_policy_dev: 0 .. {CHAIN_MAX} stages, got {K}")
+        if (stages[-1][0] if K else dyn) is not self:
+            raise ValueError("rollout_policy_dev: the last stage's handle (without stages: dyn) must be the handle the call is made on")
+        arr = (ChainStage * max(K, 1))()
+        for k, (h, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr) in enumerate(stages):
+            arr[k] = ChainStage(h._h, R_ptr or None, c_src_ptr or None, c_dst_ptr or None, R_jac_ptr or None, float(scale))
+        check(self.lib.gpt_rollout_policy_dev(arr if K else None, K, dyn._h, _vp(y0_ptr or None), _vp(x0_ptr or None), int(M), int(n_steps),
+                                              float(dt), float(rtol), int(max_passes), _vp(path_ptr or None), _vp(vel_ptr or None),
+                                              _vp(x_ptr or None), _vp(steps_done_ptr or None), _vp(status_ptr or None)),
+              "gpt_rollout_policy_dev")
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -17,25 +17,9 @@
 //               queries around it.
 //  k_chain_variance : one thread per query, plain fp64 FMA: the first-order propagation of each stage's Jacobian variance and
 //               of the dynamics variance through the stages after it.
-#include "gpt_chain.h"
-#include "gpt_newton.h"
+#include "gpt_chain_body.h"
 
 namespace gpt {
-
-// f = mean of the model at x; the kernel type is the same in every wave of the launch
-template <int D>
-__device__ __forceinline__ void ch_mean(const ChainModel& m, const double* __restrict__ Tt, const int lane, const double (&x)[D],
-                                        double (&f)[D]) {
-    double qsc[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) qsc[d] = m.inv_ls[d] * 0.70710678118654752440;
-    switch (m.ktype) {
-        case KT_MATERN12: inv_mean<KT_MATERN12, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        case KT_MATERN32: inv_mean<KT_MATERN32, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        case KT_MATERN52: inv_mean<KT_MATERN52, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f); break;
-        default: inv_mean<KT_RBF, D>(m.N, m.lnc, m.Xs, m.A4, Tt, lane, qsc, x, f);
-    }
-}
 
 template <int D>
 __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
@@ -45,90 +29,21 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (m >= a.M) return;
-    const int K = a.K;
-    double y[D], x[D], Q[D][D], A[D][D];
-    double start[CHAIN_MAX][D];                       // only ever indexed by unrolled constants: registers
+    double y[D], x0[D], x[D], f[D], vel[D];
 #pragma unroll
-    for (int k = 0; k < CHAIN_MAX; ++k)
-#pragma unroll
-        for (int d = 0; d < D; ++d) start[k][d] = 0.0;
-    if (a.X0) {                                       // g_0 = x0; stage k starts at gamma_k(g_k); g_{k+1} = gamma_k(g_k) + mean_k(gamma_k(g_k))
-        double g[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) g[d] = a.X0[m * D + d];
-        for (int k = 0; k < K; ++k) {
-            double z0[D];
-            sm_affine<D>(a.st[k], a.st[k].R, g, z0);     // the arithmetic of k_affine (gpt_transport.hip)
-#pragma unroll
-            for (int j = 0; j < CHAIN_MAX; ++j)
-                if (j == k) {
-#pragma unroll
-                    for (int d = 0; d < D; ++d) start[j][d] = z0[d];
-                }
-            if (k + 1 < K) {
-                double mu[D];
-                ch_mean<D>(a.st[k].m, Tt, lane, z0, mu);
-#pragma unroll
-                for (int d = 0; d < D; ++d) g[d] = z0[d] + mu[d];
-            }
-        }
+    for (int d = 0; d < D; ++d) {
+        y[d] = a.Y[m * D + d];
+        x0[d] = a.X0 ? a.X0[m * D + d] : 0.0;
     }
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        y[i] = a.Y[m * D + i];
-        x[i] = y[i];
-#pragma unroll
-        for (int d = 0; d < D; ++d) Q[i][d] = i == d ? 1.0 : 0.0;
-    }
-    int first = INV_CONVERGED;
-    for (int k = K - 1; k >= 0; --k) {
-        const ChainStage& S = a.st[k];
-        double R[D][D], qsc[D], jsc[D], z[D], rho;
-#pragma unroll
-        for (int i = 0; i < D; ++i)
-#pragma unroll
-            for (int d = 0; d < D; ++d) R[i][d] = S.R[i * D + d];
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            qsc[d] = S.m.inv_ls[d] * 0.70710678118654752440;
-            jsc[d] = S.m.inv_ls[d] * 1.41421356237309504880;
-            z[d] = y[d];
-        }
-        if (a.X0) {
-#pragma unroll
-            for (int j = 0; j < CHAIN_MAX; ++j)
-                if (j == k) {
-#pragma unroll
-                    for (int d = 0; d < D; ++d) z[d] = start[j][d];
-                }
-        }
-        int passes, status;
-        switch (S.m.ktype) {                          // (no Matern 1/2: the API refuses such a stage before a launch is reached)
-            case KT_MATERN32:
-                status = inv_newton<KT_MATERN32, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
-                break;
-            case KT_MATERN52:
-                status = inv_newton<KT_MATERN52, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
-                break;
-            default:
-                status = inv_newton<KT_RBF, D>(S.m.N, S.m.lnc, S.m.Xs, S.m.A4, Tt, lane, qsc, jsc, y, a.rtol, a.max_passes, z, A, rho, passes);
-        }
-        if (first == INV_CONVERGED) first = status;
-        // x = (z - c_dst) R / scale + c_src, the arithmetic of k_pullback_velocity
-        double zc[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) zc[d] = z[d] - S.c_dst[d];
-#pragma unroll
-        for (int i = 0; i < D; ++i) {
-            const double r = sm_col_dot<D>(zc, R, i);
-            x[i] = r / S.scale + S.c_src[i];
-        }
-        if (lane == 0) {
+    // the per-point body, shared with k_rollout (gpt_chain_body.h); per-stage values are stored by lane 0 as each stage finishes
+    const int first = chain_point<D>(a.st, a.dyn, a.K, a.rtol, a.max_passes, Tt, lane, a.X0 != nullptr, x0, y, x, f, vel,
+        [&](const int k, const double (&z)[D], const double (&xk)[D], const double (&A)[D][D], const int status, const int passes, const double rho) {
+            if (lane != 0) return;
             const int64_t row = (int64_t)k * a.M + m;
 #pragma unroll
             for (int o = 0; o < D; ++o) {
                 if (a.stage_z) a.stage_z[row * D + o] = z[o];
-                if (a.stage_x) a.stage_x[row * D + o] = x[o];
+                if (a.stage_x) a.stage_x[row * D + o] = xk[o];
                 if (a.stage_A) {
 #pragma unroll
                     for (int d = 0; d < D; ++d) a.stage_A[(row * D + o) * D + d] = A[o][d];
@@ -138,53 +53,11 @@ __global__ __launch_bounds__(256) void k_chain_velocity(ChainArgs a) {
             if (a.stage_passes) a.stage_passes[row] = passes;
             if (a.stage_residual) a.stage_residual[row] = rho;
             if (a.stage_det) a.stage_det[row] = sm_det<D>(A);
-        }
-        if (k > 0) {                                  // Q <- Q (A_k R_jac,k); the innermost stage is applied to f below
-            double B[D][D], Qn[D][D];
-#pragma unroll
-            for (int o = 0; o < D; ++o)
-#pragma unroll
-                for (int e = 0; e < D; ++e) {
-                    double b = A[o][0] * S.R_jac[e];
-#pragma unroll
-                    for (int d = 1; d < D; ++d) b = fma(A[o][d], S.R_jac[d * D + e], b);
-                    B[o][e] = b;
-                }
-#pragma unroll
-            for (int o = 0; o < D; ++o)
-#pragma unroll
-                for (int e = 0; e < D; ++e) Qn[o][e] = sm_mat_el<D>(Q, B, o, e);
-#pragma unroll
-            for (int o = 0; o < D; ++o)
-#pragma unroll
-                for (int e = 0; e < D; ++e) Q[o][e] = Qn[o][e];
-#pragma unroll
-            for (int d = 0; d < D; ++d) y[d] = x[d];
-        }
-    }
-    double f[D], g[D], h[D];
-    ch_mean<D>(a.dyn, Tt, lane, x, f);
+        });
     if (lane != 0) return;
-    // vel = Q (A_0 (R_jac,0 f)): A and x are stage 0's here
-    const double* Rj = a.st[0].R_jac;
-#pragma unroll
-    for (int i = 0; i < D; ++i) g[i] = sm_row_dot<D>(Rj, i, f);
 #pragma unroll
     for (int o = 0; o < D; ++o) {
-        double r = A[o][0] * g[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) r = fma(A[o][d], g[d], r);
-        h[o] = r;
-    }
-#pragma unroll
-    for (int o = 0; o < D; ++o) {
-        double r = h[o];
-        if (K > 1) {                                  // (Q = I otherwise: nothing to multiply, and no 0 * inf of a point that ran away)
-            r = Q[o][0] * h[0];
-#pragma unroll
-            for (int d = 1; d < D; ++d) r = fma(Q[o][d], h[d], r);
-        }
-        a.vel[m * D + o] = r;
+        a.vel[m * D + o] = vel[o];
         if (a.x) a.x[m * D + o] = x[o];
         if (a.f) a.f[m * D + o] = f[o];
     }

@@ -4,23 +4,14 @@
 // g++ against host_stub/ and runs under the sanitizers (make host-oneshot-asan).  The resources of the call (CALL_CHAIN) are held
 // by the handle of the LAST stage; its events: ev[j] the j-th other stream has caught up, ev[CHAIN_MAX + j] the variance launch on
 // it is done, ev[2 CHAIN_MAX] the velocity launch is done.
-#include "gpt_chain.h"
-#include "gpt_stage.h"
+#include "gpt_chain_check.h"
 
 using namespace gpt;
-
-static_assert(CHAIN_MAX == AFFINE_SLOTS, "the chain is the call with the most affine parts (gpt_stage.h)");
 
 namespace {
 
 // the arguments of both entry points (host or device pointers alike), arrays indexed by CH_*
-struct ChainCall {
-    int K = 0;
-    gpt_handle* h[CHAIN_MAX] = {};
-    gpt_handle* h_dyn = nullptr;
-    ModelView v[CHAIN_MAX], v_dyn;
-    AffinePart g[CHAIN_MAX] = {};
-    double scale[CHAIN_MAX] = {};
+struct ChainCall : ChainModels {
     int64_t M = 0;
     double rtol = 0.0, std_offset = 0.0;
     int max_passes = 0;
@@ -37,55 +28,11 @@ size_t row_bytes(int which, size_t D) {
     }
 }
 
-// what the wave-level passes read of a model
-ChainModel chain_model(const ModelView& v) {
-    ChainModel m{};
-    m.N = v.p.N; m.ktype = v.p.ktype; m.lnc = v.p.lnc;
-    for (int d = 0; d < 3; ++d) m.inv_ls[d] = v.p.inv_ls[d];
-    m.Xs = v.Xs; m.A4 = v.A4;
-    return m;
-}
-
 // what both entry points refuse, in the order of the header's list; fills the views
 int chain_check(const char* who, const gpt_chain_stage* stages, ChainCall& c) {
     const std::string w(who);
-    if (c.K < 1 || c.K > CHAIN_MAX)
-        return fail(GPT_E_ARG, w + ": K must be 1 .. " + std::to_string(CHAIN_MAX) + " (GPT_CHAIN_MAX) stages, got " + std::to_string(c.K));
-    if (!stages) return fail(GPT_E_ARG, w + ": stages must not be NULL");
-    for (int k = 0; k < c.K; ++k) {
-        const std::string role = "stage " + std::to_string(k) + " map";
-        c.h[k] = stages[k].h; c.g[k] = AffinePart{stages[k].R, stages[k].R_jac, stages[k].c_src, stages[k].c_dst};
-        c.scale[k] = stages[k].scale;
-        if (!c.h[k]) return fail(GPT_E_ARG, w + ": NULL handle (" + role + ")");
-        if (!c.g[k].R || !c.g[k].c_src || !c.g[k].c_dst || !c.g[k].R_jac)
-            return fail(GPT_E_ARG, w + ": R, c_src, c_dst and R_jac must not be NULL (stage " + std::to_string(k) + ")");
-    }
-    if (!c.h_dyn) return fail(GPT_E_ARG, w + ": NULL handle (dynamics)");
-    for (int k = 0; k < c.K; ++k) {
-        for (int j = 0; j < k; ++j)
-            if (c.h[j] == c.h[k])
-                return fail(GPT_E_ARG, w + ": stages " + std::to_string(j) + " and " + std::to_string(k) + " are the same handle; every stage is a model of its own");
-        if (c.h[k] == c.h_dyn)
-            return fail(GPT_E_ARG, w + ": stage " + std::to_string(k) + " and h_dyn are the same handle; the maps and the dynamics are separate models");
-    }
-    for (int k = 0; k < c.K; ++k) {
-        const std::string role = "stage " + std::to_string(k) + " map";
-        if (int rc = check_model(c.h[k], w, ModelCheck{role.c_str(), "", PULLBACK_MATERN12, PULLBACK_MATERN}, &c.v[k])) return rc;
-    }
-    if (int rc = check_model(c.h_dyn, w, ModelCheck{"dynamics", "", nullptr, nullptr}, &c.v_dyn)) return rc;
-    const ModelView& last = c.v[c.K - 1];
-    for (int k = 0; k < c.K; ++k) {
-        const ModelView& v = k + 1 < c.K ? c.v[k] : c.v_dyn;
-        const std::string name = k + 1 < c.K ? "stage " + std::to_string(k) : std::string("the dynamics");
-        if (v.device != last.device)
-            return fail(GPT_E_ARG, w + ": the models live on different devices (stage " + std::to_string(c.K - 1) + ": " + std::to_string(last.device) +
-                                       ", " + name + ": " + std::to_string(v.device) + "); gpt_factor_copy brings one to the other's");
-        if (v.p.D != last.p.D)
-            return fail(GPT_E_ARG, w + ": every map and the dynamics must share one space (stage " + std::to_string(c.K - 1) + ": D = " +
-                                       std::to_string(last.p.D) + ", " + name + ": D = " + std::to_string(v.p.D) + ")");
-    }
-    if (!(c.rtol > 0.0)) return fail(GPT_E_ARG, w + ": rtol must be > 0");
-    if (c.max_passes < 1) return fail(GPT_E_ARG, w + ": max_passes must be >= 1");
+    if (int rc = chain_check_models(w, stages, 1, c)) return rc;
+    if (int rc = chain_check_solver(w, c.rtol, c.max_passes)) return rc;
     if (c.M < 0 || c.M >= ((int64_t)1 << 31)) return fail(GPT_E_ARG, w + ": M must be 0 .. 2^31 - 1");
     if (c.M > 0 && (!c.arr[CH_Y] || !c.arr[CH_VEL] || !c.arr[CH_STATUS])) return fail(GPT_E_ARG, w + ": y, vel and status must not be NULL");
     return GPT_OK;
@@ -114,11 +61,7 @@ int chain_dev(const ChainCall& c) {
     if (int rc = resolve_scratch(*res, u, mid, M, s, at)) return rc;
     ChainArgs a{};
     a.M = M; a.K = K;
-    for (int k = 0; k < K; ++k) {
-        a.st[k].m = chain_model(c.v[k]);
-        a.st[k].R = c.g[k].R; a.st[k].c_src = c.g[k].c_src; a.st[k].c_dst = c.g[k].c_dst; a.st[k].R_jac = c.g[k].R_jac; a.st[k].scale = c.scale[k];
-    }
-    a.dyn = chain_model(c.v_dyn);
+    chain_kernel_models(c, a.st, a.dyn);
     a.Y = static_cast<const double*>(u[CH_Y]); a.X0 = static_cast<const double*>(u[CH_X0]);
     a.rtol = c.rtol; a.max_passes = c.max_passes; a.std_offset = c.std_offset;
     a.x = at[0]; a.f = at[1]; a.vel = static_cast<double*>(u[CH_VEL]); a.status = static_cast<int*>(u[CH_STATUS]);
@@ -130,11 +73,7 @@ int chain_dev(const ChainCall& c) {
     // the other handles, stages 0 .. K-2 and the dynamics: what their streams have enqueued so far (a fit, a gpt_factor_commit)
     // comes first
     hipStream_t other[CHAIN_MAX];
-    for (int j = 0; j < K; ++j) other[j] = j + 1 < K ? c.v[j].stream : c.v_dyn.stream;
-    for (int j = 0; j < K; ++j) {
-        CALLCHK(hipEventRecord(ev_in[j], other[j]));
-        CALLCHK(hipStreamWaitEvent(s, ev_in[j], 0));
-    }
+    if (int rc = chain_wait_for_others(c, s, ev_in, other)) return rc;
     launch_chain_velocity(s, (int)D, a);
     // their streams go on once x and the z_k are there and their models have been read
     CALLCHK(hipEventRecord(ev_mid, s));

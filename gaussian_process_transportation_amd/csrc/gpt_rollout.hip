@@ -1,0 +1,114 @@
+// Whole paths of the transported policy for gfx950 (MI355X): the reference integrates its policy on the host, 1000 steps of
+// pos += vel (plot_traj_evolution); here the loop over the steps runs on the device, around the per-point body of
+// k_chain_velocity (gpt_chain_body.h: K Newton inversions, the dynamics mean and the push-forward in one wave).
+//
+//  k_rollout : one wave owns one trajectory, four waves per workgroup, one barrier at entry for the exp table.  Step t evaluates
+//               the body at y_t with the x of step t - 1 as its guess (at t = 0: X0, or none), then y_{t+1} = y_t + (dt vel_t), the
+//               product and the sum rounded separately (no fused multiply-add: numpy's y + dt * vel gives the same bits).  Every
+//               value is the same in every lane, every branch on it a scalar one; lane 0 stores each step's rows.  The
+//               trajectory ends at the first step whose status is not CONVERGED or whose y_{t+1} is not finite: the wave fills
+//               the rest of its rows with NaN and returns.  A launch evaluates steps t_begin .. t_end - 1; between launches a
+//               trajectory lives in its last path row, `state` (the last x) and steps_done, and a wave whose trajectory has
+//               ended (steps_done < t_begin) returns at once.  K = 0: x_t = y_t, vel_t = the dynamics mean.  A trajectory's sums
+//               run in a fixed order: its values do not depend on M, on the trajectories around it or on the launch boundaries.
+#include "gpt_rollout.h"
+#include "gpt_chain_body.h"
+
+namespace gpt {
+
+// y + (dt v), the product and the sum rounded separately.  (The compiler contracts a product and a sum into one fused multiply-add
+// wherever it may, the _rn intrinsics included: they are plain operators.  The pragma is what forbids it here.)
+__device__ __forceinline__ double euler_step(const double y, const double dt, const double v) {
+#pragma clang fp contract(off)
+    const double p = dt * v;
+    return y + p;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void k_rollout(RolloutArgs a) {
+    __shared__ double Tt[256];
+    Tt[threadIdx.x] = g_exp2_table[threadIdx.x];
+    __syncthreads();                                  // the only barrier
+    const int lane = threadIdx.x & 63;
+    // (the wave's number goes through readfirstlane: m and every address built on it are scalar, which leaves the vector registers to the body)
+    const int64_t m = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (m >= a.M) return;
+    const int T = a.T, t_begin = a.t_begin, t_end = a.t_end;
+    if (t_begin > 0 && __builtin_amdgcn_readfirstlane(a.steps_done[m]) != t_begin) return;     // ended in an earlier launch
+    // the trajectory's first row of path, and of vel and x (recomputed where they are used: nothing but m lives across the body)
+    auto path_row = [&](const int64_t t) { return a.path + (m * ((int64_t)T + 1) + t) * D; };
+    auto step_row = [&](double* const p, const int64_t t) { return p + (m * (int64_t)T + t) * D; };
+    double y[D], guess[D];
+    bool have_guess = true;
+    if (t_begin == 0) {
+        have_guess = a.X0 != nullptr;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            y[d] = a.Y0[m * D + d];
+            guess[d] = a.X0 ? a.X0[m * D + d] : 0.0;
+            if (lane == 0) path_row(0)[d] = y[d];
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            y[d] = path_row(t_begin)[d];
+            guess[d] = a.state[m * D + d];
+        }
+    }
+    int t = t_begin, status = INV_CONVERGED;
+    for (; t < t_end; ++t) {
+        double x[D], f[D], vel[D], yn[D];
+        if (a.K == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) x[d] = y[d];
+            ch_mean<D>(a.dyn, Tt, lane, x, vel);
+        } else {
+            status = chain_point<D>(a.st, a.dyn, a.K, a.rtol, a.max_passes, Tt, lane, have_guess, guess, y, x, f, vel,
+                                    [](int, const double (&)[D], const double (&)[D], const double (&)[D][D], int, int, double) {});
+        }
+        bool ok = status == INV_CONVERGED;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            yn[d] = euler_step(y[d], a.dt, vel[d]);
+            ok = ok && __builtin_isfinite(yn[d]);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                if (a.vel) step_row(a.vel, t)[d] = vel[d];
+                if (a.x) step_row(a.x, t)[d] = x[d];
+            }
+        }
+        if (!__builtin_amdgcn_readfirstlane(ok ? 1 : 0)) break;      // (every lane holds the same value)
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (lane == 0) path_row((int64_t)t + 1)[d] = yn[d];
+            y[d] = yn[d];
+            guess[d] = x[d];
+        }
+        have_guess = true;
+    }
+    if (t < t_end) {                                  // ended at step t: nothing after it exists
+        const double nan = __builtin_nan("");
+        for (int64_t i = ((int64_t)t + 1) * D + lane; i < ((int64_t)T + 1) * D; i += 64) path_row(0)[i] = nan;
+        for (int64_t i = ((int64_t)t + 1) * D + lane; i < (int64_t)T * D; i += 64) {
+            if (a.vel) step_row(a.vel, 0)[i] = nan;
+            if (a.x) step_row(a.x, 0)[i] = nan;
+        }
+    }
+    if (lane != 0) return;
+    a.steps_done[m] = t;
+    a.status[m] = status;
+    if (t == t_end && t_end < T) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) a.state[m * D + d] = guess[d];
+    }
+}
+
+void launch_rollout(hipStream_t s, int D, const RolloutArgs& a) {
+    if (a.M <= 0) return;
+    const dim3 grid((unsigned)((a.M + 3) / 4));           // one wave per trajectory, four per workgroup (M < 2^31: the grid fits)
+    with_small_dim(D, [&](auto d) { hipLaunchKernelGGL((k_rollout<decltype(d)::value>), grid, dim3(256), 0, s, a); });
+}
+
+}  // namespace gpt

@@ -1,6 +1,6 @@
 // What the host entry points that work on handles share (internal header; plain C++, it also compiles under g++ against
 // host_stub/, the sanitizer builds): the chunked, double-buffered staging of a host-pointer call (gpt_predict_all,
-// gpt_transport_policy, gpt_pullback_policy, gpt_pullback_chain), the device image of a call's affine parts, the "caller's array
+// gpt_transport_policy, gpt_pullback_policy, gpt_pullback_chain, gpt_rollout_policy), the device image of a call's affine parts, the "caller's array
 // or the handle's scratch" table, the one model check of the D <= 3 calls, and the three accessors through which
 // gpt_transport_host.hip and gpt_chain_host.hip reach a handle (gpt_api.hip owns the type and defines them).
 #pragma once
@@ -39,18 +39,20 @@ struct ChunkStreams {
     hipStream_t s = nullptr, copy = nullptr;
     hipEvent_t ev_done[2] = {}, ev_copied[2] = {};   // chunk computed / chunk's outputs copied out, per staging set
 };
-inline bool one_chunk(int64_t M) { return M <= HOST_CHUNK; }
+inline bool one_chunk(int64_t M, int64_t chunk = HOST_CHUNK) { return M <= chunk; }
 
-// Takes M > 0 queries through `compute(device pointers by table index, m)`, HOST_CHUNK at a time.  One chunk (the reference's own
+// Takes M > 0 queries through `compute(device pointers by table index, m)`, `chunk` (HOST_CHUNK unless a call's rows are long:
+// gpt_rollout_policy) at a time.  One chunk (the reference's own
 // batch sizes): inputs in, compute, outputs out, all in q.s — no second stream, no events.  Several chunks: chunk i computes on
 // q.s in staging set i & 1 and its outputs leave on q.copy while chunk i + 1, enqueued before chunk i's host-blocking copies,
 // computes; set b is reused only after ev_copied[b].  Returns after both streams have drained.  An input is one plane (no call
 // has a plane-major input; its `planes` is not looked at).
 template <int N, class Compute>
-int run_chunked(StagingSet (&st)[2], const ChunkStreams& q, const StagedArray (&arr)[N], int64_t M, Compute&& compute) {
+int run_chunked(StagingSet (&st)[2], const ChunkStreams& q, const StagedArray (&arr)[N], int64_t M, Compute&& compute,
+                const int64_t chunk = HOST_CHUNK) {
     static_assert(N <= STAGE_ARRAYS, "a staging set has STAGE_ARRAYS buffers");
     constexpr int n = N;
-    const int64_t cap = M < HOST_CHUNK ? M : HOST_CHUNK;
+    const int64_t cap = M < chunk ? M : chunk;
     const int64_t nchunks = (M + cap - 1) / cap;
     const bool single = nchunks == 1;
     hipStream_t s = q.s, cs = single ? q.s : q.copy;
@@ -154,7 +156,7 @@ struct ModelView {
     KernelParams p{};
     const double *Xs = nullptr, *A4 = nullptr;      // scaled sources and alpha rows of the blob (fp64 models)
 };
-enum { CALL_INVERSE = 0, CALL_TRANSPORT, CALL_PULLBACK, CALL_CHAIN, CALL_FAMILIES };
+enum { CALL_INVERSE = 0, CALL_TRANSPORT, CALL_PULLBACK, CALL_CHAIN, CALL_ROLLOUT, CALL_FAMILIES };
 
 // The model of h as it is now (nothing is checked; h not null).
 void model_view(gpt_handle* h, ModelView* v);

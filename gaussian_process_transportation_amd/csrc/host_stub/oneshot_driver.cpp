@@ -1,6 +1,6 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
-// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip)
+// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -22,6 +23,7 @@ namespace gpt {
 extern int stub_fail_model;      // stub_launchers.cpp
 extern bool stub_fail_flag;
 extern int stub_opt_launches, stub_opt_launch_count;
+extern int stub_rollout_launch_count;
 }
 
 namespace {
@@ -778,6 +780,120 @@ void chain_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- rollout (gpt_rollout_host.hip): K + 1 handles (K = 0: the dynamics alone), trajectory-major arrays whose rows grow with T, chunks of
+// max(1, 131072 / (T + 1)) trajectories through the owner's two staging sets, the launches of a chunk cut every
+// GPT_ROLLOUT_STEPS_PER_LAUNCH steps
+void rollout_cases() {
+    const int64_t N = 5, Nd = 7;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h[GPT_CHAIN_MAX] = {}, *hd = nullptr, *bare = nullptr;
+    begin("gpt_rollout_policy setup");
+    for (auto& q : h) CHECK(gpt_create(&q, 0) == GPT_OK);
+    CHECK(gpt_create(&hd, 0) == GPT_OK && gpt_create(&bare, 0) == GPT_OK);
+    for (auto& q : h) CHECK(gpt_fit(q, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    constexpr int X0 = 1, VEL = 2, XO = 4, ALL = 7;     // bits of `mask`: the optional arrays passed
+    struct Arrays {
+        D y0, x0, path, vel, x;
+        Arr<int> steps, status;
+        Arrays(int64_t M, int64_t T)
+            : y0(ramp(M * 3)), x0(ramp(M * 3)), path((size_t)M * (T + 1) * 3, SENT), vel((size_t)M * T * 3, SENT), x((size_t)M * T * 3, SENT),
+              steps(M, ISENT), status(M, ISENT) {}
+    };
+    auto stages_of = [&](int K) {
+        std::vector<gpt_chain_stage> st(K);
+        for (int k = 0; k < K; ++k) st[k] = gpt_chain_stage{h[k], R.p, c_src.p, c_dst.p, R.p, 1.0 + 0.25 * k};
+        return st;
+    };
+    auto call = [&](const gpt_chain_stage* st, int K, gpt_handle* hdyn, Arrays& a, int64_t M, int64_t T, int mask, const double* y0, double* path,
+                    double dt = 0.5, double rtol = 1e-10, int max_passes = 50) {
+        return gpt_rollout_policy(st, K, hdyn, y0, mask & X0 ? a.x0.p : nullptr, M, T, dt, rtol, max_passes, path, mask & VEL ? a.vel.p : nullptr,
+                                  mask & XO ? a.x.p : nullptr, a.steps.p, a.status.p);
+    };
+    auto untouched = [&](const Arrays& a) { CHECK(a.path.all(SENT) && a.vel.all(SENT) && a.x.all(SENT) && a.steps.all(ISENT) && a.status.all(ISENT)); };
+    {
+        Arrays a(1, 2);
+        auto st = stages_of(2);
+        begin("gpt_rollout_policy refuses K = -1"); done_held(call(st.data(), -1, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses K = 5"); done_held(call(st.data(), GPT_CHAIN_MAX + 1, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses stages = NULL with K = 2"); done_held(call(nullptr, 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses a NULL dynamics handle"); done_held(call(st.data(), 2, nullptr, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses a dynamics handle without a model, K = 0"); done_held(call(nullptr, 0, bare, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_STATE);
+        auto bad = st; bad[0].h = bare;
+        begin("gpt_rollout_policy refuses a stage handle without a model"); done_held(call(bad.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_STATE);
+        bad = st; bad[1].h = st[0].h;
+        begin("gpt_rollout_policy refuses one stage handle twice"); done_held(call(bad.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses n_steps = -1"); done_held(call(st.data(), 2, hd, a, 1, -1, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses dt = 0"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p, 0.0), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses dt = inf"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p, INFINITY), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses dt = NaN"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p, std::nan("")), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses rtol = 0"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p, 0.5, 0.0), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses max_passes = 0"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p, 0.5, 1e-10, 0), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses M = -1"); done_held(call(st.data(), 2, hd, a, -1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        // M (T + 1) at the limit, cut either way: 2^31 rows are refused before anything is sized
+        begin("gpt_rollout_policy refuses M (T + 1) = 2^31, M = 2^15"); done_held(call(st.data(), 2, hd, a, 1 << 15, (1 << 16) - 1, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses M (T + 1) = 2^31, M = 1"); done_held(call(st.data(), 2, hd, a, 1, ((int64_t)1 << 31) - 1, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses M (T + 1) = 2^31, T = 0"); done_held(call(st.data(), 2, hd, a, (int64_t)1 << 31, 0, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses y0 = NULL"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, nullptr, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy refuses path = NULL"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, nullptr), GPT_E_ARG);
+        D nan_y{0.5, std::nan(""), 0.5};
+        begin("gpt_rollout_policy refuses NaN in y0"); done_held(call(st.data(), 2, hd, a, 1, 2, ALL, nan_y.p, a.path.p), GPT_E_ARG);
+        bad = st; bad[1].scale = std::nan("");
+        begin("gpt_rollout_policy refuses a NaN scale"); done_held(call(bad.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        begin("gpt_rollout_policy M = 0 does nothing"); done_held(call(st.data(), 2, hd, a, 0, 2, ALL, a.y0.p, a.path.p), GPT_OK);
+        untouched(a);
+    }
+    // (M, T, steps per launch): T = 0; one trajectory; launches cut inside a call and at its last step; T = 255: chunks of 512, M one past
+    // one and past two of them; T = 131071: chunks of 1, three of them
+    struct Shape { int64_t M, T; int per; };
+    const Shape shapes[] = {{1, 0, 256}, {3, 0, 256}, {1, 1, 256}, {3, 7, 3}, {3, 6, 3}, {2, 300, 256}, {513, 255, 256}, {1027, 255, 100}, {3, 131071, 65536}};
+    for (int K : {0, 1, 2, GPT_CHAIN_MAX}) {
+        auto st = stages_of(K);
+        for (const Shape& sh : shapes)
+            for (int mask : {0, ALL, X0 | XO, VEL}) {
+                if (sh.M > 3 && (K != 2 || (mask != ALL && mask != 0))) continue;
+                if (sh.T > 1000 && (K != 0 || mask != ALL)) continue;
+                begin("gpt_rollout_policy K=" + std::to_string(K) + " M=" + std::to_string(sh.M) + " T=" + std::to_string(sh.T) + " steps per launch=" +
+                      std::to_string(sh.per) + " optional=" + std::to_string(mask));
+                setenv("GPT_ROLLOUT_STEPS_PER_LAUNCH", std::to_string(sh.per).c_str(), 1);
+                gpt::stub_rollout_launch_count = 0;
+                Arrays a(sh.M, sh.T);
+                const int rc = call(K ? st.data() : nullptr, K, hd, a, sh.M, sh.T, mask, a.y0.p, a.path.p);
+                CHECK(stub_live_objects >= held);                        // staging, scratch and events are kept and regrown, never dropped
+                held = stub_live_objects;
+                done_held(rc, GPT_OK);
+                const int64_t chunk = std::max<int64_t>(1, 131072 / (sh.T + 1)), chunks = (sh.M + chunk - 1) / chunk;
+                CHECK(gpt::stub_rollout_launch_count == chunks * std::max<int64_t>(1, (sh.T + sh.per - 1) / sh.per));
+                CHECK(a.path.all(0.0) && a.status.all(0) && a.steps.all((int)sh.T));
+                CHECK(a.vel.all(mask & VEL ? 0.0 : SENT) && a.x.all(mask & XO ? 0.0 : SENT));
+            }
+    }
+    unsetenv("GPT_ROLLOUT_STEPS_PER_LAUNCH");
+    {
+        begin("gpt_rollout_policy refuses models of different dimension");
+        D X2 = ramp(Nd * 2), Y2 = ramp(Nd * 2, 0.01, 0.01), ls2{0.5, 0.75};
+        CHECK(gpt_fit(hd, X2.p, Y2.p, Nd, 2, 2, ls2.p, 2, 1.0, 0.01, 1e-10) == GPT_OK);
+        held = stub_live_objects;
+        Arrays a(1, 2);
+        auto st = stages_of(2);
+        done_held(call(st.data(), 2, hd, a, 1, 2, ALL, a.y0.p, a.path.p), GPT_E_ARG);
+        untouched(a);
+    }
+    begin("gpt_rollout_policy teardown");
+    for (auto& q : h) gpt_destroy(q);
+    gpt_destroy(hd);
+    gpt_destroy(bare);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -806,6 +922,7 @@ int main() {
     transport_cases();
     pullback_cases();
     chain_cases();
+    rollout_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

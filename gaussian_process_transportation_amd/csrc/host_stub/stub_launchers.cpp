@@ -237,6 +237,16 @@ extern "C" int gpt_pullback_chain(const gpt_chain_stage*, int, gpt_handle*, cons
     gpt::set_last_error("gpt_pullback_chain: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_rollout_policy_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, int64_t, double, double,
+                                      int, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_policy_dev: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_rollout_policy(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, int64_t, double, double, int,
+                                  double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_policy: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
                                int*) {
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
@@ -256,6 +266,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 #include "../gpt_svgp_train.h"
 #include "../gpt_svgp_surface.h"
 #include "../gpt_chain.h"
+#include "../gpt_rollout.h"
 #include <cstdio>
 
 namespace gpt {
@@ -403,6 +414,42 @@ void launch_chain_variance(hipStream_t, int D_, const ChainArgs& a) {
         stub_check(a.stage_A && a.var_dyn);
         touch_r(a.stage_A, K * M * D * D * 8); touch_r(a.var_dyn, M * 8); touch_w(a.vel_var_dyn, M * D * 8);
     }
+}
+
+// ---- gpt_rollout.hip ----------------------------------------------------------------------------------------------------------
+// k_rollout: the models and affine parts as k_chain_velocity; a launch with t_begin == 0 reads y0 and x0 and writes row 0 of every
+// path, a later one reads steps_done and, of the trajectories alive, `state` and path row t_begin.  The stand-in ends no
+// trajectory: every launch writes its steps' rows, steps_done = t_end and status, and `state` when another launch follows
+int stub_rollout_launch_count = 0;         // launches since the driver last reset it
+void launch_rollout(hipStream_t, int D_, const RolloutArgs& a) {
+    if (a.M <= 0) return;
+    ++stub_rollout_launch_count;
+    stub_check(a.K >= 0 && a.K <= CHAIN_MAX && a.path && a.steps_done && a.status);
+    stub_check(a.T >= 0 && a.t_begin >= 0 && a.t_begin <= a.t_end && a.t_end <= a.T && (a.t_begin < a.t_end || a.T == 0));
+    stub_check(a.M * ((int64_t)a.T + 1) < ((int64_t)1 << 31));
+    const size_t M = (size_t)a.M, D = (size_t)D_, T = (size_t)a.T, t0 = (size_t)a.t_begin, t1 = (size_t)a.t_end;
+    auto model = [](const ChainModel& m) {
+        const size_t NP = ((size_t)m.N + PAD_N - 1) / PAD_N * PAD_N;
+        touch_r(m.Xs, NP * 4 * 8); touch_r(m.A4, NP * 4 * 8);
+    };
+    for (int k = 0; k < a.K; ++k) {
+        const ChainStage& S = a.st[k];
+        model(S.m);
+        touch_r(S.R, D * D * 8); touch_r(S.R_jac, D * D * 8); touch_r(S.c_src, D * 8); touch_r(S.c_dst, D * 8);
+    }
+    model(a.dyn);
+    if (t0 == 0) { touch_r(a.Y0, M * D * 8); touch_r(a.X0, M * D * 8); }
+    else { stub_check(a.state); touch_r(a.state, M * D * 8); }
+    for (size_t m = 0; m < M; ++m) {
+        if (t0 == 0) touch_w(a.path + m * (T + 1) * D, D * 8);
+        else { stub_check(a.steps_done[m] == a.t_begin); touch_r(a.path + (m * (T + 1) + t0) * D, D * 8); }
+        touch_w(a.path + (m * (T + 1) + t0 + 1) * D, (t1 - t0) * D * 8);
+        if (a.vel) touch_w(a.vel + (m * T + t0) * D, (t1 - t0) * D * 8);
+        if (a.x) touch_w(a.x + (m * T + t0) * D, (t1 - t0) * D * 8);
+        a.steps_done[m] = a.t_end;
+        a.status[m] = 0;
+    }
+    if (t1 < T) { stub_check(a.state); touch_w(a.state, M * D * 8); }
 }
 
 // ---- gpt_svgp_train.hip, gpt_svgp_surface.hip ---------------------------------------------------------------------------------

@@ -400,6 +400,55 @@ class GaussianProcess:
             res.update({k: out[k] for k in names if k.startswith("post_")})
         return res
 
+    @staticmethod
+    def _check_chain(what, maps, dynamics, affine, k_min):
+        """What pullback_chain() and rollout_chain() refuse of their models before anything reaches a device: the number of maps
+        (k_min .. CHAIN_MAX) and of affine parts, kinds, fits, dimensions, dtypes, derivatives of the maps, one object twice, devices.
+        The model the others are compared with is the last map (without maps: the dynamics).  Returns the affine parts as a list."""
+        if not k_min <= len(maps) <= _lib.CHAIN_MAX:
+            raise ValueError(f"{what}(): {k_min} .. {_lib.CHAIN_MAX} maps, got {len(maps)}")
+        affine = list(affine)
+        if len(affine) != len(maps):
+            raise ValueError(f"{what}(): {len(maps)} maps, {len(affine)} affine parts")
+        if not isinstance(dynamics, GaussianProcess):
+            raise NotImplementedError(f"{what}(): the dynamics ({type(dynamics).__name__}) must be a fitted GaussianProcess")
+        for k, g in enumerate(maps):
+            if not isinstance(g, GaussianProcess):
+                raise NotImplementedError(f"{what}(): the map of stage {k} ({type(g).__name__}) must be a fitted GaussianProcess")
+            g._require_fit()
+            g._require_self_map(what, f"map of stage {k}")
+            g._require_derivatives(what)
+        dynamics._require_fit()
+        dynamics._require_self_map(what, "dynamics")
+        models = maps + [dynamics]
+        if len({id(g) for g in models}) != len(models):
+            raise ValueError(f"{what}(): one object twice among the maps and the dynamics; each is a model of its own")
+        last = models[-2] if maps else dynamics
+        for k, g in enumerate(models):
+            who = "the dynamics" if g is dynamics else f"the map of stage {k}"
+            if g.n_features != last.n_features:
+                raise ValueError(f"{what}(): the last map has {last.n_features} features, {who} {g.n_features}")
+            if g.device != last.device:
+                raise ValueError(f"{what}(): the last map holds its fit on device {last.device}, {who} on {g.device}")
+        return affine
+
+    def _check_chain_points(self, what, y, x0, rtol, max_passes, name):
+        """The solver's arguments and the points (M,D) with their optional guesses, as float64 arrays."""
+        if not float(rtol) > 0.0:
+            raise ValueError(f"{what}(): rtol must be > 0")
+        if int(max_passes) < 1:
+            raise ValueError(f"{what}(): max_passes must be >= 1")
+        y = _lib.as_f64(y, 2, name)
+        if y.shape[1] != self.n_features:
+            raise ValueError(f"{name} has {y.shape[1]} columns, the model {self.n_features} features")
+        if x0 is not None:
+            x0 = _lib.as_f64(x0, 2, "x0")
+            if x0.shape != y.shape:
+                raise ValueError(f"x0 has shape {x0.shape}, {name} {y.shape}")
+        if y.shape[0] >= 2 ** 31:
+            raise ValueError(f"{what}(): fewer than 2^31 points per call")
+        return y, x0
+
     def pullback_chain(self, inner, dynamics, y, affine, x0=None, rtol=1e-10, max_passes=64, variances=False, outputs=None):
         """The transported policy at the target-space points y (M,D) through a CHAIN of transports Phi = Phi_{K-1} o ... o Phi_0,
         this model the displacement psi_{K-1} of the LAST one and `inner` the GaussianProcess models psi_0 .. psi_{K-2} of the
@@ -416,43 +465,8 @@ class GaussianProcess:
         handful of points is most of the call.  Every model needs n_outputs == n_features <= 3 (the
         same), float64, a fit on one device; the maps, if Matern, matern_derivatives=True."""
         maps = list(inner) + [self]
-        if not 1 <= len(maps) <= _lib.CHAIN_MAX:
-            raise ValueError(f"pullback_chain(): 1 .. {_lib.CHAIN_MAX} maps, got {len(maps)}")
-        affine = list(affine)
-        if len(affine) != len(maps):
-            raise ValueError(f"pullback_chain(): {len(maps)} maps, {len(affine)} affine parts")
-        if not isinstance(dynamics, GaussianProcess):
-            raise NotImplementedError(f"pullback_chain(): the dynamics ({type(dynamics).__name__}) must be a fitted GaussianProcess")
-        for k, g in enumerate(maps):
-            if not isinstance(g, GaussianProcess):
-                raise NotImplementedError(f"pullback_chain(): the map of stage {k} ({type(g).__name__}) must be a fitted GaussianProcess")
-            g._require_fit()
-            g._require_self_map("pullback_chain", f"map of stage {k}")
-            g._require_derivatives("pullback_chain")
-        dynamics._require_fit()
-        dynamics._require_self_map("pullback_chain", "dynamics")
-        models = maps + [dynamics]
-        if len({id(g) for g in models}) != len(models):
-            raise ValueError("pullback_chain(): one object twice among the maps and the dynamics; each is a model of its own")
-        for k, g in enumerate(models):
-            who = "the dynamics" if g is dynamics else f"the map of stage {k}"
-            if g.n_features != self.n_features:
-                raise ValueError(f"pullback_chain(): the last map has {self.n_features} features, {who} {g.n_features}")
-            if g.device != self.device:
-                raise ValueError(f"pullback_chain(): the last map holds its fit on device {self.device}, {who} on {g.device}")
-        if not float(rtol) > 0.0:
-            raise ValueError("pullback_chain(): rtol must be > 0")
-        if int(max_passes) < 1:
-            raise ValueError("pullback_chain(): max_passes must be >= 1")
-        y = _lib.as_f64(y, 2, "y")
-        if y.shape[1] != self.n_features:
-            raise ValueError(f"y has {y.shape[1]} columns, the model {self.n_features} features")
-        if x0 is not None:
-            x0 = _lib.as_f64(x0, 2, "x0")
-            if x0.shape != y.shape:
-                raise ValueError(f"x0 has shape {x0.shape}, y {y.shape}")
-        if y.shape[0] >= 2 ** 31:
-            raise ValueError("pullback_chain(): fewer than 2^31 points per call")
+        affine = self._check_chain("pullback_chain", maps, dynamics, affine, 1)
+        y, x0 = self._check_chain_points("pullback_chain", y, x0, rtol, max_passes, "y")
         if variances not in (False, True, "vel"):
             raise ValueError("pullback_chain(): variances is False, True or 'vel'")
         names = ["x", "vel", "f", "status", "stage_x", "stage_z", "stage_A", "stage_status", "stage_passes", "stage_residual", "stage_det"]
@@ -464,6 +478,44 @@ class GaussianProcess:
         stages = [(primary(g), rot, src, dst, scale, jac) for g, (rot, scale, src, dst, jac) in zip(maps, affine)]
         return primary(self).pullback_chain(stages, primary(dynamics), y, x0=x0, rtol=rtol, max_passes=max_passes,
                                             std_offset=np.sqrt(dynamics._noise), outputs=names)
+
+    # ------------------------------------------------------------------ whole paths of the transported policy
+    def rollout_chain(self, inner, dynamics, starts, n_steps, affine, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x")):
+        """The paths the transported policy of pullback_chain() drives from `starts` (M,D): n_steps explicit Euler steps
+        y_{t+1} = y_t + dt * vel(y_t), the loop over the steps on the device in one call (_lib.Handle.rollout_policy) instead of one
+        pullback_chain() per step; this model is the LAST map, `inner` the ones before it, `affine` as pullback_chain's.  Step t
+        evaluates exactly what pullback_chain() returns for the point y_t with x0 = the x of step t - 1 (at t = 0: `x0`, guesses of
+        the source-space preimages of the starts, or none).  dt: finite, not zero; negative integrates backwards.  A trajectory ends
+        at the first step whose inverse does not converge or whose next point is not finite.  Returns a dict: path
+        (M,n_steps+1,D) with row 0 the starts, steps_done (M,) the steps whose next point was recorded, status (M,) the
+        _lib.INV_* of the last step evaluated, and — `outputs` — vel, x (M,n_steps,D); every row after a trajectory's end is NaN.
+        Only the mean policy is integrated: no variance term."""
+        maps = list(inner) + [self]
+        affine = self._check_chain("rollout_chain", maps, dynamics, affine, 1)
+        return self._rollout("rollout_chain", maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs)
+
+    def rollout(self, starts, n_steps, dt=1.0, return_info=False):
+        """This model as a dynamics rolling out itself: n_steps explicit Euler steps y_{t+1} = y_t + dt * predict(y_t) from every
+        row of `starts` (M,D), the loop over the steps on the device (any of the four kernels: the model is only evaluated).
+        Returns path (M,n_steps+1,D), row 0 the starts; with return_info also a dict: vel (M,n_steps,D) the means along the path,
+        x (= the path's points), steps_done and status (M,).  A trajectory ends where its next point is not finite; the rows after
+        that are NaN.  Needs n_outputs == n_features <= 3 and float64."""
+        self._check_chain("rollout", [], self, [], 0)
+        out = self._rollout("rollout", [], [], self, starts, n_steps, dt, None, 1e-10, 64, ("vel", "x") if return_info else ())
+        return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]
+
+    def _rollout(self, what, maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs):
+        starts, x0 = self._check_chain_points(what, starts, x0, rtol, max_passes, "starts")
+        if int(n_steps) != n_steps or int(n_steps) < 0:
+            raise ValueError(f"{what}(): n_steps must be an integer >= 0, got {n_steps!r}")
+        if not np.isfinite(float(dt)) or float(dt) == 0.0:
+            raise ValueError(f"{what}(): dt must be finite and not zero, got {dt!r}")
+        if starts.shape[0] * (int(n_steps) + 1) >= 2 ** 31:
+            raise ValueError(f"{what}(): starts times (n_steps + 1), the rows of the paths, must stay below 2^31")
+        primary = lambda g: getattr(g._handle, "primary", g._handle)
+        stages = [(primary(g), rot, src, dst, scale, jac) for g, (rot, scale, src, dst, jac) in zip(maps, affine)]
+        return primary(self).rollout_policy(stages, primary(dynamics), starts, int(n_steps), dt=float(dt), x0=x0, rtol=rtol,
+                                            max_passes=max_passes, outputs=outputs)
 
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):

@@ -85,6 +85,32 @@ class TransportChain:
             res += ({k: v for k, v in out.items() if k != "vel"},)
         return res if len(res) > 1 else res[0]
 
+    def rollout(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+        """The paths the transported policy drives from `starts` (M,D) of the LAST scene: n_steps explicit Euler steps
+        y_{t+1} = y_t + dt * transported_policy(dynamics, y_t), the x of one step the guess of the next (x0: guesses for the
+        starts), the loop over the steps on the device in ONE call (GaussianProcess.rollout_chain) — equal, bit for bit, to the
+        host loop over transported_policy(dynamics, y_t, x0=x_{t-1}) that the reference's plot_traj_evolution runs.  dt: finite,
+        not zero; negative integrates backwards.  `solver` passes rtol / max_passes on.  Returns path (M,n_steps+1,D), row 0 the
+        starts; a trajectory ends at the first step whose inverse does not converge or whose next point is not finite, and its
+        rows after that are NaN.  With return_info also a dict: vel, x (M,n_steps,D), steps_done (M,) and status (M,), the
+        _lib.INV_* of the last step evaluated.  The mean policy only: no variance term."""
+        unknown = set(solver) - {"rtol", "max_passes"}
+        if unknown:
+            raise TypeError(f"TransportChain: unknown solver arguments {sorted(unknown)}")
+        rollout = getattr(self.methods[-1].delta_map, "rollout_chain", None)
+        if rollout is None:
+            raise NotImplementedError(f"TransportChain.rollout(): the delta_map of the last transport ({type(self.methods[-1].delta_map).__name__}) "
+                                      "has no rollout_chain; GaussianProcess provides one")
+        affine = [(m.affine_transform.rotation_matrix, m.affine_transform.scale, m.affine_transform.S_centroid,
+                   m.affine_transform.T_centroid, m.affine_transform.rotation_matrix) for m in self.methods]
+        maps = [m.delta_map for m in self.methods]
+        out = rollout(maps[:-1], dynamics, starts, n_steps, affine, dt=dt, x0=x0, outputs=("vel", "x") if return_info else (), **solver)
+        if self.verbose:
+            status, done = out["status"], out["steps_done"]
+            counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.INV_STATUS_NAMES))
+            print(f"Rollout of {len(done)} paths, {int(n_steps)} steps: {int(np.sum(done == int(n_steps)))} complete; last status: {counts}")
+        return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]
+
     def _still_dynamics(self):
         """A dynamics model for inverse_transport(), which asks the device call for x alone: zero velocities on two points,
         fitted once on the device of the last map."""

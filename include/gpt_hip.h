@@ -469,6 +469,44 @@ int gpt_pullback_chain(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, 
                        double* vel_var_map, double* vel_var_dyn, double* stage_x, double* stage_z, double* stage_A, double* stage_Jvar,
                        double* stage_map_var, int* stage_status, int* stage_passes, double* stage_residual, double* stage_det);
 
+/* (new) Whole paths of the transported policy: the mean policy of gpt_pullback_chain integrated from M starts with n_steps = T
+ * explicit Euler steps of size dt, the loop over the steps on the device (the reference's plot_traj_evolution is 1000 steps of
+ * pos += vel on the host).  stages, K, h_dyn, rtol, max_passes as gpt_pullback_chain, with K = 0 (stages may then be NULL) allowed:
+ * the dynamics rolls out itself.  Inputs: y0 (M,D) the starts; x0 (M,D) guesses of the SOURCE-space preimages of the starts, or
+ * NULL; dt finite and not zero (negative: backwards).  Per trajectory m, for t = 0 .. T-1:
+ *   (x_t, vel_t, status_t) = exactly what gpt_pullback_chain returns as x, vel, status for the single point y_t, with the guess
+ *                x_{t-1} (at t = 0: x0[m], or none).  K = 0: x_t = y_t, vel_t = the mean of h_dyn at y_t, status_t = CONVERGED.
+ *   y_{t+1} = y_t + (dt vel_t), the product and the sum rounded separately (no fused multiply-add: y + dt * vel in C or numpy).
+ *   The trajectory ENDS at the first t where status_t is not GPT_INV_CONVERGED or y_{t+1} is not finite: x_t, vel_t and status_t
+ *   are still recorded, y_{t+1} is not.
+ * Outputs, trajectory-major:
+ *   path (M,T+1,D)    row 0 = y0, row t+1 = y_{t+1}; NaN after a trajectory's end
+ *   vel, x (M,T,D)    either may be NULL; NaN after the end
+ *   steps_done (M, int)  the steps whose y_{t+1} was recorded (T: the trajectory never ended)
+ *   status (M, int)   the GPT_INV_* of the last step evaluated; CONVERGED when T = 0
+ * One wave per trajectory (k_rollout, around the per-point body of k_chain_velocity); a launch advances every live trajectory by at
+ * most 64 steps (the environment's GPT_ROLLOUT_STEPS_PER_LAUNCH, read per call, overrides), the launches of a call are enqueued
+ * back to back with no host read in between, and a trajectory that has ended costs a later launch one wave that returns at once.
+ * A trajectory's values do not depend on M, on the other trajectories, on their order or on where the launches are cut, bit for bit.
+ * Refusals: gpt_pullback_chain's (K = 0 .. GPT_CHAIN_MAX here; for K = 0 what it refuses of a dynamics model), and GPT_E_ARG for
+ * n_steps < 0; dt zero, NaN or infinite; M (n_steps + 1) >= 2^31; a NULL among y0, path, steps_done, status.  M = 0 does nothing;
+ * n_steps = 0 writes path = y0.
+ * Device memory.  Asynchronous: enqueued on the stream of stages[K-1].h (K = 0: of h_dyn), which first waits for what the other
+ * handles' streams hold so far; they go on after the last launch.  No host synchronisation.  Scratch, staging and events belong to
+ * stages[K-1].h (K = 0: h_dyn), grow-only; device memory per call: M D doubles (the carried x) when the call takes more than one
+ * launch, else none.  Every model is left as it was. */
+int gpt_rollout_policy_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0_dev, const double* x0_dev, int64_t M,
+                           int64_t n_steps, double dt, double rtol, int max_passes, double* path_dev, double* vel_dev, double* x_dev,
+                           int* steps_done_dev, int* status_dev);
+/* (new) The same with every data pointer in host memory; also GPT_E_ARG for NaN / infinity in y0, x0, an affine part or rtol.  The
+ * trajectories are streamed through the device in chunks of max(1, 131072 / (n_steps + 1)) through two staging sets of the owning
+ * handle, so a chunk's images hold about 131072 path rows whatever n_steps is: two sets of at most
+ * chunk ((3 n_steps + 1) D + 2 D) doubles and 2 chunk ints, less for what was not asked for; only the arrays asked for cross the
+ * bus.  Returns when every output is in place. */
+int gpt_rollout_policy(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0, const double* x0, int64_t M,
+                       int64_t n_steps, double dt, double rtol, int max_passes, double* path, double* vel, double* x, int* steps_done,
+                       int* status);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);

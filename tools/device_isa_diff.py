@@ -48,7 +48,7 @@ def main():
     other = os.path.abspath(sys.argv[1])
     units = sys.argv[2:] or ["gpt_api.hip", "gpt_fit.hip", "gpt_predict.hip", "gpt_predict_matern.hip", "gpt_svgp_train.hip",
                              "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_batch.hip", "gpt_batch_opt.hip", "gpt_inverse.hip", "gpt_transport.hip",
-                             "gpt_pullback.hip", "gpt_chain.hip"]
+                             "gpt_pullback.hip", "gpt_chain.hip", "gpt_rollout.hip"]
     bad = 0
     for unit in [u for u in units if not os.path.exists(os.path.join(other, u))]:
         print(f"{unit}: not in {other} (a new unit): nothing to compare")
