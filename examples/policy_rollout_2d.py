@@ -9,7 +9,7 @@ evaluates the dynamics there and pushes it forward.
 
 Data: tests/golden/letterS_2d.npz.  The first map folds near the demonstration, so a path can reach a point with no single
 preimage; it ends there, and the printout says how many paths ended early and with which status.  Only the mean policy is
-integrated (the reference's pull down the variance gradient is examples/dynamics_rollout_3d.py's subject)."""
+integrated (the reference's pull down the variance gradient, rollout(..., variance_gain=g), is examples/dynamics_rollout_3d.py's subject)."""
 import os
 import sys
 

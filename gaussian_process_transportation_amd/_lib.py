@@ -31,6 +31,9 @@ CHAIN_MAX = 4      # GPT_CHAIN_MAX: stages of one gpt_pullback_chain call
 # outputs of gpt_rollout_policy, in the order of its arguments (steps_done and status are int32, the rest float64)
 ROLLOUT_OUTPUTS = ("path", "vel", "x", "steps_done", "status")
 ROLLOUT_INT_OUTPUTS = ("steps_done", "status")
+# outputs of gpt_rollout_stabilised, in the order of its arguments
+ROLLOUT_STAB_OUTPUTS = ("path", "vel", "x", "f", "var", "dvar", "steps_done", "status")
+ROLLOUT_STAB_MAX_N = 1024   # training points of the dynamics of a stabilised rollout, at most (gpt_rollout_stab.h)
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -80,6 +83,10 @@ SIGNATURES = {
     "gpt_rollout_policy_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int] + [_vp] * 5),
     "gpt_rollout_policy": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int]
                            + [_dp] * 3 + [_ip] * 2),
+    "gpt_rollout_stabilised_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                              C.c_double, C.c_double] + [_vp] * 8),
+    "gpt_rollout_stabilised": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                          C.c_double, C.c_double] + [_dp] * 6 + [_ip] * 2),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -954,19 +961,15 @@ class Handle:
               "gpt_pullback_chain_dev")
 
     # ---- whole paths of the transported policy: the loop over the steps on the device
-    def rollout_policy(self, inner, dyn, y0, n_steps, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x")):
-        """gpt_rollout_policy on host arrays: n_steps explicit Euler steps y += dt * vel from every row of y0 (M,D), vel the mean
-        policy of pullback_chain at y with the x of the step before as its guess (x0 (M,D): guesses for the starts).  `inner`: the K
-        stages as pullback_chain's, 0 <= K <= CHAIN_MAX; this handle is the last stage's, or — K = 0, the model `dyn` rolls out
-        itself — dyn.  `outputs`: which of "vel" and "x" (M,n_steps,D) come back besides path (M,n_steps+1,D), steps_done and status
-        (M,).  A trajectory ends at the first step that does not converge or leaves the finite numbers; every row after its end is
-        NaN.  Returns a dict."""
+    def _rollout_host(self, what, names, optional, extra, inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs):
+        """The host entry `gpt_<what>` of a rollout family: `names` its outputs in the order of its arguments, `optional` those the
+        caller chooses among, `extra` the arguments between max_passes and the outputs."""
         stages = list(inner)
         K = len(stages)
         if K > CHAIN_MAX:
-            raise ValueError(f"rollout_policy: 0 .. {CHAIN_MAX} stages, got {K}")
+            raise ValueError(f"{what}: 0 .. {CHAIN_MAX} stages, got {K}")
         if (stages[-1][0] if K else dyn) is not self:
-            raise ValueError("rollout_policy: the last stage's handle (without stages: dyn) must be the handle the call is made on")
+            raise ValueError(f"{what}: the last stage's handle (without stages: dyn) must be the handle the call is made on")
         N, D, O, _ = self.info()
         y0 = as_f64(y0, 2, "y0")
         if y0.shape[1] != D:
@@ -976,13 +979,13 @@ class Handle:
             x0 = as_f64(x0, 2, "x0")
             if x0.shape != y0.shape:
                 raise ValueError(f"x0 has shape {x0.shape}, y0 {y0.shape}")
-        unknown = set(outputs) - {"vel", "x"}
+        unknown = set(outputs) - set(optional)
         if unknown:
-            raise ValueError(f"rollout_policy: unknown outputs {sorted(unknown)}")
+            raise ValueError(f"{what}: unknown outputs {sorted(unknown)}")
         if T < 0:
-            raise ValueError("rollout_policy: n_steps must be >= 0")
+            raise ValueError(f"{what}: n_steps must be >= 0")
         if M * (T + 1) >= 2 ** 31:
-            raise ValueError("rollout_policy: M (n_steps + 1), the rows of path, must be below 2^31")
+            raise ValueError(f"{what}: M (n_steps + 1), the rows of path, must be below 2^31")
         keep = []                                # the affine arrays live until the call returns
         arr = (ChainStage * max(K, 1))()
         for k, (h, R, c_src, c_dst, scale, R_jac) in enumerate(stages):
@@ -994,33 +997,66 @@ class Handle:
                                  f"c_dst ({D},)")
             keep += [R, R_jac, c_src, c_dst]
             arr[k] = ChainStage(h._h, R.ctypes.data, c_src.ctypes.data, c_dst.ctypes.data, R_jac.ctypes.data, float(scale))
-        shapes = {"path": (M, T + 1, D), "vel": (M, T, D), "x": (M, T, D), "steps_done": (M,), "status": (M,)}
-        want = [k for k in ROLLOUT_OUTPUTS if k not in ("vel", "x") or k in outputs]
-        out = {k: np.empty(shapes[k], dtype=np.int32 if k in ROLLOUT_INT_OUTPUTS else np.float64) for k in want}
+        shapes = {"path": (M, T + 1, D), "var": (M, T), "steps_done": (M,), "status": (M,)}
+        want = [k for k in names if k not in optional or k in outputs]
+        out = {k: np.empty(shapes.get(k, (M, T, D)), dtype=np.int32 if k in ROLLOUT_INT_OUTPUTS else np.float64) for k in want}
         ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(_ip)) if k in ROLLOUT_INT_OUTPUTS else dptr(out.get(k))
-        check(self.lib.gpt_rollout_policy(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), M, T, float(dt), float(rtol), int(max_passes),
-                                          *(ptr(k) for k in ROLLOUT_OUTPUTS)),
-              "gpt_rollout_policy")
+        check(getattr(self.lib, "gpt_" + what)(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), M, T, float(dt), float(rtol), int(max_passes),
+                                               *extra, *(ptr(k) for k in names)),
+              "gpt_" + what)
         del keep
         return out
+
+    def _rollout_dev(self, what, names, extra, inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol, max_passes, ptrs):
+        """The device entry `gpt_<what>_dev` of a rollout family; ptrs: output name -> device pointer (0: not asked for)."""
+        stages = list(inner)
+        K = len(stages)
+        if K > CHAIN_MAX:
+            raise ValueError(f"{what}_dev: 0 .. {CHAIN_MAX} stages, got {K}")
+        if (stages[-1][0] if K else dyn) is not self:
+            raise ValueError(f"{what}_dev: the last stage's handle (without stages: dyn) must be the handle the call is made on")
+        arr = (ChainStage * max(K, 1))()
+        for k, (h, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr) in enumerate(stages):
+            arr[k] = ChainStage(h._h, R_ptr or None, c_src_ptr or None, c_dst_ptr or None, R_jac_ptr or None, float(scale))
+        check(getattr(self.lib, f"gpt_{what}_dev")(arr if K else None, K, dyn._h, _vp(y0_ptr or None), _vp(x0_ptr or None), int(M), int(n_steps),
+                                                   float(dt), float(rtol), int(max_passes), *extra, *(_vp(ptrs.get(k) or None) for k in names)),
+              f"gpt_{what}_dev")
+
+    def rollout_policy(self, inner, dyn, y0, n_steps, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x")):
+        """gpt_rollout_policy on host arrays: n_steps explicit Euler steps y += dt * vel from every row of y0 (M,D), vel the mean
+        policy of pullback_chain at y with the x of the step before as its guess (x0 (M,D): guesses for the starts).  `inner`: the K
+        stages as pullback_chain's, 0 <= K <= CHAIN_MAX; this handle is the last stage's, or — K = 0, the model `dyn` rolls out
+        itself — dyn.  `outputs`: which of "vel" and "x" (M,n_steps,D) come back besides path (M,n_steps+1,D), steps_done and status
+        (M,).  A trajectory ends at the first step that does not converge or leaves the finite numbers; every row after its end is
+        NaN.  Returns a dict."""
+        return self._rollout_host("rollout_policy", ROLLOUT_OUTPUTS, ("vel", "x"), (), inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs)
 
     def rollout_policy_dev(self, inner, dyn, y0_ptr, M, n_steps, path_ptr, steps_done_ptr, status_ptr, dt=1.0, x0_ptr=0, rtol=1e-10,
                            max_passes=64, vel_ptr=0, x_ptr=0):
         """The same on device pointers (float64; steps_done / status int32), asynchronous on this handle's stream
         (gpt_rollout_policy_dev).  `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers."""
-        stages = list(inner)
-        K = len(stages)
-        if K > CHAIN_MAX:
-            raise ValueError(f"rollout_policy_dev: 0 .. {CHAIN_MAX} stages, got {K}")
-        if (stages[-1][0] if K else dyn) is not self:
-            raise ValueError("rollout_policy_dev: the last stage's handle (without stages: dyn) must be the handle the call is made on")
-        arr = (ChainStage * max(K, 1))()
-        for k, (h, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr) in enumerate(stages):
-            arr[k] = ChainStage(h._h, R_ptr or None, c_src_ptr or None, c_dst_ptr or None, R_jac_ptr or None, float(scale))
-        check(self.lib.gpt_rollout_policy_dev(arr if K else None, K, dyn._h, _vp(y0_ptr or None), _vp(x0_ptr or None), int(M), int(n_steps),
-                                              float(dt), float(rtol), int(max_passes), _vp(path_ptr or None), _vp(vel_ptr or None),
-                                              _vp(x_ptr or None), _vp(steps_done_ptr or None), _vp(status_ptr or None)),
-              "gpt_rollout_policy_dev")
+        self._rollout_dev("rollout_policy", ROLLOUT_OUTPUTS, (), inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol, max_passes,
+                          dict(path=path_ptr, vel=vel_ptr, x=x_ptr, steps_done=steps_done_ptr, status=status_ptr))
+
+    # ---- whole paths of the variance-stabilised policy
+    def rollout_stabilised(self, inner, dyn, y0, n_steps, gain, std_offset=0.0, dt=1.0, x0=None, rtol=1e-10, max_passes=64,
+                           outputs=("vel", "x", "f", "var", "dvar")):
+        """gpt_rollout_stabilised on host arrays: rollout_policy with the reference's variance stabiliser inside every step,
+        vel = push(f - gain * (sqrt(var) - std_offset) * dvar / |dvar|), var and dvar the posterior variance of `dyn` and its
+        gradient at the source-space preimage x of the step's point.  Arguments as rollout_policy's; `outputs`: which of "vel",
+        "x", "f", "dvar" (M,n_steps,D) and "var" (M,n_steps) come back besides path, steps_done and status.  gain = 0 gives
+        rollout_policy's path, vel, x, steps_done and status bit for bit.  `dyn`: at most ROLLOUT_STAB_MAX_N training points, a
+        kernel with derivatives.  Returns a dict."""
+        return self._rollout_host("rollout_stabilised", ROLLOUT_STAB_OUTPUTS, ("vel", "x", "f", "var", "dvar"), (float(gain), float(std_offset)),
+                                  inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs)
+
+    def rollout_stabilised_dev(self, inner, dyn, y0_ptr, M, n_steps, gain, path_ptr, steps_done_ptr, status_ptr, std_offset=0.0, dt=1.0,
+                               x0_ptr=0, rtol=1e-10, max_passes=64, vel_ptr=0, x_ptr=0, f_ptr=0, var_ptr=0, dvar_ptr=0):
+        """The same on device pointers (float64; steps_done / status int32), asynchronous on this handle's stream
+        (gpt_rollout_stabilised_dev).  `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers."""
+        self._rollout_dev("rollout_stabilised", ROLLOUT_STAB_OUTPUTS, (float(gain), float(std_offset)), inner, dyn, y0_ptr, x0_ptr, M, n_steps,
+                          dt, rtol, max_passes, dict(path=path_ptr, vel=vel_ptr, x=x_ptr, f=f_ptr, var=var_ptr, dvar=dvar_ptr,
+                                                     steps_done=steps_done_ptr, status=status_ptr))
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -781,7 +781,10 @@ namespace gpt {
 void model_view(gpt_handle* h, ModelView* v) {
     v->committed = h->committed; v->matern_derivatives = h->matern_derivatives;
     v->device = h->device; v->stream = h->stream; v->p = h->p;
-    if (h->committed) { v->Xs = static_cast<const double*>(h->dXs()); v->A4 = static_cast<const double*>(h->dA4()); }
+    if (h->committed) {
+        v->Xs = static_cast<const double*>(h->dXs()); v->A4 = static_cast<const double*>(h->dA4());
+        v->Wf = static_cast<const double*>(h->dWf());
+    }
 }
 
 static int create_events(CallResources& r, int events) {

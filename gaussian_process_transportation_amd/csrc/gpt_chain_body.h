@@ -22,21 +22,21 @@ __device__ __forceinline__ void ch_mean(const ChainModel& m, const double* __res
     }
 }
 
-// x = Phi^-1(y), f = the dynamics mean at x, vel = B_{K-1} ... B_1 (A_0 (R_jac,0 f)) for 1 <= K <= CHAIN_MAX stages `st` (the
+// The first half of chain_point: x = Phi^-1(y) for 1 <= K <= CHAIN_MAX stages `st` (the
 // kernel's arguments: the only thing a run-time stage number indexes).  With `guess` (wave-uniform), x0 is a guess of the
 // source-space preimage: a mean-only forward pass through stages 0 .. K-2 gives every stage its start; without it every stage
 // starts at its own y_k (x0 is not read).  The stages are solved from the last to the first, each with the damped Newton iteration
 // of k_pullback_velocity on z + psi_k(z) = y_k and the affine inverse x_k = gamma_k^-1(z_k), the y of the stage before; a stage
-// that does not converge hands on the point it reached.  The product of the outer stages is kept in registers as the sweep goes,
-// the innermost stage is applied to f in the association of k_pullback_velocity, so that K = 1 is that kernel's arithmetic.
+// that does not converge hands on the point it reached.  Q, the product B_{K-1} ... B_1 of the outer stages (B_k = A_k R_jac,k; the
+// identity for K = 1), is kept in registers as the sweep goes; A is left as stage 0's, for chain_push.
 // stage(k, z, x_k, A, status, passes, rho) is called as each stage finishes.  Returns the INV_* of the first stage in solve
 // order that is not CONVERGED, else CONVERGED.
 template <int D, class Stage>
-__device__ __forceinline__ int chain_point(const ChainStage (&st)[CHAIN_MAX], const ChainModel& dyn, const int K, const double rtol,
-                                           const int max_passes, const double* __restrict__ Tt, const int lane, const bool guess,
-                                           const double (&x0)[D], const double (&y_in)[D], double (&x)[D], double (&f)[D],
-                                           double (&vel)[D], Stage&& stage) {
-    double y[D], Q[D][D], A[D][D];
+__device__ __forceinline__ int chain_invert(const ChainStage (&st)[CHAIN_MAX], const int K, const double rtol,
+                                            const int max_passes, const double* __restrict__ Tt, const int lane, const bool guess,
+                                            const double (&x0)[D], const double (&y_in)[D], double (&x)[D], double (&Q)[D][D],
+                                            double (&A)[D][D], Stage&& stage) {
+    double y[D];
     double start[CHAIN_MAX][D];                       // only ever indexed by unrolled constants: registers
 #pragma unroll
     for (int k = 0; k < CHAIN_MAX; ++k)
@@ -137,9 +137,15 @@ __device__ __forceinline__ int chain_point(const ChainStage (&st)[CHAIN_MAX], co
             for (int d = 0; d < D; ++d) y[d] = x[d];
         }
     }
+    return first;
+}
+
+// The second half: vel = Q (A_0 (R_jac,0 f)) for a source-space vector f at the x chain_invert found (Q and A as it left them).  The
+// innermost stage is applied to f in the association of k_pullback_velocity, so that K = 1 is that kernel's arithmetic.
+template <int D>
+__device__ __forceinline__ void chain_push(const ChainStage (&st)[CHAIN_MAX], const int K, const double (&Q)[D][D],
+                                           const double (&A)[D][D], const double (&f)[D], double (&vel)[D]) {
     double g[D], h[D];
-    ch_mean<D>(dyn, Tt, lane, x, f);
-    // vel = Q (A_0 (R_jac,0 f)): A and x are stage 0's here
     const double* Rj = st[0].R_jac;
 #pragma unroll
     for (int i = 0; i < D; ++i) g[i] = sm_row_dot<D>(Rj, i, f);
@@ -160,6 +166,18 @@ __device__ __forceinline__ int chain_point(const ChainStage (&st)[CHAIN_MAX], co
         }
         vel[o] = r;
     }
+}
+
+// x = Phi^-1(y), f = the dynamics mean at x, vel = B_{K-1} ... B_1 (A_0 (R_jac,0 f)): chain_invert, the mean, chain_push.
+template <int D, class Stage>
+__device__ __forceinline__ int chain_point(const ChainStage (&st)[CHAIN_MAX], const ChainModel& dyn, const int K, const double rtol,
+                                           const int max_passes, const double* __restrict__ Tt, const int lane, const bool guess,
+                                           const double (&x0)[D], const double (&y_in)[D], double (&x)[D], double (&f)[D],
+                                           double (&vel)[D], Stage&& stage) {
+    double Q[D][D], A[D][D];
+    const int first = chain_invert<D>(st, K, rtol, max_passes, Tt, lane, guess, x0, y_in, x, Q, A, stage);
+    ch_mean<D>(dyn, Tt, lane, x, f);
+    chain_push<D>(st, K, Q, A, f, vel);
     return first;
 }
 

@@ -34,6 +34,25 @@ template <int D> __device__ __forceinline__ double inv_norm(const double (&v)[D]
     return sqrt(s);
 }
 
+// One source against one point, as every wave-level pass and the B image of k_rollout_stab (gpt_rollout_stab.hip) take it: the source row
+// xs carries X / l, the point q = x / (sqrt2 l); df_d = X_d / (sqrt2 l_d) - q_d and the return value h = |df|^2 = r^2 / 2.
+template <int D> __device__ __forceinline__ double inv_diffs(const d4& xs, const double (&q)[D], double (&df)[D]) {
+    constexpr double RS2 = 0.70710678118654752440;
+#pragma unroll
+    for (int d = 0; d < D; ++d) df[d] = xs[d] * RS2 - q[d];
+    double hh = df[0] * df[0];
+#pragma unroll
+    for (int d = 1; d < D; ++d) hh = fma(df[d], df[d], hh);
+    return hh;
+}
+// c k (returned) and c g (gpt_exp.h: the factor of a derivative, d k / d x_d = c g (sqrt2 / l_d) df_d; g = k for RBF) from h
+template <int KT> __device__ __forceinline__ double inv_kernel_kg(const double hh, const double lnc, const double* __restrict__ Tt, double& gv) {
+    double kv;
+    if constexpr (KT == KT_MATERN32 || KT == KT_MATERN52) kv = kernel_tab_kg<KT>(hh, lnc, Tt, gv);     // c k and c g from one exp
+    else { kv = kernel_tab<KT>(hh, lnc, Tt); gv = kv; }
+    return kv;
+}
+
 // One pass: r = z + mu(z) - y and A = I + J(z), the same in every lane.  qsc[d] = 1 / (sqrt(2) l_d), jsc[d] = sqrt(2) / l_d.
 template <int KT, int D>
 __device__ __forceinline__ void inv_pass(const int N, const double lnc, const double* __restrict__ Xs, const double* __restrict__ A4,
@@ -51,15 +70,9 @@ __device__ __forceinline__ void inv_pass(const int N, const double lnc, const do
     for (int n = lane; n < N; n += 64) {
         const d4 xs = *reinterpret_cast<const d4*>(Xs + (size_t)n * 4);
         const d4 al = *reinterpret_cast<const d4*>(A4 + (size_t)n * 4);
-        double df[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) df[d] = xs[d] * RS2 - q[d];
-        double hh = df[0] * df[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) hh = fma(df[d], df[d], hh);
-        double kv, gv;
-        if constexpr (KT == KT_MATERN32 || KT == KT_MATERN52) kv = kernel_tab_kg<KT>(hh, lnc, Tt, gv);     // c k and c g from one exp
-        else { kv = kernel_tab<KT>(hh, lnc, Tt); gv = kv; }
+        double df[D], gv;
+        const double hh = inv_diffs<D>(xs, q, df);
+        const double kv = inv_kernel_kg<KT>(hh, lnc, Tt, gv);
 #pragma unroll
         for (int o = 0; o < D; ++o) {
             acc[o][0] += kv * al[o];
@@ -99,11 +112,7 @@ __device__ __forceinline__ void inv_mean(const int N, const double lnc, const do
         const d4 xs = *reinterpret_cast<const d4*>(Xs + (size_t)n * 4);
         const d4 al = *reinterpret_cast<const d4*>(A4 + (size_t)n * 4);
         double df[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) df[d] = xs[d] * RS2 - q[d];
-        double hh = df[0] * df[0];
-#pragma unroll
-        for (int d = 1; d < D; ++d) hh = fma(df[d], df[d], hh);
+        const double hh = inv_diffs<D>(xs, q, df);
         const double kv = kernel_tab<KT>(hh, lnc, Tt);
 #pragma unroll
         for (int o = 0; o < D; ++o) acc[o] += kv * al[o];

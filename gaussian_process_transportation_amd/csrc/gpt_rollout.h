@@ -7,12 +7,24 @@
 #pragma once
 #include "gpt_chain.h"
 
+#include <climits>
+#include <cstdlib>
+
 namespace gpt {
 
 // Steps a launch advances a trajectory by, at most (the environment's GPT_ROLLOUT_STEPS_PER_LAUNCH overrides).  Measured with two maps
 // of 8192 points, D = 3, M = 1024 (profiles/rollout_policy.txt): 64 steps are 13 ms, 128 steps 50 ms, 256 steps 132 ms; a launch
 // is to stay well below 50 ms on a card that others share.
 constexpr int ROLLOUT_STEPS_PER_LAUNCH = 64;
+
+// steps a launch advances a trajectory by: a long rollout is many short kernels, never one long-running one (read per call)
+inline int rollout_steps_per_launch(const int by_default) {
+    if (const char* e = std::getenv("GPT_ROLLOUT_STEPS_PER_LAUNCH")) {
+        const long v = std::strtol(e, nullptr, 10);
+        if (v >= 1 && v <= INT_MAX) return (int)v;
+    }
+    return by_default;
+}
 
 struct RolloutArgs {
     int64_t M;
@@ -33,6 +45,17 @@ struct RolloutArgs {
     int* status;                         // (M) INV_* of the last step evaluated
     double* state;                       // (M,D) x of step t_end - 1, the guess of step t_end: carried to the next launch
 };
+
+#ifdef __HIPCC__
+// y + (dt v), the product and the sum rounded separately.  (The compiler contracts a product and a sum into one fused multiply-add
+// wherever it may, the _rn intrinsics included: they are plain operators.  The pragma is what forbids it here.)  The step of
+// k_rollout and of k_rollout_stab (gpt_rollout_stab.hip).
+__device__ __forceinline__ double euler_step(const double y, const double dt, const double v) {
+#pragma clang fp contract(off)
+    const double p = dt * v;
+    return y + p;
+}
+#endif
 
 // one wave per trajectory; trajectories that ended in an earlier launch return at once
 void launch_rollout(hipStream_t s, int D, const RolloutArgs& a);

@@ -16,14 +16,6 @@
 
 namespace gpt {
 
-// y + (dt v), the product and the sum rounded separately.  (The compiler contracts a product and a sum into one fused multiply-add
-// wherever it may, the _rn intrinsics included: they are plain operators.  The pragma is what forbids it here.)
-__device__ __forceinline__ double euler_step(const double y, const double dt, const double v) {
-#pragma clang fp contract(off)
-    const double p = dt * v;
-    return y + p;
-}
-
 template <int D>
 __global__ __launch_bounds__(256) void k_rollout(RolloutArgs a) {
     __shared__ double Tt[256];

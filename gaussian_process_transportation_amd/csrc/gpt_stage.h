@@ -1,6 +1,6 @@
 // What the host entry points that work on handles share (internal header; plain C++, it also compiles under g++ against
 // host_stub/, the sanitizer builds): the chunked, double-buffered staging of a host-pointer call (gpt_predict_all,
-// gpt_transport_policy, gpt_pullback_policy, gpt_pullback_chain, gpt_rollout_policy), the device image of a call's affine parts, the "caller's array
+// gpt_transport_policy, gpt_pullback_policy, gpt_pullback_chain, gpt_rollout_policy, gpt_rollout_stabilised), the device image of a call's affine parts, the "caller's array
 // or the handle's scratch" table, the one model check of the D <= 3 calls, and the three accessors through which
 // gpt_transport_host.hip and gpt_chain_host.hip reach a handle (gpt_api.hip owns the type and defines them).
 #pragma once
@@ -155,6 +155,7 @@ struct ModelView {
     hipStream_t stream = nullptr;
     KernelParams p{};
     const double *Xs = nullptr, *A4 = nullptr;      // scaled sources and alpha rows of the blob (fp64 models)
+    const double* Wf = nullptr;                     // and its inverse factor in fragment order (fp64 models; k_pack_w)
 };
 enum { CALL_INVERSE = 0, CALL_TRANSPORT, CALL_PULLBACK, CALL_CHAIN, CALL_ROLLOUT, CALL_FAMILIES };
 

@@ -1,6 +1,6 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
-// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip)
+// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -894,6 +894,97 @@ void rollout_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- stabilised rollout (gpt_rollout_stab_host.hip): the arrays of the rollout and f, dvar (rows of T D doubles) and var (rows of T
+// doubles: the one array of the table whose rows have no factor D); chunks and launches as the rollout's, 32 steps per launch unless set
+void rollout_stab_cases() {
+    const int64_t N = 5, Nd = 7;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h[2] = {}, *hd = nullptr, *m12 = nullptr, *m32 = nullptr;
+    begin("gpt_rollout_stabilised setup");
+    for (auto& q : h) CHECK(gpt_create(&q, 0) == GPT_OK);
+    CHECK(gpt_create(&hd, 0) == GPT_OK && gpt_create(&m12, 0) == GPT_OK && gpt_create(&m32, 0) == GPT_OK);
+    for (auto& q : h) CHECK(gpt_fit(q, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit_kernel(m12, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10, GPT_KERNEL_MATERN12) == GPT_OK);
+    CHECK(gpt_fit_kernel(m32, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10, GPT_KERNEL_MATERN32) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    constexpr int X0 = 1, VEL = 2, XO = 4, F = 8, VAR = 16, DVAR = 32, ALL = 63;     // bits of `mask`: the optional arrays passed
+    struct Arrays {
+        D y0, x0, path, vel, x, f, var, dvar;
+        Arr<int> steps, status;
+        Arrays(int64_t M, int64_t T)
+            : y0(ramp(M * 3)), x0(ramp(M * 3)), path((size_t)M * (T + 1) * 3, SENT), vel((size_t)M * T * 3, SENT), x((size_t)M * T * 3, SENT),
+              f((size_t)M * T * 3, SENT), var((size_t)M * T, SENT), dvar((size_t)M * T * 3, SENT), steps(M, ISENT), status(M, ISENT) {}
+    };
+    std::vector<gpt_chain_stage> st2{gpt_chain_stage{h[0], R.p, c_src.p, c_dst.p, R.p, 1.0}, gpt_chain_stage{h[1], R.p, c_src.p, c_dst.p, R.p, 1.25}};
+    auto call = [&](const gpt_chain_stage* st, int K, gpt_handle* hdyn, Arrays& a, int64_t M, int64_t T, int mask, double gain = 1.0,
+                    double off = 0.1) {
+        return gpt_rollout_stabilised(st, K, hdyn, a.y0.p, mask & X0 ? a.x0.p : nullptr, M, T, 0.5, 1e-10, 50, gain, off, a.path.p,
+                                      mask & VEL ? a.vel.p : nullptr, mask & XO ? a.x.p : nullptr, mask & F ? a.f.p : nullptr,
+                                      mask & VAR ? a.var.p : nullptr, mask & DVAR ? a.dvar.p : nullptr, a.steps.p, a.status.p);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.path.all(SENT) && a.vel.all(SENT) && a.x.all(SENT) && a.f.all(SENT) && a.var.all(SENT) && a.dvar.all(SENT) && a.steps.all(ISENT) &&
+              a.status.all(ISENT));
+    };
+    {
+        Arrays a(1, 2);
+        begin("gpt_rollout_stabilised refuses gain = -1"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, -1.0), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses gain = NaN"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, std::nan("")), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses gain = inf"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, INFINITY), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses std_offset = NaN"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, 1.0, std::nan("")), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses a Matern 1/2 dynamics"); done_held(call(nullptr, 0, m12, a, 1, 2, ALL), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses a Matern 3/2 dynamics without its derivatives"); done_held(call(st2.data(), 2, m32, a, 1, 2, ALL), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses n_steps = -1"); done_held(call(st2.data(), 2, hd, a, 1, -1, ALL), GPT_E_ARG);
+        begin("gpt_rollout_stabilised refuses stages = NULL with K = 2"); done_held(call(nullptr, 2, hd, a, 1, 2, ALL), GPT_E_ARG);
+        begin("gpt_rollout_stabilised M = 0 does nothing"); done_held(call(st2.data(), 2, hd, a, 0, 2, ALL), GPT_OK);
+        untouched(a);
+    }
+    CHECK(gpt_set_matern_derivatives(m32, 1) == GPT_OK);
+    // (M, T, steps per launch): T = 0 (the per-step arrays have no rows); one chunk, launches cut inside it and at its last step; T = 255:
+    // chunks of 512, M one past one and past two of them
+    struct Shape { int64_t M, T; int per; };
+    const Shape shapes[] = {{1, 0, 0}, {3, 0, 0}, {1, 1, 0}, {3, 7, 3}, {3, 6, 3}, {2, 70, 0}, {513, 255, 0}, {1027, 255, 100}};
+    // the optional arrays: none, all, var without dvar, dvar without var, f and vel alone
+    for (int K : {0, 2}) {
+        for (gpt_handle* dyn : {hd, m32})
+            for (const Shape& sh : shapes)
+                for (int mask : {0, ALL, X0 | VAR, XO | DVAR, VEL | F}) {
+                    if (sh.M > 3 && (K != 2 || dyn != hd || (mask != ALL && mask != (X0 | VAR)))) continue;
+                    begin("gpt_rollout_stabilised K=" + std::to_string(K) + (dyn == hd ? " RBF" : " Matern 3/2") + " M=" + std::to_string(sh.M) + " T=" +
+                          std::to_string(sh.T) + " steps per launch=" + std::to_string(sh.per) + " optional=" + std::to_string(mask));
+                    if (sh.per) setenv("GPT_ROLLOUT_STEPS_PER_LAUNCH", std::to_string(sh.per).c_str(), 1);
+                    else unsetenv("GPT_ROLLOUT_STEPS_PER_LAUNCH");
+                    const int per = sh.per ? sh.per : 32;                      // ROLLOUT_STAB_STEPS_PER_LAUNCH
+                    gpt::stub_rollout_launch_count = 0;
+                    Arrays a(sh.M, sh.T);
+                    const int rc = call(K ? st2.data() : nullptr, K, dyn, a, sh.M, sh.T, mask);      // K = 0: stages == NULL
+                    CHECK(stub_live_objects >= held);                        // staging, scratch and events are kept and regrown, never dropped
+                    held = stub_live_objects;
+                    done_held(rc, GPT_OK);
+                    const int64_t chunk = std::max<int64_t>(1, 131072 / (sh.T + 1)), chunks = (sh.M + chunk - 1) / chunk;
+                    CHECK(gpt::stub_rollout_launch_count == chunks * std::max<int64_t>(1, (sh.T + per - 1) / per));
+                    CHECK(a.path.all(0.0) && a.status.all(0) && a.steps.all((int)sh.T));
+                    CHECK(a.vel.all(mask & VEL ? 0.0 : SENT) && a.x.all(mask & XO ? 0.0 : SENT) && a.f.all(mask & F ? 0.0 : SENT));
+                    CHECK(a.var.all(mask & VAR ? 0.0 : SENT) && a.dvar.all(mask & DVAR ? 0.0 : SENT));
+                }
+    }
+    unsetenv("GPT_ROLLOUT_STEPS_PER_LAUNCH");
+    begin("gpt_rollout_stabilised teardown");
+    for (auto& q : h) gpt_destroy(q);
+    gpt_destroy(hd);
+    gpt_destroy(m12);
+    gpt_destroy(m32);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -923,6 +1014,7 @@ int main() {
     pullback_cases();
     chain_cases();
     rollout_cases();
+    rollout_stab_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

@@ -247,6 +247,16 @@ extern "C" int gpt_rollout_policy(const gpt_chain_stage*, int, gpt_handle*, cons
     gpt::set_last_error("gpt_rollout_policy: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_rollout_stabilised_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, int64_t, double,
+                                          double, int, double, double, double*, double*, double*, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_stabilised_dev: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_rollout_stabilised(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, int64_t, double, double,
+                                      int, double, double, double*, double*, double*, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_stabilised: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
                                int*) {
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
@@ -267,6 +277,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 #include "../gpt_svgp_surface.h"
 #include "../gpt_chain.h"
 #include "../gpt_rollout.h"
+#include "../gpt_rollout_stab.h"
 #include <cstdio>
 
 namespace gpt {
@@ -450,6 +461,25 @@ void launch_rollout(hipStream_t, int D_, const RolloutArgs& a) {
         a.status[m] = 0;
     }
     if (t1 < T) { stub_check(a.state); touch_w(a.state, M * D * 8); }
+}
+
+// ---- gpt_rollout_stab.hip -----------------------------------------------------------------------------------------------------
+// k_rollout_stab: what k_rollout reads and writes, and of the dynamics also the packed inverse factor (every tile of its NP, which
+// the kernel's image in LDS bounds); f, var (one double per step) and dvar are written where they are asked for
+void launch_rollout_stab(hipStream_t s, int D_, const RolloutStabArgs& sa) {
+    const RolloutArgs& a = sa.r;
+    if (a.M <= 0) return;
+    stub_check(sa.Wf && sa.NP % PAD_N == 0 && sa.NP >= a.dyn.N && sa.NP <= ROLLOUT_STAB_MAX_N && a.dyn.N >= 1);
+    stub_check(sa.gain >= 0.0 && sa.gain <= 1e300 && sa.std_offset == sa.std_offset);
+    const size_t nb = (size_t)sa.NP / WT;
+    touch_r(sa.Wf, nb * (nb + 1) / 2 * WT_TILE_DOUBLES * 8);
+    const size_t M = (size_t)a.M, D = (size_t)D_, T = (size_t)a.T, t0 = (size_t)a.t_begin, t1 = (size_t)a.t_end;
+    for (size_t m = 0; m < M; ++m) {
+        if (sa.f) touch_w(sa.f + (m * T + t0) * D, (t1 - t0) * D * 8);
+        if (sa.var) touch_w(sa.var + m * T + t0, (t1 - t0) * 8);
+        if (sa.dvar) touch_w(sa.dvar + (m * T + t0) * D, (t1 - t0) * D * 8);
+    }
+    launch_rollout(s, D_, a);                         // the mean rollout's arrays, its checks and its launch count
 }
 
 // ---- gpt_svgp_train.hip, gpt_svgp_surface.hip ---------------------------------------------------------------------------------

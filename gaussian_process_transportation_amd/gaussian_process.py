@@ -480,7 +480,8 @@ class GaussianProcess:
                                             std_offset=np.sqrt(dynamics._noise), outputs=names)
 
     # ------------------------------------------------------------------ whole paths of the transported policy
-    def rollout_chain(self, inner, dynamics, starts, n_steps, affine, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x")):
+    def rollout_chain(self, inner, dynamics, starts, n_steps, affine, dt=1.0, x0=None, rtol=1e-10, max_passes=64, outputs=("vel", "x"),
+                      variance_gain=None):
         """The paths the transported policy of pullback_chain() drives from `starts` (M,D): n_steps explicit Euler steps
         y_{t+1} = y_t + dt * vel(y_t), the loop over the steps on the device in one call (_lib.Handle.rollout_policy) instead of one
         pullback_chain() per step; this model is the LAST map, `inner` the ones before it, `affine` as pullback_chain's.  Step t
@@ -489,22 +490,35 @@ class GaussianProcess:
         at the first step whose inverse does not converge or whose next point is not finite.  Returns a dict: path
         (M,n_steps+1,D) with row 0 the starts, steps_done (M,) the steps whose next point was recorded, status (M,) the
         _lib.INV_* of the last step evaluated, and — `outputs` — vel, x (M,n_steps,D); every row after a trajectory's end is NaN.
-        Only the mean policy is integrated: no variance term."""
+        variance_gain=None integrates the mean policy only.  A number >= 0 takes the variance-stabilised step instead, still in
+        one device call (_lib.Handle.rollout_stabilised): with var and dvar the posterior variance of `dynamics` and its gradient at
+        x_t, vel_t = push(f_t - variance_gain * (sqrt(var_t) - sqrt(noise)) * dvar_t / |dvar_t|), pushed through the maps as f_t
+        is (the reference's plot_traj_evolution with gain 1; dvar / |dvar| is 0 where dvar is exactly 0).  The target-space path
+        is then, to first order in dt, the image of the stabilised source-space path: the variance descended is the dynamics' own
+        at the preimage, not that of a GP refitted on the moved demonstration.  `outputs` may then also name f, var, dvar.  The
+        dynamics needs at most _lib.ROLLOUT_STAB_MAX_N training points and a kernel with derivatives."""
         maps = list(inner) + [self]
         affine = self._check_chain("rollout_chain", maps, dynamics, affine, 1)
-        return self._rollout("rollout_chain", maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs)
+        return self._rollout("rollout_chain", maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs, variance_gain)
 
-    def rollout(self, starts, n_steps, dt=1.0, return_info=False):
+    def rollout(self, starts, n_steps, dt=1.0, return_info=False, variance_gain=None):
         """This model as a dynamics rolling out itself: n_steps explicit Euler steps y_{t+1} = y_t + dt * predict(y_t) from every
         row of `starts` (M,D), the loop over the steps on the device (any of the four kernels: the model is only evaluated).
         Returns path (M,n_steps+1,D), row 0 the starts; with return_info also a dict: vel (M,n_steps,D) the means along the path,
         x (= the path's points), steps_done and status (M,).  A trajectory ends where its next point is not finite; the rows after
-        that are NaN.  Needs n_outputs == n_features <= 3 and float64."""
+        that are NaN.  Needs n_outputs == n_features <= 3 and float64.
+        variance_gain=None: that, untouched.  A number >= 0: the variance-stabilised step of the reference's plot_traj_evolution,
+        y_{t+1} = y_t + dt * (predict(y_t) - variance_gain * std(y_t) * grad_var(y_t) / |grad_var(y_t)|), std as
+        predict(return_std=True) and grad_var as derivative_of_variance (0 / 0 taken as 0), still one device call; the info dict
+        then also holds f (the means), var (M,n_steps) and dvar (M,n_steps,D), and vel is the stabilised velocity.  One step
+        (n_steps=1) from a grid of starts with variance_gain=2 is the field of the reference's plot_vector_field_minvar, in vel.
+        The model then needs at most _lib.ROLLOUT_STAB_MAX_N training points and a kernel with derivatives."""
         self._check_chain("rollout", [], self, [], 0)
-        out = self._rollout("rollout", [], [], self, starts, n_steps, dt, None, 1e-10, 64, ("vel", "x") if return_info else ())
+        names = ("vel", "x") + (("f", "var", "dvar") if variance_gain is not None else ())
+        out = self._rollout("rollout", [], [], self, starts, n_steps, dt, None, 1e-10, 64, names if return_info else (), variance_gain)
         return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]
 
-    def _rollout(self, what, maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs):
+    def _rollout(self, what, maps, affine, dynamics, starts, n_steps, dt, x0, rtol, max_passes, outputs, variance_gain=None):
         starts, x0 = self._check_chain_points(what, starts, x0, rtol, max_passes, "starts")
         if int(n_steps) != n_steps or int(n_steps) < 0:
             raise ValueError(f"{what}(): n_steps must be an integer >= 0, got {n_steps!r}")
@@ -514,8 +528,18 @@ class GaussianProcess:
             raise ValueError(f"{what}(): starts times (n_steps + 1), the rows of the paths, must stay below 2^31")
         primary = lambda g: getattr(g._handle, "primary", g._handle)
         stages = [(primary(g), rot, src, dst, scale, jac) for g, (rot, scale, src, dst, jac) in zip(maps, affine)]
-        return primary(self).rollout_policy(stages, primary(dynamics), starts, int(n_steps), dt=float(dt), x0=x0, rtol=rtol,
-                                            max_passes=max_passes, outputs=outputs)
+        if variance_gain is None:
+            return primary(self).rollout_policy(stages, primary(dynamics), starts, int(n_steps), dt=float(dt), x0=x0, rtol=rtol,
+                                                max_passes=max_passes, outputs=outputs)
+        if not np.isfinite(float(variance_gain)) or float(variance_gain) < 0.0:
+            raise ValueError(f"{what}(): variance_gain must be finite and >= 0, got {variance_gain!r}")
+        dynamics._require_derivatives(what)
+        if len(dynamics.X) > _lib.ROLLOUT_STAB_MAX_N:
+            raise ValueError(f"{what}(): the dynamics has {len(dynamics.X)} training points; the stabilised rollout takes at most "
+                             f"{_lib.ROLLOUT_STAB_MAX_N} (larger models: predict and derivative_of_variance per step)")
+        return primary(self).rollout_stabilised(stages, primary(dynamics), starts, int(n_steps), float(variance_gain),
+                                                std_offset=np.sqrt(dynamics._noise), dt=float(dt), x0=x0, rtol=rtol,
+                                                max_passes=max_passes, outputs=outputs)
 
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):

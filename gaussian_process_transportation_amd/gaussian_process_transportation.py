@@ -84,10 +84,11 @@ class GaussianProcessTransportation:
         passes / residual / det / f per point, solver: rtol, max_passes."""
         return self.method.transported_policy(dynamics, points, x0=x0, return_std=return_std, return_info=return_info, **solver)
 
-    def rollout_policy(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+    def rollout_policy(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, variance_gain=None, **solver):
         """The paths the transported policy drives from `starts` of the target scene, n_steps steps of size dt, integrated on
         the device in one call (an addition: PolicyTransportation.rollout_policy)."""
-        return self.method.rollout_policy(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info, **solver)
+        return self.method.rollout_policy(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info, variance_gain=variance_gain,
+                                          **solver)
 
     def sample_transportation(self):
         """Posterior draws of the moved demonstration, at the positions of the last apply_transportation() (:29-30)."""

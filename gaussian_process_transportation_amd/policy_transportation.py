@@ -160,13 +160,14 @@ class PolicyTransportation:
             res += ({k: v for k, v in out.items() if k != "vel"},)
         return res if len(res) > 1 else res[0]
 
-    def rollout_policy(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+    def rollout_policy(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, variance_gain=None, **solver):
         """The paths transported_policy() drives from `starts` (M,D) of the target scene: n_steps explicit Euler steps
         y += dt * transported_policy(dynamics, y), the loop over the steps on the device in one call
         (TransportChain.rollout with this transport as its only stage).  Returns path (M,n_steps+1,D); with return_info also a
         dict: vel, x, steps_done, status."""
         from .transport_chain import TransportChain
-        return TransportChain([self], verbose=self.verbose).rollout(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info, **solver)
+        return TransportChain([self], verbose=self.verbose).rollout(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info,
+                                                                variance_gain=variance_gain, **solver)
 
     def sample_transportation(self, pos):
         pos_rotated = self.affine_transform.predict(pos)

@@ -85,7 +85,7 @@ class TransportChain:
             res += ({k: v for k, v in out.items() if k != "vel"},)
         return res if len(res) > 1 else res[0]
 
-    def rollout(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+    def rollout(self, dynamics, starts, n_steps, dt=1.0, x0=None, return_info=False, variance_gain=None, **solver):
         """The paths the transported policy drives from `starts` (M,D) of the LAST scene: n_steps explicit Euler steps
         y_{t+1} = y_t + dt * transported_policy(dynamics, y_t), the x of one step the guess of the next (x0: guesses for the
         starts), the loop over the steps on the device in ONE call (GaussianProcess.rollout_chain) — equal, bit for bit, to the
@@ -93,7 +93,10 @@ class TransportChain:
         not zero; negative integrates backwards.  `solver` passes rtol / max_passes on.  Returns path (M,n_steps+1,D), row 0 the
         starts; a trajectory ends at the first step whose inverse does not converge or whose next point is not finite, and its
         rows after that are NaN.  With return_info also a dict: vel, x (M,n_steps,D), steps_done (M,) and status (M,), the
-        _lib.INV_* of the last step evaluated.  The mean policy only: no variance term."""
+        _lib.INV_* of the last step evaluated.  variance_gain=None: the mean policy only, as described.  A number >= 0: the
+        variance-stabilised step (GaussianProcess.rollout_chain), vel_t = push(f_t - variance_gain * std_t * grad_var_t /
+        |grad_var_t|) with the dynamics' own standard deviation and variance gradient at the preimage x_t, still one device call;
+        the info dict then also holds f, var (M,n_steps) and dvar."""
         unknown = set(solver) - {"rtol", "max_passes"}
         if unknown:
             raise TypeError(f"TransportChain: unknown solver arguments {sorted(unknown)}")
@@ -104,7 +107,10 @@ class TransportChain:
         affine = [(m.affine_transform.rotation_matrix, m.affine_transform.scale, m.affine_transform.S_centroid,
                    m.affine_transform.T_centroid, m.affine_transform.rotation_matrix) for m in self.methods]
         maps = [m.delta_map for m in self.methods]
-        out = rollout(maps[:-1], dynamics, starts, n_steps, affine, dt=dt, x0=x0, outputs=("vel", "x") if return_info else (), **solver)
+        names = ("vel", "x") + (("f", "var", "dvar") if variance_gain is not None else ())
+        if variance_gain is not None:
+            solver = dict(solver, variance_gain=variance_gain)
+        out = rollout(maps[:-1], dynamics, starts, n_steps, affine, dt=dt, x0=x0, outputs=names if return_info else (), **solver)
         if self.verbose:
             status, done = out["status"], out["steps_done"]
             counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.INV_STATUS_NAMES))

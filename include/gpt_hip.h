@@ -507,6 +507,39 @@ int gpt_rollout_policy(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, 
                        int64_t n_steps, double dt, double rtol, int max_passes, double* path, double* vel, double* x, int* steps_done,
                        int* status);
 
+/* (new) Whole paths of the VARIANCE-STABILISED policy: gpt_rollout_policy with the stabiliser of the reference's plot_traj_evolution
+ * (pos += mean - std * grad_var / |grad_var|) inside every step, still one call.  Arguments, end rule, NaN filling, steps_done,
+ * status, the guesses, negative dt, launches and chunks as gpt_rollout_policy; in addition gain (finite, >= 0) and std_offset (the
+ * caller passes sqrt(noise_level), the reference's predict(return_std) quirk, as gpt_pullback_chain's).  Per trajectory and step,
+ * x_t the source-space preimage of y_t (K = 0: x_t = y_t), W = L^-1 the inverse factor of the dynamics, c its prior variance:
+ *   f_t     = the mean of h_dyn at x_t
+ *   var_t   = max(0, c + noise - |W k*(x_t)|^2),   g_t,d = -2 (W d_d k*(x_t)) . (W k*(x_t))   (gpt_predict_all's var and dvar)
+ *   s_t     = sqrt(var_t) - std_offset
+ *   ghat_t  = g_t / |g_t|, the norm taken after scaling by max_d |g_t,d| (a tiny gradient does not underflow to a zero norm);
+ *             ghat_t = 0 where every g_t,d is exactly 0 (k* has underflowed far from the data; the reference divides 0 by 0 there)
+ *   fs_t,d  = f_t,d - ((gain s_t) ghat_t,d), each product and the difference rounded on its own
+ *   vel_t   = fs_t pushed through the maps exactly as gpt_pullback_chain pushes f (K = 0: vel_t = fs_t)
+ *   y_{t+1} = y_t + (dt vel_t)
+ * A g that is not finite makes y_{t+1} not finite, which ends the trajectory.  For K >= 1 the target-space path is, to first order
+ * in dt, the image of the stabilised source-space path: the variance descended is the dynamics' own at the preimage, not that of a
+ * GP refitted on the moved demonstration.  gain = 0 gives the path, vel, x, steps_done and status of gpt_rollout_policy, bit for bit.
+ * Further outputs, each may be NULL, NaN after a trajectory's end: f (M,T,D), var (M,T), dvar (M,T,D) = g.
+ * One workgroup of four waves owns four trajectories and shares the product with W on the matrix cores (k_rollout_stab); a launch
+ * advances every live trajectory by at most 32 steps (GPT_ROLLOUT_STEPS_PER_LAUNCH overrides).  A trajectory's values do not depend
+ * on M, on the other trajectories, on their order or on where the launches are cut, bit for bit.
+ * Refusals beyond gpt_rollout_policy's, GPT_E_ARG: a dynamics of more than 1024 training points (the kernel columns of a step stay
+ * in LDS); a Matern 1/2 dynamics, or a Matern 3/2 / 5/2 one without gpt_set_matern_derivatives; gain negative, NaN or infinite;
+ * std_offset NaN or infinite.  (Multi-task and fp32 models are refused as by gpt_rollout_policy.)
+ * Device memory, asynchronous, streams and resources as gpt_rollout_policy_dev (the two calls share them). */
+int gpt_rollout_stabilised_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0_dev, const double* x0_dev, int64_t M,
+                               int64_t n_steps, double dt, double rtol, int max_passes, double gain, double std_offset, double* path_dev,
+                               double* vel_dev, double* x_dev, double* f_dev, double* var_dev, double* dvar_dev, int* steps_done_dev,
+                               int* status_dev);
+/* (new) The same with every data pointer in host memory, checked and chunked as gpt_rollout_policy. */
+int gpt_rollout_stabilised(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0, const double* x0, int64_t M,
+                           int64_t n_steps, double dt, double rtol, int max_passes, double gain, double std_offset, double* path,
+                           double* vel, double* x, double* f, double* var, double* dvar, int* steps_done, int* status);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);

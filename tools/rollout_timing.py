@@ -9,7 +9,12 @@ Warm-up, then the median of --reps runs, the two paths interleaved.  Per line: t
 the two paths agree bit for bit, and the one condition: the device call is not slower than the loop.  For the large shape also
 the longest single launch: the wall time of a call whose T is one launch's worth of steps, copies included, for several values of
 GPT_ROLLOUT_STEPS_PER_LAUNCH — the default (64) is chosen so that this stays well below 50 ms.
-usage: python tools/rollout_timing.py [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
+--stabilised times the variance-stabilised rollout (variance_gain = 1: gpt_rollout_stabilised) instead, against the host loop of
+the parent commit: per step predict(return_std=True) and derivative_of_variance of the dynamics (examples/dynamics_rollout_3d.py
+--host) and, with maps, one transported_policy call before them and the push of the stabilised mean through its per-stage A in
+numpy.  Shapes then: 3d (the demo dynamics, N = 460, M = 1, T = 1000), 2d (its 10 x 10 grid, T = 200) and large with N_dyn = 1024,
+the largest the call admits, where the longest launch is measured for 16, 32 and 64 steps (the default is 32).
+usage: python tools/rollout_timing.py [--stabilised] [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
 import argparse
 import os
 import sys
@@ -42,18 +47,123 @@ def cases(shape):
     return chain, dyn, {"M = 1024, T = 64": (np.ascontiguousarray(y[:1024]), None, 64, 0.05)}
 
 
+def stab_steps_per_launch():
+    """As the call reads it: GPT_ROLLOUT_STEPS_PER_LAUNCH, else ROLLOUT_STAB_STEPS_PER_LAUNCH of csrc/gpt_rollout_stab.h."""
+    v = os.environ.get("GPT_ROLLOUT_STEPS_PER_LAUNCH", "")
+    return int(v) if v.isdigit() and int(v) >= 1 else 32
+
+
+def stab_cases(shape):
+    """(chain or None, dynamics, label, starts, guesses, T, dt) of the stabilised rollout."""
+    from gaussian_process_transportation_amd import GaussianProcess
+    from chain_timing import kernel
+    if shape == "3d":
+        X = np.load(os.path.join(ROOT, "tests", "golden", "surface_3d.npz"))["demo"]
+        delta = np.zeros_like(X)
+        delta[:-1] = X[1:] - X[:-1]
+        dyn = GaussianProcess(kernel=kernel(np.sqrt(0.1), [1.0, 1.0, 1.0], 0.01, 1.5), optimizer=None, verbose=False, matern_derivatives=True).fit(X, delta)
+        start = np.random.default_rng(0).uniform(X.min(axis=0), X.max(axis=0)).reshape(1, 3)
+        return None, dyn, "M = 1, T = 1000", start, None, 1000, 1.0
+    if shape == "2d":
+        chain, dyn, sets = cases("2d")
+        y0, x0, T, dt = sets["M = 100 (10 x 10 grid), T = 200"]
+        return chain, dyn, "M = 100 (10 x 10 grid), T = 200", y0, x0, T, dt
+    trs, _, sets = problem("large")
+    demo = np.random.default_rng(2).uniform(0.1, 0.9, (1024, 3))
+    dyn = GaussianProcess(kernel=kernel(0.05, [0.3, 0.3, 0.3], 1e-4, 1.5), optimizer=None, verbose=False, matern_derivatives=True).fit(demo, 0.1 * np.cos(3 * demo))
+    return TransportChain(trs, verbose=False), dyn, "M = 1024, T = 64", np.ascontiguousarray(sets["M = 100000"][:1024]), None, 64, 0.05
+
+
+def stabilised_main(a, say):
+    from tests import rollout_stab_restatement as RS
+    for shape in a.shapes:
+        chain, dyn, label, y0, x0, T, dt = stab_cases(shape)
+        off, gain = np.sqrt(dyn._noise), 1.0
+        R = [] if chain is None else [np.asarray(m.affine_transform.rotation_matrix) for m in chain.methods]
+
+        def device():
+            t0 = time.perf_counter()
+            if chain is None:
+                path, info = dyn.rollout(y0, T, dt=dt, return_info=True, variance_gain=gain)
+            else:
+                path, info = chain.rollout(dyn, y0, T, dt=dt, x0=x0, return_info=True, variance_gain=gain)
+            return time.perf_counter() - t0, dict(info, path=path)
+
+        def step(y, guess):
+            if chain is None:
+                x, f, status, A = y.copy(), None, np.zeros(len(y), dtype=np.int32), None
+            else:
+                _, info = chain.transported_policy(dyn, y, x0=guess, return_info=True)
+                x, f, status, A = info["x"], info["f"], info["status"], info["stage_A"]
+            mean, std = dyn.predict(x, return_std=True)
+            grad = dyn.derivative_of_variance(x).T
+            v = (mean if f is None else f) - gain * std.reshape(len(x), -1)[:, :1] * RS.unit_gradient(grad)
+            for k in range(len(R)):                                    # B_k = A_k R_jac,k, stage 0 first
+                v = np.einsum("mij,mj->mi", A[k], v @ R[k].T)
+            return x, v, status
+
+        def loop():
+            t0 = time.perf_counter()
+            out = RO.rollout(step, y0, T, dt=dt, x0=x0)
+            return time.perf_counter() - t0, out
+        n_map = "none" if chain is None else " + ".join(str(len(m.delta_map.X)) for m in chain.methods)
+        say(f"== stabilised {shape}: N_map = {n_map}, N_dyn = {len(dyn.X)}, D = {y0.shape[1]}, {label}, dt = {dt}, gain = {gain}; "
+            f"median of {a.reps} (min .. max), ms")
+        times, res = {"device": [], "loop": []}, {}
+        for fn in (device, loop):
+            fn()
+        for _ in range(a.reps):
+            for name, fn in (("loop", loop), ("device", device)):
+                t, res[name] = fn()
+                times[name].append(t)
+        med = {n: 1e3 * float(np.median(t)) for n, t in times.items()}
+        done, done_l = res["device"]["steps_done"], res["loop"]["steps_done"]
+        both = np.minimum(done, done_l)
+        gap = max((float(np.max(np.abs(res["device"]["path"][m, :b + 1] - res["loop"]["path"][m, :b + 1]))) for m, b in enumerate(both)), default=0.0)
+        say(f"   host loop, predict(return_std) + derivative_of_variance{'' if chain is None else ' + transported_policy'} per step : {med['loop']:10.3f}  "
+            f"({1e3 * min(times['loop']):.3f} .. {1e3 * max(times['loop']):.3f})")
+        say(f"   one call (gpt_rollout_stabilised), {-(-T // stab_steps_per_launch())} launch(es) : {med['device']:10.3f}  ({1e3 * min(times['device']):.3f} .. "
+            f"{1e3 * max(times['device']):.3f})   -> {med['loop'] / med['device']:.1f} x; not slower than the loop: "
+            f"{'yes' if med['device'] <= med['loop'] else 'NO'}; {1e3 * med['device'] / max(1, T):.1f} us per step of the call; largest gap between the two "
+            f"paths over their common steps {gap:.3e}; steps done: min {int(done.min())}, median {int(np.median(done))}, max {int(done.max())} "
+            f"(loop: min {int(done_l.min())}, max {int(done_l.max())})")
+        if shape != "large":
+            continue
+        say(f"== stabilised {shape}: the longest launch, M = 1024, N_dyn = {len(dyn.X)}: wall time of a call of ONE launch (T = the steps of a launch), "
+            f"copies included; median of {a.reps}, ms")
+        for per in (16, 32, 64):
+            os.environ["GPT_ROLLOUT_STEPS_PER_LAUNCH"] = str(per)          # (read per call)
+            chain.rollout(dyn, y0, per, dt=dt, variance_gain=gain)
+            ts = []
+            for _ in range(a.reps):
+                t0 = time.perf_counter()
+                path, info = chain.rollout(dyn, y0, per, dt=dt, return_info=True, variance_gain=gain)
+                ts.append(time.perf_counter() - t0)
+            say(f"   {per:4d} steps in one launch : {1e3 * float(np.median(ts)):10.3f}  ({1e3 * min(ts):.3f} .. {1e3 * max(ts):.3f}); "
+                f"trajectories complete: {int(np.sum(info['steps_done'] == per))} of {len(y0)}")
+        del os.environ["GPT_ROLLOUT_STEPS_PER_LAUNCH"]
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", choices=("2d", "large"), default=["2d", "large"])
+    ap.add_argument("--shapes", nargs="+", choices=("2d", "large", "3d"), default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--stabilised", action="store_true", help="the variance-stabilised rollout against its host loop")
     a = ap.parse_args()
+    if a.shapes is None:
+        a.shapes = ["3d", "2d", "large"] if a.stabilised else ["2d", "large"]
+    if "3d" in a.shapes and not a.stabilised:
+        ap.error("the 3d shape is the stabilised rollout's")
     _lib.require_gpu()
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
+    if a.stabilised:
+        stabilised_main(a, say)
+        a.shapes = []
     names = ("path", "vel", "x", "steps_done", "status")
     for shape in a.shapes:
         chain, dyn, sets = cases(shape)
