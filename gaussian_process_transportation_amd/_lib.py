@@ -105,6 +105,7 @@ SIGNATURES = {
     "gpt_debug_fit_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_i64), C.POINTER(_i64)]),
     "gpt_debug_dgemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64, _dp, _i64, _dp, _i64,
                                   C.c_int, C.POINTER(C.c_int)]),
+    "gpt_debug_set_inverse_factor": (C.c_int, [_vp, _dp, _i64]),
     "gpt_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "gpt_fit_timings": (C.c_int, [_vp, _dp, C.c_int]),
     "gpt_set_profiling": (C.c_int, [_vp, C.c_int]),
@@ -692,6 +693,13 @@ class Handle:
         W = np.empty((N, N))
         check(self.lib.gpt_export_inverse_factor(self._h, dptr(W)), "gpt_export_inverse_factor")
         return W
+
+    def debug_set_inverse_factor(self, W):
+        """Replace the inverse factor of this handle's own fit by the dense (N, N) float64 array W (gpt_debug_set_inverse_factor;
+        tests only): the variance kernels then work on W's lower triangle, LML calls refuse until the next fit."""
+        if not (isinstance(W, np.ndarray) and W.dtype == np.float64 and W.ndim == 2 and W.shape[0] == W.shape[1] and W.flags.c_contiguous):
+            raise ValueError("debug_set_inverse_factor: W must be a square C-contiguous float64 array")
+        check(self.lib.gpt_debug_set_inverse_factor(self._h, dptr(W), W.shape[0]), "gpt_debug_set_inverse_factor")
 
     def lml(self) -> float:
         v = C.c_double()

@@ -1043,6 +1043,29 @@ int gpt_predict_timings(gpt_handle* h, double* ms_out) {
 
 int gpt_debug_var_path(gpt_handle* h) { return h ? h->i8.last_path : -1; }
 
+// Test hook: W (n x n, dense, row-major, host) takes the place of the inverse factor of the committed model.  dW, the packed
+// image Wf and the residue planes follow it; L in dK does not, so the calls that need both factors refuse from here on.
+int gpt_debug_set_inverse_factor(gpt_handle* h, const double* W, int64_t n) {
+    const char* who = "gpt_debug_set_inverse_factor";
+    if (!h || !W) return fail(GPT_E_ARG, std::string(who) + ": NULL argument");
+    if (!h->committed) return fail(GPT_E_STATE, std::string(who) + ": model is not fitted");
+    if (h->p.ntask != 1) return fail(GPT_E_STATE, std::string(who) + ": single-task models only");
+    if (!h->have_W || !h->ws->dW) return fail(GPT_E_STATE, std::string(who) + ": needs the handle that ran gpt_fit for this model");
+    if (n != h->p.N) return fail(GPT_E_ARG, std::string(who) + ": n differs from the model's N");
+    if (int rc = set_device(h)) return rc;
+    const int64_t N = h->p.N, NP = h->p.NP;
+    hipStream_t s = h->stream;
+    CALLCHK(hipStreamSynchronize(s));                  // launches that still read dW, Wf or the planes
+    CALLCHK(hipMemcpy2D(h->ws->dW, (size_t)NP * sizeof(double), W, (size_t)N * sizeof(double), (size_t)N * sizeof(double), (size_t)N,
+                        hipMemcpyHostToDevice));
+    launch_pack_w(s, h->ws->dW, (int)N, (int)NP, h->dWf(), h->lay.dtype, 0, 1.0);
+    CALLCHK(hipGetLastError());
+    h->have_L = false;                                 // dK holds the factor of another matrix now
+    h->i8.valid = false;
+    if (var_i8_wanted(h->p, -1)) return ensure_i8_image(h);
+    return GPT_OK;
+}
+
 int gpt_fit_timings(gpt_handle* h, double* ms_out, int n) {
     if (!h || !ms_out) return fail(GPT_E_ARG, "gpt_fit_timings: NULL argument");
     for (int i = 0; i < n && i < 6; ++i) ms_out[i] = h->fit_ms[i];

@@ -639,6 +639,16 @@ int gpt_debug_fit_plan(int n_padded, int form, int panel, int streams, int64_t* 
 int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, double alpha, const double* A, int64_t lda,
                     const double* B, int64_t ldb, double* C, int64_t ldc, int lower_only, int* tile_edge);
 
+/* Test hook (needs a GPU): W (n x n, dense, row-major, host memory) replaces the inverse factor of a committed single-task model
+ * on the handle that ran its own gpt_fit (fp64 or fp32 model), so that the variance kernels can be given operands whose answer
+ * is known exactly.  W goes to the fit workspace, is packed into the model's image with the model's element type, and the residue
+ * (int8) planes are rebuilt under the rule of gpt_factor_commit; the upper triangle of W is ignored, as the fit's own packing
+ * ignores it.  gpt_export_inverse_factor returns W afterwards - its upper triangle as the caller passed it, which no kernel reads
+ * and the next gpt_fit overwrites: compare lower triangles; gpt_export(L), gpt_lml and gpt_lml_gradient refuse until the next
+ * gpt_fit (L is the factor of another matrix).  GPT_E_ARG: NULL argument, n != N; GPT_E_STATE: no committed model, a multi-task
+ * model, a replica (gpt_factor_commit / gpt_factor_copy) that holds no factor of its own. */
+int gpt_debug_set_inverse_factor(gpt_handle* h, const double* W, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

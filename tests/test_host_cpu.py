@@ -483,6 +483,78 @@ def test_host_orchestration_under_sanitizers():
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
 
 
+SET_INVERSE_FACTOR_DRIVER = r"""
+import ctypes
+import numpy as np
+from gaussian_process_transportation_amd import _lib
+
+lib = _lib.load()
+rng = np.random.default_rng(3)
+N, D = 70, 3
+X, Y = rng.uniform(0, 1, (N, D)), rng.standard_normal((N, 2))
+W = np.tril(rng.integers(-8, 9, (N, N)).astype(np.float64))
+
+
+def refused(call, kind):
+    try:
+        call()
+    except kind:
+        return
+    raise AssertionError("an invalid call went through")
+
+
+h = _lib.Handle(0)
+refused(lambda: h.debug_set_inverse_factor(W), _lib.GptError)                     # no committed model
+for dtype in (_lib.GPT_F64, _lib.GPT_F32):
+    h.set_dtype(dtype)
+    h.fit(X, Y, np.full(D, 0.3), 1.0, 1e-2, 1e-10)
+    assert lib.gpt_debug_set_inverse_factor(None, _lib.dptr(W), N) == _lib.GPT_E_ARG
+    assert lib.gpt_debug_set_inverse_factor(h._h, None, N) == _lib.GPT_E_ARG
+    refused(lambda: h.debug_set_inverse_factor(W[:N - 1, :N - 1].copy()), ValueError)      # n != N
+    refused(lambda: h.debug_set_inverse_factor(np.zeros((N + 1, N + 1))), ValueError)
+    refused(lambda: h.debug_set_inverse_factor(W.astype(np.float32)), ValueError)
+    h.lml()
+    h.debug_set_inverse_factor(W)
+    assert np.array_equal(h.export_inverse_factor(), W)
+    refused(h.lml, _lib.GptError)                                                 # L is the factor of another matrix
+    refused(lambda: h.lml_gradient(D), _lib.GptError)
+    refused(lambda: h.export(want_alpha=False), _lib.GptError)
+    h.predict_all(rng.uniform(0, 1, (200, D)).astype(np.float32 if dtype == _lib.GPT_F32 else np.float64), var=True)
+    h.fit(X, Y, np.full(D, 0.3), 1.0, 1e-2, 1e-10)
+    h.lml()                                                                       # a new fit brings both factors back
+h.set_dtype(_lib.GPT_F64)
+h.fit(X, Y, np.full(D, 0.3), 1.0, 1e-2, 1e-10)
+rep = _lib.Handle(0)
+rep.factor_copy_from(h)
+refused(lambda: rep.debug_set_inverse_factor(W), _lib.GptError)                   # a replica holds no factor of its own
+h.fit_svgp(X, rng.standard_normal((2, N)), 1e-2 * np.eye(N) * np.ones((2, 1, 1)), np.full(D, 0.3), np.ones(2))
+refused(lambda: h.debug_set_inverse_factor(W), _lib.GptError)                     # multi-task model
+h.lml_objective(X, Y, np.full(D, 0.3), 1.0, 1e-2, 1e-10)
+refused(lambda: h.debug_set_inverse_factor(W), _lib.GptError)                     # factors, but no committed model
+h.close(); rep.close()
+print("SET_INVERSE_FACTOR_OK")
+"""
+
+
+def test_set_inverse_factor_hook_refusals_on_the_host_build(tmp_path):
+    """gpt_debug_set_inverse_factor on the host build of the handle API (g++, the inert HIP runtime and kernel stand-ins of
+    csrc/host_stub/, no sanitizer, a process of its own): every refusal comes before the first HIP call, the injected factor
+    comes back from gpt_export_inverse_factor, and the LML calls refuse until the next fit."""
+    import shutil
+    import subprocess
+    import sys
+    csrc = os.path.join(ROOT, "gaussian_process_transportation_amd", "csrc")
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    so = str(tmp_path / "libgpt_host_plain.so")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wno-subobject-linkage", "-I" + os.path.join(csrc, "host_stub"), "-DGPT_STUB_ENTRY_POINTS",
+                    "-fPIC", "-shared", "-x", "c++", os.path.join(csrc, "gpt_api.hip"), os.path.join(csrc, "gpt_transport_host.hip"),
+                    os.path.join(csrc, "host_stub", "stub_launchers.cpp"), "-o", so], check=True, capture_output=True)
+    env = dict(os.environ, GPT_HIP_LIB=so, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, "-c", SET_INVERSE_FACTOR_DRIVER], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "SET_INVERSE_FACTOR_OK" in r.stdout, (r.stdout[-1500:], r.stderr[-4000:])
+
+
 def test_hyperparameter_search_driver_sequential_and_concurrent(monkeypatch):
     """hyperopt.optimize_hyperparameters with the objective served by the CPU oracle instead of the GPU handle (a stand-in
     for `_lib.Handle`): the driver must (1) reproduce scikit-learn's own fit — same L-BFGS-B protocol, same restart

@@ -10,6 +10,7 @@ import pytest
 from scipy.linalg import solve_triangular
 
 from oracle import gp_oracle as orc
+from tests import var_int8_bound as vb
 from tests import var_int8_restatement as r8
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -170,3 +171,41 @@ def test_work_split_covers_every_pair_once(plan_program, ncols, nbi, P):
             cost[wg] = cost.get(wg, 0) + ib + 4
         mean = sum(cost.values()) / len(cost)
         assert max(cost.values()) <= 2 * mean + nbi + 4
+
+
+# ---- the models of test_var_int8_gpu.py::test_other_shapes_kernels_and_scales: the quantisation bound, and the size of the bound the
+# device is held to (tests/var_int8_bound.py has both derivations)
+def cpu_model(pr):
+    L, _ = orc.gpr_fit(pr["X"], pr["Y"], pr["c"], pr["ls"], pr["noise"], pr["jitter"], kind=pr["kind"])
+    W = solve_triangular(L, np.eye(pr["N"]), lower=True, check_finite=False)
+    Kst = orc.kernel_cross(pr["Xq"], pr["X"], pr["c"], pr["ls"], kind=pr["kind"]).T.copy()
+    return W, Kst
+
+
+@pytest.mark.parametrize("case", vb.CASES, ids=[c[0] for c in vb.CASES])
+def test_restatement_meets_the_quantisation_bound_on_every_model(case):
+    pr = vb.case_problem(case)
+    W, Kst = cpu_model(pr)
+    V = r8.product(W, Kst, pr["c"], pr["NP"])
+    Wl, Kl = W.astype(np.longdouble), Kst.astype(np.longdouble)
+    ref = Wl @ Kl
+    # the reference's own error: N roundings of 2^-64 on sums of |W| |k|
+    slack = (pr["N"] * 2.0 ** -63 * (np.abs(Wl) @ np.abs(Kl))).astype(np.float64) + vb.gamma(26) * np.abs(V)
+    err = np.abs((V.astype(np.longdouble) - ref).astype(np.float64))
+    bound = vb.quantisation_bound(W, Kst, pr["c"], pr["NP"]) + slack
+    print(f"{pr['name']}: worst |dV| / bound {np.max(err / bound):.3f}, the bound is at most {bound.max():.2e} on |V| <= {np.abs(V).max():.2e}")
+    assert np.all(err <= bound)
+    dev = vb.device_bound(W, Kst, vb.kernel_rel_error(pr["X"], pr["Xq"], pr["ls"], pr["c"], pr["kind"]), pr["c"], pr["noise"], pr["NP"])
+    print(f"{pr['name']}: device-against-restatement bound at most {dev.max():.2e} = {dev.max() / pr['c']:.2e} c")
+    assert dev.max() <= 1e-10 * pr["c"]            # the bound says something: far below the 1e-5 of the oracle comparisons
+
+
+@pytest.mark.parametrize("kind", ["rbf", "matern52"])
+def test_derived_device_bound_is_below_the_fixed_tolerance_of_the_first_shape(kind):
+    """N = 1300, c = 0.1, isotropic 0.1: test_var_int8_gpu.py holds this shape to 1e-12; the derived bound must be tighter"""
+    pr = vb.case_problem(("first", 1300, 3, kind, (0.1, 0.1, 0.1), 0.1))
+    pr["noise"], pr["jitter"] = 1e-4, 1e-10
+    W, Kst = cpu_model(pr)
+    dev = vb.device_bound(W, Kst, vb.kernel_rel_error(pr["X"], pr["Xq"], pr["ls"], pr["c"], kind), pr["c"], pr["noise"], pr["NP"])
+    print(f"N = 1300 {kind}: derived bound at most {dev.max():.2e}")
+    assert dev.max() < 1e-12

@@ -2,12 +2,14 @@
 (tests/var_int8_restatement.py, 1e-12 absolute), against the oracle (RTOL), and bit-equal between any two ways of running
 the same queries.  Model: N = 1300 (padded to 1536: three i-blocks, rows off the tile edge); column blocks have 128 columns and
 the device has one workgroup per CU, so 33 000 queries are more than 256 blocks plus a remainder (whole rounds and a split tail)
-on a 256-CU device."""
+on a 256-CU device.  Further down: N = 512 and 1024, D = 1 and 2, Matern 1/2 and 3/2, anisotropic length-scales and prior variances
+from 1e-6 to 3e5, each inside a bound derived elementwise from the model (tests/var_int8_bound.py), which the first shape meets too."""
 import numpy as np
 import pytest
 from scipy.linalg import solve_triangular
 
 from oracle import gp_oracle as orc
+from tests import var_int8_bound as vb
 from tests import var_int8_restatement as r8
 
 pytestmark = pytest.mark.gpu
@@ -175,3 +177,43 @@ def test_wide_models_fp32_models_and_derivative_launches_stay_on_k_var(forced):
     h.predict_all(Xq.astype(np.float32), var=True)
     assert h.var_path() == 0                 # fp32 model
     h.close()
+
+
+# ---- beyond the one shape: other padded sizes, dimensions, kernels, length-scales and prior variances, each against the restatement
+# fed the handle's own W and the oracle's k*, inside the bound DERIVED elementwise from W, k*, e_i, f and p (tests/var_int8_bound.py
+# has the derivation; a fixed 1e-12 was measured at c = 0.1 only)
+def derived_check(h, pr, Xq, W, what):
+    Kst = orc.kernel_cross(Xq, pr["X"], pr["c"], pr["ls"], kind=pr["kind"]).T.copy()
+    ref = r8.variance(W, Kst, pr["c"], pr["noise"], pr["NP"])
+    bound = vb.device_bound(W, Kst, vb.kernel_rel_error(pr["X"], Xq, pr["ls"], pr["c"], pr["kind"]), pr["c"], pr["noise"], pr["NP"])
+    worst = 0.0
+    for M in [m for m in vb.BATCHES if m <= Xq.shape[0]]:
+        v = var_i8(h, Xq[:M])
+        err = np.abs(v - ref[:M])
+        worst = max(worst, float(np.max(err / bound[:M])))
+        assert np.all(err <= bound[:M]), f"{what}, M = {M}: |var - restatement| up to {np.max(err / bound[:M]):.3g} of the derived bound"
+    print(f"{what}: worst error / bound {worst:.3f}; the bound is at most {bound.max():.2e} ({bound.max() / pr['c']:.2e} c)")
+    return bound
+
+
+@pytest.mark.parametrize("case", vb.CASES, ids=[c[0] for c in vb.CASES])
+def test_other_shapes_kernels_and_scales(case, forced):
+    from gaussian_process_transportation_amd import _lib
+    pr = vb.case_problem(case)
+    h = _lib.Handle(0)
+    h.fit(pr["X"], pr["Y"], pr["ls"], pr["c"], pr["noise"], pr["jitter"], kernel_type=vb.KINDS.index(pr["kind"]))
+    assert h.info()[3] == pr["NP"]
+    W = h.export_inverse_factor()
+    derived_check(h, pr, pr["Xq"], W, pr["name"])
+    h.close()
+
+
+@pytest.mark.parametrize("kind", [0, 3])
+def test_first_shape_meets_the_derived_bound_too(problem, forced, kind):
+    """N = 1300 (the cases above that hold 1e-12): the derived bound holds and is the tighter one"""
+    X, Y, Xq = problem
+    pr = dict(X=X, NP=NP, c=C0, ls=LS, noise=NOISE, kind=vb.KINDS[kind])
+    h = fit(X, Y, kind=kind)
+    bound = derived_check(h, pr, Xq[:300], h.export_inverse_factor(), f"N = {N} {vb.KINDS[kind]}")
+    h.close()
+    assert bound.max() < ATOL8
