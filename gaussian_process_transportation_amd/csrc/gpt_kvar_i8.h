@@ -16,7 +16,8 @@
 //     image in fragment order, [modulus][step][column tile 0..8)[lane] x 16 B, and staged from there through a double-buffered
 //     LDS chunk of one 512-k tile (64 KiB), one barrier per tile; the next chunk is copied piecewise between the MFMA steps.
 //   * diagonal tile: row group g has nothing beyond step g; a wave runs an even number of steps there, (g + 2) & ~1 (the A ring
-//     below is two deep and indexed by step parity), row groups paired (0,7)(1,6)(2,5)(3,4) on the SIMDs as in k_var: 10 of 16 steps.
+//     below is four deep, indexed by step & 3, and turned back by two slots behind a sweep that ran 2 or 6 of them), row groups
+//     paired (0,7)(1,6)(2,5)(3,4) on the SIMDs as in k_var: 10 of 16 steps.
 #pragma once
 #include "gpt_common.h"
 #include "gpt_dispatch.h"
@@ -33,6 +34,18 @@ constexpr size_t I8_B_STEP = (size_t)8 * 64;                             // v4i 
 constexpr size_t I8_CHUNK = I8_TILE_STEPS * I8_B_STEP;                   // v4i per LDS chunk: 4096 = 64 KiB
 constexpr size_t I8_LDS_BYTES = 2 * I8_CHUNK * sizeof(v4i);              // 128 KiB
 constexpr size_t I8_PARK_WORDS = var_i8_park_bytes() / 4;                // dwords of a workgroup's parking buffer
+
+// Timing-only ablation builds (make ablate-i8, tools/gpu_ablate_i8.sh; their outputs are wrong on purpose): 1 A fragments always from
+// the sweep's first tile, 2 B chunks always from the image's first chunk, 3 both, 4 no generation, 5 no reduce, park or
+// reconstruction, 6 = 3 with the LDS reads of the B fragments hoisted out of the steps as well (MFMAs only).
+#ifndef GPT_ABL_I8
+#define GPT_ABL_I8 0
+#endif
+constexpr bool I8_ABL_A = GPT_ABL_I8 == 1 || GPT_ABL_I8 == 3 || GPT_ABL_I8 == 6;
+constexpr bool I8_ABL_B = GPT_ABL_I8 == 2 || GPT_ABL_I8 == 3 || GPT_ABL_I8 == 6;
+constexpr bool I8_ABL_NOGEN = GPT_ABL_I8 == 4;
+constexpr bool I8_ABL_NORED = GPT_ABL_I8 == 5;
+constexpr bool I8_ABL_NOLDS = GPT_ABL_I8 == 6;
 
 // ---- constants of the reconstruction, built at compile time ------------------------------------------------------------------
 struct I8Tab {
@@ -199,7 +212,9 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
     v4i* const bim = a.bimg + (size_t)blockIdx.x * ((size_t)I8_NMOD * nst * I8_B_STEP);
     unsigned* const pk = a.park + (size_t)blockIdx.x * I8_PARK_WORDS + tid;
     const size_t a_plane = (size_t)a.ntiles * I8_TILE_STEPS * I8_A_STEP;        // v4i per A plane
-    const v4i* const a_lane = a.planes + (size_t)g * 256 + lane;
+    // operand streams are addressed as a wave-uniform base (scalar registers) plus a 32-bit lane offset: no 64-bit pointer per lane
+    const v4i* const a_group = a.planes + (size_t)g * 256;
+    const unsigned ulane = lane, utid = tid;
     constexpr double RS2 = 0.70710678118654752440;
     const double lnc = p.lnc;
     const int64_t n_rounds = pl.rnd_end - pl.rnd_begin;
@@ -228,7 +243,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
 #pragma unroll
             for (int d = 0; d < 3; ++d) q[d] = qp[d < D ? d : 0] * ((d < D) ? p.inv_ls[d] * 0.70710678118654752440 : 0.0);
 #pragma unroll 1
-            for (int s = 0; s < I8_TILE_STEPS * ib_hi; ++s) {
+            for (int s = 0; s < (I8_ABL_NOGEN ? 0 : I8_TILE_STEPS * ib_hi); ++s) {
                 const double* xp = a.Xs + (size_t)(I8_KSTEP * s + 16 * lk) * 4;
                 double x[16];
 #pragma unroll
@@ -250,27 +265,30 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
             const int nmine = (g + 2) & ~1;                             // steps of the diagonal tile this wave runs (even)
             const int lim = I8_TILE_STEPS * ib + nmine;                 // steps of a sweep this wave runs
             const size_t tile0 = (size_t)ib * (ib + 1) / 2;
-            // A fragments of step S of modulus j's sweep; past the wave's last step: the next modulus' first steps
+            // A fragments of step S < lim + 4 of modulus j's sweep; past the wave's last step: the first steps of the moduli that follow
             auto a_ptr = [&](int j, int S) -> const v4i* {
                 if (S >= lim) { S -= lim; ++j; }
+                if (S >= lim) { S -= lim; ++j; }                        // (lim = 2: steps lim + 2, lim + 3 belong to the modulus after the next)
                 if (j >= I8_NMOD) { j = I8_NMOD - 1; S = lim - 1; }     // (past the last sweep: a redundant load, in bounds)
-                return a_lane + (size_t)j * a_plane + (tile0 * I8_TILE_STEPS + S) * I8_A_STEP;
+                if (I8_ABL_A) S &= I8_TILE_STEPS - 1;
+                return a_group + (size_t)j * a_plane + (tile0 * I8_TILE_STEPS + S) * I8_A_STEP;
             };
             // first chunk: modulus 0, tile 0 -> buffer 0 (the last barrier has passed: both buffers are free)
             {
-                const v4i* src = bim + tid;
                 v4i t8[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) t8[i] = src[512 * i];
+                for (int i = 0; i < 8; ++i) t8[i] = bim[utid + 512 * i];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) Bs[tid + 512 * i] = t8[i];
             }
-            v4i ar[2][4];
+            // The A ring: four slots of four row tiles.  A sweep starts with its steps 0 .. 3 in slots 0 .. 3, step s of a tile reads
+            // slot s & 3 (a tile has 8 steps), and behind the diagonal tile's `nmine` steps the ring is turned back (below).
+            v4i ar[4][4];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < 4; ++i) {
                 const v4i* ap = a_ptr(0, i);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) ar[i][r] = ap[64 * r];
+                for (int r = 0; r < 4; ++r) ar[i][r] = ap[ulane + 64 * r];
             }
             __syncthreads();
             v4i acc[4][8];
@@ -279,51 +297,65 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
 #pragma unroll
                 for (int t = 0; t < 8; ++t) acc[r][t] = v4i{0, 0, 0, 0};
             int buf = 0;
-            // One tile of a sweep: 8 steps of 32 MFMAs.  FULL: every step runs and a chunk follows — straight-line code, no branch in
-            // it: hipcc places its waits by counting the loads in flight, and behind every join of two paths it waits for all of
-            // them, the A fragments requested two steps ahead included.  Not FULL (the diagonal tile): `nrun` steps, a chunk follows
-            // if `more_rt`.  (One straight-line copy per step count of the diagonal tile was built too: the four copies held
-            // 65 - 300 spill accesses each, accumulators moved around their join.)
-            // Order inside a step: a piece of the next chunk is requested first and written to LDS behind the MFMAs of the FOLLOWING
-            // step, the A fragments of step s + 2 are requested behind the MFMAs of step s, straight into the ring registers those
-            // have just read: no wait is for a load younger than a whole step.
+            // One tile of a sweep: 8 steps of 32 MFMAs, written as a pipeline in source order and fenced with sched_barrier(0), so
+            // that hipcc's counted waits are the ones meant (its scheduler had put six of the eight LDS reads of a step directly
+            // in front of the MFMAs that take them, behind an lgkmcnt(0) each; the group-barrier hints did not hold it).
+            // FULL: every step runs and a chunk follows — straight-line code, no branch in it: hipcc places its waits by counting
+            // the loads in flight, and behind a join of two paths it takes the worse of the two.  Not FULL (the diagonal tile): `nrun`
+            // steps, a chunk follows if `more_rt`.  (One straight-line copy per step count of the diagonal tile was built too: the
+            // four copies held 65 - 300 spill accesses each, accumulators moved around their join.)
+            // Order inside a step:
+            //   * piece s + 1 of the next chunk (pieces 0 and 1 in step 0) is requested first, and piece s - 1 is written to LDS behind
+            //     the step's MFMAs: a piece has three steps to arrive, the first and the last two, and the tile's closing barrier
+            //     waits for a load that is two steps old, not one;
+            //   * B fragments go through a register ring of 3: column tile u + 2 is requested from LDS, then the four MFMAs of
+            //     tile u are issued — the wait in front of them leaves two reads outstanding.  In a FULL tile the ring runs on
+            //     across the steps; only the chunk's last two column tiles have nothing left to request (the next chunk is behind
+            //     the barrier);
+            //   * the A fragments of step s + 4 are requested behind the MFMAs of step s, straight into the ring slot those have
+            //     just read: three whole steps, 96 MFMAs of this wave, lie between the request and the first MFMA that waits for
+            //     it (loads return in order: the chunk piece requested in front of step s + 1, which comes from HBM, has had as long).
             auto tile = [&](auto full_tag, const int nrun, const bool more_rt, const int j, const int S0, const v4i* nsrc) __attribute__((always_inline)) {
                 constexpr bool FULL = decltype(full_tag)::value;
                 const bool more = FULL || more_rt;
+                if (I8_ABL_B) nsrc = bim;
                 const v4i* bcur = Bs + (size_t)buf * I8_CHUNK + lane;
                 v4i* bnext = Bs + (size_t)(buf ^ 1) * I8_CHUNK + tid;
-                v4i st[2];                                       // pieces of the next chunk on their way to LDS
+                v4i st[3];                                       // pieces of the next chunk on their way to LDS
+                v4i bq[3];                                       // B fragments on their way to the MFMAs
+                if (I8_ABL_NOLDS) bq[0] = bq[1] = bq[2] = bcur[0];
 #pragma unroll
                 for (int s = 0; s < I8_TILE_STEPS; ++s) {
                     const bool run = FULL || s < nrun;
-                    if (more) st[s & 1] = nsrc[512 * s];
+                    if (more && s == 0) st[0] = nsrc[utid];
+                    if (more && s + 1 < I8_TILE_STEPS) st[(s + 1) % 3] = nsrc[utid + 512 * (s + 1)];
                     __builtin_amdgcn_sched_barrier(0);
                     if (run) {
+                        if (!I8_ABL_NOLDS && (s == 0 || !FULL)) {
+                            bq[(8 * s) % 3] = bcur[(8 * s) * 64];
+                            bq[(8 * s + 1) % 3] = bcur[(8 * s + 1) * 64];
+                        }
 #pragma unroll
                         for (int t = 0; t < 8; ++t) {
-                            const v4i b = bcur[(s * 8 + t) * 64];
+                            const int u = 8 * s + t;
+                            if (!I8_ABL_NOLDS && (t + 2 < 8 || (FULL && s + 1 < I8_TILE_STEPS))) bq[(u + 2) % 3] = bcur[(u + 2) * 64];
+                            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) acc[r][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[s & 1][r], b, acc[r][t], 0, 0, 0);
+                            for (int r = 0; r < 4; ++r)
+                                acc[r][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ar[s & 3][r], bq[u % 3], acc[r][t], 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
                         }
-                        // B fragments are read two column tiles ahead of the MFMAs that take them
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-#pragma unroll
-                        for (int t = 0; t < 6; ++t) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    if (more && s > 0) bnext[512 * (s - 1)] = st[(s - 1) & 1];
+                    if (more && s > 0) bnext[512 * (s - 1)] = st[(s - 1) % 3];
                     if (run) {
-                        const v4i* ap = a_ptr(j, S0 + s + 2);
+                        const v4i* ap = a_ptr(j, S0 + s + 4);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) ar[s & 1][r] = ap[64 * r];
+                        for (int r = 0; r < 4; ++r) ar[s & 3][r] = ap[ulane + 64 * r];
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (more) bnext[512 * (I8_TILE_STEPS - 1)] = st[(I8_TILE_STEPS - 1) & 1];
+                if (more) bnext[512 * (I8_TILE_STEPS - 1)] = st[(I8_TILE_STEPS - 1) % 3];
                 __syncthreads();
                 buf ^= 1;
             };
@@ -331,11 +363,16 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
             for (int j = 0; j < I8_NMOD; ++j) {
 #pragma unroll 1
                 for (int kb = 0; kb < ib; ++kb)         // full tiles; the next chunk is the next tile of this sweep
-                    tile(Bool<true>{}, I8_TILE_STEPS, true, j, kb * I8_TILE_STEPS, bim + ((size_t)j * nst + (kb + 1) * I8_TILE_STEPS) * I8_B_STEP + tid);
+                    tile(Bool<true>{}, I8_TILE_STEPS, true, j, kb * I8_TILE_STEPS, bim + ((size_t)j * nst + (kb + 1) * I8_TILE_STEPS) * I8_B_STEP);
                 // diagonal tile; the next chunk is tile 0 of the next modulus
-                tile(Bool<false>{}, nmine, j + 1 < I8_NMOD, j, ib * I8_TILE_STEPS, bim + (size_t)(j + 1) * nst * I8_B_STEP + tid);
+                tile(Bool<false>{}, nmine, j + 1 < I8_NMOD, j, ib * I8_TILE_STEPS, bim + (size_t)(j + 1) * nst * I8_B_STEP);
                 // the sweep of modulus j is complete: reduce, park (4 elements of a tile per dword), start over
-                {
+                if (I8_ABL_NORED) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[r][t]));
+                } else {
                     const double m = c_i8_mod[j], inv = c_i8_inv[j], hi = c_i8_hi[j], lo = c_i8_lo[j];
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -348,6 +385,18 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                             acc[r][t] = v4i{0, 0, 0, 0};
                         }
                 }
+                // the next sweep's steps 0 .. 3 sit in slots nmine & 3 ..: nmine = 2 or 6 leaves them two slots on.  Turn the ring back
+                // (selects, no branch).  Here, behind the reduction, their loads have long returned, and the stores above are
+                // younger: they are not waited for.
+                const bool turn = (nmine & 2) != 0;
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const v4i lo2 = ar[i][r], hi2 = ar[i + 2][r];
+                        ar[i][r] = turn ? hi2 : lo2;
+                        ar[i + 2][r] = turn ? lo2 : hi2;
+                    }
             }
             // ---- all 14 residues of this i-block's 64 x 128 elements are parked: rebuild, scale, square, sum per column
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -355,7 +404,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
             for (int t = 0; t < 8; ++t) {
                 double ssq = 0.0;
 #pragma unroll 1
-                for (int r = 0; r < 4; ++r) {
+                for (int r = 0; r < (I8_ABL_NORED ? 0 : 4); ++r) {
                     unsigned wd[I8_NMOD];
 #pragma unroll
                     for (int j = 0; j < I8_NMOD; ++j) wd[j] = pk[(size_t)(j * 32 + r * 8 + t) * 512];

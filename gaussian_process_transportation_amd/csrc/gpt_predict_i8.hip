@@ -26,11 +26,12 @@ void launch_var_i8(hipStream_t s, const KernelParams& p, const VarI8PlanDev& pla
     a.bq = std::ldexp(1.0, bits - f);
     a.colscale = std::ldexp(1.0, f - bits);
     a.ntiles = plan.nbi * (plan.nbi + 1) / 2;
-    // rounds per launch: the setting of launch_var (in rounds of 136 tiles), for the same reason — workgroups that drift apart stop
-    // sharing the W stream in L2, and a kernel boundary brings them together
+    // rounds per launch, in rounds of 136 tiles as in launch_var: workgroups that drift apart stop sharing the A stream in L2, and a
+    // kernel boundary brings them together.  One round, measured on this kernel at N = 8192, M = 500 000 (profiles/var_int8_feed.txt:
+    // var_ms 277.2 / 280.8 / 285.6 / 287.6 / 289.2 for 1 / 2 / 3 / 4 / 16 = all in one launch; launch_var's 16 had been inherited unmeasured)
     const int64_t rounds = plan.nfull / plan.P;
     const char* e = getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
-    const int rpl_set = e ? (atoi(e) < 0 ? 0 : atoi(e)) : 16;
+    const int rpl_set = e ? (atoi(e) < 0 ? 0 : atoi(e)) : 1;
     const int64_t rpl_scaled = ((int64_t)rpl_set * 136 + a.ntiles - 1) / a.ntiles;
     int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
     if (const char* x = getenv("GPT_VAR_ROUNDS_EXACT")) { if (atoi(x) > 0) rpl = atoi(x); }

@@ -3,6 +3,7 @@ quotes as `roofline.traffic`: HBM-side bytes of the dominant kernel per predicti
 
     python tools/pmc_traffic.py gpurun_out/<tag> j 8192 500000 [commit]   # key (j | jvar | svgp), n_source, queries per launch,
                                                                           # commit the GPU run was made from (default: HEAD)
+A sixth argument names the kernel by a substring of its name (default "k_var<"; mode J runs the residue kernel: "k_var_i8<").
 
 FETCH_SIZE / WRITE_SIZE are in KiB.  On gfx950 FETCH_SIZE reports exactly half of the bytes of wide (16 B per lane)
 coalesced streaming reads — /opt/skills/guides/MI355X_MICROARCH.md, section HBM: "double it before comparing with a byte
@@ -35,14 +36,16 @@ def counters(d, kernel_substr):
 
 def main():
     d, key, n_source, queries = sys.argv[1], sys.argv[2], int(sys.argv[3]), int(sys.argv[4])
-    c = counters(d, "k_var<")
+    kernel = sys.argv[6] if len(sys.argv) > 6 else "k_var<"
+    c = counters(d, kernel)
     need = ["FETCH_SIZE", "WRITE_SIZE"]
     if any(k not in c for k in need):
         raise SystemExit(f"missing counters in {d}: have {sorted(c)}")
     rec = {"n_source": n_source, "queries": queries,
            "hbm_bytes_per_launch": (2.0 * c["FETCH_SIZE"] + c["WRITE_SIZE"]) * 1024.0,
            "fetch_size_kib": c["FETCH_SIZE"], "write_size_kib": c["WRITE_SIZE"],
-           "commit": sys.argv[5] if len(sys.argv) > 5 else
+           "kernel": kernel,
+           "commit": sys.argv[5] if len(sys.argv) > 5 and sys.argv[5] else
            subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True).stdout.strip(),
            "source": os.path.relpath(d, ROOT)}
     if "TCC_HIT_sum" in c and "TCC_MISS_sum" in c:
