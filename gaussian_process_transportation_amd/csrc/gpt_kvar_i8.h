@@ -1,5 +1,7 @@
 // The residue (int8) variance kernel k_var_i8 and the kernels around it: the image of W in residue planes, the finalizing sum.
 // Arithmetic and work split: gpt_plan_i8.h; derivation and measurements: DESIGN.md section 4.  k_var (gpt_kvar.h) is untouched.
+// Residues — of the operands when the planes are written, of the int32 accumulators when a sweep ends — are taken with byte dot
+// products (v_dot4_u32_u8) and one fp32 quotient, no fp64 and no fix-up: gpt_residue_i8.h.
 //
 // Shapes:
 //   * v_mfma_i32_16x16x64_i8: A fragment = 16 B per lane, lane l holds row l & 15, k = 16 (l >> 4) + byte; B fragment the same
@@ -23,6 +25,7 @@
 #include "gpt_dispatch.h"
 #include "gpt_exp.h"
 #include "gpt_plan_i8.h"
+#include "gpt_residue_i8.h"
 
 namespace gpt {
 
@@ -37,7 +40,9 @@ constexpr size_t I8_PARK_WORDS = var_i8_park_bytes() / 4;                // dwor
 
 // Timing-only ablation builds (make ablate-i8, tools/gpu_ablate_i8.sh; their outputs are wrong on purpose): 1 A fragments always from
 // the sweep's first tile, 2 B chunks always from the image's first chunk, 3 both, 4 no generation, 5 no reduce, park or
-// reconstruction, 6 = 3 with the LDS reads of the B fragments hoisted out of the steps as well (MFMAs only).
+// reconstruction, 6 = 3 with the LDS reads of the B fragments hoisted out of the steps as well (MFMAs only); 7 and 8 split the two
+// VALU phases into arithmetic and memory: 7 the generation without its plane stores, 8 reduce and reconstruction without the park
+// stores and loads.
 #ifndef GPT_ABL_I8
 #define GPT_ABL_I8 0
 #endif
@@ -46,62 +51,28 @@ constexpr bool I8_ABL_B = GPT_ABL_I8 == 2 || GPT_ABL_I8 == 3 || GPT_ABL_I8 == 6;
 constexpr bool I8_ABL_NOGEN = GPT_ABL_I8 == 4;
 constexpr bool I8_ABL_NORED = GPT_ABL_I8 == 5;
 constexpr bool I8_ABL_NOLDS = GPT_ABL_I8 == 6;
+constexpr bool I8_ABL_NOPLANEST = GPT_ABL_I8 == 7;
+constexpr bool I8_ABL_NOPARK = GPT_ABL_I8 == 8;
 
-// ---- constants of the reconstruction, built at compile time ------------------------------------------------------------------
-struct I8Tab {
-    float m[I8_NMOD], rm[I8_NMOD];       // modulus, its reciprocal
-    float inv[I8_NMOD];                  // (m_0 .. m_{i-1})^-1 mod m_i, balanced
-    float w[I8_NMOD][I8_NMOD];           // w[l][i] = (m_0 .. m_{l-1}) mod m_i, balanced (l < i)
-};
-constexpr int i8_balanced(int x, int m) { x %= m; if (x < 0) x += m; return x > (m - 1) / 2 ? x - m : x; }
-constexpr I8Tab make_i8_tab() {
-    I8Tab t{};
-    for (int i = 0; i < I8_NMOD; ++i) {
-        const int m = I8_MODULI[i];
-        t.m[i] = (float)m; t.rm[i] = 1.0f / (float)m;
-        int prod = 1;
-        for (int l = 0; l < I8_NMOD; ++l) {
-            t.w[l][i] = l < i ? (float)i8_balanced(prod, m) : 0.0f;
-            if (l < i) prod = prod * I8_MODULI[l] % m;
-        }
-        int inv = 0;
-        for (int x = 1; x < m; ++x) if (prod * x % m == 1) inv = x;
-        t.inv[i] = (float)i8_balanced(inv, m);
-    }
-    return t;
-}
-static constexpr I8Tab I8_TAB = make_i8_tab();
-
-// run-time indexed copies for the loops over the moduli that stay rolled: modulus, reciprocal, largest and smallest balanced residue
-__constant__ double c_i8_mod[I8_NMOD] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 217, 211, 199};
-__constant__ double c_i8_inv[I8_NMOD] = {1.0 / 256, 1.0 / 255, 1.0 / 253, 1.0 / 251, 1.0 / 247, 1.0 / 241, 1.0 / 239,
-                                         1.0 / 233, 1.0 / 229, 1.0 / 227, 1.0 / 223, 1.0 / 217, 1.0 / 211, 1.0 / 199};
-__constant__ double c_i8_hi[I8_NMOD] = {127, 127, 126, 125, 123, 120, 119, 116, 114, 113, 111, 108, 105, 99};
-__constant__ double c_i8_lo[I8_NMOD] = {-128, -127, -126, -125, -123, -120, -119, -116, -114, -113, -111, -108, -105, -99};
-
-// balanced residue of the integer-valued x (|x| < 2^52) modulo m: the quotient may be off by one, the remainder is exact (fma)
-static __device__ __forceinline__ int i8_residue(const double x, const double m, const double inv, const double hi, const double lo) {
-    const double q = rint(x * inv);
-    double r = fma(-q, m, x);
-    r = r > hi ? r - m : r;
-    r = r < lo ? r + m : r;
-    return (int)r;
-}
-static __device__ __forceinline__ int i8_pack4(const int r0, const int r1, const int r2, const int r3) {
-    return (int)((unsigned)(r0 & 255) | ((unsigned)(r1 & 255) << 8) | ((unsigned)(r2 & 255) << 16) | ((unsigned)r3 << 24));
-}
-// the 14 residue words of 16 integers (a lane's fragment of one step), plane j to dst[j * stride]
+// the 14 residue words of 16 integers (a lane's fragment of one step; |x| <= 2^p, p <= 50), plane j to dst[j * stride].  The
+// integers are split into bytes once; a residue is two byte dot products and an fp32 quotient (gpt_residue_i8.h), its byte the
+// low byte of the result.  The modulus number is wave-uniform: the table arrives by scalar loads.
+template <bool STORE = true>
 static __device__ __forceinline__ void i8_store_planes(const double (&x)[16], v4i* __restrict__ dst, const size_t stride) {
+    uint32_t lo[16], hi[16];
+#pragma unroll
+    for (int b = 0; b < 16; ++b) i8_operand_split(x[b], lo[b], hi[b]);
+    const I8ResTab& T = i8_res_tab();
 #pragma unroll 1
     for (int j = 0; j < I8_NMOD; ++j) {
-        const double m = c_i8_mod[j], inv = c_i8_inv[j], hi = c_i8_hi[j], lo = c_i8_lo[j];
-        int r[16];
+        uint32_t r[16];
 #pragma unroll
-        for (int b = 0; b < 16; ++b) r[b] = i8_residue(x[b], m, inv, hi, lo);
+        for (int b = 0; b < 16; ++b) r[b] = i8_operand_bits(lo[b], hi[b], T, j);
         v4i o;
 #pragma unroll
-        for (int v = 0; v < 4; ++v) o[v] = i8_pack4(r[4 * v], r[4 * v + 1], r[4 * v + 2], r[4 * v + 3]);
-        dst[(size_t)j * stride] = o;
+        for (int v = 0; v < 4; ++v) o[v] = (int)i8_pack_bits(r[4 * v], r[4 * v + 1], r[4 * v + 2], r[4 * v + 3]);
+        if (STORE) dst[(size_t)j * stride] = o;
+        else asm volatile("" ::"v"(o));
     }
 }
 
@@ -158,27 +129,15 @@ __global__ __launch_bounds__(256) void k_i8_planes(const double* __restrict__ Wf
 }
 
 // ---- reconstruction ------------------------------------------------------------------------------------------------------------
-// r: the 14 balanced residues of an integer C, |C| < M / 2.  Mixed-radix digits d_i = ((r_i - sum_{l < i} d_l w[l][i]) inv_i) mod m_i,
-// balanced; C = d_0 + m_0 (d_1 + m_1 (d_2 + ...)).  The leading digits of a small C are zero, so the Horner sum keeps the relative
-// accuracy of fp64 (13 roundings at most).  Every fp32 value below is an integer of magnitude < 2^24, every fma exact; the
-// quotients are the nearest integers for the odd moduli (v / m stays 1 / (2 m) away from a tie, its rounding error below 2e-5),
-// and modulus 0 (256) has no digit to compute: d_0 = r_0.
+// r: the 14 balanced residues of an integer C, |C| < M / 2.  Mixed-radix digits in balanced form (i8_garner_digits,
+// gpt_residue_i8.h: fp32, every intermediate an integer below 2^24); C = d_0 + m_0 (d_1 + m_1 (d_2 + ...)).  The leading digits of
+// a small C are zero, so the Horner sum keeps the relative accuracy of fp64 (13 roundings at most).
 static __device__ __forceinline__ double i8_garner(const float (&r)[I8_NMOD]) {
     float d[I8_NMOD];
-    d[0] = r[0];
-#pragma unroll
-    for (int i = 1; i < I8_NMOD; ++i) {
-        float s = 0.0f;
-#pragma unroll
-        for (int l = 0; l < i; ++l) s = fmaf(d[l], I8_TAB.w[l][i], s);
-        float u = r[i] - s;
-        u = fmaf(-rintf(u * I8_TAB.rm[i]), I8_TAB.m[i], u);
-        const float v = u * I8_TAB.inv[i];
-        d[i] = fmaf(-rintf(v * I8_TAB.rm[i]), I8_TAB.m[i], v);
-    }
+    i8_garner_digits(r, d);
     double X = (double)d[I8_NMOD - 1];
 #pragma unroll
-    for (int i = I8_NMOD - 2; i >= 0; --i) X = fma(X, (double)I8_TAB.m[i], (double)d[i]);
+    for (int i = I8_NMOD - 2; i >= 0; --i) X = fma(X, (double)I8_GARNER.m[i], (double)d[i]);
     return X;
 }
 
@@ -255,7 +214,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                     hh = fma(d2_, d2_, hh);
                     x[b] = rint(kernel_tab<KT>(hh, lnc, Tt) * a.bq);
                 }
-                i8_store_planes(x, bim + ((size_t)s * 8 + w) * 64 + lane, (size_t)nst * I8_B_STEP);
+                i8_store_planes<!I8_ABL_NOPLANEST>(x, bim + ((size_t)s * 8 + w) * 64 + lane, (size_t)nst * I8_B_STEP);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -373,15 +332,17 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
 #pragma unroll
                         for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[r][t]));
                 } else {
-                    const double m = c_i8_mod[j], inv = c_i8_inv[j], hi = c_i8_hi[j], lo = c_i8_lo[j];
+                    const I8ResTab& T = i8_res_tab();
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
 #pragma unroll
                         for (int t = 0; t < 8; ++t) {
-                            int rr[4];
+                            uint32_t rr[4];
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) rr[e] = i8_residue((double)acc[r][t][e], m, inv, hi, lo);
-                            pk[(size_t)(j * 32 + r * 8 + t) * 512] = (unsigned)i8_pack4(rr[0], rr[1], rr[2], rr[3]);
+                            for (int e = 0; e < 4; ++e) rr[e] = i8_acc_bits(acc[r][t][e], T, j);
+                            const unsigned pw = i8_pack_bits(rr[0], rr[1], rr[2], rr[3]);
+                            if (I8_ABL_NOPARK) asm volatile("" ::"v"(pw));
+                            else pk[(size_t)(j * 32 + r * 8 + t) * 512] = pw;
                             acc[r][t] = v4i{0, 0, 0, 0};
                         }
                 }
@@ -407,7 +368,10 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                 for (int r = 0; r < (I8_ABL_NORED ? 0 : 4); ++r) {
                     unsigned wd[I8_NMOD];
 #pragma unroll
-                    for (int j = 0; j < I8_NMOD; ++j) wd[j] = pk[(size_t)(j * 32 + r * 8 + t) * 512];
+                    for (int j = 0; j < I8_NMOD; ++j) {
+                        if (I8_ABL_NOPARK) asm volatile("" : "=v"(wd[j]));
+                        else wd[j] = pk[(size_t)(j * 32 + r * 8 + t) * 512];
+                    }
                     const d4 rs = *reinterpret_cast<const d4*>(a.rowscale + (size_t)ib * I8_ROWS + 64 * g + 16 * r + 4 * lk);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
