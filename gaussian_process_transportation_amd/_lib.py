@@ -132,6 +132,12 @@ SIGNATURES = {
     "gpt_batch_optimize": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _i64,
                                      _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp,
                                      C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gpt_batch_optimize_bounded": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp,
+                                             _i64, _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _dp, _dp,
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gpt_batch_fold_scan": (C.c_int, [C.c_int, _dp, _dp, C.POINTER(_i64), _i64, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp,
+                                      C.POINTER(_i64), _i64, C.c_int, _dp, C.POINTER(_i64), C.POINTER(_i64), _dp, _dp, _dp, _dp, _dp,
+                                      C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -533,6 +539,104 @@ def batch_optimize_packed(X, Y, n_begin, n_ls, run_model, theta0, bounds, alpha,
     large = np.diff(n_begin)[run_model] > 32
     launches = sum(int(-(-int(evals[large == cls].max()) // int(evals_per_launch))) for cls in (False, True) if (large == cls).any())
     return theta, lml, iters, evals, status, launches
+
+
+def batch_optimize_bounded_packed(X, Y, n_begin, n_ls, run_model, theta0, run_bounds, alpha, kernel_type=0, device=0, pgtol=1e-5,
+                                  ftol=2.22e-9, max_iter=15000, max_evals=15000, evals_per_launch=None):
+    """gpt_batch_optimize_bounded: batch_optimize_packed with bounds of its own for every run, run_bounds (R, 2 + n_ls, 2).  A run's
+    results are, bit for bit, those of batch_optimize_packed with that run's bounds shared.  Returns the same tuple."""
+    who = "batch_optimize_bounded"
+    B, D = n_begin.size - 1, X.shape[1]
+    P = 2 + int(n_ls)
+    run_model = np.ascontiguousarray(run_model, dtype=np.int32)
+    theta0 = as_f64(theta0, 2, "theta0")
+    run_bounds = as_f64(run_bounds, 3, "run_bounds")
+    R = run_model.size
+    if not 1 <= R <= BATCH_MAX_R:
+        raise ValueError(f"{who}: a call holds 1 .. 2^20 runs, got {R}")
+    if theta0.shape != (R, P) or run_bounds.shape != (R, P, 2):
+        raise ValueError(f"{who}: theta0 must be (R, 2 + n_ls) = ({R}, {P}) and run_bounds (R, 2 + n_ls, 2), got {theta0.shape} and "
+                         f"{run_bounds.shape}")
+    if evals_per_launch is None:
+        evals_per_launch = batch_opt_evals_per_launch()
+    lib = load()
+    require_gpu()
+    theta = np.full((R, P), np.nan)
+    lml = np.full(R, np.nan)
+    iters, evals, status = (np.zeros(R, dtype=np.int32) for _ in range(3))
+    ip = C.POINTER(C.c_int)
+    check(lib.gpt_batch_optimize_bounded(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(C.POINTER(_i64)), B, D, Y.shape[1], int(n_ls),
+                                         run_model.ctypes.data_as(ip), dptr(theta0), R, dptr(run_bounds), float(alpha), int(kernel_type),
+                                         float(pgtol), float(ftol), int(max_iter), int(max_evals), int(evals_per_launch), dptr(theta),
+                                         dptr(lml), iters.ctypes.data_as(ip), evals.ctypes.data_as(ip), status.ctypes.data_as(ip)),
+          "gpt_batch_optimize_bounded")
+    large = np.diff(n_begin)[run_model] > 32
+    launches = sum(int(-(-int(evals[large == cls].max()) // int(evals_per_launch))) for cls in (False, True) if (large == cls).any())
+    return theta, lml, iters, evals, status, launches
+
+
+FOLD_SCAN_MAX_D = 3
+
+
+def batch_fold_scan_packed(X, Y, n_begin, length_scale, constant_value, noise_level, alpha, Xq, q_begin=None, surrogate=True,
+                           per_query=False, kernel_type=0, device=0):
+    """gpt_batch_fold_scan on arrays in the ragged layout (batch_pack): does x -> x + psi_b(x) fold on its queries, psi_b the
+    posterior mean of model b (Y (sum n_b, D): a displacement, D <= 3, RBF).  q_begin None: every model scans the same Xq (M, D);
+    otherwise Xq (sum M_b, D) with q_begin (B + 1).  surrogate: also the error of the reference's inverse surrogate (the GP on
+    X + Y -> -Y at the same hyper-parameters).  Returns a dict: min_det (B,), argmin (B,), n_fold (B,), err_sum (B,), err_max (B,),
+    status (B,), surrogate_status (B,), and with per_query det, z, err (lists of per-model arrays).  NaN (-1 in argmin and n_fold)
+    wherever the call left an output untouched: a model that is not PD, the err outputs without the surrogate or where the
+    surrogate's matrix is not PD."""
+    who = "batch_fold_scan"
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    n_begin = np.ascontiguousarray(n_begin, dtype=np.int64)
+    B, D = n_begin.size - 1, X.shape[1]
+    if D > FOLD_SCAN_MAX_D:
+        raise ValueError(f"{who}: D must be 1 .. {FOLD_SCAN_MAX_D} (the map x -> x + psi(x) is a displacement of the input space), got D = {D}")
+    if Y.shape != X.shape:
+        raise ValueError(f"{who}: Y must be of shape (n_b, D) = {X.shape}, a displacement per source point, got {Y.shape}")
+    ls, c, noise = _batch_hyper(B, D, length_scale, constant_value, noise_level, who)
+    Xq = np.ascontiguousarray(Xq, dtype=np.float64).reshape(-1, D)
+    if q_begin is None:
+        M, o_begin, qp = Xq.shape[0], np.arange(B + 1, dtype=np.int64) * Xq.shape[0], None
+    else:
+        o_begin = np.ascontiguousarray(q_begin, dtype=np.int64)
+        if o_begin.shape != (B + 1,) or o_begin.max() > Xq.shape[0]:
+            raise ValueError(f"{who}: q_begin must have B + 1 = {B + 1} entries ending within the {Xq.shape[0]} rows of Xq")
+        M, qp = int(o_begin[-1]), o_begin.ctypes.data_as(C.POINTER(_i64))
+    rows = max(int(o_begin.max()), 0)
+    lib = load()
+    require_gpu()
+    out = dict(min_det=np.full(B, np.nan), argmin=np.full(B, -1, dtype=np.int64), n_fold=np.full(B, -1, dtype=np.int64),
+               err_sum=np.full(B, np.nan), err_max=np.full(B, np.nan), status=np.zeros(B, dtype=np.int32),
+               surrogate_status=np.zeros(B, dtype=np.int32))
+    det, z, err = (np.full(shape, np.nan) if per_query else None for shape in ((rows,), (rows, D), (rows,)))
+    ip, lp = C.POINTER(C.c_int), C.POINTER(_i64)
+    check(lib.gpt_batch_fold_scan(int(device), dptr(X), dptr(Y), n_begin.ctypes.data_as(lp), B, D, dptr(ls), ls.shape[1], dptr(c), dptr(noise),
+                                  float(alpha), int(kernel_type), dptr(Xq), qp, M, int(bool(surrogate)), dptr(out["min_det"]),
+                                  out["argmin"].ctypes.data_as(lp), out["n_fold"].ctypes.data_as(lp), dptr(out["err_sum"]),
+                                  dptr(out["err_max"]), dptr(det), dptr(z), dptr(err), out["status"].ctypes.data_as(ip),
+                                  out["surrogate_status"].ctypes.data_as(ip)), "gpt_batch_fold_scan")
+    if per_query:
+        out.update(det=_split(det, o_begin), z=_split(z, o_begin), err=_split(err, o_begin))
+    return out
+
+
+def batch_fold_scan(Xs, Ys, length_scale, constant_value, noise_level, alpha, xq, surrogate=True, per_query=False, kernel_type=0, device=0):
+    """batch_fold_scan_packed from sequences of (n_b, D) arrays.  xq: one (M, D) array that every model scans, or a sequence of B
+    arrays (M_b, D), M_b >= 0."""
+    X, Y, n_begin = batch_pack(Xs, Ys, "batch_fold_scan")
+    if isinstance(xq, np.ndarray) and xq.ndim == 2:
+        return batch_fold_scan_packed(X, Y, n_begin, length_scale, constant_value, noise_level, alpha, xq, None, surrogate, per_query,
+                                      kernel_type, device)
+    xqs = [np.asarray(x, dtype=np.float64).reshape(-1, X.shape[1]) for x in xq]
+    if len(xqs) != n_begin.size - 1:
+        raise ValueError(f"batch_fold_scan: {n_begin.size - 1} models but {len(xqs)} query arrays")
+    q_begin = np.zeros(len(xqs) + 1, dtype=np.int64)
+    np.cumsum([x.shape[0] for x in xqs], out=q_begin[1:])
+    return batch_fold_scan_packed(X, Y, n_begin, length_scale, constant_value, noise_level, alpha, np.concatenate(xqs), q_begin, surrogate,
+                                  per_query, kernel_type, device)
 
 
 def batch_lml_objective(Xs, Ys, length_scale, constant_value, noise_level, alpha, kernel_type=0, device=0):

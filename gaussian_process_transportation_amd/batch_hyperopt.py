@@ -54,15 +54,7 @@ def check_optimizer(optimizer):
 def _device_search(kernel, runs, free, n_ls, X_all, Y_all, n_begin, alpha, kernel_type, device, stats):
     """Every run carried through a projected BFGS iteration on the device, one workgroup per run (gpt_batch_optimize):
     [(theta (free components), f = -LML, warning or None)] in the order of `runs`, the shape of the scipy path's results."""
-    p = kernel.get_params()
-    fixed = np.log(np.concatenate([[float(p["k1__k1__constant_value"])], np.atleast_1d(np.asarray(p["k1__k2__length_scale"], dtype=np.float64)),
-                                   [float(p["k2__noise_level"])]]))
-    if not np.isfinite(kernel.bounds).all():
-        raise ValueError(f"optimizer='{DEVICE_SEARCH}' requires that all bounds are finite.")
-    if not np.isfinite(fixed[~free]).all():
-        raise ValueError(f"optimizer='{DEVICE_SEARCH}' searches in log space: a fixed hyper-parameter must be > 0")
-    bounds = np.column_stack([fixed, fixed])                       # (2 + n_ls, 2), log space; lo == hi: fixed
-    bounds[free] = kernel.bounds
+    fixed, bounds = _log_box(kernel, free)                         # (2 + n_ls, 2), log space; lo == hi: fixed
     theta0 = np.tile(fixed, (len(runs), 1))
     theta0[:, free] = np.array([t for _, t in runs])
     run_model = np.array([m for m, _ in runs], dtype=np.int32)
@@ -238,6 +230,69 @@ def optimize_hyperparameters_batch(kernel, Xs, Ys, alpha=1e-10, optimizer="fmin_
     if errors:
         raise errors[0]
     return _best_per_model(kernel, results, B, n_restarts_optimizer)
+
+
+def _log_box(kernel, free):
+    """(fixed, bounds): the kernel's full theta = log [c, l.., noise] and its box (2 + n_ls, 2) in log space, lo == hi where a
+    component is fixed — what gpt_batch_optimize takes."""
+    p = kernel.get_params()
+    fixed = np.log(np.concatenate([[float(p["k1__k1__constant_value"])], np.atleast_1d(np.asarray(p["k1__k2__length_scale"], dtype=np.float64)),
+                                   [float(p["k2__noise_level"])]]))
+    if not np.isfinite(kernel.bounds).all():
+        raise ValueError(f"optimizer='{DEVICE_SEARCH}' requires that all bounds are finite.")
+    if not np.isfinite(fixed[~free]).all():
+        raise ValueError(f"optimizer='{DEVICE_SEARCH}' searches in log space: a fixed hyper-parameter must be > 0")
+    bounds = np.column_stack([fixed, fixed])
+    bounds[free] = kernel.bounds
+    return fixed, bounds
+
+
+def optimize_hyperparameters_candidates(kernels, X, Y, alpha=1e-10, n_restarts_optimizer=0, kernel_type=0, device=0, stats=None):
+    """The device search (gpt_batch_optimize_bounded) for a list of candidate kernels over ONE data set X (n, D), Y (n, O), n <= 128:
+    what a host loop `for k in kernels: GaussianProcess(k, n_restarts_optimizer=...).fit(X, Y)` searches, in one call.  The model
+    is shared (B = 1, every run's model is 0); a candidate's runs carry its own bounds.  The starts are drawn as that loop draws
+    them, candidate by candidate: first the kernel's own theta, then n_restarts_optimizer draws rng.uniform(lo, hi) from the
+    global numpy RNG, which therefore ends where the loop leaves it.  The kernels share their layout (n_ls, which components are
+    fixed).  Returns one (c, ls, noise, lml, theta) per candidate, its best run (the first on ties), theta being the free
+    components in the kernel's order.  stats (a dict, optional) receives runs, launches, evaluations."""
+    if not kernels:
+        raise ValueError("optimize_hyperparameters_candidates: no candidate kernel")
+    n_ls = int(np.size(kernels[0].get_params()["k1__k2__length_scale"]))
+    free = _free_mask(kernels[0], n_ls)
+    if not free.any():
+        raise ValueError("optimize_hyperparameters_candidates: every hyper-parameter is fixed, nothing to search")
+    rng = np.random.mtrand._rand
+    theta0, boxes = [], []
+    for k in kernels:
+        if int(np.size(k.get_params()["k1__k2__length_scale"])) != n_ls or not np.array_equal(_free_mask(k, n_ls), free):
+            raise ValueError("optimize_hyperparameters_candidates: the candidate kernels must share n_ls and their fixed components")
+        fixed, box = _log_box(k, free)
+        starts = [np.array(k.theta)] + [rng.uniform(k.bounds[:, 0], k.bounds[:, 1]) for _ in range(n_restarts_optimizer)]
+        for s in starts:
+            full = fixed.copy()
+            full[free] = s
+            theta0.append(full)
+            boxes.append(box)
+    X_all, Y_all, n_begin = _lib.batch_pack([X], [Y], "optimize_hyperparameters_candidates")
+    R, per = len(theta0), 1 + n_restarts_optimizer
+    theta, lml, iters, evals, status, launches = _lib.batch_optimize_bounded_packed(
+        X_all, Y_all, n_begin, n_ls, np.zeros(R, dtype=np.int32), np.array(theta0), np.array(boxes), alpha, kernel_type, device)
+    if stats is not None:
+        stats.update(runs=R, launches=int(launches), evaluations=int(np.sum(evals)))
+    names = {_lib.GPT_OPT_MAX_ITER: "MAX_ITER", _lib.GPT_OPT_MAX_EVALS: "MAX_EVALS", _lib.GPT_OPT_LINESEARCH: "LINESEARCH"}
+    out = []
+    for k, kernel in enumerate(kernels):
+        f = []
+        for r in range(k * per, (k + 1) * per):
+            if int(status[r]) in names:
+                warnings.warn(f"{DEVICE_SEARCH} failed to converge (status={int(status[r])}): {names[int(status[r])]} after {int(iters[r])} "
+                              f"iterations and {int(evals[r])} evaluations")
+            f.append(np.inf if status[r] == _lib.GPT_OPT_NOT_PD_START else -float(lml[r]))
+        best = k * per + int(np.argmin(f))                       # the tie rule of _best_per_model: the first
+        t = theta[best][free]
+        c, ls, noise = _unpack(kernel, t)
+        out.append((c, ls, noise, -f[best - k * per], t))
+    return out
 
 
 def _best_per_model(kernel, results, B, n_restarts_optimizer):

@@ -1,6 +1,6 @@
 // What the two halves of the device hyper-parameter search share (internal header): the kernel's argument struct, the layout of
 // a run's record and the launcher.  gpt_batch_opt.hip holds bat_optimize and defines the launcher; gpt_batch_opt_host.hip holds
-// gpt_batch_optimize.  Plain C++: the sanitizer build compiles it with g++ (host_stub/).
+// gpt_batch_optimize and gpt_batch_optimize_bounded.  Plain C++: the sanitizer build compiles it with g++ (host_stub/).
 #pragma once
 #include "gpt_batch.h"
 
@@ -18,6 +18,7 @@ constexpr size_t bat_opt_record(int P) { return (size_t)P * P + 6 * (size_t)P + 
 
 struct BatOptArgs {
     const double *X, *Y, *bounds;       // (rows, D), (rows, O), (P, 2): lo, hi in log space, lo == hi: fixed
+    int64_t bounds_stride;              // doubles from a run's bounds to the next run's: 0 (all runs share them) or 2 P
     const int64_t* n_begin;             // (B + 1)
     const int *run_model, *list;        // (R): a run's model; the runs of this launch
     double* rec;                        // (R, bat_opt_record(P))

@@ -1,4 +1,4 @@
-// The hyper-parameter search of a batch of small GPs on the device — gpt_batch_optimize (include/gpt_hip.h).  One workgroup owns
+// The hyper-parameter search of a batch of small GPs on the device — gpt_batch_optimize, gpt_batch_optimize_bounded (include/gpt_hip.h).  One workgroup owns
 // one RUN, a (model, start point) pair, and carries it through a projected BFGS iteration on f = -LML over theta = log [c, l..,
 // noise] inside a box, without returning to the host between objective evaluations:
 //     start   x = clip(x0); f, g there; H = I.  Not PD there: GPT_OPT_NOT_PD_START.
@@ -41,7 +41,7 @@ __device__ __forceinline__ bool opt_advance(const BatOptArgs& a, const int r, co
     double* __restrict__ x = a.rec + (size_t)r * bat_opt_record(P);
     double *g = x + P, *d = g + P, *xt = d + P, *gn = xt + P, *hy = gn + P, *H = hy + P, *sc = H + P * P;   // sc: f, step length
     int* __restrict__ cn = a.cnt + (size_t)r * BAT_OPT_CNT;
-    const double* __restrict__ bd = a.bounds;
+    const double* __restrict__ bd = a.bounds + (int64_t)r * a.bounds_stride;   // the run's own box, or the shared one (stride 0)
     const double INF = __builtin_huge_val();
 
     double fn = INF;

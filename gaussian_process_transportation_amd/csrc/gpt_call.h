@@ -1,7 +1,7 @@
 // Host helpers of the C entry points (internal header; plain C++, it also compiles under g++ against host_stub/, the sanitizer
 // builds).  fail() and CALLCHK serve every unit, gpt_api.hip included.  The rest is for a one-shot call without a handle, which
 // validates host arrays, opens a stream, allocates, enqueues its whole schedule through its unit's launchers, reads back and
-// frees: gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip, gpt_select_host.hip, gpt_batch_host.hip, gpt_batch_opt_host.hip (all five run under the
+// frees: gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip, gpt_select_host.hip, gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_fold_scan_host.hip (all six run under the
 // sanitizers: make host-oneshot-asan) and gpt_debug_dgemm (gpt_fit.hip).  gpt_transport_host.hip and gpt_chain_host.hip have the
 // same layout but work on handles, which keep what they allocate; what those two and gpt_api.hip share is in gpt_stage.h.  A
 // handle's long-lived resources have owners of their own: DevBuf, Stream and Event in gpt_common.h.

@@ -1,4 +1,4 @@
-// Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_select_host.hip,
+// Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_fold_scan_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
 // gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
@@ -23,6 +23,7 @@ namespace gpt {
 extern int stub_fail_model;      // stub_launchers.cpp
 extern bool stub_fail_flag;
 extern int stub_opt_launches, stub_opt_launch_count;
+extern int stub_fail_surrogate;
 extern int stub_rollout_launch_count;
 }
 
@@ -253,6 +254,127 @@ void batch_opt_refusals() {
     begin("gpt_batch_optimize refuses max_evals = 0"); done(call(run_model.p, 4, bounds.p, theta0.p, 1e-5, 0, 64), GPT_E_ARG);
     begin("gpt_batch_optimize refuses evals_per_launch = 0"); done(call(run_model.p, 4, bounds.p, theta0.p, 1e-5, 15000, 0), GPT_E_ARG);
     CHECK(theta.all(SENT) && lml.all(SENT) && iters.all(ISENT) && evals.all(ISENT) && status.all(ISENT));
+}
+
+// gpt_batch_optimize_bounded: a box per run (the boxes differ from run to run, some with a fixed component); the start of every run
+// is clipped to its own box, which a run of the failed model shows in theta.
+void batch_opt_bounded_cases(const BatchShape& s, int64_t R, int slices, int failed) {
+    const int64_t B = s.B();
+    BatchInputs in(s);
+    const size_t rows = (size_t)in.n_begin.p[B], P = 2 + (size_t)s.n_ls;
+    D X = ramp(rows * s.Dm), Y = ramp(rows * s.O), theta0 = ramp(R * P, -3.0, 0.5), bounds(R * 2 * P, 0.0);
+    for (int64_t r = 0; r < R; ++r)
+        for (size_t i = 0; i < P; ++i) {
+            bounds.p[(r * P + i) * 2] = i == 0 && r % 2 ? 1.0 : -2.0 + 0.25 * (double)(r % 5);
+            bounds.p[(r * P + i) * 2 + 1] = i == 0 && r % 2 ? 1.0 : 2.0 + 0.5 * (double)(r % 3);
+        }
+    Arr<int> run_model(R, 0);
+    for (int64_t r = 0; r < R; ++r) run_model.p[r] = (int)(r % B);
+    begin("gpt_batch_optimize_bounded " + s.name() + " R=" + std::to_string(R) + " slices=" + std::to_string(slices) +
+          (failed >= 0 ? " failed=" + std::to_string(failed) : ""));
+    gpt::stub_fail_model = failed;
+    gpt::stub_opt_launches = slices;
+    D theta(R * P, SENT), lml(R, SENT);
+    Arr<int> iters(R, ISENT), evals(R, ISENT), status(R, ISENT);
+    done(gpt_batch_optimize_bounded(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, s.n_ls, run_model.p, theta0.p, R, bounds.p, 1e-10, GPT_KERNEL_RBF,
+                                    1e-5, 2.22e-9, 15000, 15000, 7, theta.p, lml.p, iters.p, evals.p, status.p), GPT_OK);
+    for (int64_t r = 0; r < R; ++r) {
+        const bool not_pd = r % B == failed;
+        CHECK(status.p[r] == (not_pd ? GPT_OPT_NOT_PD_START : GPT_OPT_PGTOL));
+        CHECK(evals.p[r] == (not_pd ? 1 : 1 + (int)(r % slices)) && iters.p[r] == 0 && lml.p[r] == 0.0);
+        for (size_t i = 0; i < P; ++i) {
+            const double clipped = std::min(std::max(theta0.p[r * P + i], bounds.p[(r * P + i) * 2]), bounds.p[(r * P + i) * 2 + 1]);
+            CHECK(theta.p[r * P + i] == (not_pd ? clipped : 0.0));
+        }
+    }
+    gpt::stub_fail_model = -1;
+    gpt::stub_opt_launches = 1;
+    if (R < 2) return;
+    D crossed(bounds);
+    std::swap(crossed.p[((R - 1) * P + 1) * 2], crossed.p[((R - 1) * P + 1) * 2 + 1]);
+    D theta2(R * P, SENT);
+    begin("gpt_batch_optimize_bounded refuses lo > hi in the last run's box");
+    done(gpt_batch_optimize_bounded(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, s.n_ls, run_model.p, theta0.p, R, crossed.p, 1e-10, GPT_KERNEL_RBF,
+                                    1e-5, 2.22e-9, 15000, 15000, 7, theta2.p, lml.p, iters.p, evals.p, status.p), GPT_E_ARG);
+    crossed.p[((R - 1) * P + 1) * 2] = std::nan("");
+    begin("gpt_batch_optimize_bounded refuses NaN in the last run's box");
+    done(gpt_batch_optimize_bounded(0, X.p, Y.p, in.n_begin.p, B, s.Dm, s.O, s.n_ls, run_model.p, theta0.p, R, crossed.p, 1e-10, GPT_KERNEL_RBF,
+                                    1e-5, 2.22e-9, 15000, 15000, 7, theta2.p, lml.p, iters.p, evals.p, status.p), GPT_E_ARG);
+    CHECK(theta2.all(SENT));
+}
+
+// ---- fold scan ----------------------------------------------------------------------------------------------------------------
+// queries: M per member (ragged), or one entry {M} for queries that all members share (q_begin = NULL).  mask: bit 0 det, 1 z,
+// 2 err.  A member that ran holds zeros in what was asked of it; the failed member keeps every sentinel, the member whose
+// surrogate alone failed keeps those of err, err_sum and err_max, and without the surrogate nobody's err outputs are touched.
+void fold_scan_cases(const BatchShape& s, const std::vector<int>& queries, bool shared, int surrogate, int failed, int failed_surrogate) {
+    const int64_t B = s.B();
+    BatchInputs in(s);
+    const size_t rows = (size_t)in.n_begin.p[B];
+    D X = ramp(rows * s.Dm), Y = ramp(rows * s.Dm);
+    Arr<int64_t> o_begin(B + 1, 0), one_each(B + 1, 0);
+    for (int64_t b = 0; b < B; ++b) { o_begin.p[b + 1] = o_begin.p[b] + (shared ? queries[0] : queries[b]); one_each.p[b + 1] = b + 1; }
+    const size_t Mo = (size_t)o_begin.p[B], Mq = shared ? (size_t)queries[0] : Mo;
+    D Xq = ramp(Mq * s.Dm);
+    gpt::stub_fail_model = failed;
+    gpt::stub_fail_surrogate = failed_surrogate;
+    for (int mask : {0, 7, 1, 2, 4}) {
+        begin("gpt_batch_fold_scan " + s.name() + (shared ? " shared" : " ragged") + " M=" + std::to_string(Mq) + " surrogate=" +
+              std::to_string(surrogate) + " outputs=" + std::to_string(mask) + (failed >= 0 ? " failed=" + std::to_string(failed) : "") +
+              (failed_surrogate >= 0 ? " failed_surrogate=" + std::to_string(failed_surrogate) : ""));
+        D min_det(B, SENT), err_sum(B, SENT), err_max(B, SENT), det(Mo, SENT), z(Mo * s.Dm, SENT), err(Mo, SENT);
+        Arr<int64_t> argmin(B, (int64_t)ISENT), n_fold(B, (int64_t)ISENT);
+        Arr<int> status(B, ISENT), sur_status(B, ISENT);
+        const bool with_null = !surrogate && (mask & 1);                 // without the surrogate its outputs may be NULL
+        done(gpt_batch_fold_scan(0, X.p, Y.p, in.n_begin.p, B, s.Dm, in.ls.p, s.n_ls, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF,
+                                 Mq ? Xq.p : nullptr, shared ? nullptr : o_begin.p, shared ? queries[0] : -1, surrogate, min_det.p, argmin.p,
+                                 n_fold.p, with_null ? nullptr : err_sum.p, with_null ? nullptr : err_max.p, mask & 1 ? det.p : nullptr,
+                                 mask & 2 ? z.p : nullptr, mask & 4 ? err.p : nullptr, status.p, with_null ? nullptr : sur_status.p), GPT_OK);
+        check_status(status, failed);
+        check_slices(min_det, one_each, 1, failed);
+        for (int64_t b = 0; b < B; ++b) {
+            const bool ran = b != failed, sur_ran = ran && surrogate && b != failed_surrogate;
+            CHECK(argmin.p[b] == (ran ? 0 : (int64_t)ISENT) && n_fold.p[b] == (ran ? 0 : (int64_t)ISENT));
+            CHECK(sur_status.p[b] == (!ran || !surrogate ? ISENT : (b == failed_surrogate ? GPT_E_NOT_PD : GPT_OK)));
+            CHECK(err_sum.p[b] == (sur_ran ? 0.0 : SENT) && err_max.p[b] == (sur_ran ? 0.0 : SENT));
+            CHECK(err.all(sur_ran && (mask & 4) ? 0.0 : SENT, (size_t)o_begin.p[b], (size_t)o_begin.p[b + 1]));
+        }
+        if (mask & 1) check_slices(det, o_begin, 1, failed);
+        else CHECK(det.all(SENT));
+        if (mask & 2) check_slices(z, o_begin, s.Dm, failed);
+        else CHECK(z.all(SENT));
+    }
+    gpt::stub_fail_model = -1;
+    gpt::stub_fail_surrogate = -1;
+}
+
+void fold_scan_refusals() {
+    BatchShape s{{1, 32, 33}, 3, 3, 3};
+    BatchInputs in(s);
+    D X = ramp(66 * 4), Y = ramp(66 * 4), Xq = ramp(5 * 3), out(3, SENT);
+    Arr<int64_t> iout(3, (int64_t)ISENT), q_begin{0, 1, 3, 5};
+    Arr<int> status(3, ISENT);
+    auto call = [&](const int64_t* nb, int64_t B, int Dm, int ktype, const double* xq, const int64_t* qb, int64_t M, int surrogate, double* es) {
+        return gpt_batch_fold_scan(0, X.p, Y.p, nb, B, Dm, in.ls.p, Dm, in.c.p, in.noise.p, 1e-10, ktype, xq, qb, M, surrogate, out.p, iout.p, iout.p,
+                                   es, es, nullptr, nullptr, nullptr, status.p, status.p);
+    };
+    begin("gpt_batch_fold_scan refuses D = 4"); done(call(in.n_begin.p, 3, 4, GPT_KERNEL_RBF, Xq.p, q_begin.p, 0, 0, nullptr), GPT_E_ARG);
+    begin("gpt_batch_fold_scan refuses a Matern batch"); done(call(in.n_begin.p, 3, 3, GPT_KERNEL_MATERN32, Xq.p, q_begin.p, 0, 0, nullptr), GPT_E_ARG);
+    Arr<int64_t> too_many{0, 129};
+    D X129 = ramp(129 * 3);
+    begin("gpt_batch_fold_scan refuses n_b = 129");
+    done(gpt_batch_fold_scan(0, X129.p, X129.p, too_many.p, 1, 3, in.ls.p, 3, in.c.p, in.noise.p, 1e-10, GPT_KERNEL_RBF, Xq.p, nullptr, 5, 0, out.p,
+                             iout.p, iout.p, nullptr, nullptr, nullptr, nullptr, nullptr, status.p, nullptr), GPT_E_ARG);
+    Arr<int64_t> falling{0, 3, 2, 5};
+    begin("gpt_batch_fold_scan refuses a falling q_begin"); done(call(in.n_begin.p, 3, 3, GPT_KERNEL_RBF, Xq.p, falling.p, 0, 0, nullptr), GPT_E_ARG);
+    D nanq(Xq);
+    nanq.p[14] = std::nan("");
+    begin("gpt_batch_fold_scan refuses NaN in Xq (ragged)"); done(call(in.n_begin.p, 3, 3, GPT_KERNEL_RBF, nanq.p, q_begin.p, 0, 0, nullptr), GPT_E_ARG);
+    begin("gpt_batch_fold_scan refuses NaN in Xq (shared)"); done(call(in.n_begin.p, 3, 3, GPT_KERNEL_RBF, nanq.p, nullptr, 5, 0, nullptr), GPT_E_ARG);
+    begin("gpt_batch_fold_scan refuses M < 0"); done(call(in.n_begin.p, 3, 3, GPT_KERNEL_RBF, Xq.p, nullptr, -1, 0, nullptr), GPT_E_ARG);
+    begin("gpt_batch_fold_scan refuses err_sum = NULL with the surrogate");
+    done(call(in.n_begin.p, 3, 3, GPT_KERNEL_RBF, Xq.p, q_begin.p, 0, 1, nullptr), GPT_E_ARG);
+    CHECK(out.all(SENT) && iout.all((int64_t)ISENT) && status.all(ISENT));
 }
 
 // ---- select -------------------------------------------------------------------------------------------------------------------
@@ -1003,6 +1125,21 @@ int main() {
     batch_opt_cases({sizes4, 15, 1, 16}, 7, 2, 1);                         // the runs of one model start where it is not PD
     batch_opt_cases({sizes4, 15, 15, 16}, 9, 5, 0);                        // the largest record; the only large model fails
     batch_opt_refusals();
+    batch_opt_bounded_cases({{10}, 2, 2, 2}, 1, 1, -1);                    // R = 1
+    batch_opt_bounded_cases({sizes3, 1, 1, 1}, 7, 3, -1);                  // R a multiple of nothing: both size classes, several slices
+    batch_opt_bounded_cases({sizes4, 3, 3, 3}, 13, 4, 1);                  // the runs of one model start where it is not PD
+    for (int surrogate : {0, 1}) {
+        for (auto [Dm, n_ls] : {std::array<int, 2>{1, 1}, std::array<int, 2>{2, 2}, std::array<int, 2>{3, 1}}) {
+            fold_scan_cases({sizes3, Dm, n_ls, Dm}, {0, 64, 65}, false, surrogate, -1, -1);     // B odd: an empty member, a full tile, one past it
+            fold_scan_cases({sizes4, Dm, n_ls, Dm}, {65, 1, 0, 129}, false, surrogate, -1, -1); // B even
+        }
+        for (int M : {0, 1, 65}) fold_scan_cases({sizes3, 3, 3, 3}, {M}, true, surrogate, -1, -1);   // shared queries: M = 0, 1, a tile and one
+        fold_scan_cases({sizes4, 2, 2, 2}, {129}, true, surrogate, 2, -1);                      // a member that is not positive definite
+        fold_scan_cases({sizes4, 3, 3, 3}, {65, 64, 1, 65}, false, surrogate, 0, -1);
+    }
+    fold_scan_cases({sizes3, 2, 2, 2}, {65}, true, 1, -1, 1);              // the surrogate alone is not positive definite
+    fold_scan_cases({sizes4, 3, 1, 3}, {1, 65, 64, 0}, false, 1, 3, 1);    // ... beside a member that is not
+    fold_scan_refusals();
     select_cases();
     svgp_cases("gpt_svgp", gpt_svgp_train, gpt_svgp_elbo_grad, false);
     svgp_cases("gpt_svgp_surface", gpt_svgp_surface_train, gpt_svgp_surface_elbo_grad, true);

@@ -225,6 +225,18 @@ extern "C" int gpt_batch_optimize(int, const double*, const double*, const int64
     gpt::set_last_error("gpt_batch_optimize: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_batch_optimize_bounded(int, const double*, const double*, const int64_t*, int64_t, int, int, int, const int*, const double*,
+                                          int64_t, const double*, double, int, double, double, int, int, int, double*, double*, int*, int*,
+                                          int*) {
+    gpt::set_last_error("gpt_batch_optimize_bounded: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_batch_fold_scan(int, const double*, const double*, const int64_t*, int64_t, int, const double*, int, const double*,
+                                   const double*, double, int, const double*, const int64_t*, int64_t, int, double*, int64_t*, int64_t*,
+                                   double*, double*, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_batch_fold_scan: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_pullback_chain_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, int64_t, double, int, double,
                                       double*, double*, double*, int*, double*, double*, double*, double*, double*, double*, double*,
                                       double*, int*, int*, double*, double*) {
@@ -272,6 +284,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 // the program through stub_check.
 #include "../gpt_batch.h"
 #include "../gpt_batch_opt.h"
+#include "../gpt_fold_scan.h"
 #include "../gpt_select.h"
 #include "../gpt_svgp_train.h"
 #include "../gpt_svgp_surface.h"
@@ -338,9 +351,10 @@ void launch_bat_optimize(hipStream_t, int, int n_small, int n_large, const BatOp
     const size_t P = 2 + (size_t)a.n_ls, rec = bat_opt_record((int)P);
     stub_opt_launch_count += (n_small > 0) + (n_large > 0);                      // one launch per size class present
     stub_check(n_small + n_large >= 1 && a.evals_per_launch >= 1 && a.max_ls == BAT_OPT_MAX_LS);
-    touch_r(a.bounds, 2 * P * 8);
+    stub_check(a.bounds_stride == 0 || a.bounds_stride == (int64_t)(2 * P));     // one box for all runs, or one per run
     for (int k = 0; k < n_small + n_large; ++k) {
         const int r = a.list[k], b = a.run_model[r];
+        touch_r(a.bounds + (int64_t)r * a.bounds_stride, 2 * P * 8);
         const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0;
         stub_check(n >= 1 && n <= (k < n_small ? BAT_SMALL_N : BAT_MAX_N));      // the LDS image of the size class
         stub_check(k == 0 || a.list[k - 1] < r || k == n_small);                  // a run once per launch: each class in rising order
@@ -356,6 +370,54 @@ void launch_bat_optimize(hipStream_t, int, int n_small, int n_large, const BatOp
         touch_w(a.lml + r, 8); touch_w(a.iters + r, 4);
         a.evals[r] = cn[1];
         a.status[r] = not_pd ? GPT_OPT_NOT_PD_START : GPT_OPT_PGTOL;
+    }
+}
+
+// ---- gpt_fold_scan.hip --------------------------------------------------------------------------------------------------------
+// Test only (oneshot_driver.cpp): the batch member whose surrogate matrix alone reports GPT_E_NOT_PD (-1: none).
+int stub_fail_surrogate = -1;
+void launch_fs_factor(hipStream_t, int n_small, int n_large, const FoldScanArgs& a) {
+    stub_check(a.D >= 1 && a.D <= FS_MAX_D && (a.surrogate == 0) == (a.Xs == nullptr) && (a.surrogate == 0) == (a.sur_status == nullptr));
+    for (int k = 0; k < n_small + n_large; ++k) {
+        const int b = a.list[k];
+        const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0;
+        stub_check(n >= 1 && n <= (k < n_small ? BAT_SMALL_N : BAT_MAX_N));      // the LDS image of the size class
+        touch_r(a.X + n0 * a.D, n * a.D * 8); touch_r(a.Y + n0 * a.D, n * a.D * 8);
+        touch_r(a.ls + (int64_t)b * a.n_ls, a.n_ls * 8); touch_r(a.c + b, 8); touch_r(a.noise + b, 8);
+        if (b == stub_fail_model) { a.status[b] = GPT_E_NOT_PD; continue; }       // fs_factor leaves before the surrogate's pass
+        touch_w(a.alpha + n0 * a.D, n * a.D * 8);
+        a.status[b] = GPT_OK;
+        if (!a.surrogate) continue;
+        touch_r(a.Xs + n0 * a.D, n * a.D * 8); touch_r(a.Ys + n0 * a.D, n * a.D * 8);
+        if (b == stub_fail_surrogate) { a.sur_status[b] = GPT_E_NOT_PD; continue; }
+        touch_w(a.beta + n0 * a.D, n * a.D * 8);
+        a.sur_status[b] = GPT_OK;
+    }
+}
+void launch_fs_scan(hipStream_t, int tiles_small, int tiles_large, int64_t B, const FoldScanArgs& a) {
+    for (int t = 0; t < tiles_small + tiles_large; ++t) {
+        const int b = a.tile_model[t];
+        if (a.status[b] != GPT_OK) continue;
+        const int64_t n0 = a.n_begin[b], n = a.n_begin[b + 1] - n0, ob = a.o_begin[b], Mb = a.o_begin[b + 1] - ob, q0 = a.tile_q0[t];
+        stub_check(n >= 1 && n <= (t < tiles_small ? BAT_SMALL_N : BAT_MAX_N));
+        stub_check(q0 >= 0 && q0 < Mb && q0 % BAT_QT == 0 && t == a.tile_first[b] + q0 / BAT_QT);
+        const bool sur = a.surrogate && a.sur_status[b] == GPT_OK;
+        const int64_t nq = (Mb - q0 < BAT_QT ? Mb - q0 : BAT_QT), row = ob + q0;
+        touch_r(a.X + n0 * a.D, n * a.D * 8); touch_r(a.alpha + n0 * a.D, n * a.D * 8);
+        if (sur) { touch_r(a.Xs + n0 * a.D, n * a.D * 8); touch_r(a.beta + n0 * a.D, n * a.D * 8); }
+        touch_r(a.ls + (int64_t)b * a.n_ls, a.n_ls * 8); touch_r(a.c + b, 8);
+        touch_r(a.Xq + ((a.shared ? 0 : ob) + q0) * a.D, nq * a.D * 8);
+        touch_w(a.det ? a.det + row : nullptr, nq * 8); touch_w(a.z ? a.z + row * a.D : nullptr, nq * a.D * 8);
+        if (sur) touch_w(a.err ? a.err + row : nullptr, nq * 8);
+        touch_w(a.part + (int64_t)t * FS_PART_D, FS_PART_D * 8); touch_w(a.ipart + (int64_t)t * FS_PART_I, FS_PART_I * 4);
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        if (a.status[b] != GPT_OK) continue;
+        const int64_t Mb = a.o_begin[b + 1] - a.o_begin[b], nt = (Mb + BAT_QT - 1) / BAT_QT;
+        stub_check(nt == 0 || a.tile_model[a.tile_first[b]] == b);
+        touch_r(a.part + (int64_t)a.tile_first[b] * FS_PART_D, nt * FS_PART_D * 8); touch_r(a.ipart + (int64_t)a.tile_first[b] * FS_PART_I, nt * FS_PART_I * 4);
+        touch_w(a.min_det + b, 8); touch_w(a.argmin + b, 8); touch_w(a.n_fold + b, 8);
+        if (a.surrogate && a.sur_status[b] == GPT_OK) { touch_w(a.err_sum + b, 8); touch_w(a.err_max + b, 8); }
     }
 }
 

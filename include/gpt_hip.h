@@ -268,6 +268,44 @@ int gpt_batch_optimize(int device, const double* X, const double* Y, const int64
                        int kernel_type, double pgtol, double ftol, int max_iter, int max_evals, int evals_per_launch, double* theta,
                        double* lml, int* iterations, int* evaluations, int* status);
 
+/* (new) gpt_batch_optimize_bounded — gpt_batch_optimize with a box per run: run_bounds (R, 2 + n_ls, 2) in place of `bounds`, run r
+ * searching inside run_bounds[r] (the same checks per run: finite, lo <= hi, the start clipped to the run's own box).  It is the
+ * same kernel reading `bounds + run * stride` (gpt_batch_optimize: stride 0), so a run's five outputs equal, bit for bit, those of
+ * gpt_batch_optimize called with that run's box as the shared one, whatever the other runs, their order or evals_per_launch.
+ * For searches whose candidates differ in their bounds, e.g. a ceiling on the length-scale per candidate
+ * (GaussianProcessTransportationDiffeo.optimize_diffeomorphism).  Device memory: 16 (2 + n_ls) bytes per run more. */
+int gpt_batch_optimize_bounded(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D, int O, int n_ls,
+                               const int* run_model, const double* theta0, int64_t R, const double* run_bounds, double alpha_jitter,
+                               int kernel_type, double pgtol, double ftol, int max_iter, int max_evals, int evals_per_launch,
+                               double* theta, double* lml, int* iterations, int* evaluations, int* status);
+
+/* (new) gpt_batch_fold_scan — does the displacement map x -> x + psi_b(x) of each of B small GPs fold, and how badly does the
+ * reference's inverse surrogate undo it: the scoring of policy_transportation/transportation/
+ * gaussian_process_transportation_diffeomorphic.py (check_invertibility :109-121, diffeomorphism_error :123-137) for B candidate
+ * models in one call, reduced on the device to five numbers per model.  Layout, limits and status as the batch family above
+ * (ragged models, 1 <= n_b <= 128, fp64, hyper-parameters per model), with O = D <= 3 (Y (sum n_b, D): a displacement) and RBF
+ * only (GPT_E_ARG on a Matern batch, as the derivatives of gpt_batch_predict).  Queries: q_begin == NULL: every model scans the
+ * same M queries Xq (M, D) and the per-query outputs are (B, M, ..); otherwise ragged as gpt_batch_predict (q_begin (B + 1),
+ * M = q_begin[B] ignored).  B M_b summed < 2^31.
+ *   per model: K(X_b) factored, alpha = K^-1 Y_b; surrogate != 0: also the GP on inputs X_b + Y_b (rounded to fp64) with targets
+ *   -Y_b at the same hyper-parameters (:115-117), beta = K(X_b + Y_b)^-1 (-Y_b);
+ *   per query x: psi = k(x, X_b) alpha, J = d psi / d x, det = det(I + J) (closed form), z = x + psi; with the surrogate
+ *   err = |psi + k(z, X_b + Y_b) beta|_2 (:118-120);
+ *   per model: min_det (B), argmin (B; the lowest query index attaining it), n_fold (B; queries with det <= 0), err_sum (B; the
+ *   reference's number), err_max (B).  A model without queries: +infinity, -1, 0, 0, 0.
+ *   det (sum M_b), z (sum M_b, D), err (sum M_b): optional (NULL).
+ * status (B): GPT_E_NOT_PD: all of the model's outputs stay untouched.  surrogate_status (B): the same for the surrogate's
+ * matrix; then err, err_sum and err_max stay untouched, everything else is computed.  surrogate == 0: err, err_sum, err_max and
+ * surrogate_status are not touched and may be NULL.  The return value is GPT_OK whenever the batch ran.
+ * A query's det, z and err do not depend on the other queries or the batch; a model's five numbers do not depend on the batch
+ * around it nor on which optional arrays are asked for: every sum and minimum runs in an order fixed by (n_b, D, M_b), bit for bit.
+ * Device memory: the inputs, 16 n_b D bytes per model, 32 bytes per 64 queries, and the optional arrays. */
+int gpt_batch_fold_scan(int device, const double* X, const double* Y, const int64_t* n_begin, int64_t B, int D,
+                        const double* length_scale, int n_ls, const double* constant_value, const double* noise_level,
+                        double alpha_jitter, int kernel_type, const double* Xq, const int64_t* q_begin, int64_t M, int surrogate,
+                        double* min_det, int64_t* argmin, int64_t* n_fold, double* err_sum, double* err_max, double* det, double* z,
+                        double* err, int* status, int* surrogate_status);
+
 /* predict — replaces GaussianProcess.predict (gaussian_process.py:46-55 -> sklearn/_gpr.py:441-494).
  * mean (M,O); var (M,) = max(c + noise_level - |L^-1 k*|^2, 0) (the caller applies sqrt, the
  * tiling over O and the reference's `- sqrt(noise_level)` quirk).  var may be NULL. Host memory. */
