@@ -300,7 +300,7 @@ int prepare_i8(gpt_handle* h, int64_t M, VarI8PlanDev* plan) {
     *plan = build_var_i8_plan(M, h->p.NP / I8_ROWS, P);
     hipStream_t s = h->stream;
     CALLCHK(reserve(h->i8.slab, (size_t)plan->ncb * plan->nbi * I8_COLS * sizeof(double), s));
-    CALLCHK(reserve(h->i8.bimg, (size_t)P * var_i8_bimg_bytes(h->p.NP), s));
+    CALLCHK(reserve(h->i8.bimg, (size_t)var_i8_image_count(*plan) * var_i8_bimg_bytes(h->p.NP), s));
     CALLCHK(reserve(h->i8.park, (size_t)P * var_i8_park_bytes(), s));
     return GPT_OK;
 }

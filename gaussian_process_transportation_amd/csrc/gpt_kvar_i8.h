@@ -9,14 +9,17 @@
 //     file in that order (the k order inside a step only has to be the same on both sides).
 //   * A planes: [modulus j][tile (ib, kb), kb <= ib][step s 0..8)[row group g 0..8)[row tile r 0..4)[lane] x 16 B — the tiles of
 //     an i-block are consecutive, so a sweep reads one contiguous stream per wave: 4 KiB per step.
-//   * a workgroup (512 threads, 8 waves, 2 per SIMD) owns a 128-column block: wave w accumulates the 64 x 128 product of its
-//     64-row group, 4 x 8 MFMA tiles = 128 int32 accumulators per lane.  The moduli are the OUTER loop of an i-block: one
-//     accumulator set, reduced modulo m_j when the sweep of modulus j ends and parked as one byte per element (4 elements per
-//     dword, in a per-workgroup global buffer that only the writing lane reads back); after the 14th the lane rebuilds its 128
-//     integers (Garner, fp32 — every intermediate is an integer below 2^24 — then Horner in fp64), scales, squares and sums.
-//   * B planes: generated once per column block (fp64 k*, the generating code of k_var, then 14 residues) into a per-workgroup
-//     image in fragment order, [modulus][step][column tile 0..8)[lane] x 16 B, and staged from there through a double-buffered
-//     LDS chunk of one 512-k tile (64 KiB), one barrier per tile; the next chunk is copied piecewise between the MFMA steps.
+//   * B planes: k_i8_gen writes the images of a group of column blocks before their sweeps start (fp64 k*, the generating code of
+//     k_var, then 14 residues), one workgroup per (block, 512 sources), 4 waves per SIMD: [block][modulus][step][column tile 0..8)
+//     [lane] x 16 B, fragment order.  The sweeps stage an image through a double-buffered LDS chunk of one 512-k tile (64 KiB),
+//     one barrier per tile; the next chunk is copied piecewise between the MFMA steps.
+//   * k_var_i8, the sweeps: a workgroup (512 threads, 8 waves, 2 per SIMD) takes items (gpt_plan_i8.h): a 128-column block and
+//     one or two ranges of i-blocks — in a whole group the pair {nbi - 1 - q, q}, nbi + 1 tiles whatever q; in the tail a
+//     contiguous range.  Wave w accumulates the 64 x 128 product of its 64-row group, 4 x 8 MFMA tiles = 128 int32 accumulators
+//     per lane.  The moduli are the OUTER loop of an i-block: one accumulator set, reduced modulo m_j when the sweep of modulus j
+//     ends and parked as one byte per element (4 elements per dword, in a per-workgroup global buffer that only the writing lane
+//     reads back); after the 14th the lane rebuilds its 128 integers (Garner, fp32 — every intermediate is an integer below 2^24
+//     — then Horner in fp64), scales, squares and sums into the slab slot [block][i-block].
 //   * diagonal tile: row group g has nothing beyond step g; a wave runs an even number of steps there, (g + 2) & ~1 (the A ring
 //     below is four deep, indexed by step & 3, and turned back by two slots behind a sweep that ran 2 or 6 of them), row groups
 //     paired (0,7)(1,6)(2,5)(3,4) on the SIMDs as in k_var: 10 of 16 steps.
@@ -43,6 +46,7 @@ constexpr size_t I8_PARK_WORDS = var_i8_park_bytes() / 4;                // dwor
 // reconstruction, 6 = 3 with the LDS reads of the B fragments hoisted out of the steps as well (MFMAs only); 7 and 8 split the two
 // VALU phases into arithmetic and memory: 7 the generation without its plane stores, 8 reduce and reconstruction without the park
 // stores and loads.
+// 4 and 7 act on k_i8_gen (4: not launched; the sweeps then read images nobody wrote), the others on k_var_i8.
 #ifndef GPT_ABL_I8
 #define GPT_ABL_I8 0
 #endif
@@ -155,72 +159,99 @@ struct VarI8Args {
     int ntiles;                   // nbi (nbi + 1) / 2
 };
 
+// ---- the images of the kernel columns -----------------------------------------------------------------------------------------
+// Steps [s_lo, s_hi) of column block cb's image: k* in fp64 as k_var's generating sweep computes it, B' = rint(k* 2^(p - f)), 14
+// residue planes.  Wave w generates column tile w; a lane its column's 16 consecutive sources per step.  Columns past M repeat
+// column M - 1.  Tt: the exp2 table in LDS.
+template <int KT>
+static __device__ __forceinline__ void i8_gen_columns(const KernelParams& p, const VarI8Args& a, const int64_t cb, const int w, const int lane,
+                                                      const int s_lo, const int s_hi, v4i* __restrict__ bim, const int nst, const double* Tt) {
+    constexpr double RS2 = 0.70710678118654752440;
+    const int lc = lane & 15, lk = lane >> 4, D = p.D;
+    const double lnc = p.lnc;
+    const int64_t col = cb * I8_COLS + 16 * w + lc;
+    const int64_t mm = col < a.M ? col : a.M - 1;
+    const double* qp = a.Xq + mm * D;
+    double q[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) q[d] = qp[d < D ? d : 0] * ((d < D) ? p.inv_ls[d] * 0.70710678118654752440 : 0.0);
+#pragma unroll 1
+    for (int s = s_lo; s < (I8_ABL_NOGEN ? s_lo : s_hi); ++s) {
+        const double* xp = a.Xs + (size_t)(I8_KSTEP * s + 16 * lk) * 4;
+        double x[16];
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const d4 xs = *reinterpret_cast<const d4*>(xp + 4 * b);
+            const double d0 = xs[0] * RS2 - q[0], d1 = xs[1] * RS2 - q[1], d2_ = xs[2] * RS2 - q[2];
+            double hh = d0 * d0;
+            hh = fma(d1, d1, hh);
+            hh = fma(d2_, d2_, hh);
+            x[b] = rint(kernel_tab<KT>(hh, lnc, Tt) * a.bq);
+        }
+        i8_store_planes<!I8_ABL_NOPLANEST>(x, bim + ((size_t)s * 8 + w) * 64 + lane, (size_t)nst * I8_B_STEP);
+    }
+}
+
+// One workgroup per (column block cb0 + blockIdx.x, i-block blockIdx.y = 512 sources = 8 steps): image blockIdx.x of a.bimg.  A
+// streaming VALU-and-store loop without accumulators: 4 waves per SIMD (128 VGPRs), so that the stores of one wave hide behind the
+// arithmetic of three others.
+template <int KT>
+__global__ __launch_bounds__(512, 4) void k_i8_gen(KernelParams p, VarI8Args a, int64_t cb0) {
+    __shared__ double Tt[256];
+    const int tid = threadIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (tid < 256) Tt[tid] = g_exp2_table[tid];
+    __syncthreads();
+    const int nst = p.NP / I8_KSTEP;
+    v4i* const bim = a.bimg + (size_t)blockIdx.x * ((size_t)I8_NMOD * nst * I8_B_STEP);
+    const int s_lo = I8_TILE_STEPS * (int)blockIdx.y;
+    i8_gen_columns<KT>(p, a, cb0 + blockIdx.x, w, tid & 63, s_lo, s_lo + I8_TILE_STEPS, bim, nst, Tt);
+}
+
+// ---- the sweeps --------------------------------------------------------------------------------------------------------------
+// KT takes no part any more (the images arrive generated); the instantiations keep their names for the ISA checks of tools/.
 template <int KT>
 __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev pl, VarI8Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char i8_lds_raw[];
     v4i* const Bs = reinterpret_cast<v4i*>(i8_lds_raw);                 // [buffer 0..2)[step 0..8)[column tile 0..8)[lane]
     __shared__ double red[8][I8_COLS];
-    __shared__ double Tt[256];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lc = lane & 15, lk = lane >> 4;
     const int g = (w < 4) ? w : (11 - w);                               // row group of this wave: 0,1,2,3,7,6,5,4
-    const int nbi = pl.nbi, D = p.D;
+    const int nbi = pl.nbi;
     const int nst = p.NP / I8_KSTEP;                                    // steps of a whole B plane
-    if (tid < 256) Tt[tid] = g_exp2_table[tid];
-    v4i* const bim = a.bimg + (size_t)blockIdx.x * ((size_t)I8_NMOD * nst * I8_B_STEP);
-    unsigned* const pk = a.park + (size_t)blockIdx.x * I8_PARK_WORDS + tid;
+    unsigned* const pk = a.park + (size_t)blockIdx.x * I8_PARK_WORDS;     // (wave-uniform; a lane's word sits at utid + 512 x slot)
     const size_t a_plane = (size_t)a.ntiles * I8_TILE_STEPS * I8_A_STEP;        // v4i per A plane
     // operand streams are addressed as a wave-uniform base (scalar registers) plus a 32-bit lane offset: no 64-bit pointer per lane
     const v4i* const a_group = a.planes + (size_t)g * 256;
     const unsigned ulane = lane, utid = tid;
-    constexpr double RS2 = 0.70710678118654752440;
-    const double lnc = p.lnc;
-    const int64_t n_rounds = pl.rnd_end - pl.rnd_begin;
+    const int npairs = (nbi + 1) >> 1, nsteps = pl.step_end - pl.step_begin;
+    const int64_t n_items = (pl.rnd_end - pl.rnd_begin) * nsteps;
 
     for (int64_t it = 0;; ++it) {
-        int64_t cb; int ib_lo, ib_hi;
-        if (it < n_rounds) {
-            cb = (pl.rnd_begin + it) * pl.P + blockIdx.x; ib_lo = 0; ib_hi = nbi;
+        // an item: column block cb, i-blocks [lo0, hi0) then [lo1, hi1), each walked downward (var_i8_group_item, var_i8_tail_item)
+        int64_t cb; int lo0, hi0, lo1, hi1;
+        if (it < n_items) {
+            const int64_t t = (int64_t)(pl.step_begin + (int)(it % nsteps)) * pl.P + blockIdx.x;
+            const int q = (int)(t % npairs);
+            cb = (pl.rnd_begin + it / nsteps) * pl.P + t / npairs;
+            hi0 = nbi - q; lo0 = hi0 - 1; lo1 = q; hi1 = q < lo0 ? q + 1 : q;      // (odd nbi: the middle i-block is alone)
         } else {
-            if (it > n_rounds || !pl.with_tail || pl.nparts <= 0) break;
+            if (it > n_items || !pl.with_tail || pl.nparts <= 0) break;
             const int64_t c = blockIdx.x / pl.nparts;
             if (c >= pl.ncb - pl.nfull) break;
             const int q = blockIdx.x % pl.nparts;
-            cb = pl.nfull + c; ib_lo = pl.bounds[q]; ib_hi = pl.bounds[q + 1];
+            cb = pl.nfull + c; lo0 = pl.bounds[q]; hi0 = pl.bounds[q + 1]; lo1 = hi1 = 0;
         }
-        // ---- the block's kernel columns: k* in fp64 as k_var's generating sweep computes it, B' = rint(k* 2^(p - f)), 14 residue planes.
-        // Wave w generates column tile w; a lane its column's 16 consecutive sources per step.  The image changes owner: its
-        // writers and readers are the waves of this workgroup (one CU), workgroup scope orders them (see k_var).
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        {
-            const int64_t col = cb * I8_COLS + 16 * w + lc;
-            const int64_t mm = col < a.M ? col : a.M - 1;
-            const double* qp = a.Xq + mm * D;
-            double q[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) q[d] = qp[d < D ? d : 0] * ((d < D) ? p.inv_ls[d] * 0.70710678118654752440 : 0.0);
-#pragma unroll 1
-            for (int s = 0; s < (I8_ABL_NOGEN ? 0 : I8_TILE_STEPS * ib_hi); ++s) {
-                const double* xp = a.Xs + (size_t)(I8_KSTEP * s + 16 * lk) * 4;
-                double x[16];
-#pragma unroll
-                for (int b = 0; b < 16; ++b) {
-                    const d4 xs = *reinterpret_cast<const d4*>(xp + 4 * b);
-                    const double d0 = xs[0] * RS2 - q[0], d1 = xs[1] * RS2 - q[1], d2_ = xs[2] * RS2 - q[2];
-                    double hh = d0 * d0;
-                    hh = fma(d1, d1, hh);
-                    hh = fma(d2_, d2_, hh);
-                    x[b] = rint(kernel_tab<KT>(hh, lnc, Tt) * a.bq);
-                }
-                i8_store_planes<!I8_ABL_NOPLANEST>(x, bim + ((size_t)s * 8 + w) * 64 + lane, (size_t)nst * I8_B_STEP);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        // the block's image: k_i8_gen wrote it in an earlier kernel of this stream, for the blocks rnd_begin P .. of this launch
+        const v4i* const bim = a.bimg + (size_t)(cb - pl.rnd_begin * pl.P) * ((size_t)I8_NMOD * nst * I8_B_STEP);
 
-        for (int ib = ib_hi - 1; ib >= ib_lo; --ib) {
+        for (int ib = hi0 - 1, lo = lo0, second = 0;; --ib) {
+            if (ib < lo) {
+                if (second || hi1 <= lo1) break;
+                second = 1; ib = hi1 - 1; lo = lo1;
+            }
             const int nmine = (g + 2) & ~1;                             // steps of the diagonal tile this wave runs (even)
             const int lim = I8_TILE_STEPS * ib + nmine;                 // steps of a sweep this wave runs
             const size_t tile0 = (size_t)ib * (ib + 1) / 2;
@@ -342,7 +373,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                             for (int e = 0; e < 4; ++e) rr[e] = i8_acc_bits(acc[r][t][e], T, j);
                             const unsigned pw = i8_pack_bits(rr[0], rr[1], rr[2], rr[3]);
                             if (I8_ABL_NOPARK) asm volatile("" ::"v"(pw));
-                            else pk[(size_t)(j * 32 + r * 8 + t) * 512] = pw;
+                            else pk[utid + 512u * (unsigned)(j * 32 + r * 8 + t)] = pw;
                             acc[r][t] = v4i{0, 0, 0, 0};
                         }
                 }
@@ -370,7 +401,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
 #pragma unroll
                     for (int j = 0; j < I8_NMOD; ++j) {
                         if (I8_ABL_NOPARK) asm volatile("" : "=v"(wd[j]));
-                        else wd[j] = pk[(size_t)(j * 32 + r * 8 + t) * 512];
+                        else wd[j] = pk[utid + 512u * (unsigned)(j * 32 + r * 8 + t)];
                     }
                     const d4 rs = *reinterpret_cast<const d4*>(a.rowscale + (size_t)ib * I8_ROWS + 64 * g + 16 * r + 4 * lk);
 #pragma unroll

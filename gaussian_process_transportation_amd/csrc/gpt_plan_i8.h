@@ -6,18 +6,22 @@
 // product is formed modulo 14 pairwise coprime moduli that fit int8 — one int8 GEMM per modulus, int32 sums — and rebuilt by
 // Garner's mixed-radix conversion.  DESIGN.md section 4 has the derivation; tests/var_int8_restatement.py restates it in numpy.
 //
-// Work split: a workgroup owns a 128-column block and walks the 512-row i-blocks, longest first, as k_var does.  Every
-// (column block, i-block) pair writes its 128 column sums to a slab slot of its own, [cb][ib], and the finalizing kernel adds a
-// column's nbi slots in i-block order: integer partial sums are exact and the fp64 sums have one fixed grouping, so ANY
-// assignment of the pairs to workgroups gives the same bits.
-//   * Rounds: while at least P column blocks are left, workgroup p takes block r P + p whole (all workgroups walk the W planes
-//     in step: an XCD shares one copy of that stream in L2).
-//   * Tail: the ncb_t < P blocks that are left get floor(P / ncb_t) workgroups each (at most nbi); the i-blocks of a block are
-//     dealt to its workgroups in contiguous ranges of about equal cost.  Rows are independent given the kernel columns, so a part
-//     generates the columns it needs again and nothing has to be combined.
+// Work split.  Every (column block, i-block) pair writes its 128 column sums to a slab slot of its own, [cb][ib], and the
+// finalizing kernel adds a column's nbi slots in i-block order: integer partial sums are exact and the fp64 sums have one fixed
+// grouping, so ANY assignment of the pairs to workgroups gives the same bits.  The images of the kernel columns are written by a
+// kernel of their own (k_i8_gen) for a group of blocks at a time, so the i-blocks of a block can go to several workgroups.
+//   * Rounds: while at least P column blocks are left, the next P are a group.  It is dealt as items (block, i-blocks {nbi - 1 - q, q}):
+//     nbi + 1 tiles each, ceil(nbi / 2) per block, workgroup b taking items b, b + P, ... (var_i8_group_item).  Workgroups b, b + 8, ...
+//     share an XCD; when the pairs per block divide P they hold the same two i-blocks and walk the same tiles of the W planes in
+//     step, one copy of that stream in the XCD's L2.
+//   * Tail: the ncb_t < P blocks that are left are a group of their own and get floor(P / ncb_t) workgroups each (at most nbi); the
+//     i-blocks of a block are dealt to its workgroups in contiguous ranges of about equal cost (var_i8_tail_item).
+//   * Launches: a group's images, then its sweeps — GPT_VAR_ROUNDS_PER_LAUNCH / GPT_VAR_ROUNDS_EXACT groups at a time, and
+//     GPT_VAR_ITEM_STEPS_PER_LAUNCH item steps of them per launch of the sweep kernel.
 #pragma once
 #include <cstdint>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 namespace gpt {
@@ -55,8 +59,9 @@ inline bool var_i8_shape_ok(int NP) {
     return NP >= I8_ROWS && NP % I8_ROWS == 0 && NP / I8_ROWS <= I8_MAX_NBI && var_i8_bits(NP) >= I8_MIN_BITS;
 }
 
-// Device images, in bytes: the residue planes of W (one byte per element of the block lower triangle and modulus); and per
-// workgroup the planes of a column block's kernel columns and the parked residues of an i-block (512 x 128 elements x 14 bytes).
+// Device images, in bytes: the residue planes of W (one byte per element of the block lower triangle and modulus); per column
+// block of a group the planes of its kernel columns (var_i8_image_count of them); and per workgroup the parked residues of an
+// i-block (512 x 128 elements x 14 bytes).
 inline size_t var_i8_plane_bytes(int NP) { const size_t nb = NP / I8_ROWS; return (size_t)I8_NMOD * (nb * (nb + 1) / 2) * I8_ROWS * I8_ROWS; }
 inline size_t var_i8_bimg_bytes(int NP) { return (size_t)I8_NMOD * NP * I8_COLS; }
 constexpr size_t var_i8_park_bytes() { return (size_t)I8_NMOD * I8_ROWS * I8_COLS; }
@@ -70,8 +75,31 @@ struct VarI8PlanDev {
     int bounds[I8_MAX_NBI + 1];      // part q of a tail block takes the i-blocks [bounds[q], bounds[q + 1])
     // the part of the plan one launch executes (launch_var_i8: rounds are dealt to several launches, the tail goes with the last)
     int64_t rnd_begin = 0, rnd_end = 0;
+    int step_begin = 0, step_end = 0;     // item steps of each of those rounds (var_i8_group_item)
     int with_tail = 1;
 };
+
+// Rounds one launch of the sweep kernel takes.  GPT_VAR_ROUNDS_PER_LAUNCH counts rounds of 136 tiles as in launch_var (0: all in one
+// launch); GPT_VAR_ROUNDS_EXACT counts rounds as they are.  Both are read per call.  The images of every block of a launch exist
+// before it starts (k_i8_gen), so the count is held to what I8_IMAGE_BUDGET bytes of images allow, and to one round at least.
+constexpr size_t I8_IMAGE_BUDGET = (size_t)4 << 30;
+inline int64_t var_i8_rounds_per_launch(const VarI8PlanDev& d) {
+    const int64_t rounds = d.nfull / d.P;
+    const int64_t ntiles = (int64_t)d.nbi * (d.nbi + 1) / 2;
+    const char* e = std::getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
+    const int rpl_set = e ? (std::atoi(e) < 0 ? 0 : std::atoi(e)) : 1;
+    const int64_t rpl_scaled = ((int64_t)rpl_set * 136 + ntiles - 1) / ntiles;
+    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
+    if (const char* x = std::getenv("GPT_VAR_ROUNDS_EXACT")) { if (std::atoi(x) > 0) rpl = std::atoi(x); }
+    const int64_t fit = (int64_t)(I8_IMAGE_BUDGET / ((size_t)d.P * var_i8_bimg_bytes(d.nbi * I8_ROWS)));
+    if (rpl > fit) rpl = fit;
+    if (rpl > rounds) rpl = rounds;
+    return rpl < 1 ? 1 : rpl;
+}
+// images the launches of this plan need at once: the rounds of one launch, or the tail's blocks (a group of their own)
+inline int64_t var_i8_image_count(const VarI8PlanDev& d) {
+    return d.nfull > 0 ? var_i8_rounds_per_launch(d) * d.P : d.ncb - d.nfull;
+}
 
 inline int var_i8_iblock_cost(int ib) { return ib + 1 + I8_SWEEP_FIXED; }
 
@@ -114,6 +142,48 @@ inline bool var_i8_tail_item(const VarI8PlanDev& d, int wg, int64_t* cb, int* ib
     const int q = wg % d.nparts;
     *cb = d.nfull + c; *ib_lo = d.bounds[q]; *ib_hi = d.bounds[q + 1];
     return true;
+}
+
+// ---- items of a whole group (round) of P blocks -----------------------------------------------------------------------------
+// i-blocks q and nbi - 1 - q have nbi + 1 tiles together, whatever q: a block is npairs = ceil(nbi / 2) items of equal work (at odd
+// nbi the middle i-block is an item alone).  Item t of a group is block t / npairs with the i-blocks {nbi - 1 - q, q}, q = t % npairs;
+// workgroup wg takes the items wg, wg + P, ...: one per item step, npairs steps per group.  Co-resident workgroups hold consecutive
+// items, and when npairs divides P a workgroup keeps its q.  An item is at most two contiguous i-block ranges, [lo[r], hi[r]), walked
+// in order r = 0, 1 and downward inside a range; a tail part is an item with one range.  img: the block's image among those that
+// k_i8_gen wrote for the launch (the blocks of the launch's rounds; the tail's blocks in a launch of their own).
+struct VarI8Item {
+    int64_t cb, img;
+    int lo[2], hi[2];
+};
+inline int var_i8_npairs(int nbi) { return (nbi + 1) / 2; }
+inline VarI8Item var_i8_group_item(const VarI8PlanDev& d, int64_t round, int step, int wg) {
+    const int npairs = var_i8_npairs(d.nbi);
+    const int64_t t = (int64_t)step * d.P + wg;
+    const int q = (int)(t % npairs);
+    VarI8Item x{};
+    x.cb = round * d.P + t / npairs;
+    x.img = x.cb - d.rnd_begin * d.P;
+    x.hi[0] = d.nbi - q; x.lo[0] = x.hi[0] - 1;
+    x.lo[1] = q; x.hi[1] = q < x.lo[0] ? q + 1 : q;
+    return x;
+}
+// the tail part of workgroup wg as an item; false: nothing
+inline bool var_i8_tail_as_item(const VarI8PlanDev& d, int wg, VarI8Item* x) {
+    int lo, hi;
+    if (!var_i8_tail_item(d, wg, &x->cb, &lo, &hi)) return false;
+    x->img = x->cb - d.nfull;
+    x->lo[0] = lo; x->hi[0] = hi; x->lo[1] = x->hi[1] = 0;
+    return true;
+}
+// Item steps of a group that go into one launch: GPT_VAR_ITEM_STEPS_PER_LAUNCH, read per call (0 or more than npairs: all of them).
+// One, measured at N = 8192, M = 500 000 (profiles/var_int8_items_profile.txt: ms per step 235.7 / 236.4 / 238.5 / 239.9 for 1 / 2 / 4 /
+// all 8 steps per launch): as with the rounds, a kernel boundary brings the workgroups of an XCD back in step on the A stream.
+constexpr int I8_DEFAULT_ITEM_STEPS = 1;
+inline int var_i8_item_steps_per_launch(const VarI8PlanDev& d) {
+    const int npairs = var_i8_npairs(d.nbi);
+    const char* e = std::getenv("GPT_VAR_ITEM_STEPS_PER_LAUNCH");
+    const int v = e ? std::atoi(e) : I8_DEFAULT_ITEM_STEPS;
+    return v <= 0 || v > npairs ? npairs : v;
 }
 
 }  // namespace gpt

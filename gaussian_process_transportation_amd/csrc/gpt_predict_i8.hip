@@ -26,24 +26,32 @@ void launch_var_i8(hipStream_t s, const KernelParams& p, const VarI8PlanDev& pla
     a.bq = std::ldexp(1.0, bits - f);
     a.colscale = std::ldexp(1.0, f - bits);
     a.ntiles = plan.nbi * (plan.nbi + 1) / 2;
-    // rounds per launch, in rounds of 136 tiles as in launch_var: workgroups that drift apart stop sharing the A stream in L2, and a
-    // kernel boundary brings them together.  One round, measured on this kernel at N = 8192, M = 500 000 (profiles/var_int8_feed.txt:
-    // var_ms 277.2 / 280.8 / 285.6 / 287.6 / 289.2 for 1 / 2 / 3 / 4 / 16 = all in one launch; launch_var's 16 had been inherited unmeasured)
+    // rounds per launch (var_i8_rounds_per_launch): workgroups that drift apart stop sharing the A stream in L2, and a kernel boundary
+    // brings them together.  One round, measured on this kernel at N = 8192, M = 500 000 (profiles/var_int8_feed.txt: var_ms 277.2 /
+    // 280.8 / 285.6 / 287.6 / 289.2 for 1 / 2 / 3 / 4 / 16 = all in one launch; launch_var's 16 had been inherited unmeasured)
     const int64_t rounds = plan.nfull / plan.P;
-    const char* e = getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
-    const int rpl_set = e ? (atoi(e) < 0 ? 0 : atoi(e)) : 1;
-    const int64_t rpl_scaled = ((int64_t)rpl_set * 136 + a.ntiles - 1) / a.ntiles;
-    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
-    if (const char* x = getenv("GPT_VAR_ROUNDS_EXACT")) { if (atoi(x) > 0) rpl = atoi(x); }
-    for (int64_t r0 = 0; r0 == 0 || r0 < rounds; r0 += rpl) {
+    const int64_t rpl = var_i8_rounds_per_launch(plan);
+    const int npairs = var_i8_npairs(plan.nbi), spl = var_i8_item_steps_per_launch(plan);
+    // a group's images (k_i8_gen), then the sweeps of its items; the tail's blocks are a group of their own
+    auto group = [&](int64_t r0, int64_t r1, int64_t nimg, bool tail) {
         VarI8PlanDev pl = plan;
-        pl.rnd_begin = r0;
-        pl.rnd_end = r0 + rpl < rounds ? r0 + rpl : rounds;
-        pl.with_tail = pl.rnd_end >= rounds ? 1 : 0;
+        pl.rnd_begin = r0; pl.rnd_end = r1; pl.with_tail = tail ? 1 : 0;
         with_kernel_type(p.ktype, [&](auto kt) {
-            launch_lds<k_var_i8<decltype(kt)::value>>(dim3((unsigned)plan.P), dim3(512), I8_LDS_BYTES, s, p, pl, a);
+            constexpr int KT = decltype(kt)::value;
+            if (!I8_ABL_NOGEN)
+                hipLaunchKernelGGL(k_i8_gen<KT>, dim3((unsigned)nimg, (unsigned)plan.nbi), dim3(512), 0, s, p, a, r0 * plan.P);
+            for (int k0 = 0; k0 == 0 || (!tail && k0 < npairs); k0 += spl) {
+                pl.step_begin = tail ? 0 : k0;
+                pl.step_end = tail ? 0 : (k0 + spl < npairs ? k0 + spl : npairs);
+                launch_lds<k_var_i8<KT>>(dim3((unsigned)plan.P), dim3(512), I8_LDS_BYTES, s, p, pl, a);
+            }
         });
+    };
+    for (int64_t r0 = 0; r0 < rounds; r0 += rpl) {
+        const int64_t r1 = r0 + rpl < rounds ? r0 + rpl : rounds;
+        group(r0, r1, (r1 - r0) * plan.P, false);
     }
+    if (plan.ncb > plan.nfull) group(rounds, rounds, plan.ncb - plan.nfull, true);
     hipLaunchKernelGGL(k_var_i8_finalize, dim3((unsigned)plan.ncb), dim3(I8_COLS), 0, s, p, plan.nbi, slab, M, hdr, var);
 }
 

@@ -157,7 +157,7 @@ void launch_var_i8(hipStream_t, const KernelParams& p, const VarI8PlanDev& plan,
     touch_r(planes, var_i8_plane_bytes(p.NP)); touch_r(rowscale, (size_t)p.NP * 8); touch_r(Xs, (size_t)p.NP * 4 * 8);
     touch_r(Xq, (size_t)M * p.D * 8); touch_r(hdr, 17 * 8);
     touch_w(slab, (size_t)plan.ncb * plan.nbi * I8_COLS * 8);
-    touch_w(bimg, (size_t)plan.P * var_i8_bimg_bytes(p.NP)); touch_w(park, (size_t)plan.P * var_i8_park_bytes());
+    touch_w(bimg, (size_t)var_i8_image_count(plan) * var_i8_bimg_bytes(p.NP)); touch_w(park, (size_t)plan.P * var_i8_park_bytes());
     touch_w(var, (size_t)M * 8);
 }
 
