@@ -54,22 +54,10 @@ template <> struct El<float> {
     typedef f4 v4;
     typedef f4 avec;
     static constexpr int A_STEP = 512, A_GROUP = 64;
-#ifndef GPT_F32_SUBS
-#define GPT_F32_SUBS 4
-#endif
-#ifndef GPT_F32_PF
-#define GPT_F32_PF 4
-#endif
-    static constexpr int SUBS = GPT_F32_SUBS;              // 2 x 32 steps x 1 KiB = 64 KiB (64-step chunks measured 4 % slower: profiles/r02_svgp_variants.txt)
-    static constexpr int PF = GPT_F32_PF;                  // an fp32 MFMA block lasts 512 cycles, less than an L2 round trip under load
-#ifndef GPT_F32_DIAG_LDS
-#define GPT_F32_DIAG_LDS 1
-#endif
-    static constexpr bool DIAG_LDS = GPT_F32_DIAG_LDS != 0;   // diagonal tiles of the reload sweeps: B image (128 KiB) staged in LDS
-#ifndef GPT_F32_BATCH_PROLOGUE
-#define GPT_F32_BATCH_PROLOGUE 1
-#endif
-    static constexpr bool BATCH_PROLOGUE = GPT_F32_BATCH_PROLOGUE != 0;
+    static constexpr int SUBS = 4;                         // 2 x 32 steps x 1 KiB = 64 KiB (64-step chunks measured 4 % slower: profiles/r02_svgp_variants.txt)
+    static constexpr int PF = 4;                           // an fp32 MFMA block lasts 512 cycles, less than an L2 round trip under load
+    static constexpr bool DIAG_LDS = true;                 // diagonal tiles: B image (128 KiB) staged in LDS
+    static constexpr bool BATCH_PROLOGUE = true;           // a reload sweep's first chunk: its four loads in flight together (short fp32 sweeps)
     struct AF { f4 v; };
     static __device__ __forceinline__ void lda(AF& a, const avec* __restrict__ p, const int lane) { a.v = p[lane]; }
     static __device__ __forceinline__ void keep(const AF& a, const v4& b) { asm volatile("" :: "v"(a.v), "v"(b)); }
@@ -121,10 +109,11 @@ template <> struct El<float> {
 //   * the A operand streams from the fragment-ordered image Wf with 16-byte loads per lane,
 //     two k-steps ahead; in the diagonal tile a wave skips the k-steps where its row group is
 //     entirely above the diagonal (wave g has 16 (g + 1) of 128), row groups paired (0,7)(1,6)(2,5)(3,4) on
-//     the SIMDs.  In the reload sweeps the diagonal tile runs OUTSIDE the lock-step LDS pipeline (every wave
-//     on its own, B straight from the scratch image), so the pairing balances it: 0.56 of a full tile
-//     instead of 0.75 (+2.7 %) — since round 4 in every sweep, and 0.52: the last 16 k-steps of a wave's range are its own lower-
-//     triangular 64 x 64 block, whose zero 16 x 16 blocks get no MFMA (GPT_DIAG_TRIANGLE);
+//     the SIMDs.  In every sweep the diagonal tile runs OUTSIDE the lock-step LDS pipeline (every wave on its own; B from the
+//     scratch image, to which a generating sweep writes the tile's fragments first — fp64 straight from there, small models with the
+//     first half staged in LDS, fp32 with the whole tile's image staged in LDS), so the pairing balances it: 0.56 of a full tile
+//     instead of 0.75 (+2.7 %).  And 0.52: the last 16 k-steps of a wave's range are its own lower-triangular 64 x 64 block, whose
+//     zero 16 x 16 blocks get no MFMA (not in the instantiations at the register limit: TRI_OK below);
 //   * work split: gpt_plan.h (rounds of whole blocks, then an explicit item list cut at quarter tiles — inside diagonal tiles
 //     too where a workgroup's share is small).
 // Alternatives measured and dropped (profiles/r01_kvar_variant_ab.txt): per-wave B generation (v1, 53 TF),
@@ -139,36 +128,18 @@ template <> struct El<float> {
 // (wide path, NCOMP = 4 for D = 4 and 8 for D = 8): the Jacobian variance alone, dk_0 .. dk_{D-1} without the k* column —
 // half the columns of the fused layout at exactly those two dimensions.
 // ------------------------------------------------------------------------------------------
-// Timing-only ablation builds (results are wrong unless 0): -DGPT_ABL=1 no per-chunk barrier, 2 no A-operand
-// loads, 3 diagonal tile skipped, 4 no B fill (LDS image left as is), 5 no MFMAs, 6 every wave 72 steps in the diagonal
-// tile of a reload sweep (the work of a SIMD's pair split evenly).  tools/gpu_ablate.sh,
-// profiles/r01_final_ablation.txt.
+// Timing-only ablation builds (results are wrong unless 0), every live number:
+//   -DGPT_ABL=1 no per-chunk barrier, 2 no A-operand loads in the lock-step loop, 3 diagonal tile skipped, 4 no B fill (LDS image
+//   left as is), 5 no MFMAs, 6 every wave 72 steps in a diagonal tile (the work of a SIMD's pair split evenly)
+//   (make ablate, tools/gpu_ablate.sh, profiles/r01_final_ablation.txt);
+//   7 generating sweep without the exp (the squared distance itself is stored), 8 no copy of the generated fragments to the scratch
+//   image, 9 no fold of the accumulators into the column sums (small models: tools/small_n_probe.py);
+//   12 the diagonal tile without its A stream (past its first 8 k-steps), 13 the diagonal tile without its B reads.
 #ifndef GPT_ABL
 #define GPT_ABL 0
 #endif
-// Further timing-only ablations (round 4, small models: tools/small_n_probe.py): 7 generating sweep without the exp (the
-// squared distance itself is stored), 8 no copy of the generated fragments to the scratch image, 9 no fold of the
-// accumulators into the column sums.
 // -DGPT_VAR_TRACE (make trace): shader-clock stamps (s_memtime) of every wave of two workgroups at the phase boundaries of
 // their first VT_ITEMS items, written to the buffer set through gpt_debug_set_var_trace.
-#ifndef GPT_DIAG_TRIANGLE
-#define GPT_DIAG_TRIANGLE 1      // diagonal tiles: no MFMAs for the 16 x 16 blocks above the diagonal of a wave's own 64 x 64 block
-#endif
-#ifndef GPT_GEN_DIAG_FREE
-#define GPT_GEN_DIAG_FREE 1      // generating sweeps: diagonal tile barrier-free after its fragments went to the scratch image
-#endif
-#ifndef GPT_GEN_ROLLED
-#define GPT_GEN_ROLLED 1         // openings of a generating sweep: one rolled copy of the generating code (instruction cache)
-#endif
-#ifndef GPT_GEN_BATCH_PROLOGUE
-#define GPT_GEN_BATCH_PROLOGUE 1 // generating sweeps: the first chunk's four source loads in flight together
-#endif
-#ifndef GPT_GEN_STAGED_EXP
-#define GPT_GEN_STAGED_EXP 1     // openings of a generating sweep: the four exps of a lane stage by stage
-#endif
-#ifndef GPT_DIAG_RING
-#define GPT_DIAG_RING 4          // fp64 barrier-free diagonal tile: operand ring depth (2 = the loop of rounds 1-3)
-#endif
 #ifdef GPT_VAR_TRACE
 constexpr int VT_STAMPS = 16, VT_ITEMS = 24, VT_WGS = 2;
 __device__ long long* g_var_trace = nullptr;
@@ -199,7 +170,12 @@ template <typename T> constexpr size_t var_lds_bytes() {
 // fp64 Matern kernels with derivative columns: they sit at the register limit (their generating code keeps more alive: r, the
 // column kind).  Without the diagonal triangle, with the 2-deep ring of the diagonal tile and with late source loads (wide rows)
 // no spill code is left in a hot loop (tools/check_isa_spills.py; with the RBF kernels' settings 2 - 8 reloads sat in them).
-// (A namespace-scope constant: as a local constexpr read inside k_var's lambdas it changed the code hipcc emits for RBF kernels.)
+// (A namespace-scope constant: as a local constexpr read inside k_var's lambdas it changed the code hipcc emits for RBF kernels.
+// The mechanism, for whoever edits the kernel: its lambdas capture by reference, in the order of first use — and inside the generic
+// ones a name in an expression that depends on the lambda's parameter is captured even where a constant would do.  Which of k_var's
+// locals a closure holds, and in what order, reaches the instruction order and the register numbers of the code hipcc emits,
+// although the closures themselves are optimised away.  A helper that names a local in a new place — even inside a branch that is
+// compiled out — therefore changes kernels it never runs in; tools/device_isa_diff.py against the parent commit shows which.)
 template <typename T, int NCOMP, int KT>
 constexpr bool kvar_tight = NCOMP != 1 && KT != KT_RBF && std::is_same<T, double>::value;
 
@@ -304,8 +280,8 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
             // image are the waves of THAT workgroup, i.e. of one CU, and its vector L1 is coherent among them (a store through the
             // L1 updates or drops the line it hits; AMDGPU memory model, non-tgsplit mode: "no special action is required for
             // coherence between wavefronts in the same work-group") — so workgroup scope is the scope that is needed: ordering, no
-            // cache invalidation.  Until round 4 this was an AGENT-scope acquire (buffer_inv sc1): 20 000 - 35 000 clocks at the
-            // opening of every block, 3 % of the kernel at N = 1024 (ablation 10 in profiles/r04_small_n.txt).
+            // cache invalidation.  (An AGENT-scope acquire, buffer_inv sc1, cost 20 000 - 35 000 clocks at the
+            // opening of every block, 3 % of the kernel at N = 1024: profiles/r04_small_n.txt.)
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
         } else if (flags & VI_GEN) {
             __syncthreads();                               // nobody may still be reading the part of the image rewritten now
@@ -392,9 +368,22 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                 }
             };
             auto load_x = [&](const T* xp) { load_x_to(xp, gx, gx_own); };
-            auto fetch = [&](const int k4) {
-                if (GEN) load_x(Xs + (size_t)(k4 * 4 + lk) * XS);
-                else bl = (buni + (size_t)k4 * 64)[lane];
+            // The exp of a generating sweep: the kernel value of a column from its squared distance hh (scaled: t = ln c - hh).  GCOL:
+            // Matern with derivative columns, where a derivative column (dcol) takes c g(r) and the k* column c k(r), both from one exp
+            // (gpt_exp.h).  One column, or a lane's four with the exps stage by stage (their latencies overlap).  Where the four are taken
+            // one after the other, that loop stands at the call: inside a helper it changed the instruction order of four fp32 wide
+            // Matern 5/2 kernels.  -DGPT_ABL=7 stores the squared distance itself.
+            auto kernel_value = [&](const T hh) -> T {
+                if (GPT_ABL == 7) return hh;
+                if constexpr (GCOL) return kernel_tab_col<KT>(hh, lnc, Tt, dcol);
+                else return kernel_tab<KT>(hh, lnc, Tt);
+            };
+            auto kernel_values_staged = [&](T (&hh)[4], T (&kv)[4]) {
+                if (GPT_ABL == 7) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) kv[t] = hh[t];
+                } else if constexpr (GCOL) kernel_tab4_col<KT>(hh, lnc, Tt, dcol, kv);
+                else kernel_tab4<KT>(hh, lnc, Tt, kv);
             };
             // B fragments of k-step k4 -> LDS chunk buffer `buf` (to_lds) and, when generated, the scratch image
             // staged: the four exps of a lane stage by stage (gpt_exp.h kernel_tab4: their latencies overlap — the openings of a
@@ -419,16 +408,10 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                             for (int e = 0; e < 4; ++e) { const T df = fma(xv[e], RS2, -qs[4 * v + e][qi]); hh[t] = fma(df, df, hh[t]); }
                         }
                     }
-                    if constexpr (GCOL) {
-                        if constexpr (staged) kernel_tab4_col<KT>(hh, lnc, Tt, dcol, kv);
-                        else {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t) kv[t] = kernel_tab_col<KT>(hh[t], lnc, Tt, dcol);
-                        }
-                    } else if constexpr (staged) kernel_tab4<KT>(hh, lnc, Tt, kv);
+                    if constexpr (staged) kernel_values_staged(hh, kv);
                     else {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) kv[t] = kernel_tab<KT>(hh[t], lnc, Tt);
+                        for (int t = 0; t < 4; ++t) kv[t] = kernel_value(hh[t]);
                     }
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
@@ -452,16 +435,10 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
 #pragma unroll
                         for (int d = 1; d < DW; ++d) { df = x[d] - qs[d][qi]; hh[t] = fma(df, df, hh[t]); }
                     }
-                    if constexpr (GCOL) {
-                        if constexpr (staged) kernel_tab4_col<KT>(hh, lnc, Tt, dcol, kv);
-                        else {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t) kv[t] = kernel_tab_col<KT>(hh[t], lnc, Tt, dcol);
-                        }
-                    } else if constexpr (staged) kernel_tab4<KT>(hh, lnc, Tt, kv);
+                    if constexpr (staged) kernel_values_staged(hh, kv);
                     else {
 #pragma unroll
-                        for (int t = 0; t < 4; ++t) kv[t] = kernel_tab<KT>(hh[t], lnc, Tt);
+                        for (int t = 0; t < 4; ++t) kv[t] = kernel_value(hh[t]);
                     }
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
@@ -491,14 +468,7 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                             hh[t] = fma(d1[t], d1[t], hh[t]);
                             hh[t] = fma(d2_[t], d2_[t], hh[t]);
                         }
-                        if (GPT_ABL == 7) {
-#pragma unroll
-                            for (int t = 0; t < 4; ++t) kv[t] = hh[t];
-                        } else if constexpr (GCOL) {
-                            kernel_tab4_col<KT>(hh, lnc, Tt, dcol, kv);
-                        } else {
-                            kernel_tab4<KT>(hh, lnc, Tt, kv);
-                        }
+                        kernel_values_staged(hh, kv);
 #pragma unroll
                         for (int t = 0; t < 4; ++t) b[t] = column(t, kv[t], d0[t], d1[t], d2_[t]);
                     } else {
@@ -508,10 +478,7 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                             T hh = d0 * d0;
                             hh = fma(d1, d1, hh);
                             hh = fma(d2_, d2_, hh);
-                            T kv;
-                            if constexpr (GCOL) kv = (GPT_ABL == 7) ? hh : kernel_tab_col<KT>(hh, lnc, Tt, dcol);
-                            else kv = (GPT_ABL == 7) ? hh : kernel_tab<KT>(hh, lnc, Tt);
-                            b[t] = column(t, kv, d0, d1, d2_);
+                            b[t] = column(t, kernel_value(hh), d0, d1, d2_);
                         }
                     }
                     if (to_lds && lds_on) *reinterpret_cast<v4*>(dstl) = b;
@@ -534,7 +501,7 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
 #pragma unroll
                     for (int d = 0; d < (LATE_X ? 1 : DW); ++d) gx[d] = bx[j][d];
                     gx_own = bo[j];
-                    produce_to(lds_tag, std::integral_constant<bool, GPT_GEN_STAGED_EXP != 0>{}, buf, k4_0 + j * stride, to_scr, lds_on);
+                    produce_to(lds_tag, std::true_type{}, buf, k4_0 + j * stride, to_scr, lds_on);
                 }
             };
 
@@ -546,40 +513,34 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
             const int d_lo = (k_lo > VAR_KQ * ib ? k_lo - VAR_KQ * ib : 0) * VAR_CH, d_hi = (k_hi - VAR_KQ * ib) * VAR_CH;
             const int K0 = k_lo * VAR_CH;                                      // first k4-step of this item
             // The diagonal tile (where wave g only has 16 (g + 1) steps of work) runs OUT of the lock-step LDS pipeline: see
-            // below.  A generating sweep first puts that tile's fragments into the scratch image (GEN_DIAG_FREE; until round 4 it
-            // kept the tile inside the lock-step part, where it costs 0.75 of a full tile instead of 0.56).
-            constexpr bool DIAG_FREE = !GEN || GPT_GEN_DIAG_FREE != 0;
-            const int lock_end = ((!DIAG_FREE || !has_diag) ? k_hi : VAR_KQ * ib) * VAR_CH;
+            // below.  A generating sweep first puts that tile's fragments into the scratch image (inside the lock-step part the
+            // tile costs 0.75 of a full one instead of 0.56).
+            // (GEN stands in this expression although both kinds of sweep do the same: without a name that depends on the lambda's
+            // parameter, `sweep` no longer captures VAR_CH, and hipcc then allocates the registers of the fp32 k* kernels differently —
+            // cf. kvar_tight above)
+            const int lock_end = ((GEN ? !has_diag : !has_diag) ? k_hi : VAR_KQ * ib) * VAR_CH;
             const int ch0 = K0 / VAR_CH, ch1 = lock_end / VAR_CH;              // lock-step chunks [ch0, ch1)
             // fp64, small models (HALF: its own instantiation of the kernel, so that the N = 8192 kernel keeps its code and registers):
             // the first 64 k-steps of a diagonal tile's B image go through LDS — see the tile below
             constexpr bool half = HALF && !El<T>::DIAG_LDS;
-            if (GEN && DIAG_FREE && has_diag && GPT_ABL != 3 && !half) {
+            if (GEN && has_diag && GPT_ABL != 3 && !half) {
                 // 128 k-steps (of a whole tile), 16 per wave (w, w + 8, ...), VALU only; complete and visible before the barrier below
                 const int kd0 = ib * WT_K4;
-                if (GPT_GEN_ROLLED != 0) {
 #pragma unroll 1
-                    for (int j = d_lo / VAR_SUB; j < d_hi / VAR_SUB; ++j)
-                        generate_batch(std::false_type{}, std::integral_constant<int, 1>{}, 0, kd0 + w + VAR_SUB * j, VAR_SUB);
-                } else {
-#pragma unroll 1
-                    for (int j0 = d_lo / VAR_SUB; j0 < d_hi / VAR_SUB; j0 += 4)
-                        generate_batch(std::false_type{}, std::integral_constant<int, 4>{}, 0, kd0 + w + VAR_SUB * j0, VAR_SUB);
-                }
+                for (int j = d_lo / VAR_SUB; j < d_hi / VAR_SUB; ++j)
+                    generate_batch(std::false_type{}, std::integral_constant<int, 1>{}, 0, kd0 + w + VAR_SUB * j, VAR_SUB);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             GPT_VT(10);
             if (ch1 > ch0) {                                  // first chunk: wave w fills steps w, w+8, w+16, w+24
-                if (GEN && GPT_GEN_ROLLED != 0) {
+                if (GEN) {
                     // ONE copy of the generating code, run VAR_SUBS times: the opening of a sweep is straight-line code that runs once
                     // per block, i.e. from a cold instruction cache — its time followed its LENGTH, not its arithmetic (four k-steps
                     // unrolled and batched: 40 000 clocks; twenty: 60 000; serial or staged exps: no difference — r04_small_n.txt)
 #pragma unroll 1
                     for (int j = 0; j < VAR_SUBS; ++j)
                         generate_batch(std::true_type{}, std::integral_constant<int, 1>{}, ch0 & 1, K0 + j * VAR_SUB + w, VAR_SUB);
-                } else if (GEN && GPT_GEN_BATCH_PROLOGUE != 0) {
-                    generate_batch(std::true_type{}, std::integral_constant<int, VAR_SUBS>{}, ch0 & 1, K0 + w, VAR_SUB);
-                } else if (!GEN && El<T>::BATCH_PROLOGUE) {
+                } else if (El<T>::BATCH_PROLOGUE) {
                     // the four reloads in flight together instead of load -> wait -> write four times (short fp32 sweeps:
                     // 12 per block at configs[4], each opening with this latency)
                     v4 pre[VAR_SUBS];
@@ -588,9 +549,10 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
 #pragma unroll
                     for (int j = 0; j < VAR_SUBS; ++j) *reinterpret_cast<v4*>(Bs(ch0 & 1, (K0 + j * VAR_SUB + w) % VAR_CH)) = pre[j];
                 } else {
+                    // (fp64: measured in round 1, no gain from batching on its long sweeps)
 #pragma unroll
                     for (int j = 0; j < VAR_SUBS; ++j) {
-                        fetch(K0 + j * VAR_SUB + w);
+                        bl = (buni + (size_t)(K0 + j * VAR_SUB + w) * 64)[lane];
                         produce(ch0 & 1, K0 + j * VAR_SUB + w);
                     }
                 }
@@ -667,7 +629,7 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
             for (int ch = ch0; ch + 1 < ch1; ++ch) chunk(std::true_type{}, ch);
             if (ch1 > ch0) chunk(std::false_type{}, ch1 - 1);
             GPT_VT(4);
-            if (DIAG_FREE && has_diag && GPT_ABL != 3) {
+            if (has_diag && GPT_ABL != 3) {
                 // Diagonal tile, barrier-free: every wave runs its own 16 (g + 1) k-steps on its own.  No
                 // lock-step, so the waves with g and 7 - g that share a SIMD add up to the same work on every SIMD: the tile
                 // costs 0.56 of a full one instead of the 0.75 it costs inside the lock-step pipeline.
@@ -687,7 +649,7 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                 // nothing, so results are the same to the bit.  body(first row tile with work, k4) runs RR steps from k4.
                 // (Not in the instantiations that sit at the register limit — cross terms, the fp64 3-column kernel, wide Matern, fp64
                 // Matern derivatives: the peeled steps cost them a spilled pointer inside the ring loop, tools/check_isa_spills.py.)
-                constexpr bool TRI_OK = GPT_DIAG_TRIANGLE != 0 && !CROSS && !(std::is_same<T, double>::value && NCOMP == 3) && !(WIDE && KT != KT_RBF) && !kvar_tight<T, NCOMP, KT>;
+                constexpr bool TRI_OK = !CROSS && !(std::is_same<T, double>::value && NCOMP == 3) && !(WIDE && KT != KT_RBF) && !kvar_tight<T, NCOMP, KT>;
                 const bool tri = TRI_OK && limit == lim_g && limit > d_lo && GPT_ABL != 6;
                 auto tri_loop = [&](auto rtag, const int k_begin, const int k_end, const bool tri_end, auto&& body) {
                     constexpr int RR = decltype(rtag)::value;
@@ -750,9 +712,10 @@ __global__ __launch_bounds__(512, 2) void k_var(KernelParams p, VarPlanDev pl, c
                         if (GPT_ABL == 13 && k >= d_lo + 8) return;
                         b = (bp + (size_t)kk * 64)[lane];
                     };
-                    // (2: the round-1 .. 3 loop, kept for A/B — and for the 3-column kernel, whose generating side keeps more state alive:
-                    // with the deeper ring hipcc reloads a spilled pointer inside the loop, and that reload's wait drains the ring)
-                    constexpr int R = (NCOMP == 3 || kvar_tight<T, NCOMP, KT>) ? 2 : GPT_DIAG_RING;
+                    // operand ring depth: 4, or 2 = the loop of rounds 1-3 for the 3-column kernel and the register-tight ones, whose generating
+                    // side keeps more state alive: with the deeper ring hipcc reloads a spilled pointer inside the loop, and that reload's
+                    // wait drains the ring
+                    constexpr int R = (NCOMP == 3 || kvar_tight<T, NCOMP, KT>) ? 2 : 4;
                     if constexpr (half) {
                         // Small models (N <= 2560): the B images of an XCD's 32 workgroups (0.5 MB each at N = 1024) do not stay in its
                         // 4 MB of L2, a diagonal tile read straight from the scratch image is 576 wave-steps x 2 KiB from beyond L2, the

@@ -74,6 +74,22 @@ struct VarPlanDev {
     int with_tail = 1;
 };
 
+// Rounds of whole column blocks that one launch of a variance kernel takes (k_var: launch_var_t; k_var_i8 with its image budget on
+// top: gpt_plan_i8.h).  GPT_VAR_ROUNDS_PER_LAUNCH (default `dflt`; 0: all in one launch) is in rounds of the shape it was measured
+// on — 136 tiles per block, N = 8192; a launch of a smaller model gets as many rounds as make the same number of tiles, so that the
+// boundaries stay ~0.1 % of the run time.  GPT_VAR_ROUNDS_EXACT (tests) counts rounds as they are, whatever the shape.  Both are
+// read per call: tests compare settings in one process.  At most `rounds`, at least 1.
+inline int64_t var_rounds_per_launch(int64_t rounds, int64_t tiles_per_round, int dflt) {
+    const char* e = std::getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
+    const int v = e ? std::atoi(e) : dflt;
+    const int rpl_set = v < 0 ? 0 : v;
+    const int64_t rpl_scaled = tiles_per_round > 0 ? ((int64_t)rpl_set * 136 + tiles_per_round - 1) / tiles_per_round : rpl_set;
+    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : rounds;
+    if (const char* x = std::getenv("GPT_VAR_ROUNDS_EXACT")) { if (std::atoi(x) > 0) rpl = std::atoi(x); }
+    if (rpl > rounds) rpl = rounds;
+    return rpl < 1 ? 1 : rpl;
+}
+
 struct VarPlanHost {
     VarPlanDev d{};
     std::vector<int> item_begin;

@@ -23,6 +23,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <vector>
+#include "gpt_plan.h"
 
 namespace gpt {
 
@@ -79,22 +80,14 @@ struct VarI8PlanDev {
     int with_tail = 1;
 };
 
-// Rounds one launch of the sweep kernel takes.  GPT_VAR_ROUNDS_PER_LAUNCH counts rounds of 136 tiles as in launch_var (0: all in one
-// launch); GPT_VAR_ROUNDS_EXACT counts rounds as they are.  Both are read per call.  The images of every block of a launch exist
-// before it starts (k_i8_gen), so the count is held to what I8_IMAGE_BUDGET bytes of images allow, and to one round at least.
+// Rounds one launch of the sweep kernel takes: the rule of k_var (gpt_plan.h var_rounds_per_launch) with a default of one round.
+// The images of every block of a launch exist before it starts (k_i8_gen), so the count is also held to what I8_IMAGE_BUDGET bytes
+// of images allow, and to one round at least.
 constexpr size_t I8_IMAGE_BUDGET = (size_t)4 << 30;
 inline int64_t var_i8_rounds_per_launch(const VarI8PlanDev& d) {
-    const int64_t rounds = d.nfull / d.P;
-    const int64_t ntiles = (int64_t)d.nbi * (d.nbi + 1) / 2;
-    const char* e = std::getenv("GPT_VAR_ROUNDS_PER_LAUNCH");
-    const int rpl_set = e ? (std::atoi(e) < 0 ? 0 : std::atoi(e)) : 1;
-    const int64_t rpl_scaled = ((int64_t)rpl_set * 136 + ntiles - 1) / ntiles;
-    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
-    if (const char* x = std::getenv("GPT_VAR_ROUNDS_EXACT")) { if (std::atoi(x) > 0) rpl = std::atoi(x); }
+    const int64_t rpl = var_rounds_per_launch(d.nfull / d.P, (int64_t)d.nbi * (d.nbi + 1) / 2, 1);
     const int64_t fit = (int64_t)(I8_IMAGE_BUDGET / ((size_t)d.P * var_i8_bimg_bytes(d.nbi * I8_ROWS)));
-    if (rpl > fit) rpl = fit;
-    if (rpl > rounds) rpl = rounds;
-    return rpl < 1 ? 1 : rpl;
+    return fit < 1 ? 1 : (rpl > fit ? fit : rpl);
 }
 // images the launches of this plan need at once: the rounds of one launch, or the tail's blocks (a group of their own)
 inline int64_t var_i8_image_count(const VarI8PlanDev& d) {

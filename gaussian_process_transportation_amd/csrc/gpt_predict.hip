@@ -153,17 +153,11 @@ __global__ __launch_bounds__(256) void k_mean_jac(KernelParams p, const T* __res
 template <typename T, int DW>
 static void launch_mean_jac_t(hipStream_t s, const KernelParams& p, const T* Xs, const T* A4,
                               const T* Xq, int64_t M, T* mean, T* J) {
-#ifndef GPT_MJ_QPW
-#define GPT_MJ_QPW 2
-#endif
-    constexpr int QPW = DW == 3 ? GPT_MJ_QPW : 1;          // queries per wave; 500k queries at N = 8192: 1 -> 9.17 ms, 2 -> 6.19-6.26, 4 -> 6.11 (r3mj)
-#ifndef GPT_MJ_QPW_MEAN
-#define GPT_MJ_QPW_MEAN 4
-#endif
+    constexpr int QPW = DW == 3 ? 2 : 1;                   // queries per wave; 500k queries at N = 8192: 1 -> 9.17 ms, 2 -> 6.19-6.26, 4 -> 6.11 (r3mj)
     // the mean alone (no Jacobian sums: 3 accumulators per query instead of 12): more queries per wave when there are waves enough
     // (M >= 32 768: 8 per SIMD), so that a small model's short source loop (16 iterations at N = 1024) is not dwarfed by the wave's
     // prologue and its cross-lane reductions.  N = 1024, M = 50 000: 0.071 -> 0.064 ms; at M = 10^4 four per wave LOSE 7 - 10 % (r4s38)
-    constexpr int QPW_M = DW == 3 ? GPT_MJ_QPW_MEAN : 1;
+    constexpr int QPW_M = DW == 3 ? 4 : 1;
     const bool many = !J && M >= 32768 && QPW_M != QPW;
     const int qpw = many ? QPW_M : QPW;
     const int64_t waves = (M + qpw - 1) / qpw;
@@ -290,13 +284,6 @@ __global__ __launch_bounds__(64) void k_var_finalize(KernelParams p, VarPlanDev 
     }
 }
 
-// rounds of whole column blocks per launch of k_var (0: all in one launch); see launch_var_t
-static int var_rounds_per_launch() {
-    const char* e = getenv("GPT_VAR_ROUNDS_PER_LAUNCH");          // read per call: tests compare settings in one process
-    const int v = e ? atoi(e) : 16;
-    return v < 0 ? 0 : v;
-}
-
 template <typename T>
 static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspace& ws, const T* Xs, const T* Wf,
                          const T* Xq, int64_t M, int ncomp, T* var, T* Jvar, T* dvar, const double* hdr) {
@@ -309,17 +296,11 @@ static void launch_var_t(hipStream_t s, const KernelParams& p, const VarWorkspac
     // The persistent workgroups are not synchronised between rounds and drift apart; once they are further apart than a W
     // tile stays in L2 each fetches its own copy of the W stream (mode J+Jvar, 122 rounds in one launch: 155 MB fetched per
     // column block against 68 MB for the same kernel over 31 rounds, L2 hit rate 54 % against 78 %).  A kernel boundary is the
-    // one barrier that needs no co-residency: the rounds go out `var_rounds_per_launch()` at a time.  16 per launch: the same
-    // run time (269.9-270.5 k/s in one launch, 270.9-271.3 k/s at 8-16), HBM-side bytes 4.99 -> 1.40 TB per 500k queries,
+    // one barrier that needs no co-residency: the rounds go out `var_rounds_per_launch` (gpt_plan.h) at a time.  16 per launch: the
+    // same run time (269.9-270.5 k/s in one launch, 270.9-271.3 k/s at 8-16), HBM-side bytes 4.99 -> 1.40 TB per 500k queries,
     // L2 hit rate 54 -> 86 % (profiles/r03_kvar_round_drift.txt).
     const int64_t rounds = pl_all.nfull / pl_all.P;
-    // (the setting is in rounds of the shape it was measured on — 136 tiles per block, N = 8192; a launch of a smaller model
-    // gets as many rounds as make the same number of tiles, so that the boundaries stay ~0.1 % of the run time)
-    const int rpl_set = var_rounds_per_launch();
-    const int64_t tiles_per_round = (int64_t)pl_all.ntask * pl_all.tiles_per_task;
-    const int64_t rpl_scaled = tiles_per_round > 0 ? ((int64_t)rpl_set * 136 + tiles_per_round - 1) / tiles_per_round : rpl_set;
-    int64_t rpl = rpl_set > 0 ? (rpl_scaled > rpl_set ? rpl_scaled : rpl_set) : (rounds > 0 ? rounds : 1);
-    if (const char* e = getenv("GPT_VAR_ROUNDS_EXACT")) { if (atoi(e) > 0) rpl = atoi(e); }      // tests: this many, whatever the shape
+    const int64_t rpl = var_rounds_per_launch(rounds, (int64_t)pl_all.ntask * pl_all.tiles_per_task, 16);
     // fp64 diagonal tiles with the first half of their B image in LDS: for models whose scratch images do not stay in L2 (k_var);
     // GPT_VAR_DIAG_HALF = 0 / 1 forces it off / on (read per call: tests compare both in one process)
     constexpr bool HALF_OK = std::is_same<T, double>::value;          // (fp32 stages the whole image of a diagonal tile in LDS: DIAG_LDS)

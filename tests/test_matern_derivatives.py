@@ -216,7 +216,7 @@ def test_self_consistency_on_the_device(nu):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("nu", [1.5, 2.5])
-@pytest.mark.parametrize("D", [3, 5, 12])
+@pytest.mark.parametrize("D", [3, 5, 8, 12])      # 8: the fused layout of 16 columns in rows of 8 (k_var<float, 16, *, KT, 8>)
 def test_fp32_model_against_fp64(nu, D):
     X, Y, Xq = problem(1000, D, seed=20 + D, M=2000)
     c, noise = 0.5, 1e-3

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds libgpt_hip.so and named A/B variants of one source file ON THE BOX, so that every library of a session comes
 # from the sources of the same snapshot.  usage: tools/build_variants.sh [name:file:"-DFLAG ..."] ...
-#   e.g. tools/build_variants.sh kv_old:gpt_predict:"-DGPT_DIAG_RING=2" vtrace:gpt_predict:"-DGPT_VAR_TRACE"
+#   e.g. tools/build_variants.sh abl3:gpt_predict:"-DGPT_ABL=3" vtrace:gpt_predict:"-DGPT_VAR_TRACE"
 # -> csrc/build/libgpt_<name>.so (select with GPT_HIP_LIB)
 set -u
 C=gaussian_process_transportation_amd/csrc

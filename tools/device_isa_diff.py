@@ -5,7 +5,8 @@ kernel: every .amdhsa_kernel symbol present under the same name on both sides, i
 identical.  "The same name" is the demangled one (c++filt) without its namespace qualifiers: a kernel's argument struct that moves
 from the unit's anonymous namespace into a header both halves of the unit include changes the mangled symbol and nothing else.
 Two kernels of a unit that reduce to one such name are an error.  The other tree needs ../../include/gpt_hip.h next to it, as in
-a checkout.  The *_host.hip halves of the one-shot units hold no kernel and are not in the default list.
+a checkout.  The default list is the Makefile's SRCS without its ONESHOT_HOST: the *_host.hip halves of the one-shot units hold no
+kernel.
 usage: python tools/device_isa_diff.py OTHER_CSRC [unit.hip ...]   (CPU only; hipcc cross-compiles; exit 1 on any difference)"""
 import os
 import re
@@ -44,11 +45,17 @@ def kernels(csrc, unit, out):
     return found
 
 
+def makefile_list(name):
+    """The words of the Makefile variable `name` (continuation lines joined), without references to other variables."""
+    text = open(os.path.join(CSRC, "Makefile")).read().replace("\\\n", " ")
+    value = re.search(rf"^{name}\s*=(.*)$", text, flags=re.M).group(1)
+    return [w for w in value.split() if not w.startswith("$(")]
+
+
 def main():
     other = os.path.abspath(sys.argv[1])
-    units = sys.argv[2:] or ["gpt_api.hip", "gpt_fit.hip", "gpt_predict.hip", "gpt_predict_matern.hip", "gpt_svgp_train.hip",
-                             "gpt_svgp_surface.hip", "gpt_select.hip", "gpt_batch.hip", "gpt_batch_opt.hip", "gpt_inverse.hip", "gpt_transport.hip",
-                             "gpt_pullback.hip", "gpt_chain.hip", "gpt_rollout.hip"]
+    host_halves = set(makefile_list("ONESHOT_HOST"))
+    units = sys.argv[2:] or [u for u in makefile_list("SRCS") if u not in host_halves]
     bad = 0
     for unit in [u for u in units if not os.path.exists(os.path.join(other, u))]:
         print(f"{unit}: not in {other} (a new unit): nothing to compare")
