@@ -16,10 +16,13 @@
 //   * k_var_i8, the sweeps: a workgroup (512 threads, 8 waves, 2 per SIMD) takes items (gpt_plan_i8.h): a 128-column block and
 //     one or two ranges of i-blocks — in a whole group the pair {nbi - 1 - q, q}, nbi + 1 tiles whatever q; in the tail a
 //     contiguous range.  Wave w accumulates the 64 x 128 product of its 64-row group, 4 x 8 MFMA tiles = 128 int32 accumulators
-//     per lane.  The moduli are the OUTER loop of an i-block: one accumulator set, reduced modulo m_j when the sweep of modulus j
-//     ends and parked as one byte per element (4 elements per dword, in a per-workgroup global buffer that only the writing lane
-//     reads back); after the 14th the lane rebuilds its 128 integers (Garner, fp32 — every intermediate is an integer below 2^24
-//     — then Horner in fp64), scales, squares and sums into the slab slot [block][i-block].
+//     per lane.  The i-blocks of an item are walked two at a time (gpt_plan_i8.h, "the walk of an item"), and the moduli are the
+//     OUTER loop of such a group: for modulus j the sweep of the group's first i-block, then that of its second, each with the one
+//     accumulator set, reduced modulo m_j when the sweep ends and parked as one byte per element (4 elements per dword, in the
+//     i-block's slot of a per-workgroup global buffer that only the writing lane reads back); after the 14th the lane rebuilds the
+//     128 integers of each i-block (Garner, fp32 — every intermediate is an integer below 2^24 — then Horner in fp64), scales,
+//     squares and sums into the slab slot [block][i-block].  Every pair item of a block so runs nbi + 1 tiles per modulus: the
+//     workgroups that share the block's image stay in one plane of it.
 //   * diagonal tile: row group g has nothing beyond step g; a wave runs an even number of steps there, (g + 2) & ~1 (the A ring
 //     below is four deep, indexed by step & 3, and turned back by two slots behind a sweep that ran 2 or 6 of them), row groups
 //     paired (0,7)(1,6)(2,5)(3,4) on the SIMDs as in k_var: 10 of 16 steps.
@@ -145,6 +148,14 @@ static __device__ __forceinline__ double i8_garner(const float (&r)[I8_NMOD]) {
     return X;
 }
 
+// x of lane (lane ^ m) of the wave, `lane` given by the caller (the low six bits count): what __shfl_xor(x, m) returns, without the
+// lane number that __shfl_xor derives for itself and hipcc keeps in a register from the kernel's entry on
+static __device__ __forceinline__ double i8_lane_xor(const double x, const unsigned lane, const unsigned m) {
+    const int at = (int)(((lane & 63u) ^ m) << 2);
+    const int lo = __builtin_amdgcn_ds_bpermute(at, __double2loint(x)), hi = __builtin_amdgcn_ds_bpermute(at, __double2hiint(x));
+    return __hiloint2double(hi, lo);
+}
+
 struct VarI8Args {
     const v4i* planes;            // A planes
     const double* rowscale;       // 2^(e_i - p)
@@ -209,6 +220,12 @@ __global__ __launch_bounds__(512, 4) void k_i8_gen(KernelParams p, VarI8Args a, 
 }
 
 // ---- the sweeps --------------------------------------------------------------------------------------------------------------
+// where a wave's A fragments come from during one sweep: the sweep's own steps [0, l0) at offset b0 of the A planes (in v4i), then the
+// next sweep's [0, l1) at b1, then the one after at b2 (the A ring runs four steps ahead, across the end of a sweep); wave-uniform
+struct I8Feed {
+    size_t b0, b1, b2;
+    int l0, l1;
+};
 // KT takes no part any more (the images arrive generated); the instantiations keep their names for the ISA checks of tools/.
 template <int KT>
 __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev pl, VarI8Args a) {
@@ -247,23 +264,40 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
         // the block's image: k_i8_gen wrote it in an earlier kernel of this stream, for the blocks rnd_begin P .. of this launch
         const v4i* const bim = a.bimg + (size_t)(cb - pl.rnd_begin * pl.P) * ((size_t)I8_NMOD * nst * I8_B_STEP);
 
-        for (int ib = hi0 - 1, lo = lo0, second = 0;; --ib) {
-            if (ib < lo) {
-                if (second || hi1 <= lo1) break;
-                second = 1; ib = hi1 - 1; lo = lo1;
-            }
+        // The walk (gpt_plan_i8.h): the item's i-blocks two at a time.  A group of ng = 1 or 2 i-blocks is nsw = 14 ng sweeps, the
+        // moduli outermost: sweep sw is modulus sw >> (ng - 1) of the group's i-block sw & (ng - 1), parked in that slot.
+        const int nwalk = var_i8_walk_len(lo0, hi0, lo1, hi1);
+#pragma unroll 1
+        for (int k0 = 0; k0 < nwalk; k0 += 2) {
+            const int um = k0 + 1 < nwalk ? 1 : 0;                      // ng - 1: mask of the slot in sw, shift of the modulus
+            const int nsw = I8_NMOD << um;
+            const int ib0 = var_i8_walk_iblock(lo0, hi0, lo1, hi1, k0);
+            const int ib1 = um ? var_i8_walk_iblock(lo0, hi0, lo1, hi1, k0 + 1) : ib0;
             const int nmine = (g + 2) & ~1;                             // steps of the diagonal tile this wave runs (even)
-            const int lim = I8_TILE_STEPS * ib + nmine;                 // steps of a sweep this wave runs
-            const size_t tile0 = (size_t)ib * (ib + 1) / 2;
-            // A fragments of step S < lim + 4 of modulus j's sweep; past the wave's last step: the first steps of the moduli that follow
-            auto a_ptr = [&](int j, int S) -> const v4i* {
-                if (S >= lim) { S -= lim; ++j; }
-                if (S >= lim) { S -= lim; ++j; }                        // (lim = 2: steps lim + 2, lim + 3 belong to the modulus after the next)
-                if (j >= I8_NMOD) { j = I8_NMOD - 1; S = lim - 1; }     // (past the last sweep: a redundant load, in bounds)
-                if (I8_ABL_A) S &= I8_TILE_STEPS - 1;
-                return a_group + (size_t)j * a_plane + (tile0 * I8_TILE_STEPS + S) * I8_A_STEP;
+            const int lim0 = I8_TILE_STEPS * ib0 + nmine, lim1 = I8_TILE_STEPS * ib1 + nmine;      // steps of a sweep this wave runs
+            const size_t tile0 = (size_t)ib0 * (ib0 + 1) / 2, tile1 = (size_t)ib1 * (ib1 + 1) / 2;
+            // The A stream of sweep sw and of the two behind it, worked out once per sweep: a step between the MFMAs then costs two
+            // compares and four selects of scalar registers, not the products (plane, tile) of its address.  Past the group's last
+            // sweep: that sweep again (a redundant load of its first steps, in bounds).
+            auto feed_of = [&](const int sw) -> I8Feed {
+                auto base = [&](int x) -> size_t {
+                    if (x >= nsw) x = nsw - 1;
+                    return (size_t)(x >> um) * a_plane + ((x & um) ? tile1 : tile0) * (I8_TILE_STEPS * I8_A_STEP);
+                };
+                return I8Feed{base(sw), base(sw + 1), base(sw + 2), (sw & um) ? lim1 : lim0, ((sw + 1) & um) ? lim1 : lim0};
             };
-            // first chunk: modulus 0, tile 0 -> buffer 0 (the last barrier has passed: both buffers are free)
+            // A fragments of step S < lim + 4 of a sweep; past the wave's last step: the first steps of the sweeps that follow (lim = 2:
+            // steps lim + 2, lim + 3 belong to the sweep after the next)
+            auto a_ptr = [&](const I8Feed f, const int S) -> const v4i* {
+                const int S1 = S - f.l0, S2 = S1 - f.l1;
+                size_t b = f.b0;
+                int o = S;
+                if (S1 >= 0) { b = f.b1; o = S1; }
+                if (S2 >= 0) { b = f.b2; o = S2; }
+                if (I8_ABL_A) o &= I8_TILE_STEPS - 1;
+                return a_group + (b + (size_t)(unsigned)o * I8_A_STEP);
+            };
+            // first chunk, once per group: modulus 0, tile 0 -> buffer 0 (the last barrier has passed: both buffers are free)
             {
                 v4i t8[8];
 #pragma unroll
@@ -271,12 +305,12 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) Bs[tid + 512 * i] = t8[i];
             }
-            // The A ring: four slots of four row tiles.  A sweep starts with its steps 0 .. 3 in slots 0 .. 3, step s of a tile reads
+            // The A ring: four slots of four row tiles, filled once per group.  A sweep starts with its steps 0 .. 3 in slots 0 .. 3, step s of a tile reads
             // slot s & 3 (a tile has 8 steps), and behind the diagonal tile's `nmine` steps the ring is turned back (below).
             v4i ar[4][4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const v4i* ap = a_ptr(0, i);
+                const v4i* ap = a_ptr(feed_of(0), i);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) ar[i][r] = ap[ulane + 64 * r];
             }
@@ -305,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
             //   * the A fragments of step s + 4 are requested behind the MFMAs of step s, straight into the ring slot those have
             //     just read: three whole steps, 96 MFMAs of this wave, lie between the request and the first MFMA that waits for
             //     it (loads return in order: the chunk piece requested in front of step s + 1, which comes from HBM, has had as long).
-            auto tile = [&](auto full_tag, const int nrun, const bool more_rt, const int j, const int S0, const v4i* nsrc) __attribute__((always_inline)) {
+            auto tile = [&](auto full_tag, const int nrun, const bool more_rt, const I8Feed fd, const int S0, const v4i* nsrc) __attribute__((always_inline)) {
                 constexpr bool FULL = decltype(full_tag)::value;
                 const bool more = FULL || more_rt;
                 if (I8_ABL_B) nsrc = bim;
@@ -318,7 +352,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                 for (int s = 0; s < I8_TILE_STEPS; ++s) {
                     const bool run = FULL || s < nrun;
                     if (more && s == 0) st[0] = nsrc[utid];
-                    if (more && s + 1 < I8_TILE_STEPS) st[(s + 1) % 3] = nsrc[utid + 512 * (s + 1)];
+                    if (more && s + 1 < I8_TILE_STEPS) st[(s + 1) % 3] = (nsrc + 512 * (s + 1))[utid];      // (the piece's base in scalar registers)
                     __builtin_amdgcn_sched_barrier(0);
                     if (run) {
                         if (!I8_ABL_NOLDS && (s == 0 || !FULL)) {
@@ -339,7 +373,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                     __builtin_amdgcn_sched_barrier(0);
                     if (more && s > 0) bnext[512 * (s - 1)] = st[(s - 1) % 3];
                     if (run) {
-                        const v4i* ap = a_ptr(j, S0 + s + 4);
+                        const v4i* ap = a_ptr(fd, S0 + s + 4);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ar[s & 3][r] = ap[ulane + 64 * r];
                     }
@@ -350,13 +384,18 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                 buf ^= 1;
             };
 #pragma unroll 1
-            for (int j = 0; j < I8_NMOD; ++j) {
+            for (int sw = 0; sw < nsw; ++sw) {
+                const int j = sw >> um, ib = (sw & um) ? ib1 : ib0;
+                unsigned* const pku = pk + ((sw & um) ? I8_PARK_WORDS / 2 : 0);
+                const I8Feed fd = feed_of(sw);
 #pragma unroll 1
                 for (int kb = 0; kb < ib; ++kb)         // full tiles; the next chunk is the next tile of this sweep
-                    tile(Bool<true>{}, I8_TILE_STEPS, true, j, kb * I8_TILE_STEPS, bim + ((size_t)j * nst + (kb + 1) * I8_TILE_STEPS) * I8_B_STEP);
-                // diagonal tile; the next chunk is tile 0 of the next modulus
-                tile(Bool<false>{}, nmine, j + 1 < I8_NMOD, j, ib * I8_TILE_STEPS, bim + (size_t)(j + 1) * nst * I8_B_STEP);
-                // the sweep of modulus j is complete: reduce, park (4 elements of a tile per dword), start over
+                    tile(Bool<true>{}, I8_TILE_STEPS, true, fd, kb * I8_TILE_STEPS, bim + ((size_t)j * nst + (kb + 1) * I8_TILE_STEPS) * I8_B_STEP);
+                // diagonal tile; the next chunk is tile 0 of the next sweep's plane: this one again when the group's second i-block
+                // comes next, the next modulus otherwise; none behind the group's last sweep
+                tile(Bool<false>{}, nmine, sw + 1 < nsw, fd, ib * I8_TILE_STEPS, bim + (size_t)((sw + 1) >> um) * nst * I8_B_STEP);
+                // the sweep of modulus j over i-block ib is complete: reduce, park in the i-block's slot (4 elements of a tile per
+                // dword), start over
                 if (I8_ABL_NORED) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
@@ -364,6 +403,10 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                         for (int t = 0; t < 8; ++t) asm volatile("" : "+v"(acc[r][t]));
                 } else {
                     const I8ResTab& T = i8_res_tab();
+                    // (the lane's park address is rebuilt behind every sweep: hoisted out of the sweeps as a 64-bit pointer per lane it
+                    // held two VGPRs across the tiles, which have none to spare — tools/check_isa_spills.py)
+                    unsigned ut = utid;
+                    asm volatile("" : "+v"(ut));
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -373,7 +416,7 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                             for (int e = 0; e < 4; ++e) rr[e] = i8_acc_bits(acc[r][t][e], T, j);
                             const unsigned pw = i8_pack_bits(rr[0], rr[1], rr[2], rr[3]);
                             if (I8_ABL_NOPARK) asm volatile("" ::"v"(pw));
-                            else pk[utid + 512u * (unsigned)(j * 32 + r * 8 + t)] = pw;
+                            else pku[ut + 512u * (unsigned)(j * 32 + r * 8 + t)] = pw;
                             acc[r][t] = v4i{0, 0, 0, 0};
                         }
                 }
@@ -390,39 +433,47 @@ __global__ __launch_bounds__(512, 2) void k_var_i8(KernelParams p, VarI8PlanDev 
                         ar[i + 2][r] = turn ? lo2 : hi2;
                     }
             }
-            // ---- all 14 residues of this i-block's 64 x 128 elements are parked: rebuild, scale, square, sum per column
+            // ---- all 14 residues of the group's 64 x 128 elements per i-block are parked: rebuild, scale, square, sum per column
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll 1
-            for (int t = 0; t < 8; ++t) {
-                double ssq = 0.0;
+            for (int u = 0; u <= um; ++u) {
+                const int ib = u ? ib1 : ib0;
+                const unsigned* const pku = pk + (u ? I8_PARK_WORDS / 2 : 0);
+                unsigned ut = utid, ulk = (unsigned)lk;                 // (rebuilt here as above: not kept across the sweeps)
+                asm volatile("" : "+v"(ut), "+v"(ulk));
 #pragma unroll 1
-                for (int r = 0; r < (I8_ABL_NORED ? 0 : 4); ++r) {
-                    unsigned wd[I8_NMOD];
+                for (int t = 0; t < 8; ++t) {
+                    double ssq = 0.0;
+#pragma unroll 1
+                    for (int r = 0; r < (I8_ABL_NORED ? 0 : 4); ++r) {
+                        unsigned wd[I8_NMOD];
 #pragma unroll
-                    for (int j = 0; j < I8_NMOD; ++j) {
-                        if (I8_ABL_NOPARK) asm volatile("" : "=v"(wd[j]));
-                        else wd[j] = pk[utid + 512u * (unsigned)(j * 32 + r * 8 + t)];
+                        for (int j = 0; j < I8_NMOD; ++j) {
+                            if (I8_ABL_NOPARK) asm volatile("" : "=v"(wd[j]));
+                            else wd[j] = pku[ut + 512u * (unsigned)(j * 32 + r * 8 + t)];
+                        }
+                        const d4 rs = *reinterpret_cast<const d4*>(a.rowscale + (size_t)ib * I8_ROWS + 64 * g + 16 * r + 4 * ulk);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            float res[I8_NMOD];
+#pragma unroll
+                            for (int j = 0; j < I8_NMOD; ++j) res[j] = (float)((int)(wd[j] << (24 - 8 * e)) >> 24);
+                            const double v = i8_garner(res) * rs[e] * a.colscale;
+                            ssq = fma(v, v, ssq);
+                        }
                     }
-                    const d4 rs = *reinterpret_cast<const d4*>(a.rowscale + (size_t)ib * I8_ROWS + 64 * g + 16 * r + 4 * lk);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float res[I8_NMOD];
-#pragma unroll
-                        for (int j = 0; j < I8_NMOD; ++j) res[j] = (float)((int)(wd[j] << (24 - 8 * e)) >> 24);
-                        const double v = i8_garner(res) * rs[e] * a.colscale;
-                        ssq = fma(v, v, ssq);
-                    }
+                    ssq += i8_lane_xor(ssq, ut, 16);
+                    ssq += i8_lane_xor(ssq, ut, 32);
+                    if (lk == 0) red[w][16 * t + lc] = ssq;
                 }
-                ssq += __shfl_xor(ssq, 16);
-                ssq += __shfl_xor(ssq, 32);
-                if (lk == 0) red[w][16 * t + lc] = ssq;
-            }
-            __syncthreads();
-            if (tid < I8_COLS) {
-                double v = 0.0;
+                __syncthreads();
+                if (tid < I8_COLS) {
+                    double v = 0.0;
 #pragma unroll
-                for (int ww = 0; ww < 8; ++ww) v += red[ww][tid];
-                a.slab[((size_t)cb * nbi + ib) * I8_COLS + tid] = v;
+                    for (int ww = 0; ww < 8; ++ww) v += red[ww][tid];
+                    a.slab[((size_t)cb * nbi + ib) * I8_COLS + tid] = v;
+                }
+                __syncthreads();                                            // (red is written again: the group's second i-block, the next group)
             }
         }
     }

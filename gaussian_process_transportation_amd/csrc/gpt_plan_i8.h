@@ -34,7 +34,10 @@ constexpr int I8_ROWS = 512;          // rows of an i-block (= WT)
 constexpr int I8_KSTEP = 64;          // k per v_mfma_i32_16x16x64_i8
 constexpr int I8_MAX_NBI = 32;        // i-blocks of the largest model the path takes (NP <= 16384: p = 47)
 constexpr int I8_MIN_BITS = 44;       // below this many bits per operand a model stays on the fp64 kernel
-constexpr int I8_SWEEP_FIXED = 3;     // cost of an i-block beside its tiles, in tiles: reduction, reconstruction, first fill
+// Cost of an i-block beside its tiles, in tiles: its 14 reductions and its reconstruction, and its share of the first fill (chunk,
+// A ring, barrier), which a walk group of two i-blocks (var_i8_walk_iblock) pays once.  Three, as measured when every i-block
+// filled for itself; the tail shapes (M = 10^4 .. 65 536) did not ask for another value with the groups.
+constexpr int I8_SWEEP_FIXED = 3;
 
 // log2 of the product of the moduli (110.16)
 inline double var_i8_log2_modulus() {
@@ -61,11 +64,12 @@ inline bool var_i8_shape_ok(int NP) {
 }
 
 // Device images, in bytes: the residue planes of W (one byte per element of the block lower triangle and modulus); per column
-// block of a group the planes of its kernel columns (var_i8_image_count of them); and per workgroup the parked residues of an
-// i-block (512 x 128 elements x 14 bytes).
+// block of a group the planes of its kernel columns (var_i8_image_count of them); and per workgroup the parked residues of a
+// walk group's two i-blocks (2 x 512 x 128 elements x 14 bytes; slot u of the group at u x var_i8_park_slot_bytes()).
 inline size_t var_i8_plane_bytes(int NP) { const size_t nb = NP / I8_ROWS; return (size_t)I8_NMOD * (nb * (nb + 1) / 2) * I8_ROWS * I8_ROWS; }
 inline size_t var_i8_bimg_bytes(int NP) { return (size_t)I8_NMOD * NP * I8_COLS; }
-constexpr size_t var_i8_park_bytes() { return (size_t)I8_NMOD * I8_ROWS * I8_COLS; }
+constexpr size_t var_i8_park_slot_bytes() { return (size_t)I8_NMOD * I8_ROWS * I8_COLS; }
+constexpr size_t var_i8_park_bytes() { return 2 * var_i8_park_slot_bytes(); }
 
 // Passed by value to the kernels.
 struct VarI8PlanDev {
@@ -142,7 +146,7 @@ inline bool var_i8_tail_item(const VarI8PlanDev& d, int wg, int64_t* cb, int* ib
 // nbi the middle i-block is an item alone).  Item t of a group is block t / npairs with the i-blocks {nbi - 1 - q, q}, q = t % npairs;
 // workgroup wg takes the items wg, wg + P, ...: one per item step, npairs steps per group.  Co-resident workgroups hold consecutive
 // items, and when npairs divides P a workgroup keeps its q.  An item is at most two contiguous i-block ranges, [lo[r], hi[r]), walked
-// in order r = 0, 1 and downward inside a range; a tail part is an item with one range.  img: the block's image among those that
+// in order r = 0, 1 and downward inside a range (two i-blocks at a time: "the walk of an item" below); a tail part is an item with one range.  img: the block's image among those that
 // k_i8_gen wrote for the launch (the blocks of the launch's rounds; the tail's blocks in a launch of their own).
 struct VarI8Item {
     int64_t cb, img;
@@ -168,6 +172,35 @@ inline bool var_i8_tail_as_item(const VarI8PlanDev& d, int wg, VarI8Item* x) {
     x->lo[0] = lo; x->hi[0] = hi; x->lo[1] = x->hi[1] = 0;
     return true;
 }
+// ---- the walk of an item ------------------------------------------------------------------------------------------------------
+// The i-blocks of an item in the order of its ranges (r = 0, 1; downward inside a range) are taken two at a time: walk position k
+// belongs to walk group k / 2 and parks its residues in slot k % 2.  A pair item is one group, {nbi - 1 - q, q} in that order (the
+// middle i-block of an odd nbi alone); a tail part is consecutive twos walked downward, a single i-block left over when its count is
+// odd.  Inside a group the moduli are the OUTER loop: for each modulus the sweep of slot 0, then that of slot 1, each reduced and
+// parked; the reconstructions follow the last modulus.  Every pair item of a block therefore runs nbi + 1 tiles and two reductions
+// per modulus, whatever q: the workgroups that share a block's image (one per XCD) stay in the same plane of it without any
+// synchronisation, and the plane is fetched once for all of them.  k_var_i8 calls these two functions itself.
+constexpr int var_i8_walk_len(int lo0, int hi0, int lo1, int hi1) { return (hi0 - lo0) + (hi1 - lo1); }
+constexpr int var_i8_walk_iblock(int lo0, int hi0, int lo1, int hi1, int k) {
+    return k < hi0 - lo0 ? hi0 - 1 - k : hi1 - 1 - (k - (hi0 - lo0));
+}
+struct VarI8WalkEntry {
+    int group, slot, ib;
+};
+inline std::vector<VarI8WalkEntry> var_i8_item_walk(const VarI8Item& x) {
+    std::vector<VarI8WalkEntry> w;
+    const int n = var_i8_walk_len(x.lo[0], x.hi[0], x.lo[1], x.hi[1]);
+    for (int k = 0; k < n; ++k) w.push_back({k / 2, k % 2, var_i8_walk_iblock(x.lo[0], x.hi[0], x.lo[1], x.hi[1], k)});
+    return w;
+}
+// tiles a walk group runs per modulus: the sum of ib + 1 over its i-blocks
+inline int var_i8_group_tiles(const std::vector<VarI8WalkEntry>& w, int group) {
+    int t = 0;
+    for (const VarI8WalkEntry& e : w)
+        if (e.group == group) t += e.ib + 1;
+    return t;
+}
+
 // Item steps of a group that go into one launch: GPT_VAR_ITEM_STEPS_PER_LAUNCH, read per call (0 or more than npairs: all of them).
 // One, measured at N = 8192, M = 500 000 (profiles/var_int8_items_profile.txt: ms per step 235.7 / 236.4 / 238.5 / 239.9 for 1 / 2 / 4 /
 // all 8 steps per launch): as with the rounds, a kernel boundary brings the workgroups of an XCD back in step on the A stream.
