@@ -106,6 +106,7 @@ SIGNATURES = {
     "gpt_debug_dgemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _i64, _dp, _i64, _dp, _i64,
                                   C.c_int, C.POINTER(C.c_int)]),
     "gpt_debug_set_inverse_factor": (C.c_int, [_vp, _dp, _i64]),
+    "gpt_debug_set_task_inverse_factor": (C.c_int, [_vp, C.c_int, _dp, _i64]),
     "gpt_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_i64)]),
     "gpt_fit_timings": (C.c_int, [_vp, _dp, C.c_int]),
     "gpt_set_profiling": (C.c_int, [_vp, C.c_int]),
@@ -804,6 +805,13 @@ class Handle:
         if not (isinstance(W, np.ndarray) and W.dtype == np.float64 and W.ndim == 2 and W.shape[0] == W.shape[1] and W.flags.c_contiguous):
             raise ValueError("debug_set_inverse_factor: W must be a square C-contiguous float64 array")
         check(self.lib.gpt_debug_set_inverse_factor(self._h, dptr(W), W.shape[0]), "gpt_debug_set_inverse_factor")
+
+    def debug_set_task_inverse_factor(self, task, W):
+        """The same for task `task` of a gpt_fit_svgp model (gpt_debug_set_task_inverse_factor; tests only): W is packed into the
+        task's slot times the task's outputscale, as the fit packs it."""
+        if not (isinstance(W, np.ndarray) and W.dtype == np.float64 and W.ndim == 2 and W.shape[0] == W.shape[1] and W.flags.c_contiguous):
+            raise ValueError("debug_set_task_inverse_factor: W must be a square C-contiguous float64 array")
+        check(self.lib.gpt_debug_set_task_inverse_factor(self._h, int(task), dptr(W), W.shape[0]), "gpt_debug_set_task_inverse_factor")
 
     def lml(self) -> float:
         v = C.c_double()

@@ -1066,6 +1066,31 @@ int gpt_debug_set_inverse_factor(gpt_handle* h, const double* W, int64_t n) {
     return GPT_OK;
 }
 
+// Test hook: the same for one task of a multi-task model (gpt_fit_svgp).  W goes through the fit workspace's dW, which holds
+// nothing the model needs (the last task's factor), and into the task's slot of Wf scaled by the task's outputscale as the
+// device header holds it — the packing of gpt_fit_svgp.  A single-task handle takes gpt_debug_set_inverse_factor's way.
+int gpt_debug_set_task_inverse_factor(gpt_handle* h, int task, const double* W, int64_t n) {
+    const char* who = "gpt_debug_set_task_inverse_factor";
+    if (!h || !W) return fail(GPT_E_ARG, std::string(who) + ": NULL argument");
+    if (!h->committed) return fail(GPT_E_STATE, std::string(who) + ": model is not fitted");
+    if (task < 0 || task >= h->p.ntask) return fail(GPT_E_ARG, std::string(who) + ": no such task");
+    if (h->p.ntask == 1) return gpt_debug_set_inverse_factor(h, W, n);
+    if (!h->ws->dW || h->ws->np != h->p.NP) return fail(GPT_E_STATE, std::string(who) + ": needs the handle that ran gpt_fit_svgp for this model");
+    if (n != h->p.N) return fail(GPT_E_ARG, std::string(who) + ": n differs from the model's N");
+    if (int rc = set_device(h)) return rc;
+    const int64_t N = h->p.N, NP = h->p.NP;
+    hipStream_t s = h->stream;
+    CALLCHK(hipStreamSynchronize(s));                  // launches that still read dW or Wf
+    double scale = 0.0;
+    CALLCHK(hipMemcpy(&scale, h->dHdr() + HDR_TASK_C + task, sizeof(double), hipMemcpyDeviceToHost));
+    CALLCHK(hipMemcpy2D(h->ws->dW, (size_t)NP * sizeof(double), W, (size_t)N * sizeof(double), (size_t)N * sizeof(double), (size_t)N,
+                        hipMemcpyHostToDevice));
+    launch_pack_w(s, h->ws->dW, (int)N, (int)NP, h->dWf(), h->lay.dtype, task, scale);
+    CALLCHK(hipGetLastError());
+    CALLCHK(hipStreamSynchronize(s));                  // dW is free for the next task's factor
+    return GPT_OK;
+}
+
 int gpt_fit_timings(gpt_handle* h, double* ms_out, int n) {
     if (!h || !ms_out) return fail(GPT_E_ARG, "gpt_fit_timings: NULL argument");
     for (int i = 0; i < n && i < 6; ++i) ms_out[i] = h->fit_ms[i];

@@ -687,6 +687,13 @@ int gpt_debug_dgemm(int device, int at, int bt, int M, int N, int K, double alph
  * model, a replica (gpt_factor_commit / gpt_factor_copy) that holds no factor of its own. */
 int gpt_debug_set_inverse_factor(gpt_handle* h, const double* W, int64_t n);
 
+/* Test hook (needs a GPU): the same for task `task` of a multi-task model, on the handle that ran its gpt_fit_svgp.  W takes the
+ * place of the task's inverse factor in the packed image, multiplied by the task's outputscale as the fit's own packing does;
+ * the other tasks' factors and every alpha stay.  (A multi-task handle keeps no dense factor: nothing is exported afterwards,
+ * as nothing was before.)  A single-task model: task must be 0, and the call is gpt_debug_set_inverse_factor.  GPT_E_ARG: NULL
+ * argument, task outside 0 .. n_tasks - 1, n != N; GPT_E_STATE: no committed model, a replica without the fit's workspace. */
+int gpt_debug_set_task_inverse_factor(gpt_handle* h, int task, const double* W, int64_t n);
+
 #ifdef __cplusplus
 }
 #endif

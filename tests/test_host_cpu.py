@@ -529,6 +529,18 @@ rep.factor_copy_from(h)
 refused(lambda: rep.debug_set_inverse_factor(W), _lib.GptError)                   # a replica holds no factor of its own
 h.fit_svgp(X, rng.standard_normal((2, N)), 1e-2 * np.eye(N) * np.ones((2, 1, 1)), np.full(D, 0.3), np.ones(2))
 refused(lambda: h.debug_set_inverse_factor(W), _lib.GptError)                     # multi-task model
+# gpt_debug_set_task_inverse_factor: one task's slot of the multi-task model
+assert lib.gpt_debug_set_task_inverse_factor(None, 0, _lib.dptr(W), N) == _lib.GPT_E_ARG
+assert lib.gpt_debug_set_task_inverse_factor(h._h, 0, None, N) == _lib.GPT_E_ARG
+refused(lambda: h.debug_set_task_inverse_factor(2, W), ValueError)                # tasks 0 and 1 only
+refused(lambda: h.debug_set_task_inverse_factor(-1, W), ValueError)
+refused(lambda: h.debug_set_task_inverse_factor(1, W[:N - 1, :N - 1].copy()), ValueError)          # n != N
+refused(lambda: h.debug_set_task_inverse_factor(0, W.astype(np.float32)), ValueError)
+h.debug_set_task_inverse_factor(0, W)
+h.debug_set_task_inverse_factor(1, W)
+assert h.predict_all(rng.uniform(0, 1, (200, D)), var=True)["var"].shape == (200, 2)
+rep.factor_copy_from(h)
+refused(lambda: rep.debug_set_task_inverse_factor(0, W), _lib.GptError)           # a replica has no fit workspace
 h.lml_objective(X, Y, np.full(D, 0.3), 1.0, 1e-2, 1e-10)
 refused(lambda: h.debug_set_inverse_factor(W), _lib.GptError)                     # factors, but no committed model
 h.close(); rep.close()

@@ -22,8 +22,13 @@ a real model passes; here it changes a column by at least one unit of the design
 Plan features are asserted, not assumed: the fp64 plan through _lib.debug_var_plan for the device's workgroup count, the residue
 plan by restating build_var_i8_plan's arithmetic; a feature none of the candidate batch sizes has FAILS the test.
 
-Not covered: wide layouts (D >= 4), multi-task / SVGP models and derivative columns - their generated operand is 0 at a
-coincident site (or they stack several factors), so these designs say nothing about them."""
+This file: the k*-alone launch of single-task models with D <= 3, k_var and k_var_i8.  tests/test_var_exact_columns.py holds
+the rest of k_var to the same kind of design: wide layouts (D = 4 .. 15, on a lattice whose every coordinate separates a pair
+of sites) and multi-task models (gpt_debug_set_task_inverse_factor puts a design into each task's slot) bit for bit, and every
+launch with derivative columns - whose operand is 0 on a site, so queries sit beside the sites and the generated operand is read
+back from calibration runs (W = 2^e at one row per i-block) before the product is held to a derived bound of a few ulp.
+Still not covered by exact designs: k_var_i8 beyond D <= 3 single-task (it takes nothing else), and more than one source per site
+under derivative columns (the one-hot designs there make every V[i, m] a single product)."""
 import functools
 import os
 
