@@ -33,7 +33,12 @@ ROLLOUT_OUTPUTS = ("path", "vel", "x", "steps_done", "status")
 ROLLOUT_INT_OUTPUTS = ("steps_done", "status")
 # outputs of gpt_rollout_stabilised, in the order of its arguments
 ROLLOUT_STAB_OUTPUTS = ("path", "vel", "x", "f", "var", "dvar", "steps_done", "status")
-ROLLOUT_STAB_MAX_N = 1024   # training points of the dynamics of a stabilised rollout, at most (gpt_rollout_stab.h)
+ROLLOUT_STAB_MAX_N = 1024   # training points of the dynamics of a stabilised or sampled rollout, at most (gpt_rollout_stab.h)
+# outputs of gpt_rollout_sampled, in the order of its arguments
+ROLLOUT_SAMPLED_OUTPUTS = ("path", "vel", "x", "f", "pvar", "cvar", "chol", "steps_done", "status")
+ROLLOUT_SAMPLED_MAX_T = 256   # GPT_ROLLOUT_SAMPLED_MAX_T: steps of a sampled rollout, at most
+ROLLOUT_DEGENERATE = 4        # GPT_ROLLOUT_DEGENERATE: status of a sampled path whose conditional variance fell to rounding level
+ROLLOUT_SAMPLED_STATUS_NAMES = INV_STATUS_NAMES + ("DEGENERATE",)      # the status of a sampled path, by value
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -87,6 +92,10 @@ SIGNATURES = {
                                               C.c_double, C.c_double] + [_vp] * 8),
     "gpt_rollout_stabilised": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int,
                                           C.c_double, C.c_double] + [_dp] * 6 + [_ip] * 2),
+    "gpt_rollout_sampled_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                           C.c_double] + [_vp] * 9),
+    "gpt_rollout_sampled": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                       C.c_double] + [_dp] * 7 + [_ip] * 2),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
@@ -1081,9 +1090,10 @@ class Handle:
               "gpt_pullback_chain_dev")
 
     # ---- whole paths of the transported policy: the loop over the steps on the device
-    def _rollout_host(self, what, names, optional, extra, inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs):
+    def _rollout_host(self, what, names, optional, extra, inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs, inputs=()):
         """The host entry `gpt_<what>` of a rollout family: `names` its outputs in the order of its arguments, `optional` those the
-        caller chooses among, `extra` the arguments between max_passes and the outputs."""
+        caller chooses among, `extra` the arguments between max_passes and the outputs, `inputs` the float64 arrays (or None) it
+        takes between x0 and M."""
         stages = list(inner)
         K = len(stages)
         if K > CHAIN_MAX:
@@ -1117,18 +1127,19 @@ class Handle:
                                  f"c_dst ({D},)")
             keep += [R, R_jac, c_src, c_dst]
             arr[k] = ChainStage(h._h, R.ctypes.data, c_src.ctypes.data, c_dst.ctypes.data, R_jac.ctypes.data, float(scale))
-        shapes = {"path": (M, T + 1, D), "var": (M, T), "steps_done": (M,), "status": (M,)}
+        shapes = {"path": (M, T + 1, D), "var": (M, T), "pvar": (M, T), "cvar": (M, T), "chol": (M, T, T), "steps_done": (M,), "status": (M,)}
         want = [k for k in names if k not in optional or k in outputs]
         out = {k: np.empty(shapes.get(k, (M, T, D)), dtype=np.int32 if k in ROLLOUT_INT_OUTPUTS else np.float64) for k in want}
         ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(_ip)) if k in ROLLOUT_INT_OUTPUTS else dptr(out.get(k))
-        check(getattr(self.lib, "gpt_" + what)(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), M, T, float(dt), float(rtol), int(max_passes),
-                                               *extra, *(ptr(k) for k in names)),
+        check(getattr(self.lib, "gpt_" + what)(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), *(dptr(a) for a in inputs), M, T, float(dt),
+                                               float(rtol), int(max_passes), *extra, *(ptr(k) for k in names)),
               "gpt_" + what)
         del keep
         return out
 
-    def _rollout_dev(self, what, names, extra, inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol, max_passes, ptrs):
-        """The device entry `gpt_<what>_dev` of a rollout family; ptrs: output name -> device pointer (0: not asked for)."""
+    def _rollout_dev(self, what, names, extra, inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol, max_passes, ptrs, input_ptrs=()):
+        """The device entry `gpt_<what>_dev` of a rollout family; ptrs: output name -> device pointer (0: not asked for);
+        input_ptrs: the device pointers it takes between x0 and M."""
         stages = list(inner)
         K = len(stages)
         if K > CHAIN_MAX:
@@ -1138,7 +1149,8 @@ class Handle:
         arr = (ChainStage * max(K, 1))()
         for k, (h, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr) in enumerate(stages):
             arr[k] = ChainStage(h._h, R_ptr or None, c_src_ptr or None, c_dst_ptr or None, R_jac_ptr or None, float(scale))
-        check(getattr(self.lib, f"gpt_{what}_dev")(arr if K else None, K, dyn._h, _vp(y0_ptr or None), _vp(x0_ptr or None), int(M), int(n_steps),
+        check(getattr(self.lib, f"gpt_{what}_dev")(arr if K else None, K, dyn._h, _vp(y0_ptr or None), _vp(x0_ptr or None),
+                                                   *(_vp(q or None) for q in input_ptrs), int(M), int(n_steps),
                                                    float(dt), float(rtol), int(max_passes), *extra, *(_vp(ptrs.get(k) or None) for k in names)),
               f"gpt_{what}_dev")
 
@@ -1177,6 +1189,38 @@ class Handle:
         self._rollout_dev("rollout_stabilised", ROLLOUT_STAB_OUTPUTS, (float(gain), float(std_offset)), inner, dyn, y0_ptr, x0_ptr, M, n_steps,
                           dt, rtol, max_passes, dict(path=path_ptr, vel=vel_ptr, x=x_ptr, f=f_ptr, var=var_ptr, dvar=dvar_ptr,
                                                      steps_done=steps_done_ptr, status=status_ptr))
+
+    # ---- whole paths of functions drawn from the dynamics posterior
+    def rollout_sampled(self, inner, dyn, y0, normals, n_steps, nugget, dt=1.0, x0=None, rtol=1e-10, max_passes=64,
+                        outputs=("vel", "x", "f", "pvar", "cvar")):
+        """gpt_rollout_sampled on host arrays: rollout_policy with, in place of the mean of `dyn`, one function drawn from its
+        posterior per path, the draw of a step conditioned on the path's own earlier draws (only `dyn` is sampled; the maps of
+        `inner` act through their means).  y0 (P,D): one start per path; normals (P,n_steps,D): the caller's standard normal
+        numbers, the only randomness; nugget >= 0: added to the diagonal of a path's covariance (the noise level of `dyn`: noisy
+        values, predict(return_cov=True)'s convention).  `outputs`: which of "vel", "x", "f" (P,n_steps,D), "pvar", "cvar"
+        (P,n_steps: the marginal and the conditional variance of a step's draw) and "chol" (P,n_steps,n_steps: the lower Cholesky
+        factor of the path's covariance) come back besides path, steps_done and status; status takes the INV_* values and
+        ROLLOUT_DEGENERATE (ROLLOUT_SAMPLED_STATUS_NAMES).  Zero normals give rollout_policy's path.  `dyn`: at most
+        ROLLOUT_STAB_MAX_N training points, any kernel; n_steps at most ROLLOUT_SAMPLED_MAX_T.  Returns a dict."""
+        y0 = as_f64(y0, 2, "y0")
+        T = int(n_steps)
+        if T > ROLLOUT_SAMPLED_MAX_T:
+            raise ValueError(f"rollout_sampled: n_steps must be at most {ROLLOUT_SAMPLED_MAX_T} (ROLLOUT_SAMPLED_MAX_T), got {T}")
+        if not np.isfinite(float(nugget)) or float(nugget) < 0.0:
+            raise ValueError(f"rollout_sampled: nugget must be finite and >= 0, got {nugget!r}")
+        normals = as_f64(normals, 3, "normals")
+        if normals.shape != (y0.shape[0], max(T, 0), y0.shape[1]):
+            raise ValueError(f"normals has shape {normals.shape}, expected (paths, n_steps, D) = {(y0.shape[0], T, y0.shape[1])}")
+        return self._rollout_host("rollout_sampled", ROLLOUT_SAMPLED_OUTPUTS, ("vel", "x", "f", "pvar", "cvar", "chol"), (float(nugget),),
+                                  inner, dyn, y0, T, dt, x0, rtol, max_passes, outputs, inputs=(normals,))
+
+    def rollout_sampled_dev(self, inner, dyn, y0_ptr, normals_ptr, M, n_steps, nugget, path_ptr, steps_done_ptr, status_ptr, dt=1.0,
+                            x0_ptr=0, rtol=1e-10, max_passes=64, vel_ptr=0, x_ptr=0, f_ptr=0, pvar_ptr=0, cvar_ptr=0, chol_ptr=0):
+        """The same on device pointers (float64; steps_done / status int32), asynchronous on this handle's stream
+        (gpt_rollout_sampled_dev).  `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers."""
+        self._rollout_dev("rollout_sampled", ROLLOUT_SAMPLED_OUTPUTS, (float(nugget),), inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol,
+                          max_passes, dict(path=path_ptr, vel=vel_ptr, x=x_ptr, f=f_ptr, pvar=pvar_ptr, cvar=cvar_ptr, chol=chol_ptr,
+                                           steps_done=steps_done_ptr, status=status_ptr), input_ptrs=(normals_ptr,))
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

@@ -1,7 +1,7 @@
-// What the two rollout families share on the host (gpt_rollout_host.hip: the mean policy; gpt_rollout_stab_host.hip: the
-// variance-stabilised one): the refusals both state in the same words, the launches of one call enqueued back to back with the
-// hand-over between the handles' streams, and the chunked staging of the host call.  A family brings its array table (its first two
-// arrays are the inputs y0 and x0), the bytes of a row of each array, and its launcher.  Internal header, host code only; plain C++,
+// What the rollout families share on the host (gpt_rollout_host.hip: the mean policy; gpt_rollout_stab_host.hip: the
+// variance-stabilised one; gpt_rollout_sampled_host.hip: the sampled one): the refusals all state in the same words, the launches
+// of one call enqueued back to back with the hand-over between the handles' streams, and the chunked staging of the host call.  A
+// family brings its array table (its first arrays are the inputs, y0 and x0 ahead), the bytes of a row of each array, and its launcher.  Internal header, host code only; plain C++,
 // it also compiles under g++ against host_stub/.  The resources of a call (CALL_ROLLOUT) are held by the handle of the LAST stage,
 // or by the dynamics' when there is no stage; its events: ev[j] the j-th other stream has caught up, ev[2 CHAIN_MAX] the last
 // launch is done.
@@ -71,9 +71,12 @@ int rollout_enqueue(const RolloutCallBase& c, RolloutArgs& a, int per, Launch&& 
 
 // The host entry of a family after its checks, M > 0: the finite inputs, then the trajectories through the device in chunks of about
 // ROLLOUT_CHUNK_ROWS path rows, whatever T is.  Call: a RolloutCallBase with `void* arr[N]`, arr[0] = y0, arr[1] = x0 the inputs;
-// row_bytes(k, D, T): bytes per trajectory of array k; dev(call): the family's device entry on a chunk.
+// row_bytes(k, D, T): bytes per trajectory of array k; dev(call): the family's device entry on a chunk.  n_inputs: the first so many
+// arrays travel to the device (a family checks its inputs beyond y0 and x0 itself); max_chunk > 0: trajectories a chunk may hold at
+// most, where a family's device scratch sets a limit of its own.
 template <int N, class Call, class RowBytes, class Dev>
-int rollout_host_chunks(const std::string& w, const Call& c, RowBytes&& row_bytes, Dev&& dev) {
+int rollout_host_chunks(const std::string& w, const Call& c, RowBytes&& row_bytes, Dev&& dev, const int n_inputs = RO_INPUTS,
+                        const int64_t max_chunk = 0) {
     const size_t D = c.owner_view().p.D, T = (size_t)c.T;
     const double *y0 = static_cast<const double*>(c.arr[0]), *x0 = static_cast<const double*>(c.arr[1]);
     bool finite = all_finite(y0, (size_t)c.M * D) && (!x0 || all_finite(x0, (size_t)c.M * D)) && std::isfinite(c.rtol);
@@ -82,7 +85,8 @@ int rollout_host_chunks(const std::string& w, const Call& c, RowBytes&& row_byte
     gpt_handle* const owner = c.owner();
     CallResources* const res = call_resources(owner, CALL_ROLLOUT, CALL_EVENTS);
     if (!res) return GPT_E_HIP;
-    const int64_t chunk = std::max<int64_t>(1, ROLLOUT_CHUNK_ROWS / (c.T + 1));
+    int64_t chunk = std::max<int64_t>(1, ROLLOUT_CHUNK_ROWS / (c.T + 1));
+    if (max_chunk > 0) chunk = std::min(chunk, max_chunk);
     ChunkStreams q;
     if (int rc = handle_copy_stream(owner, !one_chunk(c.M, chunk), &q)) return rc;
     if (int rc = upload_affine(*res, CHAIN_MAX, c.g, c.K, D, q.s)) return rc;
@@ -90,7 +94,7 @@ int rollout_host_chunks(const std::string& w, const Call& c, RowBytes&& row_byte
     StagedArray table[N];
     for (int k = 0; k < N; ++k) {
         const size_t rb = row_bytes(k, D, T);
-        table[k] = StagedArray{rb ? c.arr[k] : nullptr, rb, k < RO_INPUTS, 1};
+        table[k] = StagedArray{rb ? c.arr[k] : nullptr, rb, k < n_inputs, 1};
     }
     return run_chunked(res->st, q, table, c.M, [&](void* const* dev_arr, int64_t m) {
         Call d = c;

@@ -1,6 +1,6 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_fold_scan_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
-// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip)
+// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip), gpt_rollout_sampled (gpt_rollout_sampled_host.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -1107,6 +1107,110 @@ void rollout_stab_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- sampled rollout (gpt_rollout_sampled_host.hip): three inputs (y0, x0, normals: rows of T D doubles), the arrays of the rollout
+// and f (T D), pvar, cvar (T) and chol (T T doubles per path); chunks as the rollout's and further held to the paths whose device
+// scratch fits the budget (GPT_ROLLOUT_SAMPLED_SCRATCH_BYTES), sixteen at the least
+void rollout_sampled_cases() {
+    const int64_t N = 5, Nd = 7;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h[2] = {}, *hd = nullptr, *m12 = nullptr;
+    begin("gpt_rollout_sampled setup");
+    for (auto& q : h) CHECK(gpt_create(&q, 0) == GPT_OK);
+    CHECK(gpt_create(&hd, 0) == GPT_OK && gpt_create(&m12, 0) == GPT_OK);
+    for (auto& q : h) CHECK(gpt_fit(q, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit_kernel(m12, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10, GPT_KERNEL_MATERN12) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    constexpr int X0 = 1, VEL = 2, XO = 4, F = 8, PVAR = 16, CVAR = 32, CHOL = 64, ALL = 127;     // bits of `mask`: the optional arrays passed
+    struct Arrays {
+        D y0, x0, z, path, vel, x, f, pvar, cvar, chol;
+        Arr<int> steps, status;
+        Arrays(int64_t M, int64_t T)
+            : y0(ramp(M * 3)), x0(ramp(M * 3)), z(ramp(M * T * 3, 0.0, 1e-3)), path((size_t)M * (T + 1) * 3, SENT), vel((size_t)M * T * 3, SENT),
+              x((size_t)M * T * 3, SENT), f((size_t)M * T * 3, SENT), pvar((size_t)M * T, SENT), cvar((size_t)M * T, SENT),
+              chol((size_t)M * T * T, SENT), steps(M, ISENT), status(M, ISENT) {}
+    };
+    std::vector<gpt_chain_stage> st2{gpt_chain_stage{h[0], R.p, c_src.p, c_dst.p, R.p, 1.0}, gpt_chain_stage{h[1], R.p, c_src.p, c_dst.p, R.p, 1.25}};
+    auto call = [&](const gpt_chain_stage* st, int K, gpt_handle* hdyn, Arrays& a, int64_t M, int64_t T, int mask, double nugget = 0.01,
+                    const double* z = nullptr, bool no_z = false) {
+        return gpt_rollout_sampled(st, K, hdyn, a.y0.p, mask & X0 ? a.x0.p : nullptr, no_z ? nullptr : (z ? z : a.z.p), M, T, 0.5, 1e-10, 50, nugget,
+                                   a.path.p, mask & VEL ? a.vel.p : nullptr, mask & XO ? a.x.p : nullptr, mask & F ? a.f.p : nullptr,
+                                   mask & PVAR ? a.pvar.p : nullptr, mask & CVAR ? a.cvar.p : nullptr, mask & CHOL ? a.chol.p : nullptr, a.steps.p,
+                                   a.status.p);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.path.all(SENT) && a.vel.all(SENT) && a.x.all(SENT) && a.f.all(SENT) && a.pvar.all(SENT) && a.cvar.all(SENT) && a.chol.all(SENT) &&
+              a.steps.all(ISENT) && a.status.all(ISENT));
+    };
+    {
+        Arrays a(1, 2);
+        begin("gpt_rollout_sampled refuses nugget = -1"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, -1.0), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses nugget = NaN"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, std::nan("")), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses nugget = inf"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, INFINITY), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses n_steps = 257"); done_held(call(st2.data(), 2, hd, a, 1, GPT_ROLLOUT_SAMPLED_MAX_T + 1, ALL), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses n_steps = -1"); done_held(call(st2.data(), 2, hd, a, 1, -1, ALL), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses normals = NULL"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, 0.01, nullptr, true), GPT_E_ARG);
+        D nan_z{0.5, 0.5, 0.5, 0.5, std::nan(""), 0.5};
+        begin("gpt_rollout_sampled refuses NaN in normals"); done_held(call(st2.data(), 2, hd, a, 1, 2, ALL, 0.01, nan_z.p), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses stages = NULL with K = 2"); done_held(call(nullptr, 2, hd, a, 1, 2, ALL), GPT_E_ARG);
+        begin("gpt_rollout_sampled refuses P (T + 1) = 2^31"); done_held(call(st2.data(), 2, hd, a, (int64_t)1 << 23, 255, ALL), GPT_E_ARG);
+        begin("gpt_rollout_sampled M = 0 does nothing"); done_held(call(st2.data(), 2, hd, a, 0, 2, ALL), GPT_OK);
+        untouched(a);
+    }
+    // (M, T, steps per launch, scratch budget in bytes or 0): T = 0 (the per-step arrays have no rows, normals may be NULL), 1 and the
+    // largest; launches cut inside a call and at its last step; a budget of one byte: chunks of sixteen paths, M at the chunk boundary,
+    // one short of it and one past it, and past two chunks
+    struct Shape { int64_t M, T; int per; long budget; };
+    // (the steps per launch are always set: the call's default is a measured constant of gpt_rollout_sampled.h, not this driver's business)
+    const Shape shapes[] = {{1, 0, 300, 0}, {3, 0, 300, 0}, {1, 1, 300, 0}, {3, 7, 3, 0}, {3, 6, 3, 0}, {2, GPT_ROLLOUT_SAMPLED_MAX_T, 300, 0},
+                            {2, GPT_ROLLOUT_SAMPLED_MAX_T, 100, 0}, {15, 5, 300, 1}, {16, 5, 300, 1}, {17, 5, 2, 1}, {33, 5, 300, 1}, {513, 255, 128, 0}};
+    // the optional arrays: none, all, each alone, and all but each
+    std::vector<int> masks{0, ALL};
+    for (int bit = 1; bit < ALL; bit <<= 1) { masks.push_back(bit); masks.push_back(ALL & ~bit); }
+    for (int K : {0, 2}) {
+        for (gpt_handle* dyn : {hd, m12})
+            for (const Shape& sh : shapes)
+                for (int mask : masks) {
+                    if ((sh.M > 3 || sh.T > 7) && (mask != ALL && mask != 0 && mask != (ALL & ~XO))) continue;
+                    if (sh.M > 33 && (K != 2 || dyn != hd || mask != ALL)) continue;
+                    begin("gpt_rollout_sampled K=" + std::to_string(K) + (dyn == hd ? " RBF" : " Matern 1/2") + " M=" + std::to_string(sh.M) + " T=" +
+                          std::to_string(sh.T) + " steps per launch=" + std::to_string(sh.per) + " budget=" + std::to_string(sh.budget) + " optional=" +
+                          std::to_string(mask));
+                    setenv("GPT_ROLLOUT_STEPS_PER_LAUNCH", std::to_string(sh.per).c_str(), 1);
+                    if (sh.budget) setenv("GPT_ROLLOUT_SAMPLED_SCRATCH_BYTES", std::to_string(sh.budget).c_str(), 1);
+                    else unsetenv("GPT_ROLLOUT_SAMPLED_SCRATCH_BYTES");
+                    const int per = sh.per;
+                    gpt::stub_rollout_launch_count = 0;
+                    Arrays a(sh.M, sh.T);
+                    const int rc = call(K ? st2.data() : nullptr, K, dyn, a, sh.M, sh.T, mask, 0.01, nullptr, sh.T == 0);
+                    CHECK(stub_live_objects >= held);                        // staging, scratch and events are kept and regrown, never dropped
+                    held = stub_live_objects;
+                    done_held(rc, GPT_OK);
+                    int64_t chunk = std::max<int64_t>(1, 131072 / (sh.T + 1));
+                    if (sh.budget) chunk = std::min<int64_t>(chunk, 16);
+                    const int64_t chunks = (sh.M + chunk - 1) / chunk;
+                    CHECK(gpt::stub_rollout_launch_count == chunks * std::max<int64_t>(1, (sh.T + per - 1) / per));
+                    CHECK(a.path.all(0.0) && a.status.all(0) && a.steps.all((int)sh.T));
+                    CHECK(a.vel.all(mask & VEL ? 0.0 : SENT) && a.x.all(mask & XO ? 0.0 : SENT) && a.f.all(mask & F ? 0.0 : SENT));
+                    CHECK(a.pvar.all(mask & PVAR ? 0.0 : SENT) && a.cvar.all(mask & CVAR ? 0.0 : SENT) && a.chol.all(mask & CHOL ? 0.0 : SENT));
+                }
+    }
+    unsetenv("GPT_ROLLOUT_STEPS_PER_LAUNCH");
+    unsetenv("GPT_ROLLOUT_SAMPLED_SCRATCH_BYTES");
+    begin("gpt_rollout_sampled teardown");
+    for (auto& q : h) gpt_destroy(q);
+    gpt_destroy(hd);
+    gpt_destroy(m12);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -1152,6 +1256,7 @@ int main() {
     chain_cases();
     rollout_cases();
     rollout_stab_cases();
+    rollout_sampled_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

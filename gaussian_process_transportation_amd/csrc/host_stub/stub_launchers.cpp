@@ -269,6 +269,16 @@ extern "C" int gpt_rollout_stabilised(const gpt_chain_stage*, int, gpt_handle*, 
     gpt::set_last_error("gpt_rollout_stabilised: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_rollout_sampled_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, const double*, int64_t, int64_t,
+                                       double, double, int, double, double*, double*, double*, double*, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_sampled_dev: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_rollout_sampled(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, const double*, int64_t, int64_t, double,
+                                   double, int, double, double*, double*, double*, double*, double*, double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_sampled: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
                                int*) {
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
@@ -291,6 +301,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 #include "../gpt_chain.h"
 #include "../gpt_rollout.h"
 #include "../gpt_rollout_stab.h"
+#include "../gpt_rollout_sampled.h"
 #include <cstdio>
 
 namespace gpt {
@@ -540,6 +551,40 @@ void launch_rollout_stab(hipStream_t s, int D_, const RolloutStabArgs& sa) {
         if (sa.f) touch_w(sa.f + (m * T + t0) * D, (t1 - t0) * D * 8);
         if (sa.var) touch_w(sa.var + m * T + t0, (t1 - t0) * 8);
         if (sa.dvar) touch_w(sa.dvar + (m * T + t0) * D, (t1 - t0) * D * 8);
+    }
+    launch_rollout(s, D_, a);                         // the mean rollout's arrays, its checks and its launch count
+}
+
+// ---- gpt_rollout_sampled.hip --------------------------------------------------------------------------------------------------
+// k_rollout_sampled: what k_rollout reads and writes (x always: the caller's array or scratch), of the dynamics also the packed
+// inverse factor, the normals of the launch's steps, and the scratch of the call: u of the steps so far of every workgroup, the
+// transposed factor up to the launch's last row, the cross products; f, pvar, cvar and chol are written where they are asked for
+void launch_rollout_sampled(hipStream_t s, int D_, const RolloutSampledArgs& sa) {
+    const RolloutArgs& a = sa.r;
+    if (a.M <= 0) return;
+    stub_check(sa.Wf && sa.NP % PAD_N == 0 && sa.NP >= a.dyn.N && sa.NP <= ROLLOUT_STAB_MAX_N && a.dyn.N >= 1);
+    stub_check(sa.nugget >= 0.0 && sa.nugget <= 1e300 && a.T <= ROLLOUT_SAMPLED_MAX_T);
+    const size_t nb = (size_t)sa.NP / WT;
+    touch_r(sa.Wf, nb * (nb + 1) / 2 * WT_TILE_DOUBLES * 8);
+    const size_t M = (size_t)a.M, D = (size_t)D_, T = (size_t)a.T, t0 = (size_t)a.t_begin, t1 = (size_t)a.t_end;
+    const size_t wgs = (M + ROLLOUT_SAMPLED_TILE - 1) / ROLLOUT_SAMPLED_TILE, ustep = (size_t)sampled_u_rows(a.dyn.N) * 16;
+    if (T > 0) {
+        stub_check(a.x && sa.normals && sa.U && sa.Gt && sa.cb);
+        for (size_t g = 0; g < wgs; ++g) {
+            touch_r(sa.U + g * T * ustep, t0 * ustep * 8);
+            touch_w(sa.U + (g * T + t0) * ustep, (t1 - t0) * ustep * 8);
+            touch_w(sa.cb + g * (T + 1) * 16, (t1 + 1) * 16 * 8);
+        }
+    }
+    for (size_t m = 0; m < M; ++m) {
+        touch_r(sa.normals + m * T * D, t1 * D * 8);
+        if (t0 > 0) touch_r(a.x + m * T * D, t0 * D * 8);
+        for (size_t t = t0; t < t1; ++t)
+            for (size_t r = 0; r <= t; ++r) touch_w(sa.Gt + (m * T + r) * sampled_ld(a.T) + t, 8);
+        if (sa.f) touch_w(sa.f + (m * T + t0) * D, (t1 - t0) * D * 8);
+        if (sa.pvar) touch_w(sa.pvar + m * T + t0, (t1 - t0) * 8);
+        if (sa.cvar) touch_w(sa.cvar + m * T + t0, (t1 - t0) * 8);
+        if (sa.chol) touch_w(sa.chol + (m * T + t0) * T, (t1 - t0) * T * 8);
     }
     launch_rollout(s, D_, a);                         // the mean rollout's arrays, its checks and its launch count
 }

@@ -541,6 +541,74 @@ class GaussianProcess:
                                                 std_offset=np.sqrt(dynamics._noise), dt=float(dt), x0=x0, rtol=rtol,
                                                 max_passes=max_passes, outputs=outputs)
 
+    # ------------------------------------------------------------------ paths of functions drawn from the posterior
+    def rollout_samples(self, starts, n_steps, n_samples=10, dt=1.0, nugget=None, random_state=0, normals=None, return_info=False):
+        """Which paths does this model, as a dynamics, consider plausible from `starts` (M,D)?  n_samples paths per start, each the
+        rollout y_{t+1} = y_t + dt * F(y_t) of ONE function F drawn from the posterior: the value drawn at step t is conditioned
+        on what the same function was drawn to be at the path's own earlier points (the errors of a GP at neighbouring points are
+        almost perfectly correlated; independent noise per step would understate the spread of a path by orders of magnitude).
+        The loop over the steps, the covariance rows and the growing Cholesky factor run on the device in one call
+        (_lib.Handle.rollout_sampled); any of the four kernels.  nugget: added to the diagonal of a path's covariance; None takes
+        the noise level, which draws noisy values (the convention of predict(return_cov=True) and samples()); a small positive
+        number draws the latent function.  normals (M,n_samples,n_steps,D): the standard normal numbers to use, else
+        np.random.RandomState(random_state).standard_normal of that shape — sample j of start m does not depend on the other
+        starts or samples.  Returns paths (M,n_samples,n_steps+1,D); with return_info also a dict: vel, x, f (M,S,n_steps,D), pvar,
+        cvar (M,S,n_steps: the marginal and the conditional variance of a step's draw), steps_done, status (M,S; the _lib.INV_*
+        values or _lib.ROLLOUT_DEGENERATE: the conditional variance fell to rounding level, which a nugget >= the noise level
+        does not let happen); return_info="chol" adds chol (M,S,n_steps,n_steps), the factor of each path's covariance.  A path
+        ends where its next point is not finite; the rows after that are NaN.  Zero normals give rollout().  Needs
+        n_outputs == n_features <= 3, float64, at most _lib.ROLLOUT_STAB_MAX_N training points and _lib.ROLLOUT_SAMPLED_MAX_T
+        steps (beyond: the host loop of examples/sampled_rollout_2d.py --host)."""
+        self._check_chain("rollout_samples", [], self, [], 0)
+        out = self._rollout_samples("rollout_samples", [], [], self, starts, n_steps, n_samples, dt, nugget, random_state, normals, None,
+                                    1e-10, 64, return_info)
+        return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]
+
+    def rollout_chain_samples(self, inner, dynamics, starts, n_steps, affine, n_samples=10, dt=1.0, nugget=None, random_state=0,
+                              normals=None, x0=None, rtol=1e-10, max_passes=64, return_info=False):
+        """rollout_samples() through a chain of transports: the paths of rollout_chain() when the dynamics is a function drawn from
+        the posterior of `dynamics` (rollout_samples: arguments, conditioning, nugget — None: the noise level of `dynamics` —
+        and normals).  Only the dynamics is sampled; the maps (this model the last, `inner` the ones before it, `affine` as
+        pullback_chain's) act through their means: inverse, Jacobian and push-forward are rollout_chain's.  x0 (M,D): guesses
+        of the source-space preimages of the starts.  Returns a dict: path (M,S,n_steps+1,D), steps_done, status (M,S) and,
+        with return_info, vel, x, f, pvar, cvar (and chol for return_info="chol")."""
+        maps = list(inner) + [self]
+        affine = self._check_chain("rollout_chain_samples", maps, dynamics, affine, 1)
+        return self._rollout_samples("rollout_chain_samples", maps, affine, dynamics, starts, n_steps, n_samples, dt, nugget, random_state,
+                                     normals, x0, rtol, max_passes, return_info)
+
+    def _rollout_samples(self, what, maps, affine, dynamics, starts, n_steps, n_samples, dt, nugget, random_state, normals, x0, rtol,
+                         max_passes, return_info):
+        starts, x0 = self._check_chain_points(what, starts, x0, rtol, max_passes, "starts")
+        if int(n_steps) != n_steps or not 0 <= int(n_steps) <= _lib.ROLLOUT_SAMPLED_MAX_T:
+            raise ValueError(f"{what}(): n_steps must be an integer 0 .. {_lib.ROLLOUT_SAMPLED_MAX_T} (_lib.ROLLOUT_SAMPLED_MAX_T), got {n_steps!r}")
+        if int(n_samples) != n_samples or int(n_samples) < 1:
+            raise ValueError(f"{what}(): n_samples must be an integer >= 1, got {n_samples!r}")
+        if not np.isfinite(float(dt)) or float(dt) == 0.0:
+            raise ValueError(f"{what}(): dt must be finite and not zero, got {dt!r}")
+        nugget = float(dynamics._noise if nugget is None else nugget)
+        if not np.isfinite(nugget) or nugget < 0.0:
+            raise ValueError(f"{what}(): nugget must be finite and >= 0, got {nugget!r}")
+        if len(dynamics.X) > _lib.ROLLOUT_STAB_MAX_N:
+            raise ValueError(f"{what}(): the dynamics has {len(dynamics.X)} training points; the sampled rollout takes at most "
+                             f"{_lib.ROLLOUT_STAB_MAX_N} (larger models: predict(return_cov=True) over the path so far, per step)")
+        M, D = starts.shape
+        S, T = int(n_samples), int(n_steps)
+        if M * S * (T + 1) >= 2 ** 31:
+            raise ValueError(f"{what}(): starts times n_samples times (n_steps + 1), the rows of the paths, must stay below 2^31")
+        if normals is None:
+            normals = np.random.RandomState(random_state).standard_normal((M, S, T, D))
+        normals = _lib.as_f64(normals, 4, "normals")
+        if normals.shape != (M, S, T, D):
+            raise ValueError(f"{what}(): normals has shape {normals.shape}, expected (starts, n_samples, n_steps, D) = {(M, S, T, D)}")
+        names = ("vel", "x", "f", "pvar", "cvar") + (("chol",) if return_info == "chol" else ()) if return_info else ()
+        primary = lambda g: getattr(g._handle, "primary", g._handle)
+        stages = [(primary(g), rot, src, dst, scale, jac) for g, (rot, scale, src, dst, jac) in zip(maps, affine)]
+        out = primary(self).rollout_sampled(stages, primary(dynamics), np.repeat(starts, S, axis=0), normals.reshape(M * S, T, D), T, nugget,
+                                            dt=float(dt), x0=None if x0 is None else np.repeat(x0, S, axis=0), rtol=rtol,
+                                            max_passes=max_passes, outputs=names)
+        return {k: v.reshape((M, S) + v.shape[1:]) for k, v in out.items()}       # path index = m * n_samples + j
+
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):
         """Everything predict(x, return_std=True) and derivative(x, return_var=True) return, computed in ONE pass over

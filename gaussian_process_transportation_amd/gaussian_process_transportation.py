@@ -90,6 +90,14 @@ class GaussianProcessTransportation:
         return self.method.rollout_policy(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info, variance_gain=variance_gain,
                                           **solver)
 
+    def rollout_policy_samples(self, dynamics, starts, n_steps, n_samples=10, dt=1.0, nugget=None, random_state=0, normals=None,
+                               x0=None, return_info=False, **solver):
+        """n_samples paths per start of rollout_policy() when the dynamics is a function drawn from the posterior of `dynamics`,
+        each draw conditioned on the path's own earlier ones, in one device call (an addition:
+        PolicyTransportation.rollout_policy_samples).  Only the dynamics is sampled; the map acts through its mean."""
+        return self.method.rollout_policy_samples(dynamics, starts, n_steps, n_samples=n_samples, dt=dt, nugget=nugget,
+                                                  random_state=random_state, normals=normals, x0=x0, return_info=return_info, **solver)
+
     def sample_transportation(self):
         """Posterior draws of the moved demonstration, at the positions of the last apply_transportation() (:29-30)."""
         return self.method.sample_transportation(self._input("training_traj_old"))

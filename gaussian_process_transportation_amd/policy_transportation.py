@@ -169,6 +169,16 @@ class PolicyTransportation:
         return TransportChain([self], verbose=self.verbose).rollout(dynamics, starts, n_steps, dt=dt, x0=x0, return_info=return_info,
                                                                 variance_gain=variance_gain, **solver)
 
+    def rollout_policy_samples(self, dynamics, starts, n_steps, n_samples=10, dt=1.0, nugget=None, random_state=0, normals=None,
+                               x0=None, return_info=False, **solver):
+        """n_samples paths per start of rollout_policy() when the dynamics is a function drawn from the posterior of `dynamics`
+        (TransportChain.rollout_samples with this transport as its only stage).  Only the dynamics is sampled; the map acts
+        through its mean.  Returns paths (M,n_samples,n_steps+1,D); with return_info also a dict."""
+        from .transport_chain import TransportChain
+        return TransportChain([self], verbose=self.verbose).rollout_samples(dynamics, starts, n_steps, n_samples=n_samples, dt=dt,
+                                                                        nugget=nugget, random_state=random_state, normals=normals, x0=x0,
+                                                                        return_info=return_info, **solver)
+
     def sample_transportation(self, pos):
         pos_rotated = self.affine_transform.predict(pos)
         return pos_rotated + self.delta_map.samples(pos_rotated)

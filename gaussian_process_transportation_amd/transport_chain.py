@@ -135,3 +135,29 @@ class TransportChain:
         out = self._pull(self._still_dynamics(), points, x0, False, solver, outputs=None if return_info else ("x",))
         info = {k: v for k, v in out.items() if k not in ("vel", "f", "x")}
         return (out["x"], info) if return_info else out["x"]
+
+    def rollout_samples(self, dynamics, starts, n_steps, n_samples=10, dt=1.0, nugget=None, random_state=0, normals=None, x0=None,
+                        return_info=False, **solver):
+        """Which paths does the dynamics GP consider plausible from `starts` (M,D) of the LAST scene?  n_samples paths per start,
+        each the rollout() of ONE function drawn from the posterior of `dynamics`, the draw of a step conditioned on the path's
+        own earlier draws, in one device call (GaussianProcess.rollout_chain_samples: nugget, normals, random_state).  Only the
+        dynamics is sampled; the maps act through their means.  Returns paths (M,n_samples,n_steps+1,D); with return_info also a
+        dict: vel, x, f, pvar, cvar, steps_done, status (and chol for return_info="chol"), each with the leading shape
+        (M,n_samples).  Zero normals give rollout()."""
+        unknown = set(solver) - {"rtol", "max_passes"}
+        if unknown:
+            raise TypeError(f"TransportChain: unknown solver arguments {sorted(unknown)}")
+        rollout = getattr(self.methods[-1].delta_map, "rollout_chain_samples", None)
+        if rollout is None:
+            raise NotImplementedError(f"TransportChain.rollout_samples(): the delta_map of the last transport ({type(self.methods[-1].delta_map).__name__}) "
+                                      "has no rollout_chain_samples; GaussianProcess provides one")
+        affine = [(m.affine_transform.rotation_matrix, m.affine_transform.scale, m.affine_transform.S_centroid,
+                   m.affine_transform.T_centroid, m.affine_transform.rotation_matrix) for m in self.methods]
+        maps = [m.delta_map for m in self.methods]
+        out = rollout(maps[:-1], dynamics, starts, n_steps, affine, n_samples=n_samples, dt=dt, nugget=nugget, random_state=random_state,
+                      normals=normals, x0=x0, return_info=return_info, **solver)
+        if self.verbose:
+            status, done = out["status"], out["steps_done"]
+            counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.ROLLOUT_SAMPLED_STATUS_NAMES))
+            print(f"Sampled rollout of {done.size} paths, {int(n_steps)} steps: {int(np.sum(done == int(n_steps)))} complete; last status: {counts}")
+        return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]

@@ -578,6 +578,53 @@ int gpt_rollout_stabilised(const gpt_chain_stage* stages, int K, gpt_handle* h_d
                            int64_t n_steps, double dt, double rtol, int max_passes, double gain, double std_offset, double* path,
                            double* vel, double* x, double* f, double* var, double* dvar, int* steps_done, int* status);
 
+/* (new) Whole paths of FUNCTIONS DRAWN FROM THE DYNAMICS POSTERIOR: gpt_rollout_policy with, in place of the dynamics mean, one
+ * function drawn from the posterior of h_dyn per path, still one call.  The value drawn at step t is conditioned on what the same
+ * function was drawn to be at the path's own earlier points, so a path that revisits a region meets the same function there.  Only
+ * the dynamics is sampled; the maps act through their means.  Arguments, end rule, NaN filling, steps_done, the guesses, negative
+ * dt, launches and chunks as gpt_rollout_policy (M: the number of paths); in addition normals (M,T,D), standard normal numbers of
+ * the caller (the device generates none: given normals the call is a deterministic function), and nugget (finite, >= 0), added to
+ * the diagonal of a path's covariance: the model's noise level draws noisy values, the convention of gpt_predict_cov; a small
+ * positive number draws the latent function.  Per path and step, x_t the source-space preimage of y_t (K = 0: x_t = y_t),
+ * W = L^-1 the inverse factor of the dynamics, c its prior variance, k its kernel without noise:
+ *   f_t     = the mean of h_dyn at x_t
+ *   u_t     = W k*(x_t),   pvar_t = (c + nugget) - u_t . u_t
+ *   c_ts    = k(x_t, x_s) - u_t . u_s                                  s < t
+ *   g_ts    = (c_ts - sum_{r<s} g_tr g_sr) / g_ss, s ascending         row t of the lower factor G of the path's covariance
+ *   cvar_t  = pvar_t - sum_{s<t} g_ts^2                                the variance of the draw given the earlier ones
+ *   cvar_t NaN or <= 1024 * 2^-52 * (c + nugget): the path ENDS at step t with status GPT_ROLLOUT_DEGENERATE (x_t, f_t, pvar_t and
+ *             cvar_t are recorded, vel_t is NaN); mathematically cvar_t >= nugget, so a nugget above that floor never ends a path
+ *   g_tt    = sqrt(cvar_t)
+ *   fs_t,d  = f_t,d + sum_{r<=t} g_tr normals[r,d], r ascending, each product and sum rounded on its own
+ *   vel_t   = fs_t pushed through the maps exactly as gpt_pullback_chain pushes f (K = 0: vel_t = fs_t)
+ *   y_{t+1} = y_t + (dt vel_t)
+ * With all normals zero: the path, vel, x, steps_done and status of gpt_rollout_policy, bit for bit but for the sign of a zero.
+ * status (M, int): the GPT_INV_* of gpt_rollout_policy, or GPT_ROLLOUT_DEGENERATE.  A step whose inverse does not converge ends the
+ * path with that GPT_INV_* and its vel_t recorded, as in gpt_rollout_policy, with one exception: where the pivot of that same step is
+ * also degenerate there is no draw, and vel_t is NaN.  Further outputs, each may be NULL, NaN after a
+ * path's end: f (M,T,D), pvar (M,T), cvar (M,T), chol (M,T,T) = G, the lower triangle with zeros above it (the row of a degenerate
+ * step is NaN).
+ * One workgroup of four waves owns sixteen paths and shares the product with W on the matrix cores (k_rollout_sampled); a launch
+ * advances every live path by at most GPT_ROLLOUT_STEPS_PER_LAUNCH steps (default: gpt_rollout_sampled.h).  A path's values do not
+ * depend on M, on the other paths, on their order or on where the launches or the chunks are cut, bit for bit.
+ * Refusals beyond gpt_rollout_policy's, GPT_E_ARG: a dynamics of more than 1024 training points; n_steps above
+ * GPT_ROLLOUT_SAMPLED_MAX_T; nugget negative, NaN or infinite; normals NULL with M > 0 and n_steps > 0; a call whose scratch (u
+ * of every step, 128 ceil(M / 16) n_steps ceil(N / 64) 64 bytes, the factor, 8 M n_steps (n_steps + 8) bytes) exceeds 80 % of the device's free
+ * memory.  (Multi-task and fp32 models are refused as by gpt_rollout_policy; any of the four kernels is taken.)
+ * Device memory, asynchronous, streams and resources as gpt_rollout_policy_dev (the calls share them). */
+#define GPT_ROLLOUT_DEGENERATE 4
+#define GPT_ROLLOUT_SAMPLED_MAX_T 256
+int gpt_rollout_sampled_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0_dev, const double* x0_dev,
+                            const double* normals_dev, int64_t M, int64_t n_steps, double dt, double rtol, int max_passes, double nugget,
+                            double* path_dev, double* vel_dev, double* x_dev, double* f_dev, double* pvar_dev, double* cvar_dev,
+                            double* chol_dev, int* steps_done_dev, int* status_dev);
+/* (new) The same with every data pointer in host memory, checked and chunked as gpt_rollout_policy; also GPT_E_ARG for NaN or infinity
+ * in normals.  A chunk is further held to the paths whose scratch stays below 1 GiB (at least sixteen;
+ * GPT_ROLLOUT_SAMPLED_SCRATCH_BYTES overrides the budget). */
+int gpt_rollout_sampled(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0, const double* x0, const double* normals,
+                        int64_t M, int64_t n_steps, double dt, double rtol, int max_passes, double nugget, double* path, double* vel,
+                        double* x, double* f, double* pvar, double* cvar, double* chol, int* steps_done, int* status);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);

@@ -14,7 +14,14 @@ the parent commit: per step predict(return_std=True) and derivative_of_variance 
 --host) and, with maps, one transported_policy call before them and the push of the stabilised mean through its per-stage A in
 numpy.  Shapes then: 3d (the demo dynamics, N = 460, M = 1, T = 1000), 2d (its 10 x 10 grid, T = 200) and large with N_dyn = 1024,
 the largest the call admits, where the longest launch is measured for 16, 32 and 64 steps (the default is 32).
-usage: python tools/rollout_timing.py [--stabilised] [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
+--sampled times the sampled rollout (gpt_rollout_sampled: rollout_samples) instead, against the host loop a user would write from
+the calls that existed before it: per step and path predict(points so far, return_cov=True), np.linalg.cholesky and the draw from
+the factor's last row (with maps: one transported_policy call per step for x, f and the per-stage A, and the push in numpy).  That
+loop is serial in the paths, so on the larger shapes it is timed on the first --loop-paths paths and scaled to all of them, which
+the line says.  Shapes: 3d (the demo dynamics, N = 460, M = 1, S = 32, T = 200), 2d (10 x 10 starts, S = 8, T = 100) and large
+(N_map = 8192 twice, N_dyn = 1024, P = 1024, T = 64).  The per-launch times behind ROLLOUT_SAMPLED_STEPS_PER_LAUNCH come from the
+profiler's kernel trace, not from wall times: tools/rollout_sampled_launches.py.
+usage: python tools/rollout_timing.py [--stabilised | --sampled] [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
 import argparse
 import os
 import sys
@@ -144,17 +151,92 @@ def stabilised_main(a, say):
         del os.environ["GPT_ROLLOUT_STEPS_PER_LAUNCH"]
 
 
+def sampled_main(a, say):
+    for shape in a.shapes:
+        chain, dyn, _, y0, x0, _, dt = stab_cases(shape)
+        S, T = {"3d": (32, 200), "2d": (8, 100), "large": (1, 64)}[shape]
+        M, D = y0.shape
+        P = M * S
+        z = np.random.RandomState(0).standard_normal((M, S, T, D))
+        nug, noise = dyn._noise, dyn._noise
+        R = [] if chain is None else [np.asarray(m.affine_transform.rotation_matrix) for m in chain.methods]
+        n_loop = P if shape == "3d" else min(P, a.loop_paths)
+
+        def device():
+            t0 = time.perf_counter()
+            if chain is None:
+                path, info = dyn.rollout_samples(y0, T, n_samples=S, dt=dt, normals=z, return_info=True)
+            else:
+                path, info = chain.rollout_samples(dyn, y0, T, n_samples=S, dt=dt, normals=z, x0=x0, return_info=True)
+            return time.perf_counter() - t0, dict(info, path=path)
+
+        def loop():
+            """The first n_loop paths (path index = m S + j), one at a time."""
+            t0 = time.perf_counter()
+            paths = np.full((n_loop, T + 1, D), np.nan)
+            for p in range(n_loop):
+                m, j = divmod(p, S)
+                y, guess = y0[m:m + 1].copy(), None if x0 is None else x0[m:m + 1]
+                paths[p, 0] = y[0]
+                xs = np.zeros((0, D))
+                for t in range(T):
+                    if chain is None:
+                        x, A = y, None
+                    else:
+                        _, info = chain.transported_policy(dyn, y, x0=guess, return_info=True)
+                        if info["status"][0] != 0:
+                            break
+                        x, A = info["x"], info["stage_A"]
+                    xs = np.concatenate([xs, x])
+                    mean, cov = dyn.predict(np.ascontiguousarray(xs), return_cov=True)
+                    cov = (cov[..., 0] if cov.ndim == 3 else cov) + (nug - noise) * np.eye(t + 1)
+                    g = np.linalg.cholesky(cov)[t]
+                    v = (mean[t] + g @ z[m, j, :t + 1])[None]
+                    for k in range(len(R)):
+                        v = np.einsum("mij,mj->mi", A[k], v @ R[k].T)
+                    y = y + dt * v
+                    if not np.all(np.isfinite(y)):
+                        break
+                    paths[p, t + 1], guess = y[0], x
+            return time.perf_counter() - t0, paths
+        n_map = "none" if chain is None else " + ".join(str(len(m.delta_map.X)) for m in chain.methods)
+        say(f"== sampled {shape}: N_map = {n_map}, N_dyn = {len(dyn.X)}, D = {D}, M = {M} starts x S = {S} samples = {P} paths, T = {T}, dt = {dt}, "
+            f"nugget = noise = {nug:g}; median of {a.reps} (min .. max), ms")
+        times, res = {"device": [], "loop": []}, {}
+        for fn in (device, loop):
+            fn()
+        for _ in range(a.reps):
+            for name, fn in (("loop", loop), ("device", device)):
+                t, res[name] = fn()
+                times[name].append(t)
+        med = {n: 1e3 * float(np.median(t)) for n, t in times.items()}
+        scaled = med["loop"] * P / n_loop
+        dev_paths = res["device"]["path"].reshape(P, T + 1, D)[:n_loop]
+        both = np.isfinite(dev_paths) & np.isfinite(res["loop"])
+        gap = float(np.max(np.abs(dev_paths - res["loop"])[both])) if np.any(both) else 0.0
+        done = res["device"]["steps_done"]
+        say(f"   host loop, predict(return_cov) + cholesky + draw per step and path{'' if chain is None else ' (+ transported_policy)'}, {n_loop} of {P} paths : "
+            f"{med['loop']:10.3f}  ({1e3 * min(times['loop']):.3f} .. {1e3 * max(times['loop']):.3f})"
+            + ("" if n_loop == P else f"   -> scaled to {P} paths: {scaled:.3f}"))
+        say(f"   one call (gpt_rollout_sampled), all {P} paths : {med['device']:10.3f}  ({1e3 * min(times['device']):.3f} .. {1e3 * max(times['device']):.3f})"
+            f"   -> {scaled / med['device']:.1f} x; slower than the loop: {'NO' if med['device'] <= scaled else 'YES'}; largest gap between the two over "
+            f"their common steps {gap:.3e} (the dynamics amplifies rounding); steps done: min {int(done.min())}, max {int(done.max())}; "
+            f"status counts {np.bincount(res['device']['status'].ravel(), minlength=5).tolist()}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", choices=("2d", "large", "3d"), default=None)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
     ap.add_argument("--stabilised", action="store_true", help="the variance-stabilised rollout against its host loop")
+    ap.add_argument("--sampled", action="store_true", help="the sampled rollout against its host loop")
+    ap.add_argument("--loop-paths", type=int, default=8, help="--sampled: paths the host loop is timed on where it is scaled")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = ["3d", "2d", "large"] if a.stabilised else ["2d", "large"]
-    if "3d" in a.shapes and not a.stabilised:
-        ap.error("the 3d shape is the stabilised rollout's")
+        a.shapes = ["3d", "2d", "large"] if a.stabilised or a.sampled else ["2d", "large"]
+    if "3d" in a.shapes and not (a.stabilised or a.sampled):
+        ap.error("the 3d shape is the stabilised and the sampled rollout's")
     _lib.require_gpu()
     lines = []
 
@@ -163,6 +245,9 @@ def main():
         lines.append(s)
     if a.stabilised:
         stabilised_main(a, say)
+        a.shapes = []
+    if a.sampled:
+        sampled_main(a, say)
         a.shapes = []
     names = ("path", "vel", "x", "steps_done", "status")
     for shape in a.shapes:
