@@ -3,7 +3,8 @@
 // dynamics rolls out itself, v = its mean)  (internal header; plain C++, it also compiles under g++ for the sanitizer builds).
 // Every pointer is device memory, fp64 unless it says int; the arrays of a trajectory are contiguous (trajectory-major).  A
 // trajectory ends at the first step whose inverse is not CONVERGED or whose y_{t+1} is not finite: that step's x and vel are
-// still recorded, no y_{t+1} is, and every later row is NaN.
+// still recorded, no y_{t+1} is, and every later row is NaN.  (The device code of these rules, for the three rollout kernels:
+// gpt_rollout_body.h.)
 #pragma once
 #include "gpt_chain.h"
 
@@ -49,7 +50,7 @@ struct RolloutArgs {
 #ifdef __HIPCC__
 // y + (dt v), the product and the sum rounded separately.  (The compiler contracts a product and a sum into one fused multiply-add
 // wherever it may, the _rn intrinsics included: they are plain operators.  The pragma is what forbids it here.)  The step of
-// k_rollout and of k_rollout_stab (gpt_rollout_stab.hip).
+// k_rollout (gpt_rollout.hip), k_rollout_stab (gpt_rollout_stab.hip) and k_rollout_sampled (gpt_rollout_sampled.hip).
 __device__ __forceinline__ double euler_step(const double y, const double dt, const double v) {
 #pragma clang fp contract(off)
     const double p = dt * v;

@@ -6,12 +6,12 @@
 //               the body at y_t with the x of step t - 1 as its guess (at t = 0: X0, or none), then y_{t+1} = y_t + (dt vel_t), the
 //               product and the sum rounded separately (no fused multiply-add: numpy's y + dt * vel gives the same bits).  Every
 //               value is the same in every lane, every branch on it a scalar one; lane 0 stores each step's rows.  The
-//               trajectory ends at the first step whose status is not CONVERGED or whose y_{t+1} is not finite: the wave fills
-//               the rest of its rows with NaN and returns.  A launch evaluates steps t_begin .. t_end - 1; between launches a
-//               trajectory lives in its last path row, `state` (the last x) and steps_done, and a wave whose trajectory has
-//               ended (steps_done < t_begin) returns at once.  K = 0: x_t = y_t, vel_t = the dynamics mean.  A trajectory's sums
-//               run in a fixed order: its values do not depend on M, on the trajectories around it or on the launch boundaries.
-#include "gpt_rollout.h"
+//               trajectory ends at the first step whose status is not CONVERGED or whose y_{t+1} is not finite.  A launch
+//               evaluates steps t_begin .. t_end - 1; how a trajectory enters one, what it leaves behind and the NaN rows after
+//               its end are gpt_rollout_body.h's, shared with the other two rollout kernels; a wave whose trajectory does not
+//               enter returns at once.  K = 0: x_t = y_t, vel_t = the dynamics mean.  A trajectory's sums run in a fixed order:
+//               its values do not depend on M, on the trajectories around it or on the launch boundaries.
+#include "gpt_rollout_body.h"
 #include "gpt_chain_body.h"
 
 namespace gpt {
@@ -24,77 +24,44 @@ __global__ __launch_bounds__(256) void k_rollout(RolloutArgs a) {
     const int lane = threadIdx.x & 63;
     // (the wave's number goes through readfirstlane: m and every address built on it are scalar, which leaves the vector registers to the body)
     const int64_t m = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (m >= a.M) return;
-    const int T = a.T, t_begin = a.t_begin, t_end = a.t_end;
-    if (t_begin > 0 && __builtin_amdgcn_readfirstlane(a.steps_done[m]) != t_begin) return;     // ended in an earlier launch
-    // the trajectory's first row of path, and of vel and x (recomputed where they are used: nothing but m lives across the body)
-    auto path_row = [&](const int64_t t) { return a.path + (m * ((int64_t)T + 1) + t) * D; };
-    auto step_row = [&](double* const p, const int64_t t) { return p + (m * (int64_t)T + t) * D; };
-    double y[D], guess[D];
-    bool have_guess = true;
-    if (t_begin == 0) {
-        have_guess = a.X0 != nullptr;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            y[d] = a.Y0[m * D + d];
-            guess[d] = a.X0 ? a.X0[m * D + d] : 0.0;
-            if (lane == 0) path_row(0)[d] = y[d];
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            y[d] = path_row(t_begin)[d];
-            guess[d] = a.state[m * D + d];
-        }
-    }
+    if (!rollout_enters(a, m)) return;
+    const int t_begin = a.t_begin, t_end = a.t_end;
+    RolloutCarry<D> c = rollout_entry<D>(a, m, lane == 0);
     int t = t_begin, status = INV_CONVERGED;
     for (; t < t_end; ++t) {
         double x[D], f[D], vel[D], yn[D];
         if (a.K == 0) {
 #pragma unroll
-            for (int d = 0; d < D; ++d) x[d] = y[d];
+            for (int d = 0; d < D; ++d) x[d] = c.y[d];
             ch_mean<D>(a.dyn, Tt, lane, x, vel);
         } else {
-            status = chain_point<D>(a.st, a.dyn, a.K, a.rtol, a.max_passes, Tt, lane, have_guess, guess, y, x, f, vel,
+            status = chain_point<D>(a.st, a.dyn, a.K, a.rtol, a.max_passes, Tt, lane, c.have_guess, c.guess, c.y, x, f, vel,
                                     [](int, const double (&)[D], const double (&)[D], const double (&)[D][D], int, int, double) {});
         }
         bool ok = status == INV_CONVERGED;
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            yn[d] = euler_step(y[d], a.dt, vel[d]);
+            yn[d] = euler_step(c.y[d], a.dt, vel[d]);
             ok = ok && __builtin_isfinite(yn[d]);
         }
         if (lane == 0) {
 #pragma unroll
             for (int d = 0; d < D; ++d) {
-                if (a.vel) step_row(a.vel, t)[d] = vel[d];
-                if (a.x) step_row(a.x, t)[d] = x[d];
+                if (a.vel) step_row<D>(a, a.vel, m, t)[d] = vel[d];
+                if (a.x) step_row<D>(a, a.x, m, t)[d] = x[d];
             }
         }
         if (!__builtin_amdgcn_readfirstlane(ok ? 1 : 0)) break;      // (every lane holds the same value)
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            if (lane == 0) path_row((int64_t)t + 1)[d] = yn[d];
-            y[d] = yn[d];
-            guess[d] = x[d];
+            if (lane == 0) path_row<D>(a, m, (int64_t)t + 1)[d] = yn[d];
+            c.y[d] = yn[d];
+            c.guess[d] = x[d];
         }
-        have_guess = true;
+        c.have_guess = true;
     }
-    if (t < t_end) {                                  // ended at step t: nothing after it exists
-        const double nan = __builtin_nan("");
-        for (int64_t i = ((int64_t)t + 1) * D + lane; i < ((int64_t)T + 1) * D; i += 64) path_row(0)[i] = nan;
-        for (int64_t i = ((int64_t)t + 1) * D + lane; i < (int64_t)T * D; i += 64) {
-            if (a.vel) step_row(a.vel, 0)[i] = nan;
-            if (a.x) step_row(a.x, 0)[i] = nan;
-        }
-    }
-    if (lane != 0) return;
-    a.steps_done[m] = t;
-    a.status[m] = status;
-    if (t == t_end && t_end < T) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) a.state[m * D + d] = guess[d];
-    }
+    if (t < t_end) rollout_end_fill<D>(a, RolloutOwn{}, m, t, lane);
+    if (lane == 0) rollout_leave<D>(a, m, t, status, t == t_end, c.guess);
 }
 
 void launch_rollout(hipStream_t s, int D, const RolloutArgs& a) {

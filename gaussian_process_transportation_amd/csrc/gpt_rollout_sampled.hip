@@ -9,9 +9,9 @@
 //                 2. image     each wave writes the k* columns of its four paths for every source into a rows x 16 image in LDS
 //                              (rows >= N, the columns of an ended path and of a path past P: zero): one lane per source row, the
 //                              distances and the kernel value of stab_columns, the k* column only, so any of the four kernels
-//                 3. sweep     after a barrier the four waves sweep Wf with v_mfma_f64_16x16x4_f64, the loop and the deal of
-//                              stab_sweep; the finished C tiles are u_t = W k*(x_t) of the sixteen paths and go to U[t] in
-//                              global memory, 64 consecutive doubles per store (row n, column c at 16 n + c: the C tile)
+//                 3. sweep     after a barrier the four waves sweep Wf with v_mfma_f64_16x16x4_f64 (rollout_w_sweep of
+//                              gpt_rollout_body.h); the finished C tiles are u_t = W k*(x_t) of the sixteen paths and go to U[t]
+//                              in global memory, 64 consecutive doubles per store (row n, column c at 16 n + c: the C tile)
 //                 4. cross     after a barrier the waves share s = 0 .. t in blocks of four: u_t . u_s for sixteen paths at once,
 //                              lane (c, q) sums rows q, q + 4, .. < N ascending, two shuffles add the four q; sixteen results
 //                              per s go to cb[s]
@@ -21,15 +21,15 @@
 //                              g_ts g_rs, reading column s of the factor (stored transposed, so that a column is consecutive);
 //                              the squares and the draw are summed as the pivots come, in the order of gpt_rollout_sampled.h.
 //                              Then the degenerate rule, the push-forward (chain_push), the Euler step, the step's rows, the end
-//                              rule of k_rollout.
+//                              rule of k_rollout (entering a launch, the NaN rows after an end, leaving: gpt_rollout_body.h).
 //               MFMA columns do not mix and every order is fixed by N, t and the lane layout alone: a path's values do not depend
 //               on P, on its neighbours, alive or ended, on its column, nor on the launch cuts (everything a later launch needs is
 //               in global memory; it resumes from steps_done).  Whether any path is alive is read after the barrier of step 2 from
 //               flags set in step 5 of the step before, so a workgroup leaves together, one (empty) image late.
 #include "gpt_rollout_sampled.h"
+#include "gpt_rollout_body.h"
 #include "gpt_chain_body.h"
 #include "gpt_dispatch.h"
-#include "gpt_kvar.h"
 
 namespace gpt {
 
@@ -79,49 +79,16 @@ __device__ __forceinline__ void sampled_columns(const ChainModel& m, const int r
     }
 }
 
-// Step 3: this wave's share of u = W B, stored to `u` (row n, column c at 16 n + c).  Wf: tile (ib, kb) at ib (ib + 1) / 2 + kb,
-// inside it [k4][g][q][lane][p] (k_pack_w); the loop, the deal of the groups and the prefetch are stab_sweep's.  Lane l of a
-// finished C tile holds column l & 15, rows (l >> 4) + 4 e: element e of row tile r of group G is the 64 doubles at
-// 16 (64 G + 16 r + 4 e).  Row tiles with no row below N are stored as zeros.
+// Step 3: this wave's share of u = W B (rollout_w_sweep), stored to `u` (row n, column c at 16 n + c): element e of row tile r of
+// group G is the 64 doubles at 16 (64 G + 16 r + 4 e).  Row tiles with no row below N are stored as zeros.
 __device__ __forceinline__ void sampled_sweep(const double* __restrict__ Wf, const int N, const double* __restrict__ img, const int w,
                                               const int lane, double* __restrict__ u) {
-    typedef El<double>::AF AF;
-    constexpr int PF = 4;
-    const d2* const wf2 = reinterpret_cast<const d2*>(Wf);
-    const int ngroups = (N + 63) >> 6;
-    for (int G = w; G < ngroups; G += (G & 7) < 4 ? 7 - 2 * (G & 7) : 1 + 2 * (7 - (G & 7))) {
-        const int ib = G >> 3, g = G & 7;
-        const int left = N - 64 * G;
-        const int rmax = left >= 64 ? 4 : (left + 15) >> 4;
-        const int ksteps = 16 * (G + 1), kdiag = 16 * G;
-        auto aptr = [&](const int k4) {
-            return wf2 + ((size_t)(ib * (ib + 1) / 2 + (k4 >> 7)) * (WT_TILE_DOUBLES / 2) + (size_t)(((k4 & (WT_K4 - 1)) * WT_GROUPS + g) * El<double>::A_GROUP));
-        };
-        AF a[PF];
-#pragma unroll
-        for (int i = 0; i < PF; ++i) El<double>::lda(a[i], aptr(i), lane);
-        d4 acc[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = d4{0.0, 0.0, 0.0, 0.0};
-        for (int k4 = 0; k4 < ksteps; k4 += PF) {
-            const int r0 = k4 >= kdiag ? (k4 - kdiag) >> 2 : 0;
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const double b = img[(size_t)(k4 + i) * 64 + lane];
-                const AF cur = a[i];
-                const int kn = k4 + i + PF < ksteps ? k4 + i + PF : ksteps - 1;      // clamped: redundant, in bounds
-                El<double>::lda(a[i], aptr(kn), lane);
-                if (r0 <= 0 && rmax > 0) acc[0] = El<double>::mfma(cur.lo[0], b, acc[0]);
-                if (r0 <= 1 && rmax > 1) acc[1] = El<double>::mfma(cur.lo[1], b, acc[1]);
-                if (r0 <= 2 && rmax > 2) acc[2] = El<double>::mfma(cur.hi[0], b, acc[2]);
-                if (rmax > 3) acc[3] = El<double>::mfma(cur.hi[1], b, acc[3]);
-            }
-        }
+    rollout_w_sweep(Wf, N, img, w, lane, [&](const int G, const d4 (&acc)[4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
             for (int e = 0; e < 4; ++e) u[(size_t)(64 * G + 16 * r + 4 * e) * 16 + lane] = acc[r][e];
-    }
+    });
 }
 
 // Step 4: u_t . u_s for s = 0 .. t, sixteen paths at once; wave w takes the blocks of four s numbered w, w + 4, ..
@@ -221,15 +188,12 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
     double* const cb = s.cb + (size_t)blockIdx.x * ((size_t)T + 1) * 16;
     const double cn = s.c + s.nugget;
     const double nan = __builtin_nan("");
-    auto path_row = [&](const int64_t m, const int64_t t) { return a.path + (m * ((int64_t)T + 1) + t) * D; };
-    auto step_row = [&](double* const p, const int64_t m, const int64_t t) { return p + (m * (int64_t)T + t) * D; };
 
 #pragma unroll 1
     for (int j = 0; j < 4; ++j) {
         const int c = 4 * w + j;
         const int64_t m = m0 + c;
-        bool alive = m < a.M;
-        if (alive && t_begin > 0 && __builtin_amdgcn_readfirstlane(a.steps_done[m]) != t_begin) alive = false;     // ended in an earlier launch
+        const bool alive = rollout_enters(a, m);
         if (lane == 0) {
             SampledPath& P = ps[c];
             P.alive = P.entered = alive ? 1 : 0;
@@ -237,21 +201,10 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) { P.y[d] = 0.0; P.guess[d] = 0.0; P.x[d] = 0.0; P.f[d] = 0.0; }
             if (alive) {
-                if (t_begin == 0) {
-                    P.have_guess = a.X0 != nullptr;
+                const RolloutCarry<D> e = rollout_entry<D>(a, m, true);
+                P.have_guess = e.have_guess;
 #pragma unroll
-                    for (int d = 0; d < D; ++d) {
-                        P.y[d] = a.Y0[m * D + d];
-                        P.guess[d] = a.X0 ? a.X0[m * D + d] : 0.0;
-                        path_row(m, 0)[d] = P.y[d];
-                    }
-                } else {
-#pragma unroll
-                    for (int d = 0; d < D; ++d) {
-                        P.y[d] = path_row(m, t_begin)[d];
-                        P.guess[d] = a.state[m * D + d];
-                    }
-                }
+                for (int d = 0; d < D; ++d) { P.y[d] = e.y[d]; P.guess[d] = e.guess[d]; }
             }
         }
     }
@@ -327,7 +280,7 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
             int status = P.status;
             if (lane == 0) {                          // x_t joins the path's points (earlier rows are read below: other lanes, other rows)
 #pragma unroll
-                for (int d = 0; d < D; ++d) step_row(a.x, m, t)[d] = x[d];
+                for (int d = 0; d < D; ++d) step_row<D>(a, a.x, m, t)[d] = x[d];
             }
             double* const gt = s.Gt + (size_t)m * T * ld;
             const double* const zp = s.normals + (size_t)m * T * D;
@@ -339,7 +292,7 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
 #pragma unroll
                 for (int d = 0; d < D; ++d) z[i][d] = 0.0;
                 if (r < t) {
-                    const double* const xr = step_row(a.x, m, r);
+                    const double* const xr = step_row<D>(a, a.x, m, r);
                     double kv;
                     switch (a.dyn.ktype) {
                         case KT_MATERN12: kv = sampled_prior<KT_MATERN12, D>(a.dyn, Tt, q, xr); break;
@@ -390,8 +343,8 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
             if (lane == 0) {
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    if (a.vel) step_row(a.vel, m, t)[d] = vel[d];
-                    if (s.f) step_row(s.f, m, t)[d] = f[d];
+                    if (a.vel) step_row<D>(a, a.vel, m, t)[d] = vel[d];
+                    if (s.f) step_row<D>(a, s.f, m, t)[d] = f[d];
                 }
                 if (s.pvar) s.pvar[m * (int64_t)T + t] = pvar;
                 if (s.cvar) s.cvar[m * (int64_t)T + t] = cvar;
@@ -400,7 +353,7 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
                 if (lane == 0) {
 #pragma unroll
                     for (int d = 0; d < D; ++d) {
-                        path_row(m, (int64_t)t + 1)[d] = yn[d];
+                        path_row<D>(a, m, (int64_t)t + 1)[d] = yn[d];
                         P.y[d] = yn[d];
                         P.guess[d] = x[d];
                     }
@@ -409,18 +362,7 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
                 }
             } else {                                  // ended at step t: nothing after it exists
                 if (lane == 0) { P.alive = 0; P.t_stop = t; P.status = status; }
-                for (int64_t i = ((int64_t)t + 1) * D + lane; i < ((int64_t)T + 1) * D; i += 64) path_row(m, 0)[i] = nan;
-                for (int64_t i = ((int64_t)t + 1) * D + lane; i < (int64_t)T * D; i += 64) {
-                    if (a.vel) step_row(a.vel, m, 0)[i] = nan;
-                    step_row(a.x, m, 0)[i] = nan;
-                    if (s.f) step_row(s.f, m, 0)[i] = nan;
-                }
-                for (int64_t i = (int64_t)t + 1 + lane; i < T; i += 64) {
-                    if (s.pvar) s.pvar[m * (int64_t)T + i] = nan;
-                    if (s.cvar) s.cvar[m * (int64_t)T + i] = nan;
-                }
-                if (s.chol)
-                    for (int64_t i = ((int64_t)t + 1) * T + lane; i < (int64_t)T * T; i += 64) s.chol[(size_t)m * T * T + i] = nan;
+                rollout_end_fill<D>(a, RolloutOwn{{s.f, nullptr}, {s.pvar, s.cvar}, s.chol}, m, t, lane);
             }
         }
         __syncthreads();                              // (the records again, and the flags the next step's exit reads)
@@ -431,13 +373,7 @@ __global__ __launch_bounds__(256) void k_rollout_sampled(RolloutSampledArgs s) {
         const int c = 4 * w + j;
         const SampledPath& P = ps[c];
         if (!P.entered) continue;
-        const int64_t m = m0 + c;
-        a.steps_done[m] = P.t_stop;
-        a.status[m] = P.status;
-        if (P.t_stop == t_end && P.alive && t_end < T) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) a.state[m * D + d] = P.guess[d];
-        }
+        rollout_leave<D>(a, m0 + c, P.t_stop, P.status, P.alive != 0, P.guess);
     }
 }
 

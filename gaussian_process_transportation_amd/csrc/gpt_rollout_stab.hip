@@ -10,26 +10,25 @@
 //                              into an NP x 16 image in LDS (trajectory j of the workgroup: columns 4j .. 4j+3; rows >= N, the
 //                              columns of an ended trajectory and of a wave past M: zero).  One lane per source row, k and g
 //                              from one exp (gpt_exp.h), the column formulas of k_var's generating sweep.
-//                 3. sweep     after a barrier the four waves sweep Wf with v_mfma_f64_16x16x4_f64: sixteen columns are one
-//                              MFMA tile, so four trajectories fill the instruction one alone would use a quarter of.  A wave
-//                              takes whole 64-row groups (the 2 KiB records of k_pack_w, 16 bytes per lane), dealt 0 1 2 3 3 2 1 0
-//                              per eight groups: the triangle gives group G 16 (G + 1) k4-steps, and this deal gives every wave
-//                              the same number where round-robin would give the last wave twice the first's.  A row tile runs k
-//                              to its diagonal only; row tiles >= N are skipped.  The finished C tile is squared and
-//                              cross-multiplied with its k* column (the shuffle of k_var) into two sums per lane.
+//                 3. sweep     after a barrier the four waves sweep Wf with v_mfma_f64_16x16x4_f64 (rollout_w_sweep of
+//                              gpt_rollout_body.h: the deal of the 64-row groups, the layout of Wf, the prefetch): sixteen columns
+//                              are one MFMA tile, so four trajectories fill the instruction one alone would use a quarter of.  The
+//                              finished C tiles are squared and cross-multiplied with their k* column (the shuffle of k_var) into
+//                              two sums per lane.
 //                 4. reduce    across the lanes (two shuffles), then across the waves through LDS in wave order; a wave reads the
 //                              four sums of its own columns.  MFMA columns do not mix and every order is fixed by N alone: a
 //                              trajectory's var and gradient do not depend on its neighbours, alive or ended, nor on which of
 //                              the four column groups it sits in.
 //                 5. finish    each live wave: var, g, s, ghat, fs (gpt_rollout_stab.h), the push-forward (chain_push), the
 //                              Euler step, the step's rows (lane 0), the end rule of k_rollout.
+//               Entering a launch, the NaN rows after an end and leaving: gpt_rollout_body.h, as k_rollout.
 //               Three barriers per step would be one too many: whether any trajectory is alive is read after the barrier of
 //               step 2 from flags the waves set in step 5 of the step before, so a workgroup leaves together, one (empty) image
 //               late.  Waves whose trajectory has ended keep writing zeros, sweeping and meeting the barriers until then.
 #include "gpt_rollout_stab.h"
+#include "gpt_rollout_body.h"
 #include "gpt_chain_body.h"
 #include "gpt_dispatch.h"
-#include "gpt_kvar.h"
 
 namespace gpt {
 
@@ -58,46 +57,12 @@ __device__ __forceinline__ void stab_columns(const ChainModel& m, const int NP, 
     }
 }
 
-// Step 3: this wave's share of V = W B, folded into ssq = sum of squares and crs = sum of products with the k* column of the
-// lane's column (lane & 15), over the rows the lane holds.  Wf: tile (ib, kb) at ib (ib + 1) / 2 + kb, inside it
-// [k4][g][q][lane][p] (k_pack_w); the image: row n, column c at 16 n + c, so that k4-step k is the 64 consecutive doubles at 64 k.
+// Step 3: this wave's share of V = W B (rollout_w_sweep), folded into ssq = sum of squares and crs = sum of products with the k*
+// column of the lane's column (lane & 15), over the rows the lane holds.
 __device__ __forceinline__ void stab_sweep(const double* __restrict__ Wf, const int N, const double* __restrict__ img, const int w,
                                            const int lane, double& ssq, double& crs) {
-    typedef El<double>::AF AF;
-    constexpr int PF = 4;                             // A fragments in flight (k4-steps ahead); divides 16
-    const d2* const wf2 = reinterpret_cast<const d2*>(Wf);
-    const int ngroups = (N + 63) >> 6;
     ssq = 0.0; crs = 0.0;
-    for (int G = w; G < ngroups; G += (G & 7) < 4 ? 7 - 2 * (G & 7) : 1 + 2 * (7 - (G & 7))) {
-        // (wave w: groups w, 7 - w, 8 + w, 15 - w)
-        const int ib = G >> 3, g = G & 7;
-        const int left = N - 64 * G;                  // rows of the model in this group
-        const int rmax = left >= 64 ? 4 : (left + 15) >> 4;      // row tiles with a row below N
-        const int ksteps = 16 * (G + 1), kdiag = 16 * G;      // the group's own 64 x 64 block of W starts at k4-step kdiag
-        auto aptr = [&](const int k4) {
-            return wf2 + ((size_t)(ib * (ib + 1) / 2 + (k4 >> 7)) * (WT_TILE_DOUBLES / 2) + (size_t)(((k4 & (WT_K4 - 1)) * WT_GROUPS + g) * El<double>::A_GROUP));
-        };
-        AF a[PF];
-#pragma unroll
-        for (int i = 0; i < PF; ++i) El<double>::lda(a[i], aptr(i), lane);
-        d4 acc[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = d4{0.0, 0.0, 0.0, 0.0};
-        for (int k4 = 0; k4 < ksteps; k4 += PF) {
-            // row tile r of the group is zero from k4-step kdiag + 4 (r + 1) on: it runs to its diagonal only
-            const int r0 = k4 >= kdiag ? (k4 - kdiag) >> 2 : 0;
-#pragma unroll
-            for (int i = 0; i < PF; ++i) {
-                const double b = img[(size_t)(k4 + i) * 64 + lane];
-                const AF cur = a[i];
-                const int kn = k4 + i + PF < ksteps ? k4 + i + PF : ksteps - 1;      // clamped: redundant, in bounds
-                El<double>::lda(a[i], aptr(kn), lane);
-                if (r0 <= 0 && rmax > 0) acc[0] = El<double>::mfma(cur.lo[0], b, acc[0]);
-                if (r0 <= 1 && rmax > 1) acc[1] = El<double>::mfma(cur.lo[1], b, acc[1]);
-                if (r0 <= 2 && rmax > 2) acc[2] = El<double>::mfma(cur.hi[0], b, acc[2]);
-                if (rmax > 3) acc[3] = El<double>::mfma(cur.hi[1], b, acc[3]);
-            }
-        }
+    rollout_w_sweep(Wf, N, img, w, lane, [&](int, const d4 (&acc)[4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -106,7 +71,7 @@ __device__ __forceinline__ void stab_sweep(const double* __restrict__ Wf, const 
                 ssq += v * v;
                 crs += v * __shfl(v, lane & ~3);
             }
-    }
+    });
 }
 
 template <int D>
@@ -122,32 +87,11 @@ __global__ __launch_bounds__(256) void k_rollout_stab(RolloutStabArgs s) {
     const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t m = (int64_t)blockIdx.x * 4 + w;
     const int T = a.T, t_begin = a.t_begin, t_end = a.t_end;
-    bool alive = m < a.M;
-    if (alive && t_begin > 0 && __builtin_amdgcn_readfirstlane(a.steps_done[m]) != t_begin) alive = false;     // ended in an earlier launch
-    const bool entered = alive;
-    auto path_row = [&](const int64_t t) { return a.path + (m * ((int64_t)T + 1) + t) * D; };
-    auto step_row = [&](double* const p, const int64_t t) { return p + (m * (int64_t)T + t) * D; };
-    double y[D], guess[D];
-    bool have_guess = true;
-#pragma unroll
-    for (int d = 0; d < D; ++d) { y[d] = 0.0; guess[d] = 0.0; }
-    if (alive) {
-        if (t_begin == 0) {
-            have_guess = a.X0 != nullptr;
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                y[d] = a.Y0[m * D + d];
-                guess[d] = a.X0 ? a.X0[m * D + d] : 0.0;
-                if (lane == 0) path_row(0)[d] = y[d];
-            }
-        } else {
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                y[d] = path_row(t_begin)[d];
-                guess[d] = a.state[m * D + d];
-            }
-        }
-    }
+    const bool entered = rollout_enters(a, m);
+    bool alive = entered;
+    RolloutCarry<D> c{};
+    c.have_guess = true;
+    if (alive) c = rollout_entry<D>(a, m, lane == 0);
     if (lane == 0) live[w] = alive ? 1 : 0;
     __syncthreads();
     int status = INV_CONVERGED, t_stop = t_end;
@@ -163,9 +107,9 @@ __global__ __launch_bounds__(256) void k_rollout_stab(RolloutStabArgs s) {
         if (alive) {
             if (a.K == 0) {
 #pragma unroll
-                for (int d = 0; d < D; ++d) x[d] = y[d];
+                for (int d = 0; d < D; ++d) x[d] = c.y[d];
             } else {
-                status = chain_invert<D>(a.st, a.K, a.rtol, a.max_passes, Tt, lane, have_guess, guess, y, x, Q, A,
+                status = chain_invert<D>(a.st, a.K, a.rtol, a.max_passes, Tt, lane, c.have_guess, c.guess, c.y, x, Q, A,
                                          [](int, const double (&)[D], const double (&)[D], const double (&)[D][D], int, int, double) {});
             }
             ch_mean<D>(a.dyn, Tt, lane, x, f);
@@ -188,7 +132,7 @@ __global__ __launch_bounds__(256) void k_rollout_stab(RolloutStabArgs s) {
         __syncthreads();
         if (!alive) continue;
         // ---- 5. finish
-        auto total = [&](const int which, const int c) { return ((red[0][which][c] + red[1][which][c]) + red[2][which][c]) + red[3][which][c]; };
+        auto total = [&](const int which, const int col) { return ((red[0][which][col] + red[1][which][col]) + red[2][which][col]) + red[3][which][col]; };
         double var = s.c + s.noise - total(0, 4 * w);
         var = var < 0.0 ? 0.0 : var;
         double g[D], ghat[D], fs[D], vel[D], yn[D];
@@ -207,50 +151,35 @@ __global__ __launch_bounds__(256) void k_rollout_stab(RolloutStabArgs s) {
         bool ok = status == INV_CONVERGED;
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            yn[d] = euler_step(y[d], a.dt, vel[d]);
+            yn[d] = euler_step(c.y[d], a.dt, vel[d]);
             ok = ok && __builtin_isfinite(yn[d]);
         }
         if (lane == 0) {
 #pragma unroll
             for (int d = 0; d < D; ++d) {
-                if (a.vel) step_row(a.vel, t)[d] = vel[d];
-                if (a.x) step_row(a.x, t)[d] = x[d];
-                if (s.f) step_row(s.f, t)[d] = f[d];
-                if (s.dvar) step_row(s.dvar, t)[d] = g[d];
+                if (a.vel) step_row<D>(a, a.vel, m, t)[d] = vel[d];
+                if (a.x) step_row<D>(a, a.x, m, t)[d] = x[d];
+                if (s.f) step_row<D>(a, s.f, m, t)[d] = f[d];
+                if (s.dvar) step_row<D>(a, s.dvar, m, t)[d] = g[d];
             }
             if (s.var) s.var[m * (int64_t)T + t] = var;
         }
         if (__builtin_amdgcn_readfirstlane(ok ? 1 : 0)) {      // (every lane holds the same value)
 #pragma unroll
             for (int d = 0; d < D; ++d) {
-                if (lane == 0) path_row((int64_t)t + 1)[d] = yn[d];
-                y[d] = yn[d];
-                guess[d] = x[d];
+                if (lane == 0) path_row<D>(a, m, (int64_t)t + 1)[d] = yn[d];
+                c.y[d] = yn[d];
+                c.guess[d] = x[d];
             }
-            have_guess = true;
+            c.have_guess = true;
         } else {                                      // ended at step t: nothing after it exists
             alive = false;
             t_stop = t;
             if (lane == 0) live[w] = 0;
-            const double nan = __builtin_nan("");
-            for (int64_t i = ((int64_t)t + 1) * D + lane; i < ((int64_t)T + 1) * D; i += 64) path_row(0)[i] = nan;
-            for (int64_t i = ((int64_t)t + 1) * D + lane; i < (int64_t)T * D; i += 64) {
-                if (a.vel) step_row(a.vel, 0)[i] = nan;
-                if (a.x) step_row(a.x, 0)[i] = nan;
-                if (s.f) step_row(s.f, 0)[i] = nan;
-                if (s.dvar) step_row(s.dvar, 0)[i] = nan;
-            }
-            if (s.var)
-                for (int64_t i = (int64_t)t + 1 + lane; i < T; i += 64) s.var[m * (int64_t)T + i] = nan;
+            rollout_end_fill<D>(a, RolloutOwn{{s.f, s.dvar}, {s.var, nullptr}, nullptr}, m, t, lane);
         }
     }
-    if (!entered || lane != 0) return;
-    a.steps_done[m] = t_stop;
-    a.status[m] = status;
-    if (t_stop == t_end && alive && t_end < T) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) a.state[m * D + d] = guess[d];
-    }
+    if (entered && lane == 0) rollout_leave<D>(a, m, t_stop, status, alive, c.guess);
 }
 
 void launch_rollout_stab(hipStream_t st, int D, const RolloutStabArgs& a) {
