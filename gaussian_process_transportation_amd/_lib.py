@@ -39,6 +39,10 @@ ROLLOUT_SAMPLED_OUTPUTS = ("path", "vel", "x", "f", "pvar", "cvar", "chol", "ste
 ROLLOUT_SAMPLED_MAX_T = 256   # GPT_ROLLOUT_SAMPLED_MAX_T: steps of a sampled rollout, at most
 ROLLOUT_DEGENERATE = 4        # GPT_ROLLOUT_DEGENERATE: status of a sampled path whose conditional variance fell to rounding level
 ROLLOUT_SAMPLED_STATUS_NAMES = INV_STATUS_NAMES + ("DEGENERATE",)      # the status of a sampled path, by value
+# outputs of gpt_rollout_pathwise, in the order of its arguments
+ROLLOUT_PATHWISE_OUTPUTS = ("path", "vel", "x", "f", "steps_done", "status")
+ROLLOUT_NO_FUNCTION = -1      # GPT_ROLLOUT_NO_FUNCTION: status of a path of rollout_pathwise_dev whose func entry names no function
+PATHWISE_MAX_FREQ = 8192      # GPT_PATHWISE_MAX_FREQ: frequencies of the drawn functions of a pathwise rollout, at most
 MAX_D = 15         # input dimensions the library accepts (gpt_common.h MAX_DIMS: D <= 3 tuned layout, 4 .. 8 rows of 8, 9 .. 15 rows of 16)
 _NP_DTYPE = {GPT_F64: np.float64, GPT_F32: np.float32}
 
@@ -96,9 +100,14 @@ SIGNATURES = {
                                            C.c_double] + [_vp] * 9),
     "gpt_rollout_sampled": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _dp, _i64, _i64, C.c_double, C.c_double, C.c_int,
                                        C.c_double] + [_dp] * 7 + [_ip] * 2),
+    "gpt_rollout_pathwise_dev": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _vp, _vp, _vp, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                            _i64, _vp, _i64, _vp, _vp] + [_vp] * 6),
+    "gpt_rollout_pathwise": (C.c_int, [C.POINTER(ChainStage), C.c_int, _vp, _dp, _dp, _ip, _i64, _i64, C.c_double, C.c_double, C.c_int,
+                                        _i64, _dp, _i64, _dp, _dp] + [_dp] * 4 + [_ip] * 2),
     "gpt_predict_cov": (C.c_int, [_vp, _dp, _i64, _dp, _dp]),
     "gpt_export": (C.c_int, [_vp, _dp, _dp]),
     "gpt_export_inverse_factor": (C.c_int, [_vp, _dp]),
+    "gpt_apply_inverse": (C.c_int, [_vp, _dp, _i64, _dp]),
     "gpt_lml": (C.c_int, [_vp, _dp]),
     "gpt_lml_gradient": (C.c_int, [_vp, _dp, _dp]),
     "gpt_lml_objective": (C.c_int, [_vp, _dp, _dp, _i64, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
@@ -808,6 +817,20 @@ class Handle:
         check(self.lib.gpt_export_inverse_factor(self._h, dptr(W)), "gpt_export_inverse_factor")
         return W
 
+    def apply_inverse(self, R):
+        """(K + sigma^2 I)^-1 R for the columns of R (N,C) or one column (N,), with the inverse factor of this handle's own fit
+        (gpt_apply_inverse: the launches that compute alpha in the fit, four columns per pass).  R = Y gives the alpha of
+        export(), bit for bit; a column's result does not depend on the other columns.  float64, single-task, exact-GP models."""
+        N = self.info()[0]
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        one = R.ndim == 1
+        R2 = R.reshape(N, -1) if one and R.shape == (N,) else R
+        if R2.ndim != 2 or R2.shape[0] != N:
+            raise ValueError(f"apply_inverse: R has shape {R.shape}, expected ({N}, C) or ({N},): one row per training point")
+        out = np.empty_like(R2)
+        check(self.lib.gpt_apply_inverse(self._h, dptr(R2), R2.shape[1], dptr(out)), "gpt_apply_inverse")
+        return out[:, 0] if one else out
+
     def debug_set_inverse_factor(self, W):
         """Replace the inverse factor of this handle's own fit by the dense (N, N) float64 array W (gpt_debug_set_inverse_factor;
         tests only): the variance kernels then work on W's lower triangle, LML calls refuse until the next fit."""
@@ -1092,8 +1115,8 @@ class Handle:
     # ---- whole paths of the transported policy: the loop over the steps on the device
     def _rollout_host(self, what, names, optional, extra, inner, dyn, y0, n_steps, dt, x0, rtol, max_passes, outputs, inputs=()):
         """The host entry `gpt_<what>` of a rollout family: `names` its outputs in the order of its arguments, `optional` those the
-        caller chooses among, `extra` the arguments between max_passes and the outputs, `inputs` the float64 arrays (or None) it
-        takes between x0 and M."""
+        caller chooses among, `extra` the arguments between max_passes and the outputs, `inputs` the arrays it takes between
+        x0 and M: float64 ones (or None) go as double pointers, int32 ones as int pointers."""
         stages = list(inner)
         K = len(stages)
         if K > CHAIN_MAX:
@@ -1131,7 +1154,8 @@ class Handle:
         want = [k for k in names if k not in optional or k in outputs]
         out = {k: np.empty(shapes.get(k, (M, T, D)), dtype=np.int32 if k in ROLLOUT_INT_OUTPUTS else np.float64) for k in want}
         ptr = lambda k: (None if k not in out else out[k].ctypes.data_as(_ip)) if k in ROLLOUT_INT_OUTPUTS else dptr(out.get(k))
-        check(getattr(self.lib, "gpt_" + what)(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), *(dptr(a) for a in inputs), M, T, float(dt),
+        check(getattr(self.lib, "gpt_" + what)(arr if K else None, K, dyn._h, dptr(y0), dptr(x0), *(a.ctypes.data_as(_ip) if a is not None and a.dtype == np.int32 else dptr(a) for a in inputs), M, T,
+                                               float(dt),
                                                float(rtol), int(max_passes), *extra, *(ptr(k) for k in names)),
               "gpt_" + what)
         del keep
@@ -1221,6 +1245,47 @@ class Handle:
         self._rollout_dev("rollout_sampled", ROLLOUT_SAMPLED_OUTPUTS, (float(nugget),), inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt, rtol,
                           max_passes, dict(path=path_ptr, vel=vel_ptr, x=x_ptr, f=f_ptr, pvar=pvar_ptr, cvar=cvar_ptr, chol=chol_ptr,
                                            steps_done=steps_done_ptr, status=status_ptr), input_ptrs=(normals_ptr,))
+
+    # ---- whole paths of whole functions drawn from the dynamics posterior (pathwise conditioning)
+    def rollout_pathwise(self, inner, dyn, y0, func, weights, omega, amp, n_steps, dt=1.0, x0=None, rtol=1e-10, max_passes=64,
+                         outputs=("vel", "x", "f")):
+        """gpt_rollout_pathwise on host arrays: rollout_policy with, in place of the mean of `dyn`, the drawn function
+        F_s(x) = k(x, X) weights[s] + sum_j amp[s, j, 0] cos(omega[j] . x) + amp[s, j, 1] sin(omega[j] . x), s = func[p] for path p
+        (only `dyn` is sampled; the maps of `inner` act through their means).  y0 (P,D): one start per path; func (P,) ints in
+        0 .. S - 1; weights (S,N,D); omega (J,D), J <= PATHWISE_MAX_FREQ (J = 0: the kernel part alone); amp (S,J,2,D).
+        `outputs`: which of "vel", "x", "f" (P,n_steps,D; f = F_s at x) come back besides path, steps_done and status.  With J = 0
+        and weights = alpha: rollout_policy's path.  Any kernel, any N, any n_steps.  Returns a dict."""
+        N, D, O, _ = dyn.info()
+        y0 = as_f64(y0, 2, "y0")
+        func = np.ascontiguousarray(func, dtype=np.int32)
+        if func.shape != (y0.shape[0],):
+            raise ValueError(f"func has shape {func.shape}, expected (paths,) = {(y0.shape[0],)}")
+        weights = as_f64(weights, 3, "weights")
+        S = weights.shape[0]
+        if S < 1 or weights.shape != (S, N, D):
+            raise ValueError(f"weights has shape {weights.shape}, expected (functions >= 1, N, D) = (S, {N}, {D})")
+        omega = as_f64(omega, 2, "omega")
+        J = omega.shape[0]
+        amp = as_f64(amp, 4, "amp")
+        if omega.shape != (J, D) or amp.shape != (S, J, 2, D):
+            raise ValueError(f"omega has shape {omega.shape} and amp {amp.shape}, expected (J, {D}) and ({S}, J, 2, {D})")
+        if J > PATHWISE_MAX_FREQ:
+            raise ValueError(f"rollout_pathwise: at most {PATHWISE_MAX_FREQ} (PATHWISE_MAX_FREQ) frequencies, got {J}")
+        if func.size and (func.min() < 0 or func.max() >= S):
+            raise ValueError(f"rollout_pathwise: func must hold indices 0 .. {S - 1}")
+        return self._rollout_host("rollout_pathwise", ROLLOUT_PATHWISE_OUTPUTS, ("vel", "x", "f"),
+                                  (S, dptr(weights), J, dptr(omega) if J else None, dptr(amp) if J else None), inner, dyn, y0, n_steps, dt,
+                                  x0, rtol, max_passes, outputs, inputs=(func,))
+
+    def rollout_pathwise_dev(self, inner, dyn, y0_ptr, func_ptr, M, n_steps, S, weights4_ptr, J, omega_ptr, amp_ptr, path_ptr, steps_done_ptr,
+                             status_ptr, dt=1.0, x0_ptr=0, rtol=1e-10, max_passes=64, vel_ptr=0, x_ptr=0, f_ptr=0):
+        """The same on device pointers (float64; func / steps_done / status int32), asynchronous on this handle's stream
+        (gpt_rollout_pathwise_dev).  weights4_ptr: (S,NP,4), one image per function in the layout of the model's alpha rows.
+        `inner`: tuples (handle, R_ptr, c_src_ptr, c_dst_ptr, scale, R_jac_ptr), device pointers."""
+        self._rollout_dev("rollout_pathwise", ROLLOUT_PATHWISE_OUTPUTS, (int(S), _vp(weights4_ptr or None), int(J), _vp(omega_ptr or None),
+                                                                         _vp(amp_ptr or None)), inner, dyn, y0_ptr, x0_ptr, M, n_steps, dt,
+                          rtol, max_passes, dict(path=path_ptr, vel=vel_ptr, x=x_ptr, f=f_ptr, steps_done=steps_done_ptr, status=status_ptr),
+                          input_ptrs=(func_ptr,))
 
     # ---- predict (device pointers, asynchronous)
     def predict_all_dev(self, xq_ptr, M, mean_ptr=0, var_ptr=0, J_ptr=0, Jvar_ptr=0, dvar_ptr=0):

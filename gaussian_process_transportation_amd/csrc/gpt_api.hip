@@ -865,6 +865,42 @@ int gpt_export_inverse_factor(gpt_handle* h, double* W) {
     return GPT_OK;
 }
 
+int gpt_apply_inverse(gpt_handle* h, const double* R, int64_t C, double* out) {
+    if (!h) return fail(GPT_E_ARG, "gpt_apply_inverse: NULL handle");
+    if (!h->committed) return fail(GPT_E_STATE, "gpt_apply_inverse: model is not fitted");
+    if (h->lay.dtype != DT_F64) return fail(GPT_E_ARG, "gpt_apply_inverse: fp64 models only (this model was fitted with GPT_F32)");
+    if (h->p.ntask != 1) return fail(GPT_E_ARG, "gpt_apply_inverse: single-task models only (this model is a multi-task gpt_fit_svgp model)");
+    if (!h->have_W)
+        return fail(GPT_E_ARG, "gpt_apply_inverse: exact-GP models on the handle that ran gpt_fit only (this handle holds no inverse factor)");
+    if (C < 0 || C > INT_MAX) return fail(GPT_E_ARG, "gpt_apply_inverse: C must be 0 .. 2^31 - 1");
+    if (C > 0 && (!R || !out)) return fail(GPT_E_ARG, "gpt_apply_inverse: R and out must not be NULL");
+    if (C == 0) return GPT_OK;
+    if (int rc = set_device(h)) return rc;
+    const int64_t N = h->p.N, NP = h->p.NP;
+    hipStream_t s = h->stream;
+    if (int rc = ensure_scratch(h, NP)) return rc;
+    // [right-hand sides | result], each [NP][4]: the images launch_alpha reads and writes for the targets of a fit
+    const size_t img = (size_t)NP * 4;
+    CALLCHK(reserve(h->cov_buf, 2 * img * sizeof(double), s));
+    double* const dR4 = reinterpret_cast<double*>(h->cov_buf.p);
+    double* const dO4 = dR4 + img;
+    std::vector<double> r4(img), o4(img);
+    for (int64_t c0 = 0; c0 < C; c0 += 4) {                      // four columns per pass, the last one padded with zero columns
+        const int nc = (int)std::min<int64_t>(4, C - c0);
+        std::fill(r4.begin(), r4.end(), 0.0);
+        for (int64_t i = 0; i < N; ++i)
+            for (int k = 0; k < nc; ++k) r4[(size_t)i * 4 + k] = R[i * C + c0 + k];
+        CALLCHK(hipMemcpyAsync(dR4, r4.data(), img * sizeof(double), hipMemcpyHostToDevice, s));
+        launch_alpha(s, h->ws->dW, dR4, (int)N, (int)NP, h->ws->dT4, dO4, h->ws->dScr);
+        CALLCHK(hipGetLastError());
+        CALLCHK(hipMemcpyAsync(o4.data(), dO4, img * sizeof(double), hipMemcpyDeviceToHost, s));
+        CALLCHK(hipStreamSynchronize(s));                        // (r4 and o4 are reused by the next pass)
+        for (int64_t i = 0; i < N; ++i)
+            for (int k = 0; k < nc; ++k) out[i * C + c0 + k] = o4[(size_t)i * 4 + k];
+    }
+    return GPT_OK;
+}
+
 int gpt_lml(gpt_handle* h, double* lml) {
     if (!h || !lml) return fail(GPT_E_ARG, "gpt_lml: NULL argument");
     if (!(h->committed || h->objective_ready) || !h->have_L || !h->have_W) return fail(GPT_E_STATE, "gpt_lml: needs the handle that ran gpt_fit");

@@ -1,6 +1,7 @@
 // Driver of `make host-oneshot-asan`: calls the real entry points of the one-shot units (gpt_batch_host.hip, gpt_batch_opt_host.hip, gpt_fold_scan_host.hip, gpt_select_host.hip,
 // gpt_svgp_train_host.hip, gpt_svgp_surface_host.hip), gpt_predict_all (gpt_api.hip), gpt_inverse_map, gpt_transport_policy and
-// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip), gpt_rollout_sampled (gpt_rollout_sampled_host.hip)
+// gpt_pullback_policy (gpt_transport_host.hip), gpt_pullback_chain (gpt_chain_host.hip), gpt_rollout_policy (gpt_rollout_host.hip), gpt_rollout_stabilised (gpt_rollout_stab_host.hip), gpt_rollout_sampled (gpt_rollout_sampled_host.hip),
+// gpt_rollout_pathwise (gpt_rollout_pathwise_host.hip), gpt_apply_inverse (gpt_api.hip)
 // on the stand-in "device" memory of host_stub/, at the smallest shapes at which each piece of their packing, carving and sizing arithmetic can go wrong.  Every
 // array is allocated at its exact size, so AddressSanitizer sees a read or write past it; every output starts as a sentinel.
 // The stand-in launchers (stub_launchers.cpp) write zeros where the kernels write, so after a call an output that was asked for
@@ -1211,6 +1212,124 @@ void rollout_sampled_cases() {
     done(GPT_OK, GPT_OK);
 }
 
+// ---- pathwise rollout (gpt_rollout_pathwise_host.hip): three per-path inputs (y0, x0, func: an int per path), the arrays of the
+// rollout and f; what the functions bring has no row per path and is uploaded once: the weights (S,N,D) packed into images
+// [S][NP][4], omega (J,D), amp (S,J,2,D), each at its exact size; chunks as the rollout's, or GPT_ROLLOUT_PATHWISE_CHUNK paths
+void rollout_pathwise_cases() {
+    const int64_t N = 5, Nd = 7;
+    D X = ramp(N * 3), Y = ramp(N * 3, 0.01, 0.01), Xd = ramp(Nd * 3), Yd = ramp(Nd * 3, 0.02, 0.01), ls{0.5, 0.75, 0.6};
+    D R{1, 0, 0, 0, 1, 0, 0, 0, 1}, c_src{0.1, 0.2, 0.3}, c_dst{0.3, 0.2, 0.1};
+    gpt_handle *h[2] = {}, *hd = nullptr;
+    begin("gpt_rollout_pathwise setup");
+    for (auto& q : h) CHECK(gpt_create(&q, 0) == GPT_OK);
+    CHECK(gpt_create(&hd, 0) == GPT_OK);
+    for (auto& q : h) CHECK(gpt_fit(q, X.p, Y.p, N, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    CHECK(gpt_fit(hd, Xd.p, Yd.p, Nd, 3, 3, ls.p, 3, 1.0, 0.01, 1e-10) == GPT_OK);
+    long held = stub_live_objects;
+    auto done_held = [&](int rc, int want) {
+        CHECK(rc == want);
+        CHECK(stub_live_objects == held);
+        printf("ok  %s\n", g_case.c_str());
+        ++g_cases;
+    };
+    struct Arrays {
+        D y0, x0, path, vel, x, f, w, omega, amp;
+        Arr<int> func, steps, status;
+        Arrays(int64_t M, int64_t T, int64_t S, int64_t J, int64_t Nd_)
+            : y0(ramp(M * 3)), x0(ramp(M * 3)), path((size_t)M * (T + 1) * 3, SENT), vel((size_t)M * T * 3, SENT), x((size_t)M * T * 3, SENT),
+              f((size_t)M * T * 3, SENT), w(ramp(S * Nd_ * 3)), omega(ramp(J * 3)), amp(ramp(S * J * 6)), func(M, 0), steps(M, ISENT),
+              status(M, ISENT) {
+            for (int64_t m = 0; m < M; ++m) func.p[m] = (int)((m * 5 + 1) % S);
+        }
+    };
+    std::vector<gpt_chain_stage> st2{gpt_chain_stage{h[0], R.p, c_src.p, c_dst.p, R.p, 1.0}, gpt_chain_stage{h[1], R.p, c_src.p, c_dst.p, R.p, 1.25}};
+    constexpr int X0 = 1, VEL = 2, XO = 4, FO = 8, ALL = 15;
+    auto call = [&](const gpt_chain_stage* st, int K, Arrays& a, int64_t M, int64_t T, int64_t S, int64_t J, int mask, const int* func,
+                    const double* w, const double* om, const double* amp) {
+        return gpt_rollout_pathwise(st, K, hd, a.y0.p, mask & X0 ? a.x0.p : nullptr, func, M, T, 0.5, 1e-10, 50, S, w, J, om, amp, a.path.p,
+                                    mask & VEL ? a.vel.p : nullptr, mask & XO ? a.x.p : nullptr, mask & FO ? a.f.p : nullptr, a.steps.p, a.status.p);
+    };
+    auto untouched = [&](const Arrays& a) {
+        CHECK(a.path.all(SENT) && a.vel.all(SENT) && a.x.all(SENT) && a.f.all(SENT) && a.steps.all(ISENT) && a.status.all(ISENT));
+    };
+    {
+        Arrays a(2, 2, 3, 4, Nd);
+        const gpt_chain_stage* st = st2.data();
+        begin("gpt_rollout_pathwise refuses S = 0"); done_held(call(st, 2, a, 2, 2, 0, 4, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses J = -1"); done_held(call(st, 2, a, 2, 2, 3, -1, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses J = 8193");
+        done_held(call(st, 2, a, 2, 2, 3, GPT_PATHWISE_MAX_FREQ + 1, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses func = NULL"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, nullptr, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses weights = NULL"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, nullptr, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses omega = NULL with J > 0"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, a.w.p, nullptr, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses amp = NULL with J > 0"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, a.w.p, a.omega.p, nullptr), GPT_E_ARG);
+        Arr<int> bad_f{0, 3}, neg_f{-1, 0};
+        begin("gpt_rollout_pathwise refuses func = S"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, bad_f.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses func = -1"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, neg_f.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        D nan_w(a.w), nan_o(a.omega), nan_a(a.amp);
+        nan_w.p[nan_w.n - 1] = std::nan(""); nan_o.p[nan_o.n - 1] = INFINITY; nan_a.p[nan_a.n - 1] = std::nan("");
+        begin("gpt_rollout_pathwise refuses NaN in weights"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, nan_w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses infinity in omega"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, a.w.p, nan_o.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses NaN in amp"); done_held(call(st, 2, a, 2, 2, 3, 4, ALL, a.func.p, a.w.p, a.omega.p, nan_a.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses n_steps = -1"); done_held(call(st, 2, a, 2, -1, 3, 4, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise refuses stages = NULL with K = 2"); done_held(call(nullptr, 2, a, 2, 2, 3, 4, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_E_ARG);
+        begin("gpt_rollout_pathwise M = 0 does nothing"); done_held(call(st, 2, a, 0, 2, 3, 4, ALL, a.func.p, a.w.p, a.omega.p, a.amp.p), GPT_OK);
+        untouched(a);
+    }
+    // (M, T, S, J, steps per launch, paths per chunk or 0): J = 0 without omega and amp; one function; M S no multiple of the chunk,
+    // one path past one and past two chunks; T = 0; launches cut inside a call
+    struct Shape { int64_t M, T, S, J; int per; int64_t chunk; };
+    const Shape shapes[] = {{1, 0, 1, 0, 32, 0}, {3, 1, 1, 0, 32, 0}, {3, 7, 2, 1, 3, 0}, {5, 6, 3, 65, 3, 4}, {9, 7, 3, 64, 32, 4}, {7, 40, 4, 130, 32, 3},
+                            {513, 255, 2, 3, 256, 0}};
+    for (int K : {0, 2})
+        for (const Shape& sh : shapes)
+            for (int mask : {0, ALL, X0 | XO, VEL | FO}) {
+                if (sh.M > 9 && (K != 2 || mask != ALL)) continue;
+                begin("gpt_rollout_pathwise K=" + std::to_string(K) + " M=" + std::to_string(sh.M) + " T=" + std::to_string(sh.T) + " S=" + std::to_string(sh.S) +
+                      " J=" + std::to_string(sh.J) + " steps per launch=" + std::to_string(sh.per) + " chunk=" + std::to_string(sh.chunk) + " optional=" +
+                      std::to_string(mask));
+                setenv("GPT_ROLLOUT_STEPS_PER_LAUNCH", std::to_string(sh.per).c_str(), 1);
+                if (sh.chunk) setenv("GPT_ROLLOUT_PATHWISE_CHUNK", std::to_string(sh.chunk).c_str(), 1);
+                else unsetenv("GPT_ROLLOUT_PATHWISE_CHUNK");
+                gpt::stub_rollout_launch_count = 0;
+                Arrays a(sh.M, sh.T, sh.S, sh.J, Nd);
+                const int rc = call(K ? st2.data() : nullptr, K, a, sh.M, sh.T, sh.S, sh.J, mask, a.func.p, a.w.p, sh.J ? a.omega.p : nullptr,
+                                    sh.J ? a.amp.p : nullptr);
+                CHECK(stub_live_objects >= held);                        // staging, scratch and events are kept and regrown, never dropped
+                held = stub_live_objects;
+                done_held(rc, GPT_OK);
+                int64_t chunk = std::max<int64_t>(1, 131072 / (sh.T + 1));
+                if (sh.chunk) chunk = std::min(chunk, sh.chunk);
+                const int64_t chunks = (sh.M + chunk - 1) / chunk;
+                CHECK(gpt::stub_rollout_launch_count == chunks * std::max<int64_t>(1, (sh.T + sh.per - 1) / sh.per));
+                CHECK(a.path.all(0.0) && a.status.all(0) && a.steps.all((int)sh.T));
+                CHECK(a.vel.all(mask & VEL ? 0.0 : SENT) && a.x.all(mask & XO ? 0.0 : SENT) && a.f.all(mask & FO ? 0.0 : SENT));
+            }
+    unsetenv("GPT_ROLLOUT_STEPS_PER_LAUNCH");
+    unsetenv("GPT_ROLLOUT_PATHWISE_CHUNK");
+    {
+        // gpt_apply_inverse (gpt_api.hip): the columns of a call in passes of four, the last one padded; R and out at their exact sizes
+        for (int64_t C : {1, 4, 5, 9}) {
+            begin("gpt_apply_inverse C=" + std::to_string(C));
+            D Rh = ramp(Nd * C), out((size_t)(Nd * C), SENT);
+            const int rc = gpt_apply_inverse(hd, Rh.p, C, out.p);
+            CHECK(stub_live_objects >= held);
+            held = stub_live_objects;
+            done_held(rc, GPT_OK);
+            CHECK(out.all(0.0));
+        }
+        D Rh = ramp(Nd), out((size_t)Nd, SENT);
+        begin("gpt_apply_inverse refuses C = -1"); done_held(gpt_apply_inverse(hd, Rh.p, -1, out.p), GPT_E_ARG);
+        begin("gpt_apply_inverse refuses R = NULL"); done_held(gpt_apply_inverse(hd, nullptr, 1, out.p), GPT_E_ARG);
+        begin("gpt_apply_inverse C = 0 does nothing"); done_held(gpt_apply_inverse(hd, nullptr, 0, nullptr), GPT_OK);
+        CHECK(out.all(SENT));
+    }
+    begin("gpt_rollout_pathwise teardown");
+    for (auto& q : h) gpt_destroy(q);
+    gpt_destroy(hd);
+    done(GPT_OK, GPT_OK);
+}
+
 }  // namespace
 
 int main() {
@@ -1257,6 +1376,7 @@ int main() {
     rollout_cases();
     rollout_stab_cases();
     rollout_sampled_cases();
+    rollout_pathwise_cases();
     printf("ONESHOT_DRIVER_OK %d cases\n", g_cases);
     return 0;
 }

@@ -279,6 +279,18 @@ extern "C" int gpt_rollout_sampled(const gpt_chain_stage*, int, gpt_handle*, con
     gpt::set_last_error("gpt_rollout_sampled: not in the host sanitizer build");
     return GPT_E_HIP;
 }
+extern "C" int gpt_rollout_pathwise_dev(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, const int*, int64_t, int64_t,
+                                        double, double, int, int64_t, const double*, int64_t, const double*, const double*, double*, double*,
+                                        double*, double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_pathwise_dev: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
+extern "C" int gpt_rollout_pathwise(const gpt_chain_stage*, int, gpt_handle*, const double*, const double*, const int*, int64_t, int64_t, double,
+                                    double, int, int64_t, const double*, int64_t, const double*, const double*, double*, double*, double*,
+                                    double*, int*, int*) {
+    gpt::set_last_error("gpt_rollout_pathwise: not in the host sanitizer build");
+    return GPT_E_HIP;
+}
 extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const double*, int64_t, const double*, int64_t, double*, int64_t, int,
                                int*) {
     gpt::set_last_error("gpt_debug_dgemm: not in the host sanitizer build");
@@ -302,6 +314,7 @@ extern "C" int gpt_debug_dgemm(int, int, int, int, int, int, double, const doubl
 #include "../gpt_rollout.h"
 #include "../gpt_rollout_stab.h"
 #include "../gpt_rollout_sampled.h"
+#include "../gpt_rollout_pathwise.h"
 #include <cstdio>
 
 namespace gpt {
@@ -585,6 +598,29 @@ void launch_rollout_sampled(hipStream_t s, int D_, const RolloutSampledArgs& sa)
         if (sa.pvar) touch_w(sa.pvar + m * T + t0, (t1 - t0) * 8);
         if (sa.cvar) touch_w(sa.cvar + m * T + t0, (t1 - t0) * 8);
         if (sa.chol) touch_w(sa.chol + (m * T + t0) * T, (t1 - t0) * T * 8);
+    }
+    launch_rollout(s, D_, a);                         // the mean rollout's arrays, its checks and its launch count
+}
+
+// ---- gpt_rollout_pathwise.hip -------------------------------------------------------------------------------------------------
+// k_rollout_pathwise: what k_rollout reads and writes, with the dynamics' alpha rows replaced by the image of each path's function
+// (whole images of NP rows), func of every path, the frequencies and the amplitudes of the functions in use; f is written where
+// it is asked for
+void launch_rollout_pathwise(hipStream_t s, int D_, const RolloutPathwiseArgs& pa) {
+    const RolloutArgs& a = pa.r;
+    if (a.M <= 0) return;
+    const size_t NP = ((size_t)a.dyn.N + PAD_N - 1) / PAD_N * PAD_N;
+    stub_check(pa.S >= 1 && pa.J >= 0 && pa.J <= PATHWISE_MAX_FREQ && pa.func && pa.V4 && pa.image == NP * 4);
+    stub_check(pa.J == 0 || (pa.omega && pa.amp));
+    const size_t M = (size_t)a.M, D = (size_t)D_, T = (size_t)a.T, t0 = (size_t)a.t_begin, t1 = (size_t)a.t_end, J = (size_t)pa.J;
+    touch_r(pa.func, M * 4);
+    touch_r(pa.omega, J * D * 8);
+    for (size_t m = 0; m < M; ++m) {
+        stub_check(pa.func[m] >= 0 && pa.func[m] < pa.S);
+        const size_t fn = (size_t)pa.func[m];
+        touch_r(pa.V4 + fn * pa.image, pa.image * 8);
+        touch_r(pa.amp + fn * J * 2 * D, J * 2 * D * 8);
+        if (pa.f) touch_w(pa.f + (m * T + t0) * D, (t1 - t0) * D * 8);
     }
     launch_rollout(s, D_, a);                         // the mean rollout's arrays, its checks and its launch count
 }

@@ -143,6 +143,7 @@ class GaussianProcess:
         self._handle.set_matern_derivatives(self.matern_derivatives)
         self._handle.fit(self.X, self.Y, ls, c, noise, self.alpha, self._ktype)
         self._K_inv = None
+        self._fit_token = object()               # what was drawn from an earlier fit knows that it is not this one (posterior_functions.py)
         # fitted kernel object with the reference's attribute protocol (:38-41)
         fitted = copy.deepcopy(self._kernel_in)
         keep_array = np.iterable(self._kernel_in.get_params()[_PARAM_LS])
@@ -608,6 +609,41 @@ class GaussianProcess:
                                             dt=float(dt), x0=None if x0 is None else np.repeat(x0, S, axis=0), rtol=rtol,
                                             max_passes=max_passes, outputs=names)
         return {k: v.reshape((M, S) + v.shape[1:]) for k, v in out.items()}       # path index = m * n_samples + j
+
+    # ------------------------------------------------------------------ whole functions drawn from the posterior
+    def sample_functions(self, n_functions=10, n_frequencies=2048, random_state=0, frequencies=None, draws=None):
+        """n_functions whole functions drawn from the posterior of this model by pathwise conditioning (posterior_functions.py):
+        the prior as a sum of n_frequencies random Fourier features, corrected by one solve against the training data per function
+        on the device (_lib.Handle.apply_inverse).  Unlike the paths of rollout_samples(), each of which is a function of its own,
+        these exist everywhere: they can be evaluated at any points (a sampled vector field), rolled out for any number of steps
+        and from any number of starts under the same functions (PosteriorFunctions.predict / rollout), at a cost per step that
+        does not grow with the step, for a model of any size.  The approximation is in the prior only: the covariance error falls
+        as 1 / sqrt(n_frequencies); rollout_samples() stays the exact call for short paths.  The draws come from
+        np.random.RandomState(random_state) in this order: the frequencies (posterior_functions.draw_frequencies), the amplitudes
+        (draw_amplitudes), then eps = standard_normal((S, N, O)); V = apply_inverse(Y - prior_at(X) - sqrt(noise_var_) * eps), X and
+        Y as fitted (NaN rows dropped).  frequencies (J,D): use these instead of drawing them.  draws = (w, eps): the standard
+        normal numbers to use, w (S,J,2,O) for the amplitudes sqrt(c / J) * w and eps (S,N,O); zero draws give weights equal to
+        alpha_, bit for bit, and functions equal to the posterior mean.  Needs n_outputs == n_features <= 3, float64, RBF or
+        Matern 3/2 or 5/2 (the frequencies of Matern 1/2 do not converge usefully), at most _lib.PATHWISE_MAX_FREQ frequencies.
+        Returns a PosteriorFunctions."""
+        from .posterior_functions import sample_functions
+        return sample_functions(self, n_functions, n_frequencies, random_state, frequencies, draws)
+
+    def rollout_chain_functions(self, inner, functions, starts, n_steps, affine, dt=1.0, x0=None, rtol=1e-10, max_passes=64,
+                                return_info=False):
+        """PosteriorFunctions.rollout() through a chain of transports: the paths of rollout_chain() when the dynamics is, in turn,
+        each of the `functions` drawn from its posterior (functions.gp is the dynamics; sample_functions()).  Only the dynamics is
+        sampled; the maps (this model the last, `inner` the ones before it, `affine` as pullback_chain's) act through their
+        means: inverse, Jacobian and push-forward are rollout_chain's.  Every start runs under every function.  x0 (M,D): guesses
+        of the source-space preimages of the starts.  Returns a dict: path (M,S,n_steps+1,D), steps_done, status (M,S) and, with
+        return_info, vel, x, f (M,S,n_steps,D)."""
+        from .posterior_functions import PosteriorFunctions
+        if not isinstance(functions, PosteriorFunctions):
+            raise TypeError(f"rollout_chain_functions(): functions must be a PosteriorFunctions (GaussianProcess.sample_functions), got "
+                            f"{type(functions).__name__}")
+        maps = list(inner) + [self]
+        affine = self._check_chain("rollout_chain_functions", maps, functions.gp, affine, 1)
+        return functions._rollout("rollout_chain_functions", maps, affine, starts, n_steps, dt, x0, rtol, max_passes, return_info)
 
     # ------------------------------------------------------------------ fused metric path
     def prefetch_posterior(self, x):

@@ -98,6 +98,12 @@ class GaussianProcessTransportation:
         return self.method.rollout_policy_samples(dynamics, starts, n_steps, n_samples=n_samples, dt=dt, nugget=nugget,
                                                   random_state=random_state, normals=normals, x0=x0, return_info=return_info, **solver)
 
+    def rollout_policy_functions(self, functions, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+        """The paths of rollout_policy() from every start under each of `functions`, whole functions drawn from the posterior of the
+        dynamics (GaussianProcess.sample_functions), any number of steps, in one device call (an addition:
+        PolicyTransportation.rollout_policy_functions).  Only the dynamics is sampled; the map acts through its mean."""
+        return self.method.rollout_policy_functions(functions, starts, n_steps, dt=dt, x0=x0, return_info=return_info, **solver)
+
     def sample_transportation(self):
         """Posterior draws of the moved demonstration, at the positions of the last apply_transportation() (:29-30)."""
         return self.method.sample_transportation(self._input("training_traj_old"))

@@ -179,6 +179,14 @@ class PolicyTransportation:
                                                                         nugget=nugget, random_state=random_state, normals=normals, x0=x0,
                                                                         return_info=return_info, **solver)
 
+    def rollout_policy_functions(self, functions, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+        """The paths of rollout_policy() from every start under each of `functions`, whole functions drawn from the posterior of the
+        dynamics (GaussianProcess.sample_functions; TransportChain.rollout_functions with this transport as its only stage).  Only
+        the dynamics is sampled; the map acts through its mean.  Returns paths (M,S,n_steps+1,D); with return_info also a dict."""
+        from .transport_chain import TransportChain
+        return TransportChain([self], verbose=self.verbose).rollout_functions(functions, starts, n_steps, dt=dt, x0=x0, return_info=return_info,
+                                                                          **solver)
+
     def sample_transportation(self, pos):
         pos_rotated = self.affine_transform.predict(pos)
         return pos_rotated + self.delta_map.samples(pos_rotated)

@@ -161,3 +161,27 @@ class TransportChain:
             counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.ROLLOUT_SAMPLED_STATUS_NAMES))
             print(f"Sampled rollout of {done.size} paths, {int(n_steps)} steps: {int(np.sum(done == int(n_steps)))} complete; last status: {counts}")
         return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]
+
+    def rollout_functions(self, functions, starts, n_steps, dt=1.0, x0=None, return_info=False, **solver):
+        """Where does the same plausible policy take the robot from all the `starts` (M,D) of the LAST scene?  The rollout() of
+        every function of `functions` (GaussianProcess.sample_functions() of the dynamics: whole functions drawn from its
+        posterior) from every start, all starts under the same functions, any number of steps, in one device call
+        (GaussianProcess.rollout_chain_functions).  Only the dynamics is sampled; the maps act through their means.  Returns paths
+        (M,S,n_steps+1,D); with return_info also a dict: vel, x, f, steps_done, status, each with the leading shape (M,S).
+        Functions drawn with zero draws give rollout()."""
+        unknown = set(solver) - {"rtol", "max_passes"}
+        if unknown:
+            raise TypeError(f"TransportChain: unknown solver arguments {sorted(unknown)}")
+        rollout = getattr(self.methods[-1].delta_map, "rollout_chain_functions", None)
+        if rollout is None:
+            raise NotImplementedError(f"TransportChain.rollout_functions(): the delta_map of the last transport ({type(self.methods[-1].delta_map).__name__}) "
+                                      "has no rollout_chain_functions; GaussianProcess provides one")
+        affine = [(m.affine_transform.rotation_matrix, m.affine_transform.scale, m.affine_transform.S_centroid,
+                   m.affine_transform.T_centroid, m.affine_transform.rotation_matrix) for m in self.methods]
+        maps = [m.delta_map for m in self.methods]
+        out = rollout(maps[:-1], functions, starts, n_steps, affine, dt=dt, x0=x0, return_info=return_info, **solver)
+        if self.verbose:
+            status, done = out["status"], out["steps_done"]
+            counts = ", ".join(f"{name} {int(np.sum(status == code))}" for code, name in enumerate(_lib.INV_STATUS_NAMES))
+            print(f"Rollout of {done.size} paths of drawn functions, {int(n_steps)} steps: {int(np.sum(done == int(n_steps)))} complete; last status: {counts}")
+        return (out["path"], {k: v for k, v in out.items() if k != "path"}) if return_info else out["path"]

@@ -625,6 +625,56 @@ int gpt_rollout_sampled(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn,
                         int64_t M, int64_t n_steps, double dt, double rtol, int max_passes, double nugget, double* path, double* vel,
                         double* x, double* f, double* pvar, double* cvar, double* chol, int* steps_done, int* status);
 
+/* (new) Whole paths of WHOLE FUNCTIONS DRAWN FROM THE DYNAMICS POSTERIOR by pathwise conditioning (Matheron's rule, the prior as a
+ * sum of random Fourier features): gpt_rollout_policy with, in place of the dynamics mean, one of S deterministic functions
+ *   F_s(x) = sum_n k(x, X_n) V_s[n, :]  +  sum_j ( a_sj cos(omega_j . x) + b_sj sin(omega_j . x) ),
+ * k and X the kernel (without noise) and the training points of h_dyn.  The caller draws omega and the amplitudes and solves for
+ * V_s = (K + sigma^2 I)^-1 (Y - prior_s(X) - sigma eps_s) once per function (gpt_apply_inverse); the device generates no random
+ * number, so the call is a deterministic function of its arguments.  Unlike gpt_rollout_sampled, a function here exists everywhere:
+ * paths of one function from different starts see the same field, a step costs O(N + J) whatever t is, and neither N nor n_steps
+ * has a limit of its own.  The approximation is in the prior only (its covariance error falls as 1 / sqrt(J)); the update against
+ * the data is exact.  Only the dynamics is sampled; the maps act through their means.
+ * Arguments, end rule, NaN filling, steps_done, status, the guesses, negative dt, launches and chunks as gpt_rollout_policy (M: the
+ * number of paths); in addition
+ *   func (M, int)      path p follows function func[p], 0 .. S - 1
+ *   S                  the number of functions, >= 1
+ *   weights            the V_s.  Host entry: (S,N,D).  Device entry: (S,NP,4), one image per function in the layout of the model's
+ *                      alpha rows: row n = (V_s[n, 0 .. D-1], zeros), zero rows from N up to NP = N rounded up to a multiple of 512
+ *   J                  the number of frequencies, 0 .. GPT_PATHWISE_MAX_FREQ
+ *   omega (J,D), amp (S,J,2,D)   the frequencies; per function and frequency the D cosine amplitudes, then the D sine amplitudes
+ * Per path and step, s = func[p], x_t the source-space preimage of y_t (K = 0: x_t = y_t):
+ *   u_t     = sum_n k(x_t, X_n) V_s[n, :], the arithmetic of the dynamics mean on the function's weights
+ *   theta_j = sum_d omega_jd x_t,d, d ascending;   p_t = sum_j a_sj cos(theta_j) + b_sj sin(theta_j), one sincos per j
+ *   fs_t    = u_t + p_t
+ *   vel_t   = fs_t pushed through the maps exactly as gpt_pullback_chain pushes f (K = 0: vel_t = fs_t)
+ *   y_{t+1} = y_t + (dt vel_t)
+ * With J = 0 and every V_s the model's alpha: the path, vel, x, steps_done and status of gpt_rollout_policy, bit for bit but for
+ * the sign of a zero.  Further output, may be NULL, NaN after a path's end: f (M,T,D) = fs.
+ * One wave per path (k_rollout_pathwise: k_rollout's step with the feature sum added); a launch advances every live path by at
+ * most 128 steps (GPT_ROLLOUT_STEPS_PER_LAUNCH overrides; gpt_rollout_pathwise.h).  A path's values do not depend on M, on S, on the other paths or functions,
+ * on their order or on where the launches or the chunks are cut, bit for bit.
+ * Refusals beyond gpt_rollout_policy's, GPT_E_ARG: S < 1; J < 0 or J > GPT_PATHWISE_MAX_FREQ; func or weights NULL with M > 0; omega
+ * or amp NULL with M > 0 and J > 0.  (Multi-task and fp32 models are refused as by gpt_rollout_policy; any of the four kernels is
+ * taken as the dynamics.)  The device entry does not read func on the host: a path whose entry is
+ * outside 0 .. S - 1 ends before its first step with steps_done = 0, status = GPT_ROLLOUT_NO_FUNCTION and NaN in every row of its
+ * outputs, row 0 of path included; nothing is read out of bounds.
+ * Device memory, asynchronous, streams and resources as gpt_rollout_policy_dev (the calls share them). */
+#define GPT_PATHWISE_MAX_FREQ 8192
+#define GPT_ROLLOUT_NO_FUNCTION (-1)
+int gpt_rollout_pathwise_dev(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0_dev, const double* x0_dev,
+                             const int* func_dev, int64_t M, int64_t n_steps, double dt, double rtol, int max_passes, int64_t S,
+                             const double* weights4_dev, int64_t J, const double* omega_dev, const double* amp_dev, double* path_dev,
+                             double* vel_dev, double* x_dev, double* f_dev, int* steps_done_dev, int* status_dev);
+/* (new) The same with every data pointer in host memory, checked and chunked as gpt_rollout_policy; weights (S,N,D) are packed into
+ * the images here.  Also GPT_E_ARG for a func entry outside 0 .. S - 1 and for NaN or infinity in weights, omega or amp.  The
+ * images, omega and amp are uploaded once per call into the scratch of the owning handle (S NP 4 + J D + 2 S J D doubles,
+ * grow-only); the paths are chunked as gpt_rollout_policy's (GPT_ROLLOUT_PATHWISE_CHUNK in the environment: at most so many paths
+ * per chunk). */
+int gpt_rollout_pathwise(const gpt_chain_stage* stages, int K, gpt_handle* h_dyn, const double* y0, const double* x0, const int* func,
+                         int64_t M, int64_t n_steps, double dt, double rtol, int max_passes, int64_t S, const double* weights, int64_t J,
+                         const double* omega, const double* amp, double* path, double* vel, double* x, double* f, int* steps_done,
+                         int* status);
+
 /* predict(return_cov=True) — replaces sklearn/_gpr.py:458-470: mean (M,O) (may be NULL) and the joint
  * posterior covariance cov (M,M) = k(Xq,Xq) + noise_level*I - V^T V, V = L^-1 K*^T (identical for every
  * output; the caller tiles it).  Small-M path used by GaussianProcess.samples (gaussian_process.py:57-60);
@@ -636,6 +686,16 @@ int gpt_predict_cov(gpt_handle* h, const double* Xq, int64_t M, double* mean, do
 int gpt_export(gpt_handle* h, double* L, double* alpha);
 /* W = L^-1 (N,N) lower triangular, host memory (tests only). */
 int gpt_export_inverse_factor(gpt_handle* h, double* W);
+/* (new) out = (K + sigma^2 I)^-1 R for C caller-supplied columns: W^T (W R) with the inverse factor of the fitted model, through the
+ * launches that compute alpha in gpt_fit (R = Y gives the alpha of gpt_export, bit for bit).  R, out: (N,C) row-major, host memory,
+ * may be the same array.  The columns go through the device four per pass, the last pass padded with zero columns; a column's
+ * result does not depend on the other columns of the call, bit for bit.  Rows of R beyond the model's N do not exist: R has exactly
+ * the N rows of the training set, in its order.  C = 0 does nothing.
+ * Refusals: GPT_E_STATE without a fitted model; GPT_E_ARG for an fp32 model, a multi-task gpt_fit_svgp model, a handle that did not
+ * run gpt_fit for this model (a gpt_factor_copy replica, a committed blob: they hold no W), C < 0, R or out NULL with C > 0.
+ * Synchronous on the handle's stream: returns when out is in place.  Device memory: 2 NP 4 doubles of the handle's covariance
+ * scratch (grow-only); the model and the factors are left as they were. */
+int gpt_apply_inverse(gpt_handle* h, const double* R, int64_t C, double* out);
 
 /* Log-marginal likelihood of the fitted theta (sklearn/_gpr.py:598-606): sum over outputs of
  * -0.5 y^T alpha - sum(log diag L) - N/2 log(2 pi). */

@@ -21,7 +21,15 @@ loop is serial in the paths, so on the larger shapes it is timed on the first --
 the line says.  Shapes: 3d (the demo dynamics, N = 460, M = 1, S = 32, T = 200), 2d (10 x 10 starts, S = 8, T = 100) and large
 (N_map = 8192 twice, N_dyn = 1024, P = 1024, T = 64).  The per-launch times behind ROLLOUT_SAMPLED_STEPS_PER_LAUNCH come from the
 profiler's kernel trace, not from wall times: tools/rollout_sampled_launches.py.
-usage: python tools/rollout_timing.py [--stabilised | --sampled] [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
+--pathwise times the rollout of whole drawn functions (gpt_rollout_pathwise: GaussianProcess.sample_functions, PosteriorFunctions.rollout,
+TransportChain.rollout_functions; 2048 frequencies) against the numpy loop of the same functions (all paths of a step at once;
+with maps one transported_policy call per step for x and the per-stage A, and the push in numpy) and, where that call admits the
+shape, against rollout_samples with as many paths.  Shapes: 3d (N = 460, M = 1, S = 32, T = 200), 2d (10 x 10 starts, S = 8: 800
+paths, T = 100, and T = 1000, which rollout_samples does not admit).  The time of sample_functions (one solve per function) is
+on a line of its own.  --pathwise-launches: the calls behind ROLLOUT_PATHWISE_STEPS_PER_LAUNCH at the largest admitted shape (two
+maps of 8192 points, N_dyn = 8192, J = 8192, D = 3, 1024 paths), one launch of 8, 16, 32, 64, 128 and 256 steps each, to be run under
+`rocprofv3 --kernel-trace -f csv -d DIR --`; --pathwise-report DIR prints the launches of k_rollout_pathwise from that trace.
+usage: python tools/rollout_timing.py [--stabilised | --sampled | --pathwise] [--shapes 2d large] [--reps 5] [--out FILE (appended)]"""
 import argparse
 import os
 import sys
@@ -224,6 +232,137 @@ def sampled_main(a, say):
             f"status counts {np.bincount(res['device']['status'].ravel(), minlength=5).tolist()}")
 
 
+def pathwise_main(a, say):
+    from tests import pathwise_restatement as PW
+    kind_of = {0: "rbf", 2: "matern32", 3: "matern52"}
+    for shape in a.shapes:
+        chain, dyn, _, y0, x0, _, dt = stab_cases(shape)
+        for S, T in {"3d": [(32, 200)], "2d": [(8, 100), (8, 1000)]}[shape]:
+            M, D = y0.shape
+            P = M * S
+            t0 = time.perf_counter()
+            fn = dyn.sample_functions(n_functions=S, n_frequencies=2048, random_state=0)
+            t_draw = time.perf_counter() - t0
+            R = [] if chain is None else [np.asarray(m.affine_transform.rotation_matrix) for m in chain.methods]
+            kind = kind_of[dyn._ktype]
+
+            def device():
+                t0 = time.perf_counter()
+                if chain is None:
+                    path, info = fn.rollout(y0, T, dt=dt, return_info=True)
+                else:
+                    path, info = chain.rollout_functions(fn, y0, T, dt=dt, x0=x0, return_info=True)
+                return time.perf_counter() - t0, dict(info, path=path)
+
+            func = np.tile(np.arange(S), M)
+            Vp, ap = fn.weights[func], fn.amplitudes[func]            # (P,N,D), (P,J,2,D)
+
+            def step(y, guess, idx):
+                if chain is None:
+                    x, status, A = y.copy(), np.zeros(len(y), dtype=np.int32), None
+                else:
+                    _, info = chain.transported_policy(dyn, y, x0=guess, return_info=True)
+                    x, status, A = info["x"], info["status"], info["stage_A"]
+                theta = x @ fn.omega.T
+                v = (np.einsum("pn,pnd->pd", PW.kernel_matrix(x, dyn.X, dyn._c, dyn._ls, kind), Vp[idx])
+                     + np.einsum("pj,pjd->pd", np.cos(theta), ap[idx, :, 0]) + np.einsum("pj,pjd->pd", np.sin(theta), ap[idx, :, 1]))
+                for k in range(len(R)):
+                    v = np.einsum("mij,mj->mi", A[k], v @ R[k].T)
+                return x, v, status
+
+            def loop():
+                """tests/rollout_restatement.rollout with the indices of the live paths handed to the step (a path has its own function)."""
+                t0 = time.perf_counter()
+                path = np.full((P, T + 1, D), np.nan)
+                path[:, 0] = np.repeat(y0, S, axis=0)
+                alive, guess = np.arange(P), None if x0 is None else np.repeat(x0, S, axis=0)
+                for t in range(T):
+                    if len(alive) == 0:
+                        break
+                    xt, vt, st = step(np.ascontiguousarray(path[alive, t]), guess, alive)
+                    with np.errstate(over="ignore", invalid="ignore"):
+                        nxt = path[alive, t] + dt * vt
+                    go = (np.asarray(st) == 0) & np.all(np.isfinite(nxt), axis=1)
+                    path[alive[go], t + 1] = nxt[go]
+                    alive, guess = alive[go], np.ascontiguousarray(xt[go])
+                return time.perf_counter() - t0, {"path": path}
+
+            def exact():
+                t0 = time.perf_counter()
+                if chain is None:
+                    dyn.rollout_samples(y0, T, n_samples=S, dt=dt)
+                else:
+                    chain.rollout_samples(dyn, y0, T, n_samples=S, dt=dt, x0=x0)
+                return time.perf_counter() - t0, None
+            calls = {"device": device, "loop": loop}
+            if T <= _lib.ROLLOUT_SAMPLED_MAX_T and len(dyn.X) <= _lib.ROLLOUT_STAB_MAX_N:
+                calls["exact"] = exact
+            n_map = "none" if chain is None else " + ".join(str(len(m.delta_map.X)) for m in chain.methods)
+            say(f"== pathwise {shape}: N_map = {n_map}, N_dyn = {len(dyn.X)}, D = {D}, M = {M} starts x S = {S} functions = {P} paths, T = {T}, dt = {dt}, "
+                f"J = 2048; median of {a.reps} (min .. max), ms")
+            say(f"   sample_functions, {S} functions (frequencies, amplitudes, one solve each) : {1e3 * t_draw:10.3f}  (once)")
+            times, res = {n: [] for n in calls}, {}
+            for f_ in calls.values():
+                f_()
+            for _ in range(a.reps):
+                for name, f_ in calls.items():
+                    t, res[name] = f_()
+                    times[name].append(t)
+            med = {n: 1e3 * float(np.median(t)) for n, t in times.items()}
+            rng = lambda n: f"({1e3 * min(times[n]):.3f} .. {1e3 * max(times[n]):.3f})"
+            dev_paths = res["device"]["path"].reshape(P, T + 1, D)
+            both = np.isfinite(dev_paths) & np.isfinite(res["loop"]["path"])
+            gap = float(np.max(np.abs(dev_paths - res["loop"]["path"])[both])) if np.any(both) else 0.0
+            done = res["device"]["steps_done"]
+            say(f"   numpy loop of the same functions{'' if chain is None else ' (+ transported_policy per step)'} : {med['loop']:10.3f}  {rng('loop')}")
+            say(f"   one call (gpt_rollout_pathwise), {-(-T // 128)} launch(es) : {med['device']:10.3f}  {rng('device')}   -> {med['loop'] / med['device']:.1f} x; "
+                f"slower than the loop: {'NO' if med['device'] <= med['loop'] else 'YES'}; {1e3 * med['device'] / max(1, T):.1f} us per step of the call; largest "
+                f"gap between the two over their common steps {gap:.3e} (the dynamics amplifies rounding); steps done: min {int(done.min())}, max "
+                f"{int(done.max())}")
+            if "exact" in calls:
+                say(f"   rollout_samples, as many paths (exact, each path a function of its own) : {med['exact']:10.3f}  {rng('exact')}   -> the pathwise call "
+                    f"takes {med['device'] / med['exact']:.2f} x its time; slower than rollout_samples: {'NO' if med['device'] <= med['exact'] else 'YES'}")
+            else:
+                say(f"   rollout_samples does not admit this shape (n_steps <= {_lib.ROLLOUT_SAMPLED_MAX_T}, N_dyn <= {_lib.ROLLOUT_STAB_MAX_N})")
+
+
+def pathwise_large():
+    """(chain, dynamics of 8192 points, the drawn functions with 8192 frequencies, 1024 starts, dt)."""
+    from gaussian_process_transportation_amd import GaussianProcess
+    from chain_timing import kernel
+    trs, _, sets = problem("large")
+    demo = np.random.default_rng(2).uniform(0.1, 0.9, (8192, 3))
+    dyn = GaussianProcess(kernel=kernel(0.05, [0.3, 0.3, 0.3], 1e-4, 1.5), optimizer=None, verbose=False).fit(demo, 0.1 * np.cos(3 * demo))
+    fn = dyn.sample_functions(n_functions=8, n_frequencies=_lib.PATHWISE_MAX_FREQ, random_state=0)
+    return TransportChain(trs, verbose=False), dyn, fn, np.ascontiguousarray(sets["M = 100000"][:128]), 0.05
+
+
+def pathwise_launches(a, say):
+    chain, dyn, fn, y0, dt = pathwise_large()
+    say(f"== pathwise large: N_map = 8192 + 8192, N_dyn = {len(dyn.X)}, J = {fn.omega.shape[0]}, D = 3, {len(y0)} starts x {len(fn)} functions = "
+        f"{len(y0) * len(fn)} paths; one call of ONE launch per window (T = the steps of a launch)")
+    for per in (8, 8, 16, 32, 64, 128, 256):                         # (the first call is the warm-up)
+        os.environ["GPT_ROLLOUT_STEPS_PER_LAUNCH"] = str(per)          # (read per call)
+        t0 = time.perf_counter()
+        path, info = chain.rollout_functions(fn, y0, per, dt=dt, return_info=True)
+        say(f"   {per:4d} steps in one launch : wall {1e3 * (time.perf_counter() - t0):10.3f} ms, copies included; paths complete: "
+            f"{int(np.sum(info['steps_done'] == per))} of {info['steps_done'].size}")
+    del os.environ["GPT_ROLLOUT_STEPS_PER_LAUNCH"]
+
+
+def pathwise_report(a, say):
+    import csv
+    import glob
+    rows = []
+    for f_ in glob.glob(os.path.join(a.pathwise_report, "**", "*kernel_trace.csv"), recursive=True):
+        with open(f_) as fh:
+            rows += [r for r in csv.DictReader(fh) if "k_rollout_pathwise" in r["Kernel_Name"]]
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    say(f"== launches of k_rollout_pathwise in the kernel trace, in order (the windows of --pathwise-launches: 8 (warm-up), 8, 16, 32, 64, 128, 256 steps), ms")
+    for r in rows:
+        say(f"   grid {r.get('Grid_Size', r.get('Grid_Size_X', '?'))} : {(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e6:10.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", choices=("2d", "large", "3d"), default=None)
@@ -231,18 +370,33 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--stabilised", action="store_true", help="the variance-stabilised rollout against its host loop")
     ap.add_argument("--sampled", action="store_true", help="the sampled rollout against its host loop")
+    ap.add_argument("--pathwise", action="store_true", help="the rollout of whole drawn functions against its numpy loop and rollout_samples")
+    ap.add_argument("--pathwise-launches", action="store_true", help="one launch of 8 .. 256 steps at the largest shape (run under the profiler)")
+    ap.add_argument("--pathwise-report", default=None, metavar="DIR", help="the launches of k_rollout_pathwise in the kernel trace under DIR")
     ap.add_argument("--loop-paths", type=int, default=8, help="--sampled: paths the host loop is timed on where it is scaled")
     a = ap.parse_args()
     if a.shapes is None:
-        a.shapes = ["3d", "2d", "large"] if a.stabilised or a.sampled else ["2d", "large"]
-    if "3d" in a.shapes and not (a.stabilised or a.sampled):
-        ap.error("the 3d shape is the stabilised and the sampled rollout's")
-    _lib.require_gpu()
+        a.shapes = ["3d", "2d"] if a.pathwise else ["3d", "2d", "large"] if a.stabilised or a.sampled else ["2d", "large"]
+    if "3d" in a.shapes and not (a.stabilised or a.sampled or a.pathwise):
+        ap.error("the 3d shape is the stabilised, the sampled and the pathwise rollout's")
+    if a.pathwise and "large" in a.shapes:
+        ap.error("--pathwise takes the shapes 3d and 2d; the large shape is --pathwise-launches'")
     lines = []
 
     def say(s):
         print(s, flush=True)
         lines.append(s)
+    if a.pathwise_report:
+        pathwise_report(a, say)
+        a.shapes = []
+    else:
+        _lib.require_gpu()
+    if a.pathwise:
+        pathwise_main(a, say)
+        a.shapes = []
+    if a.pathwise_launches:
+        pathwise_launches(a, say)
+        a.shapes = []
     if a.stabilised:
         stabilised_main(a, say)
         a.shapes = []
